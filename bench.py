@@ -61,7 +61,56 @@ def parse():
     ap.add_argument("--no-alt", action="store_true", help="skip the second measurement with --hip.conv3x3_split! (fp32-MFMA convolutions)")
     ap.add_argument("--alt-steps", type=int, default=60)
     ap.add_argument("--opt", action="append", default=[], help="extra option override(s), e.g. --opt=--hip.fused_backward!")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (losses, the forward's "
+                    "outputs, a fixed sample of the weights, buffers and gradients after it) as DIR/<name>.npy (rank 0)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20      # all files of --dump-outputs together
+DUMP_SAMPLE = 4096               # elements kept of a weight / buffer / gradient tensor larger than this (fixed positions per name)
+DUMP_VAR_SAMPLE = 1 << 20        # ... of an output of the forward pass larger than this
+
+
+def _sample(name, flat, k):
+    """`flat` itself when it has at most `k` elements, else `k` of them at positions fixed by `name` and the size alone."""
+    import zlib
+    import numpy as np
+    if flat.size <= k:
+        return flat
+    idx = np.sort(np.random.RandomState(zlib.crc32(name.encode())).choice(flat.size, k, replace=False))
+    return flat[idx]
+
+
+def dump_outputs(out_dir, loss, var, inputs, graph):
+    """--dump-outputs: the arrays of the last timed step as out_dir/<name>.npy, float32 (float64 for the loss values).
+      loss.<key>     every loss of the step (what train_iteration returns)
+      var.<key>      every floating-point tensor the forward pass wrote into the step's batch dict (renders, poses, latents)
+      param.<name>   weights and buffers after the optimizer step, grad.<name> their gradients; a tensor over DUMP_SAMPLE elements is
+                     sampled at fixed positions.
+    The inputs are seeded (options seed, synthetic.make_batch(seed=rank), torch.manual_seed(rank)): the same arguments give the same
+    inputs on every run, so that two builds can be compared file by file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for k, v in loss.items():
+        arrays["loss." + k] = np.asarray(v.detach().double().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64)
+    for k, v in var.items():
+        if torch.is_tensor(v) and v.is_floating_point() and v is not inputs.get(k):        # what the forward wrote, not the inputs
+            arrays["var." + k] = _sample("var." + k, v.detach().float().cpu().numpy().ravel(), DUMP_VAR_SAMPLE)
+    for name, t in graph.state_dict().items():
+        arrays["param." + name] = _sample(name, t.detach().cpu().numpy().astype(np.float32).ravel(), DUMP_SAMPLE)
+    for name, p in graph.named_parameters():
+        if p.grad is not None:
+            arrays["grad." + name] = _sample(name, p.grad.detach().float().cpu().numpy().ravel(), DUMP_SAMPLE)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return dict(dir=out_dir, files=len(arrays), bytes=total)
 
 
 def _host_cpu():
@@ -331,9 +380,9 @@ def main():
         return
     runner, opt, batch = build_runner(a.batch, rank, local, world, a.opt)
 
-    def step():
+    def step(var=None):
         opt.H, opt.W = opt.image_size
-        return runner.train_iteration(opt, edict(batch), None)
+        return runner.train_iteration(opt, edict(batch) if var is None else var, None)
 
     for _ in range(a.warmup):
         step()
@@ -342,8 +391,9 @@ def main():
         torch.distributed.barrier()
     torch.cuda.synchronize()
     t0 = time.time()
-    for _ in range(a.steps):
-        loss = step()
+    for i in range(a.steps):
+        last = edict(batch) if i == a.steps - 1 else None     # the last step's batch dict: the forward adds its outputs to it
+        loss = step(last)
     host_dt = time.time() - t0          # host time to enqueue the K steps (the GPU is still working)
     if world > 1:
         torch.distributed.barrier()
@@ -366,6 +416,10 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = t.item()
     assert torch.isfinite(loss.all.detach()).item(), "non-finite loss in the timed region"
+    dumped = None
+    if a.dump_outputs and rank == 0:                 # before the steps below change the weights again
+        dumped = dump_outputs(a.dump_outputs, loss, last, batch, runner.graph)
+    del last
     # the K-step region above is a burst (clocks have not settled): time a longer run as well
     sustained = None
     if a.sustained > 0:
@@ -490,6 +544,8 @@ def main():
             out["fp32_mfma_convolutions"] = alt
         if config1 is not None:
             out["config1_bs16"] = config1
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if not a.no_cpu_baseline and world == 1:      # reported at N = 1 only (the other ranks must not wait for rank 0)
             out["cpu_baseline"] = _guarded(lambda: cpu_baseline(a.cpu_batch or a.batch, explicit=bool(a.cpu_batch)))
         if not a.no_workloads and world == 1:
