@@ -6,6 +6,10 @@ passed as a flat ``dict[str, Tensor]`` using the reference's state-dict keys
 small ``Cfg`` object.  Every function cites the reference file:line it follows
 (paths relative to /root/reference).  All tensors fp32 unless stated.
 
+Precision: every floating tensor the oracle creates itself follows ``torch.get_default_dtype()``, so under
+``with default_dtype(torch.float64):`` (inputs converted to float64) the same code is a float64 restatement; under the
+fp32 default it computes exactly what it always did.
+
 Autograd: everything here is differentiable with ``create_graph=True`` exactly
 where the reference is, so ``torch.autograd.grad`` of a scalar functional of
 ``render()`` gives the oracle gradients (including the second-order terms
@@ -14,6 +18,7 @@ through d(density)/dx and d(sdf)/dx).
 from __future__ import annotations
 
 import math
+from contextlib import contextmanager
 from dataclasses import dataclass, field
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -22,6 +27,18 @@ import torch
 import torch.nn.functional as F
 
 Tensor = torch.Tensor
+
+
+@contextmanager
+def default_dtype(dtype: torch.dtype):
+    """Run a block under ``torch.set_default_dtype(dtype)``; the previous default is restored however the block exits
+    (a float64 default leaking out of one test would silently change every later one)."""
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(dtype)
+    try:
+        yield
+    finally:
+        torch.set_default_dtype(prev)
 
 
 # --------------------------------------------------------------------------------------
@@ -224,7 +241,8 @@ def make_pose(R: Optional[Tensor] = None, t: Optional[Tensor] = None) -> Tensor:
         R = torch.eye(3).repeat(*t.shape[:-1], 1, 1)
     elif t is None:
         t = torch.zeros(R.shape[:-1])
-    return torch.cat([R.float(), t.float()[..., None]], dim=-1)
+    dt = torch.get_default_dtype()
+    return torch.cat([R.to(dt), t.to(dt)[..., None]], dim=-1)
 
 
 def pose_invert(pose: Tensor) -> Tensor:
@@ -265,8 +283,8 @@ def get_center_and_ray(cfg: Cfg, pose: Tensor, intr: Tensor):
     Returns center [B,1,3], ray [B,HW,3] (ray = grid - center, un-normalised).
     """
     B = pose.shape[0]
-    y = torch.arange(cfg.H, dtype=torch.float32).add_(0.5)
-    x = torch.arange(cfg.W, dtype=torch.float32).add_(0.5)
+    y = torch.arange(cfg.H, dtype=torch.get_default_dtype()).add_(0.5)
+    x = torch.arange(cfg.W, dtype=torch.get_default_dtype()).add_(0.5)
     Y, X = torch.meshgrid(y, x, indexing="ij")
     xy = torch.stack([X, Y], dim=-1).view(-1, 2).repeat(B, 1, 1)
     grid = to_hom(xy) @ intr.inverse().transpose(-1, -2)
@@ -313,7 +331,7 @@ def roll_to_R(trig: Tensor) -> Tensor:
 
 def pose_from_trig(cfg: Cfg, trig_azim, trig_elev, trig_theta, scale_dist):
     """Graph.pred_pose math, model/graph.py:272-289: R = Rz Rx Ry P, t = (0,0,dist*scale)."""
-    P = torch.tensor([[-1, 0, 0], [0, 0, -1], [0, -1, 0]]).float().unsqueeze(0)
+    P = torch.tensor([[-1, 0, 0], [0, 0, -1], [0, -1, 0]]).to(torch.get_default_dtype()).unsqueeze(0)
     R = roll_to_R(trig_theta) @ elev_to_R(trig_elev) @ azim_to_R(trig_azim) @ P.expand(len(trig_azim), 3, 3)
     pose_R = make_pose(R=R)
     tz = scale_dist * cfg.cam_dist
@@ -411,7 +429,7 @@ def render(cfg: Cfg, W_sdf, W_rgb, beta_param: Tensor, pose: Tensor, intr: Tenso
 
     acc = torch.sum(weights, -1)
     rgb_out = torch.sum(weights.unsqueeze(-1) * rgb, 1) + (1.0 - acc.unsqueeze(1).repeat(1, 3)) * cfg.bgcolor
-    mask_hard = (acc > 0.5).float()
+    mask_hard = (acc > 0.5).to(acc.dtype)
 
     grad_eik = None
     if training:
@@ -505,7 +523,7 @@ def cam_uniform_loss(cfg: Cfg, trig):
     B = trig.shape[0]
     cos_e, sin_e = trig[:, 0], trig[:, 1]
     prod_e = cos_e * sin_e
-    grid = torch.arange(1.0, 2 * B, 2.0).float() * np.pi / B
+    grid = torch.arange(1.0, 2 * B, 2.0) * np.pi / B
     cos_p, sin_p = torch.cos(grid), torch.sin(grid)
     prod_p = cos_p * sin_p
     srt = lambda v: v.sort(dim=0, descending=False)[0]

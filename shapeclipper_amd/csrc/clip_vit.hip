@@ -33,10 +33,8 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef uint16_t bf16_t;
 
-__device__ __forceinline__ bf16_t f2bf(float f) {      // round-to-nearest-even
-    uint32_t u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (bf16_t)(u >> 16);
+__device__ __forceinline__ bf16_t f2bf(float f) {      // round-to-nearest-even, NaN stays NaN: gfx950's v_cvt_pk_bf16_f32
+    return __builtin_bit_cast(bf16_t, (__bf16)f);
 }
 __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 

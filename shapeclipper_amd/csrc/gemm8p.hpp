@@ -68,10 +68,10 @@ __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
         h2 v = {(_Float16)lo, (_Float16)hi};
         return __builtin_bit_cast(uint32_t, v);
     }
-    uint32_t a = __float_as_uint(lo), b = __float_as_uint(hi);
-    a += 0x7FFFu + ((a >> 16) & 1u);
-    b += 0x7FFFu + ((b >> 16) & 1u);
-    return (a >> 16) | (b & 0xFFFF0000u);
+    // round to nearest even, NaN stays NaN: one v_cvt_pk_bf16_f32 (an integer rounding carry used to turn large-payload NaNs into +-Inf / -0)
+    typedef __attribute__((ext_vector_type(2))) __bf16 b2;
+    b2 v = {(__bf16)lo, (__bf16)hi};
+    return __builtin_bit_cast(uint32_t, v);
 }
 
 // One LDS-DMA wave instruction (see clip_vit.hip glds16): lane i's 16 bytes land at LDS byte `lds_dst` (wave-uniform) + 16 i.  Issued from

@@ -49,6 +49,12 @@ __device__ __forceinline__ uint32_t order_key(float f) {   // monotone float -> 
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// Angular-error slots of the robust normal loss hold either a masked ray's error or OUT_OF_MASK.  A masked ray whose error is NaN is
+// stored as IN_MASK_NAN instead: its key (0xFFFFFFFF) ranks it after +Inf, as torch.sort puts NaN last, so it is a candidate like any
+// other and the selection always finds its n_keep-th key among the n candidates.
+constexpr uint32_t OUT_OF_MASK = 0x7FC00000u, IN_MASK_NAN = 0x7FFFFFFFu;
+__device__ __forceinline__ bool in_mask(float v) { return __float_as_uint(v) != OUT_OF_MASK; }
+
 __global__ __launch_bounds__(1024) void loss_fused_kernel(LossArgs a) {
     __shared__ float red[16];
     __shared__ unsigned int hist[256];
@@ -121,10 +127,11 @@ __global__ __launch_bounds__(1024) void loss_fused_kernel(LossArgs a) {
     unsigned int n_local = 0;
     auto angle = [&](int i) {
         const bool m = a.mask_t[i] > 0.5f && a.mask[i] > 0.5f;
-        float ang = __builtin_nanf("");                 // NaN marks "not in the mask"
+        float ang = __uint_as_float(OUT_OF_MASK);
         if (m) {
             ang = 1.f - (a.normal[i * 3] * a.normal_t[i * 3] + a.normal[i * 3 + 1] * a.normal_t[i * 3 + 1]
                          + a.normal[i * 3 + 2] * a.normal_t[i * 3 + 2]);
+            if (ang != ang) ang = __uint_as_float(IN_MASK_NAN);
             ++n_local;
         }
         return ang;
@@ -132,7 +139,7 @@ __global__ __launch_bounds__(1024) void loss_fused_kernel(LossArgs a) {
 #pragma unroll
     for (int j = 0; j < LOSS_VR; ++j) {
         const int i = tid + j * nt;
-        vreg[j] = i < N ? angle(i) : __builtin_nanf("");
+        vreg[j] = i < N ? angle(i) : __uint_as_float(OUT_OF_MASK);
     }
     for (int i = tid + LOSS_VR * nt; i < N; i += nt) a.ang_ws[i] = angle(i);
     if (tid == 0) sh_n = 0;
@@ -150,7 +157,7 @@ __global__ __launch_bounds__(1024) void loss_fused_kernel(LossArgs a) {
             __syncthreads();
             const uint32_t hi_mask = pass == 3 ? 0u : (0xFFFFFFFFu << (8 * (pass + 1)));
             auto count = [&](float v) {
-                if (v == v) {
+                if (in_mask(v)) {
                     const uint32_t key = order_key(v);
                     if ((key & hi_mask) == (prefix & hi_mask)) atomicAdd(&hist[(key >> (8 * pass)) & 255u], 1u);
                 }
@@ -171,7 +178,7 @@ __global__ __launch_bounds__(1024) void loss_fused_kernel(LossArgs a) {
                     if (tid >= d) incl += t;
                 }
                 unsigned int acc = incl - sum;
-                if (acc < r && r <= incl) {             // exactly one lane (the total is >= remaining)
+                if (acc < r && r <= incl) {             // exactly one lane: every masked ray is a candidate, so the total is >= remaining
                     int d = 4 * tid;
 #pragma unroll
                     for (int q = 0; q < 3; ++q)
@@ -208,7 +215,7 @@ __global__ __launch_bounds__(1024) void loss_fused_kernel(LossArgs a) {
             } else {
                 v = a.ang_ws[i];
             }
-            if (v == v && n_keep > 0) {
+            if (in_mask(v) && n_keep > 0) {
                 const uint32_t key = order_key(v);
                 keep = key < kth_key;
                 tie = key == kth_key;
