@@ -349,7 +349,11 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? 1 : 2) void rgb_composit
             tbl_load(a.feat, tile, p, g, f);
             __builtin_amdgcn_sched_barrier(0);
             float e[PE_STEPS], d1[PE_STEPS], d2[PE_STEPS];
-            pe_slots<true, false, true>(x0, x1, x2, g, a.symmetric != 0, e, d1, d2);
+            // FAST (hardware sin / cos) only where the encoding feeds gradients alone.  Without the stash the encoding also feeds the
+            // recomputed forward chain, whose ReLU masks and colours must be the forward's: the forward evaluates it with the accurate
+            // sincosf, and the hardware sine's ~1e-6 moves pre-activations near zero across the ReLU kink (measured at 2 images x 512
+            // rays: point gradients 3.5e-4 of max off float64, 1300x the fp32 oracle).
+            pe_slots<true, false, STASH>(x0, x1, x2, g, a.symmetric != 0, e, d1, d2);
             RB_STAMP(sid++)                                  /* +0: inputs requested, PE evaluated */
             if (STASH) {
                 col[0] = __shfl(c0, src); col[1] = __shfl(c1, src); col[2] = __shfl(c2, src);

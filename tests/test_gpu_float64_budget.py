@@ -300,10 +300,12 @@ def test_eval_render_one_image_float64_budget(golden):
 # kernel: the SDF backward (csrc/sdf_bwdw.hip, fused: n_per_image % 16 == 0), every weight, latent and point gradient
 # ---------------------------------------------------------------------------------------------------------------------------------
 K_SDF_BWD = dict(w_sdf=4.0, z=4.0, points=4.0)          # measured: <= 2.5 (w_sdf), 0.9 (z), 1.2 (points) x the fp32 oracle
+# non-fused path (test_sdf_backward_nonfused_float64_budget) measured: <= 3.1 (w_sdf), 1.3 (z), 1.6 (points) x the fp32 oracle
 
 
 def _sdf_bwd_oracle(cfg, W, z, pts, c, B, dt):
-    """L = <sdf, c1> + <d sdf/dx, c2> + <feat, c3> through R.sdf_mlp with the latent attached, in dtype dt (double backward)."""
+    """L = <sdf, c1> + <d sdf/dx, c2> + <feat, c3> through R.sdf_mlp with the latent attached, in dtype dt (double backward).  c2 / c3
+    None: that term is absent (c2 None: no d sdf/dx at all, a single backward -- the value-only path of pretrain.py)."""
     from oracle import reference_ops as R
     with R.default_dtype(dt):
         Wl = {k: v.to(dt).clone().requires_grad_(True) for k, v in W.items()}
@@ -311,21 +313,32 @@ def _sdf_bwd_oracle(cfg, W, z, pts, c, B, dt):
         N = pts.shape[0] // B
         out = R.sdf_mlp(cfg, Wl, pl, zl.unsqueeze(1).repeat(1, N, 1).view(B * N, -1))
         sdf, feat = out[:, :1], out[:, 1:]
-        grad = torch.autograd.grad(sdf, pl, torch.ones_like(sdf), create_graph=True)[0]
-        L = (sdf[:, 0] * c[0].to(dt)).sum() + (grad * c[1].to(dt)).sum() + (feat * c[2].to(dt)).sum()
-        gs = torch.autograd.grad(L, list(Wl.values()) + [zl, pl])
-    return dict(zip(list(Wl) + ["z", "points"], [x.detach() for x in gs]))
+        L = (sdf[:, 0] * c[0].to(dt)).sum()
+        if c[1] is not None:
+            grad = torch.autograd.grad(sdf, pl, torch.ones_like(sdf), create_graph=True)[0]
+            L = L + (grad * c[1].to(dt)).sum()
+        if c[2] is not None:
+            L = L + (feat * c[2].to(dt)).sum()
+        gs = torch.autograd.grad(L, list(Wl.values()) + [zl, pl], allow_unused=True)
+    return dict(zip(list(Wl) + ["z", "points"], [(x if x is not None else torch.zeros_like(v)).detach()
+                                                   for x, v in zip(gs, list(Wl.values()) + [zl, pl])]))
 
 
-def _sdf_bwd_hip(W, z, pts, c, N):
+def _sdf_bwd_hip(W, z, pts, c, N, symmetric=True, fused=True):
+    """SdfFunction forward + backward; d sdf/dx is computed (and differentiated) only when c2 is given, the feature term only when
+    c3 is given (otherwise g_feat is None in the backward)."""
     from shapeclipper_amd import packing
     from shapeclipper_amd.functional import SdfFunction
     dev = torch.device("cuda:0")
     Wd = {k: v.to(dev).requires_grad_(True) for k, v in W.items()}
     zd, pd = z.to(dev).requires_grad_(True), pts.to(dev).requires_grad_(True)
     pack, cb = packing.pack_sdf(Wd, zd)
-    sdf, grad, feat = SdfFunction.apply(pd, pack, cb, N, True, True, True, True)
-    L = (sdf * c[0].to(dev)).sum() + (grad * c[1].to(dev)).sum() + (packing.tbl_to_rows(feat, pts.shape[0]) * c[2].to(dev)).sum()
+    sdf, grad, feat = SdfFunction.apply(pd, pack, cb, N, symmetric, c[1] is not None, True, fused)
+    L = (sdf * c[0].to(dev)).sum()
+    if c[1] is not None:
+        L = L + (grad * c[1].to(dev)).sum()
+    if c[2] is not None:
+        L = L + (packing.tbl_to_rows(feat, pts.shape[0]) * c[2].to(dev)).sum()
     gs = torch.autograd.grad(L, list(Wd.values()) + [zd, pd])
     torch.cuda.synchronize()
     return dict(zip(list(Wd) + ["z", "points"], [x.cpu() for x in gs]))
@@ -352,6 +365,50 @@ def test_sdf_backward_fused_float64_budget(B, N):
         t = _sdf_bwd_hip(W, z, pts, c, N)
     rows = {k: ("w_sdf" if k.startswith("lin") else k, _err(d[k], r64[k]), _err(t[k], r64[k]), _err(r32[k], r64[k])) for k in r64}
     _check("SDF backward (fused) B=%d N=%d" % (B, N), rows, K_SDF_BWD, rule_a=False)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the non-fused SDF backward: csrc/sdf_bwd.hip, 8 sc_wgrad launches, tbl_sum.  Production reaches it without any flag: pretrain.py
+# (value only), the eikonal call of a training render when 2 R % 16 != 0, the per-point-latent SDFNetwork.forward (n_per_image = 1).
+# ---------------------------------------------------------------------------------------------------------------------------------
+NONFUSED = {
+    "pretrain": (4, 10000, False),         # options/pix3d/config.yaml pre.sample_points; folded bias sums, fixed-order tbl_sum
+    "fused_shape": (3, 1040, True),        # the inputs of test_sdf_backward_fused_float64_budget, fused=False; the fused arm beside it
+    "ragged_eik": (3, 74, True),           # 2 R at R = 37: tiles straddle images, unfolded tbl_sum (atomics) for the latent biases
+    "per_point_latent": (3000, 1, False),  # SDFNetwork.forward: one latent per point
+}
+
+
+@pytest.mark.parametrize("feat", [True, False])
+@pytest.mark.parametrize("symmetric", [True, False])
+@pytest.mark.parametrize("case", list(NONFUSED))
+def test_sdf_backward_nonfused_float64_budget(case, symmetric, feat):
+    """sdf_bwd.hip + sc_wgrad + tbl_sum against float64 (double) backward of R.sdf_mlp, rule (b) with K_SDF_BWD.  Second arm: the
+    fused backward on the same inputs where it applies (fused_shape), else the non-fused path after the fp32-MFMA forward.  feat=False
+    leaves g_feat None: the W5 / B5 feature rows are the wrapper's zero fill."""
+    from oracle import reference_ops as R
+    B, N, with_grad = NONFUSED[case]
+    cfg = R.Cfg(force_symmetry=symmetric)
+    g = torch.Generator().manual_seed(B * 7 + N)
+    W = {k: v + 0.05 * torch.randn(v.shape, generator=g) for k, v in R.init_sdf_weights(cfg, 1).items()}
+    z = torch.randn(B, 64, generator=g)
+    pts = torch.rand(B * N, 3, generator=g) * 2 - 1
+    c = (torch.randn(B * N, generator=g), torch.randn(B * N, 3, generator=g), torch.randn(B * N, 64, generator=g) * 0.1)
+    c = (c[0], c[1] if with_grad else None, c[2] if feat else None)
+    r64, r32 = _sdf_bwd_oracle(cfg, W, z, pts, c, B, torch.float64), _sdf_bwd_oracle(cfg, W, z, pts, c, B, torch.float32)
+    d = _sdf_bwd_hip(W, z, pts, c, N, symmetric, fused=False)
+    if case == "fused_shape":
+        second = "fused"
+        t = _sdf_bwd_hip(W, z, pts, c, N, symmetric, fused=True)
+    else:
+        second = "non-fused after the fp32 forward"
+        with _twins():
+            t = _sdf_bwd_hip(W, z, pts, c, N, symmetric, fused=False)
+    if not feat:
+        assert float(d["lin5.weight"][1:].abs().max()) == 0.0 and float(d["lin5.bias"][1:].abs().max()) == 0.0
+    rows = {k: ("w_sdf" if k.startswith("lin") else k, _err(d[k], r64[k]), _err(t[k], r64[k]), _err(r32[k], r64[k])) for k in r64}
+    _check("SDF backward (non-fused) [%s] B=%d N=%d symmetric=%s feat=%s; columns: non-fused | %s | fp32 oracle"
+           % (case, B, N, symmetric, feat, second), rows, K_SDF_BWD, rule_a=False)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -434,10 +491,8 @@ def _rgb_hip(ins, Wr, zr, rpi, cot):
     return outs, grads
 
 
-@pytest.mark.parametrize("n_images,rpi", [(3, 40), (3, 37), (2, 512)])
-def test_rgb_composite_float64_budget(n_images, rpi):
-    """sc_rgb_composite_forward_split + backward_fused_split (default) / forward_stash + the fp32 fused backward (twins) against a float64
-    restatement that starts from the same fp32 points, z_vals, depth factors, sdf, d sdf/dx, features and weights."""
+def _rgb_refs(n_images, rpi):
+    """Inputs, the rays that hit, cotangents (normals only where a ray hits) and the float64 / fp32 oracle outputs and gradients."""
     cfg, ins, Wr, zr = _rgb_case(n_images, rpi, seed=n_images * 100 + rpi)
     n_rays = n_images * rpi
     o64, _ = _rgb_oracle(cfg, ins, Wr, zr, rpi, None, torch.float64)
@@ -448,10 +503,11 @@ def test_rgb_composite_float64_budget(n_images, rpi):
                normal=torch.randn(n_rays, 3, generator=g) * hit.unsqueeze(1))
     o64, g64 = _rgb_oracle(cfg, ins, Wr, zr, rpi, cot, torch.float64)
     o32, g32 = _rgb_oracle(cfg, ins, Wr, zr, rpi, cot, torch.float32)
-    od, gd = _rgb_hip(ins, Wr, zr, rpi, cot)
-    with _twins():
-        ot, gt = _rgb_hip(ins, Wr, zr, rpi, cot)
-    assert torch.equal(od["mask_hard"], ot["mask_hard"])
+    return (ins, Wr, zr, hit, cot), (o64, g64, o32, g32)
+
+
+def _rgb_rows(ref, hit, od, gd, ot, gt):
+    o64, g64, o32, g32 = ref
     rows = {}
     for k in ("rgb", "mask", "depth", "normal"):
         sel = (lambda x: x * hit.unsqueeze(1)) if k == "normal" else (lambda x: x)
@@ -461,5 +517,207 @@ def test_rgb_composite_float64_budget(n_images, rpi):
             continue
         c = "w_rgb" if n.startswith("rgb_network.") else ("latent" if n == "z_rgb" else "point")
         rows[n] = (c, _err(gd[n], g64[n]), _err(gt[n], g64[n]), _err(g32[n], g64[n]))
+    return rows
+
+
+@pytest.mark.parametrize("n_images,rpi", [(3, 40), (3, 37), (2, 512)])
+def test_rgb_composite_float64_budget(n_images, rpi):
+    """sc_rgb_composite_forward_split + backward_fused_split (default) / forward_stash + the fp32 fused backward (twins) against a float64
+    restatement that starts from the same fp32 points, z_vals, depth factors, sdf, d sdf/dx, features and weights."""
+    (ins, Wr, zr, hit, cot), ref = _rgb_refs(n_images, rpi)
+    od, gd = _rgb_hip(ins, Wr, zr, rpi, cot)
+    with _twins():
+        ot, gt = _rgb_hip(ins, Wr, zr, rpi, cot)
+    assert torch.equal(od["mask_hard"], ot["mask_hard"])
     print("hit fraction %.2f" % float(hit.float().mean()))
-    _check("RGB composite n_images=%d rays/image=%d" % (n_images, rpi), rows, K_RGB)
+    _check("RGB composite n_images=%d rays/image=%d" % (n_images, rpi), _rgb_rows(ref, hit, od, gd, ot, gt), K_RGB)
+
+
+@contextmanager
+def _switches(**kw):
+    """ops module switches set for the block and restored however it exits."""
+    from shapeclipper_amd import ops
+    saved = {k: getattr(ops, k) for k in kw}
+    try:
+        for k, v in kw.items():
+            setattr(ops, k, v)
+        yield
+    finally:
+        for k, v in saved.items():
+            setattr(ops, k, v)
+
+
+@contextmanager
+def _count_wgrad():
+    """Counts the sc_wgrad launches of ops (the RGB backward without in-kernel weight gradients makes three)."""
+    from shapeclipper_amd import ops
+    calls, real = [], ops._wgrad
+
+    def spy(*a, **k):
+        calls.append(1)
+        return real(*a, **k)
+    ops._wgrad = spy
+    try:
+        yield calls
+    finally:
+        ops._wgrad = real
+
+
+# --hip.fused_rgb_wgrad!: sc_rgb_composite_backward_v3 + 3 sc_wgrad launches; --hip.rgb_stash!: the fused backward recomputes the forward.
+# measured at (3, 40), (3, 37) and (2, 512): <= 1.4 (out), 3.4 (point), 2.1 (w_rgb), 2.1 (latent) x the fp32 oracle -- the default path's factors.
+# 257 images (test_rgb_composite_257_images_float64_budget) measured: <= 1.4 (out), 4.3 (point), 3.7 (w_rgb), 1.4 (latent).
+RGB_ALTS = {"fused_rgb_wgrad_off": (dict(FUSED_RGB_WGRAD=False), 3), "rgb_stash_off": (dict(RGB_STASH=False), 0)}
+
+
+# Finding (fixed): both alternates recompute the RGB forward chain inside the backward (rgb_composite_bwd_kernel without STASH).  The
+# recomputation evaluated the positional encoding with the hardware sine / cosine, the forward with the accurate sincosf; the ~1e-6 difference
+# moved pre-activations near zero across the ReLU kink, so the backward's masks were not the forward's.  At 2 images x 512 rays that put
+# points 3.5e-4, feat 4.3e-4, lin0 / lin1 weights and biases 2.7e-5 .. 6.6e-5 and z_rgb 2.2e-5 of max off float64 (points 1300x, feat 1270x,
+# lin1.bias 550x, z_rgb 115x the fp32 oracle) while lin2, lin3, the outputs and the compositing gradients matched.  The recomputation now
+# uses the accurate sincosf: test_rgb_backward_recomputes_the_forward_activations_bit_for_bit.
+@pytest.mark.parametrize("alt", list(RGB_ALTS))
+@pytest.mark.parametrize("n_images,rpi", [(3, 40), (3, 37), (2, 512)])
+def test_rgb_composite_alternate_backward_float64_budget(n_images, rpi, alt):
+    """The RGB backward's alternate paths on the inputs of test_rgb_composite_float64_budget, rule (b) with K_RGB; columns: default |
+    alternate | fp32 oracle."""
+    kw, n_wgrad = RGB_ALTS[alt]
+    (ins, Wr, zr, hit, cot), ref = _rgb_refs(n_images, rpi)
+    od, gd = _rgb_hip(ins, Wr, zr, rpi, cot)
+    with _switches(**kw), _count_wgrad() as calls:
+        ot, gt = _rgb_hip(ins, Wr, zr, rpi, cot)
+    assert len(calls) == n_wgrad
+    assert torch.equal(od["mask_hard"], ot["mask_hard"])
+    _check("RGB composite n_images=%d rays/image=%d; columns: default | %s | fp32 oracle" % (n_images, rpi, alt),
+           _rgb_rows(ref, hit, od, gd, ot, gt), K_RGB, rule_a=False)
+
+
+@pytest.mark.parametrize("n_images,rpi", [(3, 37), (2, 512)])
+def test_rgb_backward_recomputes_the_forward_activations_bit_for_bit(n_images, rpi):
+    """sc_rgb_composite_backward_v3 recomputes the RGB chain and hands r0, r1 to sc_wgrad: they must be bit-equal to what the fp32 forward
+    (sc_rgb_composite_forward_stash, the same rgb_chain) parks, so that the backward's ReLU masks are the forward's."""
+    import ctypes
+    from shapeclipper_amd import _lib, ops, packing
+    dev = torch.device("cuda:0")
+    cfg, ins, Wr, zr = _rgb_case(n_images, rpi, seed=n_images * 100 + rpi)
+    x = {k: (packing.rows_to_tbl(v) if k == "feat" else v).to(dev).contiguous() for k, v in ins.items()}
+    v_pack, dbias = packing.pack_rgb({k: v.to(dev) for k, v in Wr.items()}, zr.to(dev))
+    args = (x["points"], x["z_vals"], x["depth_fac"], x["sdf"], x["grad"], x["feat"], v_pack, dbias, x["beta"])
+    with _switches(RGB_FWD_SPLIT=False):
+        o = ops.rgb_composite_forward(*args, rpi, True, 1e-4, 1.0, 1.0, keep_rgb_flat=True, keep_rr=True)
+    n_rays = n_images * rpi
+    P, T = n_rays * 64, n_rays * 4 * 1024
+    g = torch.Generator().manual_seed(rpi)
+    G = [torch.randn(n_rays, 3, generator=g), torch.randn(n_rays, generator=g), torch.randn(n_rays, generator=g),
+         torch.randn(n_rays, 3, generator=g)]
+    G = [t.to(dev) for t in G]
+    e = lambda *shape: torch.empty(*shape, device=dev)
+    outs = [e(P), e(P, 3), e(T), e(P, 3), e(n_rays, 64), e(n_rays), e(ops.RGB_BWD_BETA_PARTS)]
+    gy, rr = e(3 * T), torch.full((2 * T,), float("nan"), device=dev)
+    v3_part = e(ops.RGB_BWD_BETA_PARTS * 196)
+    lib = _lib.load()
+    code = lib.sc_rgb_composite_backward_v3(*[_lib.ptr(t) for t in args + (o["rgb_flat"],)], ctypes.c_int(n_rays), ctypes.c_int(rpi),
+                                            ctypes.c_int(n_images), ctypes.c_int(1), ctypes.c_float(1e-4), ctypes.c_float(1.0),
+                                            ctypes.c_float(1.0), *[_lib.ptr(t) for t in G], *[_lib.ptr(t) for t in outs], _lib.ptr(gy),
+                                            _lib.ptr(rr), None, _lib.ptr(v3_part), _lib.stream())
+    assert code == 0
+    torch.cuda.synchronize()
+    fwd = o["rr"][:2 * T]
+    n_diff = int((rr.view(torch.int32) != fwd.view(torch.int32)).sum())
+    print("recomputed r0, r1 differing from the forward's: %d of %d" % (n_diff, 2 * T))
+    assert n_diff == 0
+
+
+def test_rgb_composite_257_images_float64_budget():
+    """257 images (4 rays each): past the 256-image limit of the fused backward, so the default switches take
+    sc_rgb_composite_backward_v3 + 3 sc_wgrad launches (ops.rgb_composite_backward) and the forward parks no activations.  Columns:
+    default | twins | fp32 oracle."""
+    n_images, rpi = 257, 4
+    (ins, Wr, zr, hit, cot), ref = _rgb_refs(n_images, rpi)
+    with _count_wgrad() as calls:
+        od, gd = _rgb_hip(ins, Wr, zr, rpi, cot)
+    assert len(calls) == 3
+    with _twins():
+        ot, gt = _rgb_hip(ins, Wr, zr, rpi, cot)
+    _check("RGB composite n_images=257 rays/image=4", _rgb_rows(ref, hit, od, gd, ot, gt), K_RGB, rule_a=False)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# kernel: ray sampling (csrc/render.hip ray_sample_kernel / ray_sample_bwd_kernel), plain and with the eikonal points
+# ---------------------------------------------------------------------------------------------------------------------------------
+K_RAY = dict(leaf=4.0)          # measured: <= 2.2 x fp32 torch autograd (larger ratios only below the 2^-22 floor)
+
+
+def _ray_restated(o, d, sd, u, eik_idx, R, dist):
+    """UniformSampler.get_z_vals + the sample points + the near-surface eikonal points, as torch ops in the inputs' dtype."""
+    n = d.shape[0]
+    c = (dist * sd).repeat_interleave(R).view(n, 1)
+    near, far = c - 0.7, c + 0.7
+    t = torch.linspace(0.0, 1.0, steps=64).to(d.device, d.dtype)
+    z = near * (1.0 - t) + far * t
+    if u is not None:
+        mids = 0.5 * (z[..., 1:] + z[..., :-1])
+        upper = torch.cat([mids, z[..., -1:]], -1)
+        lower = torch.cat([z[..., :1], mids], -1)
+        z = lower + (upper - lower) * u.to(d.dtype)
+    pts = (o.unsqueeze(1) + z.unsqueeze(2) * d.unsqueeze(1)).reshape(-1, 3)
+    near_pts = pts.view(n, 64, 3)[torch.arange(n, device=d.device), eik_idx]
+    return z, pts, near_pts
+
+
+def _ray_case(B, R, training, seed):
+    g = torch.Generator().manual_seed(seed)
+    n = B * R
+    o = torch.randn(n, 3, generator=g)
+    d = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1)
+    sd = 0.8 + 0.4 * torch.rand(B, generator=g)
+    u = torch.rand(n, 64, generator=g) if training else None
+    eik_idx = torch.randint(64, (n,), generator=g)
+    eik_idx[0], eik_idx[-1] = (63, 0) if n > 1 else ((63,) * 2 if training else (0,) * 2)
+    eik_u = torch.rand(n, 3, generator=g) * 2 - 1
+    cot = dict(z=torch.randn(n, 64, generator=g), pts=torch.randn(n * 64, 3, generator=g), eik=torch.randn(B, 2 * R, 3, generator=g))
+    return o, d, sd, u, eik_idx, eik_u, cot
+
+
+@pytest.mark.parametrize("eik", [True, False])
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("B,R", [(1, 1), (3, 37), (2, 1000), (32, 512)])
+def test_ray_sample_float64_budget(B, R, training, eik):
+    """RaySampleEikFunction / RaySampleFunction.  Forward: z and the points bit-equal to the fp32 torch restatement, the eikonal points
+    bit-equal to [eik_uniform | points[ray, eik_idx]] per image.  Backward: g_cam_loc, g_ray_dirs and the per-image g_scale_dist (a sum
+    of R x 64 terms) against float64 autograd of the restatement, rule (b) against fp32 torch autograd."""
+    from shapeclipper_amd.functional import RaySampleEikFunction, RaySampleFunction
+    dev = torch.device("cuda:0")
+    dist = 5.0
+    o, d, sd, u, eik_idx, eik_u, cot = _ray_case(B, R, training, seed=B * 1000 + R + training)
+    n = B * R
+    leaf = lambda t, dt=torch.float32, dv=dev: t.to(dv, dt).clone().requires_grad_(True)
+    od, dd, sdd = leaf(o), leaf(d), leaf(sd)
+    ud = u.to(dev) if u is not None else None
+    cz, cp, ce = cot["z"].to(dev), cot["pts"].to(dev), cot["eik"].to(dev)
+    if eik:
+        z, p, e = RaySampleEikFunction.apply(od, dd, sdd, ud, eik_idx.to(dev), eik_u.to(dev), R, dist)
+        L = (z * cz).sum() + (p * cp).sum() + (e * ce).sum()
+    else:
+        z, p = RaySampleFunction.apply(od, dd, sdd, ud, R, dist)
+        L = (z * cz).sum() + (p * cp).sum()
+    gh = [x.cpu() for x in torch.autograd.grad(L, [od, dd, sdd])]
+    # fp32 torch restatement on the device: the forward bit for bit, and the fp32 autograd arm
+    o32, d32, sd32 = leaf(o), leaf(d), leaf(sd)
+    zr, pr, nr = _ray_restated(o32, d32, sd32, ud, eik_idx.to(dev), R, dist)
+    assert torch.equal(z, zr) and torch.equal(p, pr)
+    L32 = (zr * cz).sum() + (pr * cp).sum()
+    if eik:
+        assert torch.equal(e, torch.cat([eik_u.to(dev).view(B, R, 3), nr.view(B, R, 3)], 1))
+        L32 = L32 + (nr.view(B, R, 3) * ce[:, R:]).sum()
+    g32 = [x.cpu() for x in torch.autograd.grad(L32, [o32, d32, sd32])]
+    torch.cuda.synchronize()
+    # float64 autograd from the same fp32 inputs
+    cpu = torch.device("cpu")
+    o64, d64, sd64 = leaf(o, torch.float64, cpu), leaf(d, torch.float64, cpu), leaf(sd, torch.float64, cpu)
+    z64, p64, n64 = _ray_restated(o64, d64, sd64, u.double() if u is not None else None, eik_idx, R, dist)
+    L64 = (z64 * cot["z"].double()).sum() + (p64 * cot["pts"].double()).sum()
+    if eik:
+        L64 = L64 + (n64.view(B, R, 3) * cot["eik"][:, R:].double()).sum()
+    g64 = torch.autograd.grad(L64, [o64, d64, sd64])
+    rows = {k: ("leaf", _err(a, r), _err(a, r), _err(b, r)) for k, a, b, r in zip(("g_cam_loc", "g_ray_dirs", "g_scale_dist"), gh, g32, g64)}
+    _check("ray sampling B=%d R=%d training=%s eik=%s; columns: HIP | HIP | fp32 torch" % (B, R, training, eik), rows, K_RAY, rule_a=False)

@@ -510,3 +510,136 @@ def test_rgb_composite_ignores_nan_padding_and_poisoned_blocks(split, n_images, 
         assert torch.isfinite(got_o[k]).all() and _bits_equal(got_o[k], ref_o[k]), k
     for k in ref_g:
         assert torch.isfinite(got_g[k]).all() and _bits_equal(got_g[k], ref_g[k]), k
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the SDF backward (fused and non-fused) and ray sampling on NaN-padded inputs, NaN blocks waiting for their outputs and scratch
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _poison_scratch():
+    """NaN into every cached scratch buffer of ops (forward scratch, parked second-order terms, partial images of the row sums and
+    of tbl_sum): each must be written before it is read."""
+    from shapeclipper_amd import ops
+    for v in ops._SCRATCH.values():
+        v.fill_(float("nan"))
+
+
+def _sdf_bwd_inputs(B, N, seed):
+    from shapeclipper_amd import ops, packing
+    cfg, W, z, pts = _sdf_case(B, N, seed=seed)
+    dev = torch.device("cuda:0")
+    pack, cb = packing.pack_sdf({k: v.to(dev) for k, v in W.items()}, z.to(dev))
+    p = pts.to(dev)
+    _, _, _, sa, sp = ops.sdf_forward(p, pack, cb, N, stash=True)
+    g = torch.Generator().manual_seed(seed + 1)
+    n = B * N
+    gs, gg = torch.randn(n, generator=g).to(dev), torch.randn(n, 3, generator=g).to(dev)
+    gf = packing.rows_to_tbl(torch.randn(n, 64, generator=g) * 0.1).to(dev)
+    return dict(points=p, w_pack=pack, stash_a=sa, stash_p=sp, g_sdf=gs, g_grad=gg, g_feat=gf)
+
+
+def _sdf_bwd_call(x, B, N, fused):
+    from shapeclipper_amd import ops
+    a = (x["points"], x["w_pack"], N, B, True, x["stash_a"], x["stash_p"], x["g_sdf"], x["g_grad"], x["g_feat"])
+    out = ops.sdf_backward_fused(*a) if fused else ops.sdf_backward(*a, fused=False)
+    torch.cuda.synchronize()
+    return [t.clone() for t in out]
+
+
+@pytest.mark.parametrize("fused,B,N", [(True, 1, 16), (True, 3, 1040), (False, 3, 17), (False, 3, 74), (False, 1, 1000)])
+def test_sdf_backward_ignores_nan_padding_and_poisoned_blocks(fused, B, N):
+    """sdf_backward_fused (stash, upstream gradients, points, pack as interior slices of NaN-padded buffers) and the non-fused
+    sdf_backward at n_per_image % 16 != 0 (at most 1024 points: one tbl_sum block, so its float atomics add in a fixed order), whose hand-off tensors ga / gp / r0 are whole-tile torch.empty blocks: their padding lanes
+    (points past n) come from the caching allocator NaN-filled here, and sc_wgrad / tbl_sum must never sum them."""
+    from shapeclipper_amd import _lib, ops, packing
+    x = _sdf_bwd_inputs(B, N, seed=B * 100 + N)
+    ref = _sdf_bwd_call(x, B, N, fused)
+    xp = {k: _padded(v) for k, v in x.items()}
+    n, T = B * N, packing.n_tiles(B * N) * 1024
+    lib = _lib.load()
+    if fused:
+        parts, stride = int(lib.sc_sdf_backward_fused_parts(ctypes.c_int(n))), int(lib.sc_sdf_backward_fused_partial_floats(ctypes.c_int(B)))
+        sizes = (n * 3, parts * stride, stride, B * 5 * 64)
+    else:
+        assert int(lib.sc_tbl_sum_blocks(ctypes.c_int(n))) == 1      # one block: its float atomics add in a fixed order (bit-equal runs)
+        sizes = (5 * T, 4 * T, T, n * 3, ops.WGRAD_PARTS * packing.SDF_PACK_FLOATS, packing.SDF_PACK_FLOATS, 5 * B * 64, 2 * 64,
+                 5 * B * 64)
+    _poison_scratch()
+    for s in sizes:
+        _poison_allocator(s)
+    got = _sdf_bwd_call(xp, B, N, fused)
+    for name, a, b in zip(("points", "w_pack", "cbias"), got, ref):
+        assert torch.isfinite(a).all(), name
+        assert _bits_equal(a, b), name
+
+
+def _ray_inputs(B, R, training, seed):
+    g = torch.Generator().manual_seed(seed)
+    dev = torch.device("cuda:0")
+    n = B * R
+    x = dict(cam_loc=torch.randn(n, 3, generator=g), ray_dirs=torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1),
+             scale_dist=0.8 + 0.4 * torch.rand(B, generator=g), eik_uniform=torch.rand(n, 3, generator=g) * 2 - 1,
+             g_points=torch.randn(n * 64, 3, generator=g), g_z=torch.randn(n, 64, generator=g), g_eik=torch.randn(B, 2 * R, 3, generator=g))
+    if training:
+        x["u"] = torch.rand(n, 64, generator=g)
+    x = {k: v.to(dev) for k, v in x.items()}
+    x["eik_idx"] = torch.randint(64, (n,), generator=g).to(dev)
+    return x
+
+
+def _ray_run(x, B, R, eik):
+    """forward + backward, plain or with the eikonal points -> dict of every output."""
+    from shapeclipper_amd import ops
+    u = x.get("u")
+    if eik:
+        z, p, e = ops.ray_sample_forward_eik(x["cam_loc"], x["ray_dirs"], x["scale_dist"], u, x["eik_idx"], x["eik_uniform"], R, 5.0)
+        go, gd, gsd = ops.ray_sample_backward_eik(x["ray_dirs"], z, x["g_points"], x["g_z"], x["eik_idx"], x["g_eik"], R, B, 5.0)
+        out = dict(eik=e)
+    else:
+        z, p = ops.ray_sample_forward(x["cam_loc"], x["ray_dirs"], x["scale_dist"], u, R, 5.0)
+        go, gd, gsd = ops.ray_sample_backward(x["ray_dirs"], z, x["g_points"], x["g_z"], R, B, 5.0)
+        out = {}
+    torch.cuda.synchronize()
+    out.update(z=z, points=p, g_cam_loc=go, g_ray_dirs=gd, g_scale_dist=gsd)
+    return {k: v.clone() for k, v in out.items()}
+
+
+@pytest.mark.parametrize("eik", [True, False])
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("B,R", [(1, 1), (3, 37)])
+def test_ray_sample_ignores_nan_padding_and_poisoned_blocks(B, R, training, eik):
+    x = _ray_inputs(B, R, training, seed=B * R + training)
+    ref = _ray_run(x, B, R, eik)
+    xp = {k: (_padded(v) if v.is_floating_point() else v) for k, v in x.items()}
+    n = B * R
+    for s in (n * 64, n * 64 * 3, B * 2 * R * 3, n * 3, n):
+        _poison_allocator(s)
+    got = _ray_run(xp, B, R, eik)
+    for k in ref:
+        assert torch.isfinite(got[k]).all() and _bits_equal(got[k], ref[k]), k
+
+
+@pytest.mark.parametrize("eik", [True, False])
+@pytest.mark.parametrize("training", [True, False])
+def test_ray_sample_one_poisoned_direction_stays_in_its_ray(training, eik):
+    """Ray 40 (image 1) gets a NaN direction.  Only its points (and its near-surface eikonal point) and its image's g_scale_dist may
+    become non-finite -- they must -- and everything else is bit-identical to the clean run."""
+    B, R, ray = 3, 37, 40
+    x = _ray_inputs(B, R, training, seed=11 + training)
+    clean = _ray_run(x, B, R, eik)
+    bad = dict(x)
+    bad["ray_dirs"] = x["ray_dirs"].clone()
+    bad["ray_dirs"][ray, 1] = float("nan")
+    got = _ray_run(bad, B, R, eik)
+    n = B * R
+    may = {k: torch.zeros_like(v, dtype=torch.bool) for k, v in clean.items()}
+    may["points"].view(n, 64, 3)[ray] = True
+    may["g_scale_dist"][ray // R] = True
+    if eik:
+        may["eik"][ray // R, R + ray % R] = True
+    for k in clean:
+        nf = ~torch.isfinite(got[k])
+        assert not (nf & ~may[k]).any(), k
+        assert _bits_equal(got[k][~may[k]], clean[k][~may[k]]), k
+    assert (~torch.isfinite(got["points"].view(n, 64, 3)[ray])).any() and not torch.isfinite(got["g_scale_dist"][ray // R])
+    if eik:
+        assert not torch.isfinite(got["eik"][ray // R, R + ray % R]).all()
