@@ -125,6 +125,33 @@ int sc_rgb_composite_forward_split(const float* points, const float* z_vals, con
                                    float* rgb, float* mask, float* mask_hard, float* depth, float* normal,
                                    float* weights, float* alpha, float* rgb_flat, float* rr, void* stream);
 
+/* Sample counts other than 64.  The _ns entry points below take n_samples = S, the samples per ray, right after n_rays; every
+ * "64" in the shapes above becomes S (points [n_rays*S][3], z_vals [n_rays][S], TBL64 tensors n_rays * (S / 16) * 1024 floats).
+ * S must satisfy SC_N_SAMPLES_SUPPORTED (a multiple of 32 in [32, 256]); any other S returns hipErrorInvalidValue before anything
+ * is launched.  S = 64 runs exactly the kernels of the symbols without _ns, which are these entry points with S = 64.             */
+#define SC_N_SAMPLES_SUPPORTED(n) ((n) >= 32 && (n) <= 256 && (n) % 32 == 0)
+int sc_rgb_composite_forward_ns(const float* points, const float* z_vals, const float* depth_fac,
+                                const float* sdf, const float* grad, const float* feat,
+                                const float* v_pack, const float* dbias, const float* beta_param,
+                                int n_rays, int n_samples, int rays_per_image, int n_images, int symmetric,
+                                float beta_min, float bgcolor, float normal_pow,
+                                float* rgb, float* mask, float* mask_hard, float* depth, float* normal,
+                                float* weights, float* alpha, float* rgb_flat, void* stream);
+int sc_rgb_composite_forward_stash_ns(const float* points, const float* z_vals, const float* depth_fac,
+                                      const float* sdf, const float* grad, const float* feat,
+                                      const float* v_pack, const float* dbias, const float* beta_param,
+                                      int n_rays, int n_samples, int rays_per_image, int n_images, int symmetric,
+                                      float beta_min, float bgcolor, float normal_pow,
+                                      float* rgb, float* mask, float* mask_hard, float* depth, float* normal,
+                                      float* weights, float* alpha, float* rgb_flat, float* rr, void* stream);
+int sc_rgb_composite_forward_split_ns(const float* points, const float* z_vals, const float* depth_fac,
+                                      const float* sdf, const float* grad, const float* feat,
+                                      const float* v_pack, const float* dbias, const float* beta_param,
+                                      int n_rays, int n_samples, int rays_per_image, int n_images, int symmetric,
+                                      float beta_min, float bgcolor, float normal_pow,
+                                      float* rgb, float* mask, float* mask_hard, float* depth, float* normal,
+                                      float* weights, float* alpha, float* rgb_flat, float* rr, void* stream);
+
 /* Reverse pass.  G_* are the upstream per-ray gradients (NULL = zero).  g_beta: SC_RGB_BWD_BETA_PARTS floats, fully
  * written: one partial of d/d(raw beta parameter) per wave of the grid; the gradient is their sum in index order
  * (sc_partial_reduce(g_beta, SC_RGB_BWD_BETA_PARTS, 1, 1, out)) -- a fixed summation order, no float atomics.
@@ -179,6 +206,37 @@ int sc_rgb_composite_backward_fused_split(
     const float* points, const float* z_vals, const float* depth_fac, const float* sdf, const float* grad,
     const float* feat, const float* v_pack, const float* dbias, const float* beta_param, const float* rgb_flat,
     int n_rays, int rays_per_image, int n_images, int symmetric, float beta_min, float bgcolor, float normal_pow,
+    const float* G_rgb, const float* G_mask, const float* G_depth, const float* G_normal,
+    float* g_sdf, float* g_grad, float* g_feat, float* g_points, float* g_z, float* g_depth_fac, float* g_beta,
+    float* partial, float* v3_part, const float* rr, void* stream);
+
+/* The four reverse forms at S samples per ray (see SC_N_SAMPLES_SUPPORTED above); g_z is [n_rays][S].  Same summation orders: the
+ * per-wave g_beta / v3_part partials and the per-workgroup partial images are what the S = 64 forms write.                      */
+int sc_rgb_composite_backward_v3_ns(
+    const float* points, const float* z_vals, const float* depth_fac, const float* sdf, const float* grad,
+    const float* feat, const float* v_pack, const float* dbias, const float* beta_param, const float* rgb_flat,
+    int n_rays, int n_samples, int rays_per_image, int n_images, int symmetric, float beta_min, float bgcolor, float normal_pow,
+    const float* G_rgb, const float* G_mask, const float* G_depth, const float* G_normal,
+    float* g_sdf, float* g_grad, float* g_feat, float* g_points, float* g_z, float* g_depth_fac, float* g_beta,
+    float* gy, float* rr, float* gy3, float* v3_part, void* stream);
+int sc_rgb_composite_backward_fused_ns(
+    const float* points, const float* z_vals, const float* depth_fac, const float* sdf, const float* grad,
+    const float* feat, const float* v_pack, const float* dbias, const float* beta_param, const float* rgb_flat,
+    int n_rays, int n_samples, int rays_per_image, int n_images, int symmetric, float beta_min, float bgcolor, float normal_pow,
+    const float* G_rgb, const float* G_mask, const float* G_depth, const float* G_normal,
+    float* g_sdf, float* g_grad, float* g_feat, float* g_points, float* g_z, float* g_depth_fac, float* g_beta,
+    float* partial, float* v3_part, void* stream);
+int sc_rgb_composite_backward_fused_stash_ns(
+    const float* points, const float* z_vals, const float* depth_fac, const float* sdf, const float* grad,
+    const float* feat, const float* v_pack, const float* dbias, const float* beta_param, const float* rgb_flat,
+    int n_rays, int n_samples, int rays_per_image, int n_images, int symmetric, float beta_min, float bgcolor, float normal_pow,
+    const float* G_rgb, const float* G_mask, const float* G_depth, const float* G_normal,
+    float* g_sdf, float* g_grad, float* g_feat, float* g_points, float* g_z, float* g_depth_fac, float* g_beta,
+    float* partial, float* v3_part, const float* rr, void* stream);
+int sc_rgb_composite_backward_fused_split_ns(
+    const float* points, const float* z_vals, const float* depth_fac, const float* sdf, const float* grad,
+    const float* feat, const float* v_pack, const float* dbias, const float* beta_param, const float* rgb_flat,
+    int n_rays, int n_samples, int rays_per_image, int n_images, int symmetric, float beta_min, float bgcolor, float normal_pow,
     const float* G_rgb, const float* G_mask, const float* G_depth, const float* G_normal,
     float* g_sdf, float* g_grad, float* g_feat, float* g_points, float* g_z, float* g_depth_fac, float* g_beta,
     float* partial, float* v3_part, const float* rr, void* stream);
@@ -305,7 +363,23 @@ int sc_ray_sample_backward_eik(const float* ray_dirs, const float* z_vals, const
                                const float* g_eik_points, int n_rays, int rays_per_image, int n_images, float cam_dist, float* g_cam_loc,
                                float* g_ray_dirs, float* g_scale_dist, void* stream);
 
-/* One render in a single call (Renderer.forward, model/renderer.py:57-152):
+/* The sampler pair at S samples per ray (SC_N_SAMPLES_SUPPORTED): u, z_vals, g_z_extra [n_rays][S], points [n_rays*S][3],
+ * eik_idx in [0, S).  Bit-identical to the torch op sequence of UniformSampler.get_z_vals at every S.                      */
+int sc_ray_sample_forward_ns(const float* cam_loc, const float* ray_dirs, const float* scale_dist, const float* u,
+                             int n_rays, int n_samples, int rays_per_image, int n_images, float cam_dist, float* z_vals,
+                             float* points, void* stream);
+int sc_ray_sample_backward_ns(const float* ray_dirs, const float* z_vals, const float* g_points,
+                              const float* g_z_extra, int n_rays, int n_samples, int rays_per_image, int n_images, float cam_dist,
+                              float* g_cam_loc, float* g_ray_dirs, float* g_scale_dist, void* stream);
+int sc_ray_sample_forward_eik_ns(const float* cam_loc, const float* ray_dirs, const float* scale_dist, const float* u, const long long* eik_idx,
+                                 const float* eik_uniform, int n_rays, int n_samples, int rays_per_image, int n_images, float cam_dist,
+                                 float* z_vals, float* points, float* eik_points, void* stream);
+int sc_ray_sample_backward_eik_ns(const float* ray_dirs, const float* z_vals, const float* g_points, const float* g_z_extra,
+                                  const long long* eik_idx, const float* g_eik_points, int n_rays, int n_samples, int rays_per_image,
+                                  int n_images, float cam_dist, float* g_cam_loc, float* g_ray_dirs, float* g_scale_dist, void* stream);
+
+/* One render in a single call (Renderer.forward, model/renderer.py:57-152), at 64 samples per ray (sc_render_forward and
+ * sc_render_backward take no sample count; other S go through the _ns entry points one by one):
  * sc_ray_sample_forward -> sc_sdf_forward -> sc_rgb_composite_forward.  z_vals, points, sdf, grad, feat and
  * scratch are caller-provided work buffers (sizes as in the three entry points).  Inference: stash_a = stash_p =
  * rgb_flat = NULL.  Training: pass stash_a (5 x TBL64), stash_p (4 x TBL64) and rgb_flat [P][3]; together with

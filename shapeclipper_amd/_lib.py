@@ -36,6 +36,11 @@ SYMBOLS = (
     "sc_linear_bn_supported", "sc_linear_bn_forward", "sc_linear_bn_backward", "sc_linear_backward_data",
     "sc_latent_bias_forward", "sc_latent_bias_backward", "sc_rgb_composite_backward_fused", "sc_rgb_composite_backward_fused_stash", "sc_rgb_composite_backward_fused_split", "sc_rgb_composite_forward_stash", "sc_rgb_composite_forward_split", "sc_rgb_composite_backward_fused_parts",
     "sc_rgb_composite_backward_fused_partial_floats",
+    # S != 64 samples per ray (SC_N_SAMPLES_SUPPORTED)
+    "sc_ray_sample_forward_ns", "sc_ray_sample_backward_ns", "sc_ray_sample_forward_eik_ns", "sc_ray_sample_backward_eik_ns",
+    "sc_rgb_composite_forward_ns", "sc_rgb_composite_forward_stash_ns", "sc_rgb_composite_forward_split_ns",
+    "sc_rgb_composite_backward_v3_ns", "sc_rgb_composite_backward_fused_ns", "sc_rgb_composite_backward_fused_stash_ns",
+    "sc_rgb_composite_backward_fused_split_ns",
 )
 # entry points that do not return an int status
 SYMBOLS_OTHER = ("sc_clip_cluster_pack_elems", "sc_render_backward_workspace_bytes", "sc_chamfer3d_grid_workspace_bytes", "sc_clip_vit_workspace_bytes", "sc_conv3x3_pack_floats", "sc_conv3x3_workspace_floats", "sc_conv3x3_wgrad_workspace_floats", "sc_conv3x3_pack_floats_split", "sc_conv3x3_workspace_floats_split", "sc_conv_stem_wgrad_workspace_floats", "sc_conv1x1s2_wgrad_workspace_floats", "sc_conv3x3s2_pack_floats", "sc_conv3x3s2_workspace_floats", "sc_conv3x3s2_bd_pack_floats", "sc_conv3x3s2_bd_workspace_floats")

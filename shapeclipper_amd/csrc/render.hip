@@ -1,7 +1,8 @@
 // render.hip -- ray sampling kernels and single-call orchestration of one render (C ABI level).
 //
 //   sc_ray_sample_forward / _backward : UniformSampler.get_z_vals + point generation
-//                                       (model/renderer.py:13-37, :84-86) and their adjoints
+//                                       (model/renderer.py:13-37, :84-86) and their adjoints; the _ns forms take any
+//                                       SC_N_SAMPLES_SUPPORTED sample count per ray
 //   sc_render_forward                 : sample -> sdf_fwd -> rgb_composite_fwd, i.e. Renderer.forward
 //                                       (model/renderer.py:57-152) for a host that does not want to
 //                                       sequence the kernels itself (evaluation / visualisation path)
@@ -91,6 +92,85 @@ __global__ __launch_bounds__(256) void ray_sample_bwd_kernel(const float* __rest
     }
 }
 
+// S != 64 samples per ray (a multiple of 32 up to 256): the ray is walked in chunks of 64 lanes, sample i = 64 c + lane.  The jitter
+// bounds need z of samples i - 1 and i + 1, which at a chunk edge live in another chunk: every lane evaluates its neighbours with the same
+// formula instead of a shuffle (same operations, same bits).
+__device__ __forceinline__ float ray_sample_z(int i, int S, float nearv, float farv) {
+    const float t = linspace01(i, S);
+    return __fadd_rn(__fmul_rn(nearv, __fsub_rn(1.0f, t)), __fmul_rn(farv, t));
+}
+
+__global__ __launch_bounds__(256) void ray_sample_ns_kernel(const float* __restrict__ cam_loc, const float* __restrict__ ray_dirs,
+                                                            const float* __restrict__ scale_dist, const float* __restrict__ u,
+                                                            int n_rays, int S, int rays_per_image, int n_images, float cam_dist,
+                                                            float* __restrict__ z_vals, float* __restrict__ points,
+                                                            const long long* __restrict__ eik_idx, const float* __restrict__ eik_uniform,
+                                                            float* __restrict__ eik_points) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    for (int ray = blockIdx.x * 4 + (threadIdx.x >> 6); ray < n_rays; ray += gridDim.x * 4) {
+        const int img = min(ray / rays_per_image, n_images - 1);
+        const float c = __fmul_rn(cam_dist, scale_dist[img]);
+        const float nearv = __fsub_rn(c, 0.7f), farv = __fadd_rn(c, 0.7f);
+        const int ei = eik_points ? (int)eik_idx[ray] : -1;
+        for (int i = lane; i < S; i += 64) {
+            float z = ray_sample_z(i, S, nearv, farv);
+            if (u) {   // stratified jitter inside [lower, upper] (renderer.py:24-30)
+                const float upper = i == S - 1 ? z : __fmul_rn(0.5f, __fadd_rn(ray_sample_z(i + 1, S, nearv, farv), z));
+                const float lower = i == 0 ? z : __fmul_rn(0.5f, __fadd_rn(z, ray_sample_z(i - 1, S, nearv, farv)));
+                z = __fadd_rn(lower, __fmul_rn(__fsub_rn(upper, lower), u[(size_t)ray * S + i]));
+            }
+            const size_t p = (size_t)ray * S + i;
+            z_vals[p] = z;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float v = __fadd_rn(cam_loc[(size_t)ray * 3 + k], __fmul_rn(z, ray_dirs[(size_t)ray * 3 + k]));
+                points[p * 3 + k] = v;
+                if (i == ei) eik_points[((size_t)(img * 2 + 1) * rays_per_image + (ray - img * rays_per_image)) * 3 + k] = v;
+            }
+        }
+        if (eik_points && lane < 3)
+            eik_points[((size_t)(img * 2) * rays_per_image + (ray - img * rays_per_image)) * 3 + lane] = eik_uniform[(size_t)ray * 3 + lane];
+    }
+}
+
+__global__ __launch_bounds__(256) void ray_sample_bwd_ns_kernel(const float* __restrict__ ray_dirs, const float* __restrict__ z_vals,
+                                                                const float* __restrict__ g_points, const float* __restrict__ g_z_extra,
+                                                                int n_rays, int S, int rays_per_image, int n_images, float cam_dist,
+                                                                float* __restrict__ g_cam_loc, float* __restrict__ g_ray_dirs,
+                                                                float* __restrict__ g_scale_dist, const long long* __restrict__ eik_idx,
+                                                                const float* __restrict__ g_eik_points) {
+    const int lane = threadIdx.x & 63;
+    for (int ray = blockIdx.x * 4 + (threadIdx.x >> 6); ray < n_rays; ray += gridDim.x * 4) {
+        const int ei = g_eik_points ? (int)eik_idx[ray] : -1;
+        const float d0 = ray_dirs[(size_t)ray * 3], d1 = ray_dirs[(size_t)ray * 3 + 1], d2 = ray_dirs[(size_t)ray * 3 + 2];
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, t0 = 0.f, t1 = 0.f, t2 = 0.f, gz = 0.f;     // this lane's share, over its samples
+        for (int i = lane; i < S; i += 64) {
+            const size_t p = (size_t)ray * S + i;
+            const float z = z_vals[p];
+            float g0 = g_points ? g_points[p * 3] : 0.f, g1 = g_points ? g_points[p * 3 + 1] : 0.f, g2 = g_points ? g_points[p * 3 + 2] : 0.f;
+            if (i == ei) {        // the near-surface eikonal point of this ray is this sample
+                const int img = min(ray / rays_per_image, n_images - 1);
+                const float* ge = g_eik_points + ((size_t)(img * 2 + 1) * rays_per_image + (ray - img * rays_per_image)) * 3;
+                g0 += ge[0]; g1 += ge[1]; g2 += ge[2];
+            }
+            gz += g0 * d0 + g1 * d1 + g2 * d2 + (g_z_extra ? g_z_extra[p] : 0.f);
+            s0 += g0; s1 += g1; s2 += g2;
+            t0 += z * g0; t1 += z * g1; t2 += z * g2;
+        }
+        for (int o = 32; o >= 1; o >>= 1) {
+            s0 += __shfl_xor(s0, o); s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o);
+            t0 += __shfl_xor(t0, o); t1 += __shfl_xor(t1, o); t2 += __shfl_xor(t2, o);
+            gz += __shfl_xor(gz, o);
+        }
+        if (lane == 0) {
+            g_cam_loc[(size_t)ray * 3] = s0; g_cam_loc[(size_t)ray * 3 + 1] = s1; g_cam_loc[(size_t)ray * 3 + 2] = s2;
+            g_ray_dirs[(size_t)ray * 3] = t0; g_ray_dirs[(size_t)ray * 3 + 1] = t1; g_ray_dirs[(size_t)ray * 3 + 2] = t2;
+            g_scale_dist[ray] = cam_dist * gz;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void grid_points_kernel(float lo, float hi, int n_axis, int n_images, float* __restrict__ points) {
     // torch.linspace(lo, hi, n_axis) with 'ij' meshgrid, repeated per image (eval_3D.py:9-18)
     const size_t per = (size_t)n_axis * n_axis * n_axis, total = per * n_images;
@@ -117,50 +197,88 @@ __global__ __launch_bounds__(256) void scale4_kernel(const float* __restrict__ G
 
 extern "C" {
 
-int sc_ray_sample_forward(const float* cam_loc, const float* ray_dirs, const float* scale_dist, const float* u, int n_rays,
-                          int rays_per_image, int n_images, float cam_dist, float* z_vals, float* points, void* stream_) {
+int sc_ray_sample_forward_ns(const float* cam_loc, const float* ray_dirs, const float* scale_dist, const float* u, int n_rays, int n_samples,
+                             int rays_per_image, int n_images, float cam_dist, float* z_vals, float* points, void* stream_) {
+    if (!SC_N_SAMPLES_SUPPORTED(n_samples)) return (int)hipErrorInvalidValue;
     if (n_rays <= 0) return 0;
     int blocks = (n_rays + 3) / 4;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(sc::ray_sample_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, cam_loc, ray_dirs, scale_dist, u,
-                       n_rays, rays_per_image, n_images, cam_dist, z_vals, points, (const long long*)nullptr, (const float*)nullptr, (float*)nullptr);
+    if (n_samples == 64)
+        hipLaunchKernelGGL(sc::ray_sample_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, cam_loc, ray_dirs, scale_dist, u,
+                           n_rays, rays_per_image, n_images, cam_dist, z_vals, points, (const long long*)nullptr, (const float*)nullptr, (float*)nullptr);
+    else
+        hipLaunchKernelGGL(sc::ray_sample_ns_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, cam_loc, ray_dirs, scale_dist, u,
+                           n_rays, n_samples, rays_per_image, n_images, cam_dist, z_vals, points, (const long long*)nullptr, (const float*)nullptr,
+                           (float*)nullptr);
+    return (int)hipGetLastError();
+}
+
+int sc_ray_sample_forward(const float* cam_loc, const float* ray_dirs, const float* scale_dist, const float* u, int n_rays,
+                          int rays_per_image, int n_images, float cam_dist, float* z_vals, float* points, void* stream_) {
+    return sc_ray_sample_forward_ns(cam_loc, ray_dirs, scale_dist, u, n_rays, 64, rays_per_image, n_images, cam_dist, z_vals, points, stream_);
+}
+
+int sc_ray_sample_forward_eik_ns(const float* cam_loc, const float* ray_dirs, const float* scale_dist, const float* u, const long long* eik_idx,
+                                 const float* eik_uniform, int n_rays, int n_samples, int rays_per_image, int n_images, float cam_dist,
+                                 float* z_vals, float* points, float* eik_points, void* stream_) {
+    if (!SC_N_SAMPLES_SUPPORTED(n_samples)) return (int)hipErrorInvalidValue;
+    if (n_rays <= 0) return 0;
+    if (!eik_idx || !eik_uniform || !eik_points || n_rays != rays_per_image * n_images) return (int)hipErrorInvalidValue;
+    int blocks = (n_rays + 3) / 4;
+    if (blocks > 2048) blocks = 2048;
+    if (n_samples == 64)
+        hipLaunchKernelGGL(sc::ray_sample_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, cam_loc, ray_dirs, scale_dist, u,
+                           n_rays, rays_per_image, n_images, cam_dist, z_vals, points, eik_idx, eik_uniform, eik_points);
+    else
+        hipLaunchKernelGGL(sc::ray_sample_ns_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, cam_loc, ray_dirs, scale_dist, u,
+                           n_rays, n_samples, rays_per_image, n_images, cam_dist, z_vals, points, eik_idx, eik_uniform, eik_points);
     return (int)hipGetLastError();
 }
 
 int sc_ray_sample_forward_eik(const float* cam_loc, const float* ray_dirs, const float* scale_dist, const float* u, const long long* eik_idx,
                               const float* eik_uniform, int n_rays, int rays_per_image, int n_images, float cam_dist, float* z_vals,
                               float* points, float* eik_points, void* stream_) {
+    return sc_ray_sample_forward_eik_ns(cam_loc, ray_dirs, scale_dist, u, eik_idx, eik_uniform, n_rays, 64, rays_per_image, n_images, cam_dist,
+                                        z_vals, points, eik_points, stream_);
+}
+
+int sc_ray_sample_backward_eik_ns(const float* ray_dirs, const float* z_vals, const float* g_points, const float* g_z_extra,
+                                  const long long* eik_idx, const float* g_eik_points, int n_rays, int n_samples, int rays_per_image,
+                                  int n_images, float cam_dist, float* g_cam_loc, float* g_ray_dirs, float* g_scale_dist, void* stream_) {
+    if (!SC_N_SAMPLES_SUPPORTED(n_samples)) return (int)hipErrorInvalidValue;
     if (n_rays <= 0) return 0;
-    if (!eik_idx || !eik_uniform || !eik_points || n_rays != rays_per_image * n_images) return (int)hipErrorInvalidValue;
+    if (g_eik_points && (!eik_idx || n_rays != rays_per_image * n_images)) return (int)hipErrorInvalidValue;
     int blocks = (n_rays + 3) / 4;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(sc::ray_sample_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, cam_loc, ray_dirs, scale_dist, u,
-                       n_rays, rays_per_image, n_images, cam_dist, z_vals, points, eik_idx, eik_uniform, eik_points);
+    if (n_samples == 64)
+        hipLaunchKernelGGL(sc::ray_sample_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, ray_dirs, z_vals, g_points,
+                           g_z_extra, n_rays, rays_per_image, n_images, cam_dist, g_cam_loc, g_ray_dirs, g_scale_dist, eik_idx, g_eik_points);
+    else
+        hipLaunchKernelGGL(sc::ray_sample_bwd_ns_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, ray_dirs, z_vals, g_points,
+                           g_z_extra, n_rays, n_samples, rays_per_image, n_images, cam_dist, g_cam_loc, g_ray_dirs, g_scale_dist, eik_idx,
+                           g_eik_points);
     return (int)hipGetLastError();
 }
 
 int sc_ray_sample_backward_eik(const float* ray_dirs, const float* z_vals, const float* g_points, const float* g_z_extra, const long long* eik_idx,
                                const float* g_eik_points, int n_rays, int rays_per_image, int n_images, float cam_dist, float* g_cam_loc,
                                float* g_ray_dirs, float* g_scale_dist, void* stream_) {
-    if (n_rays <= 0) return 0;
-    if (g_eik_points && (!eik_idx || n_rays != rays_per_image * n_images)) return (int)hipErrorInvalidValue;
-    int blocks = (n_rays + 3) / 4;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(sc::ray_sample_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, ray_dirs, z_vals, g_points,
-                       g_z_extra, n_rays, rays_per_image, n_images, cam_dist, g_cam_loc, g_ray_dirs, g_scale_dist, eik_idx, g_eik_points);
-    return (int)hipGetLastError();
+    return sc_ray_sample_backward_eik_ns(ray_dirs, z_vals, g_points, g_z_extra, eik_idx, g_eik_points, n_rays, 64, rays_per_image, n_images,
+                                         cam_dist, g_cam_loc, g_ray_dirs, g_scale_dist, stream_);
+}
+
+int sc_ray_sample_backward_ns(const float* ray_dirs, const float* z_vals, const float* g_points, const float* g_z_extra, int n_rays,
+                              int n_samples, int rays_per_image, int n_images, float cam_dist, float* g_cam_loc, float* g_ray_dirs,
+                              float* g_scale_dist, void* stream_) {
+    return sc_ray_sample_backward_eik_ns(ray_dirs, z_vals, g_points, g_z_extra, nullptr, nullptr, n_rays, n_samples, rays_per_image, n_images,
+                                         cam_dist, g_cam_loc, g_ray_dirs, g_scale_dist, stream_);
 }
 
 int sc_ray_sample_backward(const float* ray_dirs, const float* z_vals, const float* g_points, const float* g_z_extra, int n_rays,
                            int rays_per_image, int n_images, float cam_dist, float* g_cam_loc, float* g_ray_dirs,
                            float* g_scale_dist, void* stream_) {
-    if (n_rays <= 0) return 0;
-    int blocks = (n_rays + 3) / 4;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(sc::ray_sample_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, ray_dirs, z_vals, g_points,
-                       g_z_extra, n_rays, rays_per_image, n_images, cam_dist, g_cam_loc, g_ray_dirs, g_scale_dist, (const long long*)nullptr,
-                       (const float*)nullptr);
-    return (int)hipGetLastError();
+    return sc_ray_sample_backward_ns(ray_dirs, z_vals, g_points, g_z_extra, n_rays, 64, rays_per_image, n_images, cam_dist, g_cam_loc,
+                                     g_ray_dirs, g_scale_dist, stream_);
 }
 
 int sc_render_forward(const float* cam_loc, const float* ray_dirs, const float* depth_fac, const float* scale_dist,

@@ -11,9 +11,11 @@
 // Phase 2 (four 16-point MFMA tiles): recompute the RGB chain, run it in reverse
 //   (Gy2 -> V2^T -> Gy1 -> V1^T -> Gy0 -> V0f^T -> G feature, PE Jacobian -> G point) and leave
 //   Gy_l / r_l in HBM (TBL64) for the weight-gradient GEMMs (wgrad.hip).
+#include "../../include/shapeclipper_hip.h"
 #include "rgb_common.hpp"
 #include "mlp_xch.hpp"
 #include "mlp_presplit.hpp"
+#include <type_traits>
 
 namespace sc {
 
@@ -44,6 +46,47 @@ struct RgbBwdArgs {
                          // of gy3_j (= db3 [3]) and one zero -- fully written; their sum in index order (sc_partial_reduce) is the gradient of
                          // the output layer.  With it rr[2] and gy3 are NOT written (nobody else reads them): 280 MB less per launch.
 };
+// the arguments of the GEN instances (S != 64 samples per ray): the same and S; the S = 64 instances keep their argument block as it was
+struct RgbBwdArgsS : RgbBwdArgs {
+    int n_samples;
+};
+template <bool GEN> using RgbBwdArgsT = std::conditional_t<GEN, RgbBwdArgsS, RgbBwdArgs>;
+__device__ __forceinline__ int samples_per_ray(const RgbBwdArgs&) { return 64; }
+__device__ __forceinline__ int samples_per_ray(const RgbBwdArgsS& a) { return a.n_samples; }
+
+// Phase-1 quantities of one sample that need nothing but the sample and the exclusive prefix Ec of E over the chunks before this one
+// (GEN instances: sample 64 c + lane of the ray; lanes past its end read nothing and hold sigma = 0, so E = w = wn = 0).
+struct P1Sample {
+    float z, s, gx, gy, gz, c0, c1, c2, ex, sigma, kk, vnorm, n0, n1, n2, delta, E, emE, alpha, T, w, wn, sc;
+};
+template <class A>
+__device__ __forceinline__ void p1_sample(const A& a, int ray, int S, int c, int lane, float beta, float Ec, P1Sample& q) {
+    const int i = 64 * c + lane;
+    const bool valid = i < S;
+    const size_t sp = (size_t)ray * S + i;
+    q.z = valid ? a.z_vals[sp] : 0.f;
+    q.s = valid ? a.sdf[sp] : 0.f;
+    q.gx = valid ? a.grad[sp * 3 + 0] : 0.f; q.gy = valid ? a.grad[sp * 3 + 1] : 0.f; q.gz = valid ? a.grad[sp * 3 + 2] : 0.f;
+    q.c0 = valid ? a.rgb_flat[sp * 3 + 0] : 0.f; q.c1 = valid ? a.rgb_flat[sp * 3 + 1] : 0.f; q.c2 = valid ? a.rgb_flat[sp * 3 + 2] : 0.f;
+    q.ex = expf(-fabsf(q.s) / beta);
+    const float psi = q.s >= 0.f ? 0.5f * q.ex : 1.f - 0.5f * q.ex;
+    q.sigma = valid ? psi / beta : 0.f;
+    q.kk = (0.5f / (beta * beta)) * q.ex;
+    const float vx = q.kk * q.gx, vy = q.kk * q.gy, vz = q.kk * q.gz;
+    q.vnorm = sqrtf(vx * vx + vy * vy + vz * vz);
+    const float vden = fmaxf(q.vnorm, 1e-12f);
+    q.n0 = vx / vden; q.n1 = vy / vden; q.n2 = vz / vden;
+    float znext = __shfl_down(q.z, 1);
+    if (lane == 63 && i + 1 < S) znext = a.z_vals[sp + 1];             // first sample of the next chunk
+    q.delta = i + 1 < S ? znext - q.z : 0.f;
+    q.E = q.delta * q.sigma;
+    q.emE = expf(-q.E);
+    q.alpha = 1.f - q.emE;
+    q.sc = wave_inclusive_scan(q.E);
+    q.T = expf(-(Ec + (q.sc - q.E)));
+    q.w = q.alpha * q.T;
+    q.wn = !valid ? 0.f : (a.normal_pow == 1.f ? q.w : powf(q.w, a.normal_pow));
+}
 
 // FUSED (round 5): the weight gradients of V0, V1, V2 and the per-image bias gradients are formed INSIDE this kernel by
 // four more waves (the scheme of sdf_bwdw.hip: the chain waves drop each layer's operand pair -- Gy_l and the layer's input -- into a
@@ -88,8 +131,13 @@ __device__ int rgbb_prof_block = -1, rgbb_prof_iter = -1;
 // STASH (round 5, second half; FUSED only): the forward pass parked r0, r1, r2 (sc_rgb_composite_forward_stash) and they are LOADED here
 // instead of recomputed -- the phase profile (tools/prof_rgb_bwd.py) charges the recomputed forward chain 48 k of the chain wave's 155 k
 // cycles per ray; the colours come from rgb_flat, which phase 1 loads anyway.
-template <bool FUSED, bool STASH = false, bool SPLIT = false>
-__global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? 1 : 2) void rgb_composite_bwd_kernel(RgbBwdArgs a) {
+//
+// GEN (S != 64 samples per ray, a multiple of 32 up to 256): the ray is walked in chunks of 64 samples (4 tiles; the last chunk 2 when
+// S % 64 == 32).  No per-sample state of one chunk survives into the next: pass A1 recomputes E, T, w and forms the normal sums N; pass
+// A2 forms each chunk's total of the suffix quantity GC (at most four wave-uniform values); pass B runs phase 1 of a chunk with the
+// carried prefix of E and the suffix of GC, then phase 2 on its tiles, which are handed to the weight-gradient waves as at S = 64.
+template <bool FUSED, bool STASH = false, bool SPLIT = false, bool GEN = false>
+__global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? 1 : 2) void rgb_composite_bwd_kernel(RgbBwdArgsT<GEN> a) {
     static_assert(!SPLIT || (FUSED && STASH), "the split reverse chain exists for the fused form that reads the parked activations");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int XCH = SPLIT ? RBS_XCH : RB_XCH, PTS = XCH + RB_NBUF * RB_XSET, LDS_FLOATS = PTS + RB_NBUF * RB_PSET;
@@ -110,6 +158,7 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? 1 : 2) void rgb_composit
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int S = samples_per_ray(a), NTR = S >> 4;                                     // samples and 16-point tiles per ray
     const int n_iter = (a.n_rays + (int)gridDim.x * 4 - 1) / ((int)gridDim.x * 4);       // ray of (iteration, wave): (it * grid + block) * 4 + wave
     if (FUSED && wave >= 4) {
         // ================= weight-gradient role: wave 4 + w owns rows 16 w .. 16 w + 15 of dV0 [64][48 | 64], dV1, dV2 [64][64] =================
@@ -175,7 +224,7 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? 1 : 2) void rgb_composit
                 cur_img = img0 == img3 ? img0 : -2;
             }
 #pragma unroll 1
-            for (int k = 0; k < 4; ++k) {
+            for (int k = 0; k < NTR; ++k) {
                 RB_CONSUME(d2, d0e, false, 2)               // Gy2 x r1
                 RB_CONSUME(d1, d0e, false, 1)               // Gy1 x r0
                 RB_CONSUME(d0f, d0e, true, 0)               // Gy0 x (feature | E)
@@ -206,9 +255,9 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? 1 : 2) void rgb_composit
 // hand operand pair J (0, 1, 2) of tile k to the weight-gradient waves.  One set of slots: B1 (they have finished the previous pair),
 // write, B2 (visible).  Two sets: write into set (k + J) & 1, one barrier (see SC_RGBB_DB above).
 #define RB_SLOTS(J)                                                                          \
-        [[maybe_unused]] float* slotA = slot0 + (SC_RGBB_DB ? ((k + (J)) & 1) : 0) * RB_XSET; \
-        [[maybe_unused]] float* slotB = slotA + 1024;                                        \
-        [[maybe_unused]] float* ptsw = pts0 + (SC_RGBB_DB ? (k & 1) : 0) * RB_PSET;
+        [[maybe_unused]] float* slotA = slot0 + (SC_RGBB_DB ? ((kt + (J)) & 1) : 0) * RB_XSET; \
+        [[maybe_unused]] float* slotB = slotA + 1024;                                         \
+        [[maybe_unused]] float* ptsw = pts0 + (SC_RGBB_DB ? (kt & 1) : 0) * RB_PSET;
 #ifdef SC_RGBB_PROFILE
 #define RB_EXCHANGE(J, WRITES) if (FUSED) { RB_SLOTS(J) if (!SC_RGBB_DB) lds_barrier(); RB_STAMP(sid++) WRITES RB_STAMP(sid++) lds_barrier(); RB_STAMP(sid++) }
 #else
@@ -217,7 +266,8 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? 1 : 2) void rgb_composit
     const float bp = a.beta_param[0];
     const float beta = fabsf(bp) + a.beta_min;
     const float dbeta_dbp = bp > 0.f ? 1.f : (bp < 0.f ? -1.f : 0.f);
-    const size_t tbl = (size_t)a.n_rays * 4 * 1024;
+    const size_t tbl = (size_t)a.n_rays * NTR * 1024;
+    [[maybe_unused]] const int NCH = (S + 63) >> 6;
     float gbeta_acc = 0.f;
     float v3acc[3][ACT_STEPS], b3acc[3] = {0.f, 0.f, 0.f};     // this lane's share of dV3 (channels kp(s) + 4 g of its point column) and db3
 #pragma unroll
@@ -232,10 +282,11 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? 1 : 2) void rgb_composit
         int sid = 2;
 #endif
         RB_STAMP(0)
-        const int ray = (it * (int)gridDim.x + (int)blockIdx.x) * 4 + wave;
+        const int ray = GEN ? __builtin_amdgcn_readfirstlane((it * (int)gridDim.x + (int)blockIdx.x) * 4 + wave)     // GEN: a scalar, as are
+                            : (it * (int)gridDim.x + (int)blockIdx.x) * 4 + wave;                                   // its per-ray carries
         if (ray >= a.n_rays) {
             if (!FUSED) break;
-            for (int st = 0; st < 12; ++st) {               // tail: keep the barrier count of an iteration (4 tiles x 3 steps), feed zeros
+            for (int st = 0; st < 3 * NTR; ++st) {          // tail: keep the barrier count of an iteration (S / 16 tiles x 3 steps), feed zeros
                 if (!SC_RGBB_DB) lds_barrier();
                 if (st < RB_NBUF) {                         // every set is cleared at the hand-over that would write it (st = 3 k + J: set st & 1)
                     xch_zero(slot0 + st * RB_XSET, lane); xch_zero(slot0 + st * RB_XSET + 1024, lane);
@@ -249,12 +300,121 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? 1 : 2) void rgb_composit
         }
         const int img = min(ray / a.rays_per_image, a.n_images - 1);
         const float* db = a.dbias + (size_t)img * 192 + 4 * g;
+        float Gc0, Gc1, Gc2, c0, c1, c2;             // phase 1 -> phase 2: this lane's sample's colour and its gradient
+        // GEN: per-ray values (wave-uniform) carried across the chunks
+        [[maybe_unused]] float GN0, GN1, GN2, t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f, EcB, Gdp, Gdfac_acc;
+        // the per-ray upstream gradients, loaded where they are used (not carried through phase 2)
+        [[maybe_unused]] float Gr0, Gr1, Gr2, Gm, Gd, dfac;
+        [[maybe_unused]] auto load_ray_grads = [&]() {
+            Gr0 = a.G_rgb ? a.G_rgb[(size_t)ray * 3 + 0] : 0.f;
+            Gr1 = a.G_rgb ? a.G_rgb[(size_t)ray * 3 + 1] : 0.f;
+            Gr2 = a.G_rgb ? a.G_rgb[(size_t)ray * 3 + 2] : 0.f;
+            Gm = a.G_mask ? a.G_mask[ray] : 0.f;
+            Gd = a.G_depth ? a.G_depth[ray] : 0.f;
+            dfac = a.depth_fac[ray];
+        };
+        // dL/dw of a sample: the code of phase 1 below
+        [[maybe_unused]] auto rb_gw = [&](const P1Sample& q, float& gn_dot) {
+            gn_dot = GN0 * q.n0 + GN1 * q.n1 + GN2 * q.n2;
+            const float pw = a.normal_pow;
+            float Gw = (Gr0 * q.c0 + Gr1 * q.c1 + Gr2 * q.c2) - a.bgcolor * (Gr0 + Gr1 + Gr2) + Gm + Gd * q.z * dfac;
+            Gw += pw == 1.f ? gn_dot : (q.w > 0.f ? pw * powf(q.w, pw - 1.f) * gn_dot : 0.f);
+            return Gw;
+        };
+        if constexpr (GEN) {
+            // ---- pass A1: the normal sums N over the ray (E prefix carried from chunk to chunk) ----
+            float Ec = 0.f, N0 = 0.f, N1 = 0.f, N2 = 0.f;
+#pragma unroll 1
+            for (int c = 0; c < NCH; ++c) {
+                P1Sample q;
+                p1_sample(a, ray, S, c, lane, beta, Ec, q);
+                N0 = uniform_f(N0 + wave_sum(q.wn * q.n0)); N1 = uniform_f(N1 + wave_sum(q.wn * q.n1)); N2 = uniform_f(N2 + wave_sum(q.wn * q.n2));
+                Ec = uniform_f(Ec + __shfl(q.sc, 63));
+            }
+            load_ray_grads();
+            GN0 = 0.f, GN1 = 0.f, GN2 = 0.f;
+            if (a.G_normal) {
+                const float q0 = a.G_normal[(size_t)ray * 3 + 0], q1 = a.G_normal[(size_t)ray * 3 + 1], q2 = a.G_normal[(size_t)ray * 3 + 2];
+                const float nn = sqrtf(N0 * N0 + N1 * N1 + N2 * N2);
+                if (nn > 1e-12f) {   // F.normalize backward: (G - (G.n) n) / |N|
+                    const float o0 = N0 / nn, o1 = N1 / nn, o2 = N2 / nn;
+                    const float dt = q0 * o0 + q1 * o1 + q2 * o2;
+                    GN0 = (q0 - dt * o0) / nn; GN1 = (q1 - dt * o1) / nn; GN2 = (q2 - dt * o2) / nn;
+                } else {             // clamped branch: output = N / eps
+                    GN0 = q0 / 1e-12f; GN1 = q1 / 1e-12f; GN2 = q2 / 1e-12f;
+                }
+                GN0 = uniform_f(GN0); GN1 = uniform_f(GN1); GN2 = uniform_f(GN2);
+            }
+            // ---- pass A2: per chunk the total of GC = dL/dC (the suffix sums of phase 1 cross chunk edges); t_c = 0 past the last chunk ----
+            Ec = 0.f;
+#pragma unroll 1
+            for (int c = 0; c < NCH; ++c) {
+                P1Sample q;
+                p1_sample(a, ray, S, c, lane, beta, Ec, q);
+                float gn_dot;
+                const float Gw = rb_gw(q, gn_dot);
+                const float t = uniform_f(wave_sum(-(Gw * q.alpha) * q.T));
+                if (c == 0) t0 = t; else if (c == 1) t1 = t; else if (c == 2) t2 = t; else t3 = t;
+                Ec = uniform_f(Ec + __shfl(q.sc, 63));
+            }
+            EcB = 0.f, Gdp = 0.f, Gdfac_acc = 0.f;
+        }
+        for (int ch = 0; ch < (GEN ? NCH : 1); ++ch) {
+        if constexpr (GEN) {
+            // ---- pass B, phase 1 of chunk ch: the S = 64 code with the carries ----
+            P1Sample q;
+            p1_sample(a, ray, S, ch, lane, beta, EcB, q);
+            EcB = uniform_f(EcB + __shfl(q.sc, 63));
+            load_ray_grads();
+            const int i = 64 * ch + lane;
+            const bool valid = i < S;
+            const size_t sp = (size_t)ray * S + i;
+            c0 = q.c0; c1 = q.c1; c2 = q.c2;
+            Gc0 = q.w * Gr0, Gc1 = q.w * Gr1, Gc2 = q.w * Gr2;
+            float gn_dot;
+            const float Gw = rb_gw(q, gn_dot);
+            const float Gnh0 = q.wn * GN0, Gnh1 = q.wn * GN1, Gnh2 = q.wn * GN2;
+            const float Galpha = Gw * q.T;
+            const float GC = -(Gw * q.alpha) * q.T;
+            float suf = 0.f;                                 // GC over the chunks after this one, summed from the end
+            if (ch < 3) suf += t3;
+            if (ch < 2) suf += t2;
+            if (ch < 1) suf += t1;
+            const float GE = (wave_exclusive_suffix(GC) + suf) + Galpha * q.emE;
+            const float Gsigma = GE * q.delta;
+            const float Gdelta = GE * q.sigma;
+            float Gdelta_prev = __shfl_up(Gdelta, 1);
+            if (lane == 0) Gdelta_prev = Gdp;                 // the last sample of the chunk before
+            const float Gz = Gd * q.w * dfac - (i == S - 1 ? 0.f : Gdelta) + (i == 0 ? 0.f : Gdelta_prev);
+            Gdp = uniform_f(__shfl(Gdelta, 63));
+            Gdfac_acc = uniform_f(Gdfac_acc + wave_sum(Gd * q.w * q.z));
+            float Gv0, Gv1, Gv2;
+            if (q.vnorm > 1e-12f) {
+                const float dt = Gnh0 * q.n0 + Gnh1 * q.n1 + Gnh2 * q.n2;
+                Gv0 = (Gnh0 - dt * q.n0) / q.vnorm; Gv1 = (Gnh1 - dt * q.n1) / q.vnorm; Gv2 = (Gnh2 - dt * q.n2) / q.vnorm;
+            } else {
+                Gv0 = Gnh0 / 1e-12f; Gv1 = Gnh1 / 1e-12f; Gv2 = Gnh2 / 1e-12f;
+            }
+            const float Gkk = Gv0 * q.gx + Gv1 * q.gy + Gv2 * q.gz;
+            const float sgn = q.s >= 0.f ? 1.f : -1.f;
+            const float Gs = -Gsigma * q.kk - Gkk * sgn * q.kk / beta;
+            const float Gbeta = Gsigma * (-q.sigma / beta + 0.5f * q.ex * q.s / (beta * beta * beta))
+                              + Gkk * q.kk * (-2.f / beta + fabsf(q.s) / (beta * beta));
+            if (valid) {
+                gbeta_acc += Gbeta;
+                a.g_sdf[sp] = Gs;
+                a.g_grad[sp * 3 + 0] = q.kk * Gv0;
+                a.g_grad[sp * 3 + 1] = q.kk * Gv1;
+                a.g_grad[sp * 3 + 2] = q.kk * Gv2;
+                a.g_z[sp] = Gz;
+            }
+        } else {
         const size_t sp = (size_t)ray * 64 + lane;   // this lane's sample
         // ---------------- phase 1: compositing backward, lane == sample ----------------
         const float z = a.z_vals[sp];
         const float s = a.sdf[sp];
         const float gx = a.grad[sp * 3 + 0], gy_ = a.grad[sp * 3 + 1], gz = a.grad[sp * 3 + 2];
-        const float c0 = a.rgb_flat[sp * 3 + 0], c1 = a.rgb_flat[sp * 3 + 1], c2 = a.rgb_flat[sp * 3 + 2];
+        c0 = a.rgb_flat[sp * 3 + 0], c1 = a.rgb_flat[sp * 3 + 1], c2 = a.rgb_flat[sp * 3 + 2];
         const float dfac = a.depth_fac[ray];
         const float ex = expf(-fabsf(s) / beta);
         const float psi = s >= 0.f ? 0.5f * ex : 1.f - 0.5f * ex;
@@ -292,7 +452,7 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? 1 : 2) void rgb_composit
                 GN0 = q0 / 1e-12f; GN1 = q1 / 1e-12f; GN2 = q2 / 1e-12f;
             }
         }
-        const float Gc0 = w * Gr0, Gc1 = w * Gr1, Gc2 = w * Gr2;
+        Gc0 = w * Gr0, Gc1 = w * Gr1, Gc2 = w * Gr2;
         const float gn_dot = GN0 * n0 + GN1 * n1 + GN2 * n2;
         float Gw = (Gr0 * c0 + Gr1 * c1 + Gr2 * c2) - a.bgcolor * (Gr0 + Gr1 + Gr2) + Gm + Gd * z * dfac;
         Gw += pw == 1.f ? gn_dot : (w > 0.f ? pw * powf(w, pw - 1.f) * gn_dot : 0.f);
@@ -325,15 +485,17 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? 1 : 2) void rgb_composit
         a.g_grad[sp * 3 + 2] = kk * Gv2;
         a.g_z[sp] = Gz;
         if (lane == 0) a.g_depth_fac[ray] = Gdfac;
+        }
 
-        // ---------------- phase 2: RGB MLP reverse, four 16-point tiles ----------------
+        // ---------------- phase 2: RGB MLP reverse, four 16-point tiles (GEN: the chunk's) ----------------
         RB_STAMP(1)
 #pragma unroll 1
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < (GEN ? min(4, NTR - 4 * ch) : 4); ++k) {
 #ifdef SC_RGBB_PROFILE
             sid = 2 + 15 * k;
 #endif
-            const int tile = ray * 4 + k;
+            const int kt = 4 * ch + k;                       // tile of the ray
+            const int tile = ray * NTR + kt;
             const size_t pt = (size_t)tile * TP + p;
             const int src = 16 * k + p;
             const float gc0 = __shfl(Gc0, src), gc1 = __shfl(Gc1, src), gc2 = __shfl(Gc2, src);
@@ -437,6 +599,10 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? 1 : 2) void rgb_composit
             }
             if (g == 0) { a.g_points[pt * 3 + 0] = gxs[0]; a.g_points[pt * 3 + 1] = gxs[1]; a.g_points[pt * 3 + 2] = gxs[2]; }
         }
+        }
+        if constexpr (GEN) {
+            if (lane == 0) a.g_depth_fac[ray] = Gdfac_acc;
+        }
         RB_STAMP(62)
     }
     const float gb = wave_sum(gbeta_acc);
@@ -467,13 +633,28 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? 1 : 2) void rgb_composit
 
 }  // namespace sc
 
-extern "C" int sc_rgb_composite_backward_v3(
+namespace sc {
+// launch instance <FUSED, STASH, SPLIT> of the reverse kernel: the S = 64 one, or its GEN twin with the sample count in the arguments
+template <bool FUSED, bool STASH, bool SPLIT>
+static void launch_rgb_bwd(const RgbBwdArgs& a, int n_samples, int blocks, size_t lds_bytes, hipStream_t stream) {
+    auto go = [&](auto kernel, const auto& args) {
+        if (FUSED) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(FUSED ? 512 : 256), lds_bytes, stream, args);
+    };
+    if (n_samples == 64) go(rgb_composite_bwd_kernel<FUSED, STASH, SPLIT>, a);
+    else go(rgb_composite_bwd_kernel<FUSED, STASH, SPLIT, true>, RgbBwdArgsS{a, n_samples});
+}
+}  // namespace sc
+
+// n_samples: S per ray (SC_N_SAMPLES_SUPPORTED); g_z [n_rays][S]; 64 runs the S = 64 instances.
+extern "C" int sc_rgb_composite_backward_v3_ns(
     const float* points, const float* z_vals, const float* depth_fac, const float* sdf, const float* grad,
     const float* feat, const float* v_pack, const float* dbias, const float* beta_param, const float* rgb_flat,
-    int n_rays, int rays_per_image, int n_images, int symmetric, float beta_min, float bgcolor, float normal_pow,
+    int n_rays, int n_samples, int rays_per_image, int n_images, int symmetric, float beta_min, float bgcolor, float normal_pow,
     const float* G_rgb, const float* G_mask, const float* G_depth, const float* G_normal,
     float* g_sdf, float* g_grad, float* g_feat, float* g_points, float* g_z, float* g_depth_fac, float* g_beta,
     float* gy, float* rr, float* gy3, float* v3_part, void* stream_) {
+    if (!SC_N_SAMPLES_SUPPORTED(n_samples)) return (int)hipErrorInvalidValue;
     if (n_rays <= 0) return 0;
     sc::RgbBwdArgs a{points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta_param, rgb_flat,
                      n_rays, rays_per_image, n_images, symmetric, beta_min, bgcolor, normal_pow,
@@ -482,8 +663,20 @@ extern "C" int sc_rgb_composite_backward_v3(
     int blocks = (n_rays + 3) / 4;
     if (blocks > 512) blocks = 512;
     const size_t lds_bytes = sc::RgbLds::TOTAL * sizeof(float);
-    hipLaunchKernelGGL(sc::rgb_composite_bwd_kernel<false>, dim3(blocks), dim3(256), lds_bytes, (hipStream_t)stream_, a);
+    sc::launch_rgb_bwd<false, false, false>(a, n_samples, blocks, lds_bytes, (hipStream_t)stream_);
     return (int)hipGetLastError();
+}
+
+extern "C" int sc_rgb_composite_backward_v3(
+    const float* points, const float* z_vals, const float* depth_fac, const float* sdf, const float* grad,
+    const float* feat, const float* v_pack, const float* dbias, const float* beta_param, const float* rgb_flat,
+    int n_rays, int rays_per_image, int n_images, int symmetric, float beta_min, float bgcolor, float normal_pow,
+    const float* G_rgb, const float* G_mask, const float* G_depth, const float* G_normal,
+    float* g_sdf, float* g_grad, float* g_feat, float* g_points, float* g_z, float* g_depth_fac, float* g_beta,
+    float* gy, float* rr, float* gy3, float* v3_part, void* stream_) {
+    return sc_rgb_composite_backward_v3_ns(points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta_param, rgb_flat, n_rays, 64, rays_per_image,
+                                           n_images, symmetric, beta_min, bgcolor, normal_pow, G_rgb, G_mask, G_depth, G_normal, g_sdf, g_grad,
+                                           g_feat, g_points, g_z, g_depth_fac, g_beta, gy, rr, gy3, v3_part, stream_);
 }
 
 // Workgroups (= partial images) of sc_rgb_composite_backward_fused for n_rays, and floats per partial image.
@@ -495,6 +688,40 @@ extern "C" int sc_rgb_composite_backward_fused_partial_floats(int n_images) { re
 
 // The same reverse pass with the gradients of V0, V1, V2 and of the per-image biases formed in the kernel (no gy / rr hand-off tensors):
 // partial [parts][partial_floats(n_images)] receives one image per workgroup, fully written; v3_part as in the _v3 form (required).
+// rr: null (the forward chain is recomputed), or the activations the forward parked (STASH); split: the reverse chain in bf16x3 pieces.
+static int rgb_bwd_fused(
+    const float* points, const float* z_vals, const float* depth_fac, const float* sdf, const float* grad,
+    const float* feat, const float* v_pack, const float* dbias, const float* beta_param, const float* rgb_flat,
+    int n_rays, int n_samples, int rays_per_image, int n_images, int symmetric, float beta_min, float bgcolor, float normal_pow,
+    const float* G_rgb, const float* G_mask, const float* G_depth, const float* G_normal,
+    float* g_sdf, float* g_grad, float* g_feat, float* g_points, float* g_z, float* g_depth_fac, float* g_beta,
+    float* partial, float* v3_part, const float* rr, bool split, void* stream_) {
+    if (!SC_N_SAMPLES_SUPPORTED(n_samples)) return (int)hipErrorInvalidValue;
+    if (n_rays <= 0) return 0;
+    if (!partial || !v3_part || n_images <= 0 || n_images > 256) return (int)hipErrorInvalidValue;
+    sc::RgbBwdArgs a{points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta_param, rgb_flat,
+                     n_rays, rays_per_image, n_images, symmetric, beta_min, bgcolor, normal_pow,
+                     G_rgb, G_mask, G_depth, G_normal, g_sdf, g_grad, g_feat, g_points, g_z, g_depth_fac, g_beta,
+                     nullptr, const_cast<float*>(rr), nullptr, partial, sc_rgb_composite_backward_fused_partial_floats(n_images), v3_part};
+    const int blocks = sc_rgb_composite_backward_fused_parts(n_rays);
+    const hipStream_t stream = (hipStream_t)stream_;
+    if (split) sc::launch_rgb_bwd<true, true, true>(a, n_samples, blocks, (size_t)sc::RBS_LDS_FLOATS * sizeof(float), stream);
+    else if (rr) sc::launch_rgb_bwd<true, true, false>(a, n_samples, blocks, (size_t)sc::RB_LDS_FLOATS * sizeof(float), stream);
+    else sc::launch_rgb_bwd<true, false, false>(a, n_samples, blocks, (size_t)sc::RB_LDS_FLOATS * sizeof(float), stream);
+    return (int)hipGetLastError();
+}
+
+extern "C" int sc_rgb_composite_backward_fused_ns(
+    const float* points, const float* z_vals, const float* depth_fac, const float* sdf, const float* grad,
+    const float* feat, const float* v_pack, const float* dbias, const float* beta_param, const float* rgb_flat,
+    int n_rays, int n_samples, int rays_per_image, int n_images, int symmetric, float beta_min, float bgcolor, float normal_pow,
+    const float* G_rgb, const float* G_mask, const float* G_depth, const float* G_normal,
+    float* g_sdf, float* g_grad, float* g_feat, float* g_points, float* g_z, float* g_depth_fac, float* g_beta,
+    float* partial, float* v3_part, void* stream_) {
+    return rgb_bwd_fused(points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta_param, rgb_flat, n_rays, n_samples, rays_per_image,
+                                           n_images, symmetric, beta_min, bgcolor, normal_pow, G_rgb, G_mask, G_depth, G_normal, g_sdf, g_grad,
+                                           g_feat, g_points, g_z, g_depth_fac, g_beta, partial, v3_part, nullptr, false, stream_);
+}
 extern "C" int sc_rgb_composite_backward_fused(
     const float* points, const float* z_vals, const float* depth_fac, const float* sdf, const float* grad,
     const float* feat, const float* v_pack, const float* dbias, const float* beta_param, const float* rgb_flat,
@@ -502,21 +729,25 @@ extern "C" int sc_rgb_composite_backward_fused(
     const float* G_rgb, const float* G_mask, const float* G_depth, const float* G_normal,
     float* g_sdf, float* g_grad, float* g_feat, float* g_points, float* g_z, float* g_depth_fac, float* g_beta,
     float* partial, float* v3_part, void* stream_) {
-    if (n_rays <= 0) return 0;
-    if (!partial || !v3_part || n_images <= 0 || n_images > 256) return (int)hipErrorInvalidValue;
-    sc::RgbBwdArgs a{points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta_param, rgb_flat,
-                     n_rays, rays_per_image, n_images, symmetric, beta_min, bgcolor, normal_pow,
-                     G_rgb, G_mask, G_depth, G_normal, g_sdf, g_grad, g_feat, g_points, g_z, g_depth_fac, g_beta,
-                     nullptr, nullptr, nullptr, partial, sc_rgb_composite_backward_fused_partial_floats(n_images), v3_part};
-    const int blocks = sc_rgb_composite_backward_fused_parts(n_rays);
-    const size_t lds_bytes = (size_t)sc::RB_LDS_FLOATS * sizeof(float);
-    (void)hipFuncSetAttribute((const void*)sc::rgb_composite_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL(sc::rgb_composite_bwd_kernel<true>, dim3(blocks), dim3(512), lds_bytes, (hipStream_t)stream_, a);
-    return (int)hipGetLastError();
+    return sc_rgb_composite_backward_fused_ns(points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta_param, rgb_flat, n_rays, 64, rays_per_image,
+                                           n_images, symmetric, beta_min, bgcolor, normal_pow, G_rgb, G_mask, G_depth, G_normal, g_sdf, g_grad,
+                                           g_feat, g_points, g_z, g_depth_fac, g_beta, partial, v3_part, stream_);
 }
 
 // sc_rgb_composite_backward_fused with the hidden activations of the forward pass (rr: what sc_rgb_composite_forward_stash wrote) instead of
 // their recomputation.  Everything else as above.
+extern "C" int sc_rgb_composite_backward_fused_stash_ns(
+    const float* points, const float* z_vals, const float* depth_fac, const float* sdf, const float* grad,
+    const float* feat, const float* v_pack, const float* dbias, const float* beta_param, const float* rgb_flat,
+    int n_rays, int n_samples, int rays_per_image, int n_images, int symmetric, float beta_min, float bgcolor, float normal_pow,
+    const float* G_rgb, const float* G_mask, const float* G_depth, const float* G_normal,
+    float* g_sdf, float* g_grad, float* g_feat, float* g_points, float* g_z, float* g_depth_fac, float* g_beta,
+    float* partial, float* v3_part, const float* rr, void* stream_) {
+    if (!rr) return (int)hipErrorInvalidValue;
+    return rgb_bwd_fused(points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta_param, rgb_flat, n_rays, n_samples, rays_per_image,
+                                           n_images, symmetric, beta_min, bgcolor, normal_pow, G_rgb, G_mask, G_depth, G_normal, g_sdf, g_grad,
+                                           g_feat, g_points, g_z, g_depth_fac, g_beta, partial, v3_part, rr, false, stream_);
+}
 extern "C" int sc_rgb_composite_backward_fused_stash(
     const float* points, const float* z_vals, const float* depth_fac, const float* sdf, const float* grad,
     const float* feat, const float* v_pack, const float* dbias, const float* beta_param, const float* rgb_flat,
@@ -524,21 +755,25 @@ extern "C" int sc_rgb_composite_backward_fused_stash(
     const float* G_rgb, const float* G_mask, const float* G_depth, const float* G_normal,
     float* g_sdf, float* g_grad, float* g_feat, float* g_points, float* g_z, float* g_depth_fac, float* g_beta,
     float* partial, float* v3_part, const float* rr, void* stream_) {
-    if (n_rays <= 0) return 0;
-    if (!partial || !v3_part || !rr || n_images <= 0 || n_images > 256) return (int)hipErrorInvalidValue;
-    sc::RgbBwdArgs a{points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta_param, rgb_flat,
-                     n_rays, rays_per_image, n_images, symmetric, beta_min, bgcolor, normal_pow,
-                     G_rgb, G_mask, G_depth, G_normal, g_sdf, g_grad, g_feat, g_points, g_z, g_depth_fac, g_beta,
-                     nullptr, const_cast<float*>(rr), nullptr, partial, sc_rgb_composite_backward_fused_partial_floats(n_images), v3_part};
-    const int blocks = sc_rgb_composite_backward_fused_parts(n_rays);
-    const size_t lds_bytes = (size_t)sc::RB_LDS_FLOATS * sizeof(float);
-    (void)hipFuncSetAttribute((const void*)sc::rgb_composite_bwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL((sc::rgb_composite_bwd_kernel<true, true>), dim3(blocks), dim3(512), lds_bytes, (hipStream_t)stream_, a);
-    return (int)hipGetLastError();
+    return sc_rgb_composite_backward_fused_stash_ns(points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta_param, rgb_flat, n_rays, 64, rays_per_image,
+                                           n_images, symmetric, beta_min, bgcolor, normal_pow, G_rgb, G_mask, G_depth, G_normal, g_sdf, g_grad,
+                                           g_feat, g_points, g_z, g_depth_fac, g_beta, partial, v3_part, rr, stream_);
 }
 
 // sc_rgb_composite_backward_fused_stash with the reverse chain's transposed products and the encoding's Jacobian in the exact bf16x3 split
 // arithmetic from pre-split fragments (round 6; same operands and outputs, gradients equal up to fp32 rounding).
+extern "C" int sc_rgb_composite_backward_fused_split_ns(
+    const float* points, const float* z_vals, const float* depth_fac, const float* sdf, const float* grad,
+    const float* feat, const float* v_pack, const float* dbias, const float* beta_param, const float* rgb_flat,
+    int n_rays, int n_samples, int rays_per_image, int n_images, int symmetric, float beta_min, float bgcolor, float normal_pow,
+    const float* G_rgb, const float* G_mask, const float* G_depth, const float* G_normal,
+    float* g_sdf, float* g_grad, float* g_feat, float* g_points, float* g_z, float* g_depth_fac, float* g_beta,
+    float* partial, float* v3_part, const float* rr, void* stream_) {
+    if (!rr) return (int)hipErrorInvalidValue;
+    return rgb_bwd_fused(points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta_param, rgb_flat, n_rays, n_samples, rays_per_image,
+                                           n_images, symmetric, beta_min, bgcolor, normal_pow, G_rgb, G_mask, G_depth, G_normal, g_sdf, g_grad,
+                                           g_feat, g_points, g_z, g_depth_fac, g_beta, partial, v3_part, rr, true, stream_);
+}
 extern "C" int sc_rgb_composite_backward_fused_split(
     const float* points, const float* z_vals, const float* depth_fac, const float* sdf, const float* grad,
     const float* feat, const float* v_pack, const float* dbias, const float* beta_param, const float* rgb_flat,
@@ -546,17 +781,9 @@ extern "C" int sc_rgb_composite_backward_fused_split(
     const float* G_rgb, const float* G_mask, const float* G_depth, const float* G_normal,
     float* g_sdf, float* g_grad, float* g_feat, float* g_points, float* g_z, float* g_depth_fac, float* g_beta,
     float* partial, float* v3_part, const float* rr, void* stream_) {
-    if (n_rays <= 0) return 0;
-    if (!partial || !v3_part || !rr || n_images <= 0 || n_images > 256) return (int)hipErrorInvalidValue;
-    sc::RgbBwdArgs a{points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta_param, rgb_flat,
-                     n_rays, rays_per_image, n_images, symmetric, beta_min, bgcolor, normal_pow,
-                     G_rgb, G_mask, G_depth, G_normal, g_sdf, g_grad, g_feat, g_points, g_z, g_depth_fac, g_beta,
-                     nullptr, const_cast<float*>(rr), nullptr, partial, sc_rgb_composite_backward_fused_partial_floats(n_images), v3_part};
-    const int blocks = sc_rgb_composite_backward_fused_parts(n_rays);
-    const size_t lds_bytes = (size_t)sc::RBS_LDS_FLOATS * sizeof(float);
-    (void)hipFuncSetAttribute((const void*)sc::rgb_composite_bwd_kernel<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL((sc::rgb_composite_bwd_kernel<true, true, true>), dim3(blocks), dim3(512), lds_bytes, (hipStream_t)stream_, a);
-    return (int)hipGetLastError();
+    return sc_rgb_composite_backward_fused_split_ns(points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta_param, rgb_flat, n_rays, 64, rays_per_image,
+                                           n_images, symmetric, beta_min, bgcolor, normal_pow, G_rgb, G_mask, G_depth, G_normal, g_sdf, g_grad,
+                                           g_feat, g_points, g_z, g_depth_fac, g_beta, partial, v3_part, rr, stream_);
 }
 
 extern "C" int sc_rgb_composite_backward(

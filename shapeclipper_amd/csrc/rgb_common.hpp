@@ -52,6 +52,9 @@ __device__ __forceinline__ void rgb_chain(const RgbLanePtrs& L, const float* db,
     }
 }
 
+// a wave-uniform value (a per-ray carry of the chunked S != 64 passes) moved to a scalar register
+__device__ __forceinline__ float uniform_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);

@@ -48,10 +48,11 @@ class SdfFunction(torch.autograd.Function):
 class RgbCompositeFunction(torch.autograd.Function):
     """Per-point SDF results -> per-ray render outputs (reference model/renderer.py:110-152,187-209).
 
-    inputs : points [P,3], z_vals [n_rays,64], depth_fac [n_rays], sdf [P], grad [P,3], feat TBL64,
+    inputs : points [P,3], z_vals [n_rays,S], depth_fac [n_rays], sdf [P], grad [P,3], feat TBL64,
              v_pack, dbias [B,3,64], beta (raw parameter, shape [1] or [])
     outputs: rgb [n_rays,3], mask [n_rays], mask_hard [n_rays], depth [n_rays], normal [n_rays,3]
-             (+ weights, alpha [n_rays,64], rgb_flat [P,3] when keep_samples; non-differentiable)"""
+             (+ weights, alpha [n_rays,S], rgb_flat [P,3] when keep_samples; non-differentiable)
+    S = z_vals.shape[1] samples per ray, P = n_rays * S; S must pass ops.sample_count_supported."""
 
     @staticmethod
     def forward(ctx, points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta, rays_per_image, symmetric,
@@ -116,14 +117,16 @@ class FusedRenderLoss(torch.autograd.Function):
 
 
 class RaySampleFunction(torch.autograd.Function):
-    """cam_loc, ray_dirs [n_rays,3], scale_dist [B], u [n_rays,64] | None -> z_vals [n_rays,64], points [n_rays*64,3]
-    (UniformSampler.get_z_vals + point generation, reference model/renderer.py:13-37,84-86) with a hand-written adjoint."""
+    """cam_loc, ray_dirs [n_rays,3], scale_dist [B], u [n_rays,S] | None -> z_vals [n_rays,S], points [n_rays*S,3]
+    (UniformSampler.get_z_vals + point generation, reference model/renderer.py:13-37,84-86) with a hand-written adjoint.
+    S = n_samples (default 64; u's second dimension when u is given)."""
 
     @staticmethod
-    def forward(ctx, cam_loc, ray_dirs, scale_dist, u, rays_per_image, cam_dist):
+    def forward(ctx, cam_loc, ray_dirs, scale_dist, u, rays_per_image, cam_dist, n_samples=64):
         ctx.set_materialize_grads(False)
         cam_loc, ray_dirs, scale_dist = cam_loc.contiguous(), ray_dirs.contiguous(), scale_dist.contiguous()
-        z, pts = ops.ray_sample_forward(cam_loc, ray_dirs, scale_dist, u, rays_per_image, cam_dist)
+        z, pts = ops.ray_sample_forward(cam_loc, ray_dirs, scale_dist, u, rays_per_image, cam_dist,
+                                        n_samples=u.shape[1] if u is not None else n_samples)
         ctx.save_for_backward(ray_dirs, z)
         ctx.meta = (rays_per_image, scale_dist.shape[0], cam_dist)
         return z, pts
@@ -136,12 +139,12 @@ class RaySampleFunction(torch.autograd.Function):
             g_points = torch.zeros(z.numel(), 3, device=z.device)
         g_o, g_d, g_sd = ops.ray_sample_backward(ray_dirs, z, g_points.contiguous(), g_z.contiguous() if g_z is not None else None,
                                                  rpi, n_images, cam_dist)
-        return g_o, g_d, g_sd, None, None, None
+        return g_o, g_d, g_sd, None, None, None, None
 
 
 class RaySampleEikFunction(torch.autograd.Function):
     """RaySampleFunction + the eikonal sample points of a training render (reference model/renderer.py:154-165) in the same two launches:
-    -> z_vals [n_rays,64], points [n_rays*64,3], eik_points [B, 2 R, 3] (uniform block | near-surface block).  The near point of a ray is its
+    -> z_vals [n_rays,S], points [n_rays*S,3], eik_points [B, 2 R, 3] (uniform block | near-surface block); S = u.shape[1].  The near point of a ray is its
     sample eik_idx -- no gather of z, no second evaluation of cam_loc + z * ray_dir, and in backward no scatter into a dense z gradient
     (round 5: ~15 stock launches per render)."""
 

@@ -1,10 +1,11 @@
 """Stock PyTorch-ROCm path for implicit-network configurations OUTSIDE the family the HIP chain kernels are compiled for.
 
 The hand-written kernels (csrc/sdf_fwd.hip, sdf_bwdw.hip, rgb_fwd.hip, rgb_bwd.hip) keep a whole network's weights in the 160 KiB of LDS
-of a compute unit: 5 x 64 SDF layers + 3 x 64 RGB layers, 6 octaves, 64 samples per ray, and every smaller member by zero padding
-(packing.check_arch).  The rest of the reference's configuration space (model/implicit.py:93-113,199-214: any n_hidden_layers, n_channels,
-pos_enc, skip_connection; model/renderer.py:13-37: any n_samples_uniform) does not fit that structure -- 128 channels are 320 KiB of
-weights.  Like the convolutions of shapes the trunk kernels do not take, those configurations run here on stock
+of a compute unit: 5 x 64 SDF layers + 3 x 64 RGB layers, 6 octaves, and every smaller member by zero padding (packing.check_arch); the
+render kernels (csrc/render.hip, rgb_fwd.hip, rgb_bwd.hip) walk a ray in chunks of 64 samples and take any n_samples_uniform that is a
+multiple of 32 from 32 to 256 (renderer.sample_count_supported).  The rest of the reference's configuration space (model/implicit.py:
+93-113,199-214: any n_hidden_layers, n_channels, pos_enc, skip_connection; model/renderer.py:13-37: other n_samples_uniform) does not fit
+that structure -- 128 channels are 320 KiB of weights.  Like the convolutions of shapes the trunk kernels do not take, those configurations run here on stock
 device operators and torch autograd (incl. the create_graph double backward), so a reference user's YAML with another architecture trains
 and evaluates instead of raising.  NOT a CPU fallback and not used by the shipped configuration: tensors must be on a ROCm device, and a
 one-line warning says which path is taken and why.
@@ -28,7 +29,7 @@ def warn_once(what: str):
     if what not in _WARNED:
         _WARNED.add(what)
         warnings.warn("shapeclipper_amd: %s -- outside the family of the HIP chain kernels (5x64 SDF / 3x64 RGB layers, pos_enc <= 6, skip "
-                      "within [1, 2], 64 samples per ray): this configuration runs on stock PyTorch-ROCm operators (model/eager_path.py), "
+                      "within [1, 2], a multiple of 32 from 32 to 256 samples per ray): this configuration runs on stock PyTorch-ROCm operators (model/eager_path.py), "
                       "several times slower than the compiled family" % what, stacklevel=3)
 
 

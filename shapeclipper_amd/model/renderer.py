@@ -19,9 +19,16 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as torch_F
 
+from .. import ops
 from ..functional import CameraRaysFunction, RaySampleEikFunction, RaySampleFunction, RgbCompositeFunction, SdfFunction
 from ..utils import camera
 from .implicit import LaplaceDensity
+
+
+def sample_count_supported(n_samples) -> bool:
+    """render.n_samples_uniform values the HIP render kernels take: multiples of 32 from 32 to 256 (1 to 4 chunks of 64 samples per
+    ray).  Any other value renders on model/eager_path.py."""
+    return ops.sample_count_supported(n_samples)
 
 
 
@@ -83,12 +90,14 @@ class Renderer(nn.Module):
             raise NotImplementedError("only render.normal_model=volume is implemented (the shipped setting)")
         self.ray_sampler = UniformSampler(opt)
         self.N_samples = opt.render.n_samples_uniform
-        # The compositing kernel maps the 64 samples of a ray onto one 64-lane wavefront and the chain kernels hold one architecture family
-        # in LDS: any other render.n_samples_uniform / arch.impl_* runs on stock device operators (model/eager_path.py, round 5).
-        self.eager = bool(getattr(sdf_network, "eager", False) or getattr(rgb_network, "eager", False) or self.N_samples != 64)
+        # The render kernels walk a ray in chunks of 64 samples (one 64-lane wavefront per ray) and the chain kernels hold one architecture
+        # family in LDS: a render.n_samples_uniform outside sample_count_supported or other arch.impl_* run on stock device operators
+        # (model/eager_path.py, round 5).
+        supported = sample_count_supported(self.N_samples)
+        self.eager = bool(getattr(sdf_network, "eager", False) or getattr(rgb_network, "eager", False) or not supported)
         if self.eager:
             from . import eager_path
-            eager_path.warn_once("render.n_samples_uniform = %d" % self.N_samples if self.N_samples != 64 else "implicit networks")
+            eager_path.warn_once("render.n_samples_uniform = %d" % self.N_samples if not supported else "implicit networks")
             sdf_network.eager = rgb_network.eager = True          # one path for the whole render (the HIP kernels hand TBL64 features to each other)
 
     def forward(self, opt, pose, intr, scale_dist, proj_latent_sdf, proj_latent_rgb, ray_idx=None, training=True,
@@ -136,7 +145,7 @@ class Renderer(nn.Module):
             eik_u = up(torch.empty(B * R, 3, device=rdev, pin_memory=pin).uniform_(self.eik_range[0], self.eik_range[1]))
             z_vals, points_flat, eik_points = RaySampleEikFunction.apply(cam_loc, ray_dirs, scale_dist, t_rand, eik_idx, eik_u, R, float(opt.camera.dist))
         else:
-            z_vals, points_flat = RaySampleFunction.apply(cam_loc, ray_dirs, scale_dist, t_rand, R, float(opt.camera.dist))
+            z_vals, points_flat = RaySampleFunction.apply(cam_loc, ray_dirs, scale_dist, t_rand, R, float(opt.camera.dist), S)
             z_eik = torch.gather(z_vals, 1, eik_idx.unsqueeze(-1))
         assert proj_latent_rgb.shape[1] == opt.arch.impl_rgb.proj_latent_dim
 

@@ -94,34 +94,49 @@ def rgb_composite_forward(points, z_vals, depth_fac, sdf, grad, feat, v_pack, db
                           normal_pow: float, keep_samples: bool = False, keep_rgb_flat: bool = False, keep_rr: bool = False):
     """Per-ray outputs of the renderer from the per-point SDF results.
 
-    points [n_rays*64,3], z_vals [n_rays,64], depth_fac [n_rays], sdf [P], grad [P,3], feat TBL64.
+    points [n_rays*S,3], z_vals [n_rays,S], depth_fac [n_rays], sdf [P], grad [P,3], feat TBL64 (P = n_rays*S,
+    S = samples per ray, sample_count_supported(S)).
     Returns dict(rgb [n_rays,3], mask, mask_hard, depth [n_rays], normal [n_rays,3]
-    [, weights, alpha [n_rays,64], rgb_flat [P,3]])."""
+    [, weights, alpha [n_rays,S], rgb_flat [P,3]])."""
     lib = _lib.load()
-    n_rays = z_vals.shape[0]
-    assert z_vals.shape[1] == 64, "the compositing kernel maps one 64-lane wavefront to the 64 samples of a ray"
+    n_rays, S = z_vals.shape
+    if not sample_count_supported(S):
+        raise ValueError("shapeclipper_amd: the compositing kernels take S %% 32 == 0, 32 <= S <= 256 samples per ray, not %d" % S)
     dev = points.device
     f32 = dict(device=dev, dtype=torch.float32)
     out = dict(rgb=torch.empty(n_rays, 3, **f32), mask=torch.empty(n_rays, **f32),
                mask_hard=torch.empty(n_rays, **f32), depth=torch.empty(n_rays, **f32),
                normal=torch.empty(n_rays, 3, **f32))
     if keep_samples:
-        out.update(weights=torch.empty(n_rays, 64, **f32), alpha=torch.empty(n_rays, 64, **f32))
+        out.update(weights=torch.empty(n_rays, S, **f32), alpha=torch.empty(n_rays, S, **f32))
     if keep_samples or keep_rgb_flat:
-        out.update(rgb_flat=torch.empty(n_rays * 64, 3, **f32))
-    if keep_rr:      # the hidden activations r0, r1, r2 (3 x TBL64) for rgb_composite_backward(rr=...): 805 MB per bs32 render
-        out.update(rr=torch.empty(3 * n_rays * 4 * 1024, **f32))
+        out.update(rgb_flat=torch.empty(n_rays * S, 3, **f32))
+    if keep_rr:      # the hidden activations r0, r1, r2 (3 x TBL64) for rgb_composite_backward(rr=...): 805 MB per bs32 render at S = 64
+        out.update(rr=torch.empty(3 * n_rays * (S // 16) * 1024, **f32))
     # round 6: the RGB network from pre-split bf16x3 weight fragments (csrc/rgb_fwd.hip, `--hip.rgb_split!` keeps the fp32-MFMA chain)
-    fwd = lib.sc_rgb_composite_forward_split if RGB_FWD_SPLIT else lib.sc_rgb_composite_forward_stash
+    name = "sc_rgb_composite_forward_split" if RGB_FWD_SPLIT else "sc_rgb_composite_forward_stash"
+    fwd, ns = _entry(lib, name, S)
     code = fwd(
         _lib.ptr(points), _lib.ptr(z_vals), _lib.ptr(depth_fac), _lib.ptr(sdf), _lib.ptr(grad), _lib.ptr(feat),
-        _lib.ptr(v_pack), _lib.ptr(dbias), _lib.ptr(beta_param), c_int(n_rays), c_int(rays_per_image),
+        _lib.ptr(v_pack), _lib.ptr(dbias), _lib.ptr(beta_param), c_int(n_rays), *ns, c_int(rays_per_image),
         c_int(dbias.shape[0]), c_int(1 if symmetric else 0), ctypes.c_float(beta_min), ctypes.c_float(bgcolor),
         ctypes.c_float(normal_pow), _lib.ptr(out["rgb"]), _lib.ptr(out["mask"]), _lib.ptr(out["mask_hard"]),
         _lib.ptr(out["depth"]), _lib.ptr(out["normal"]), _lib.ptr(out.get("weights")), _lib.ptr(out.get("alpha")),
         _lib.ptr(out.get("rgb_flat")), _lib.ptr(out.get("rr")), _lib.stream())
-    _lib.check(code, "sc_rgb_composite_forward_split" if RGB_FWD_SPLIT else "sc_rgb_composite_forward_stash")
+    _lib.check(code, name)
     return out
+
+
+def _entry(lib, name, S):
+    """The entry point `name` for S samples per ray and the sample-count argument it takes after n_rays: S = 64 calls the symbol
+    without the count (the kernels of the default, and the names bench.py and profiles know), any other S its _ns twin."""
+    return (getattr(lib, name), ()) if S == 64 else (getattr(lib, name + "_ns"), (c_int(S),))
+
+
+def sample_count_supported(n_samples: int) -> bool:
+    """Samples per ray the render kernels take (SC_N_SAMPLES_SUPPORTED): a multiple of 32 in [32, 256] -- 1 to 4 chunks of 64 samples
+    per ray, the last one possibly half a wave.  Pure host logic."""
+    return isinstance(n_samples, int) and 32 <= n_samples <= 256 and n_samples % 32 == 0
 
 
 # operand transform codes of sc_wgrad (csrc/wgrad.hip)
@@ -325,14 +340,14 @@ def rgb_composite_backward(points, z_vals, depth_fac, sdf, grad, feat, v_pack, d
     -> dict(points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta) gradients."""
     from .packing import RGB_OFF, RGB_PACK_FLOATS
     lib = _lib.load()
-    n_rays = z_vals.shape[0]
+    n_rays, S = z_vals.shape
     n_images = dbias.shape[0]
-    P = n_rays * 64
-    T = n_rays * 4 * 1024
+    P = n_rays * S
+    T = n_rays * (S // 16) * 1024
     dev = points.device
     f32 = dict(device=dev, dtype=torch.float32)
     g = dict(sdf=torch.empty(P, **f32), grad=torch.empty(P, 3, **f32), feat=torch.empty(T, **f32),
-             points=torch.empty(P, 3, **f32), z_vals=torch.empty(n_rays, 64, **f32),
+             points=torch.empty(P, 3, **f32), z_vals=torch.empty(n_rays, S, **f32),
              depth_fac=torch.empty(n_rays, **f32), beta=torch.empty(RGB_BWD_BETA_PARTS, **f32))
     v3_part = torch.empty(RGB_BWD_BETA_PARTS * 196, **f32)     # per-wave partial sums of dV3 [3][64] | db3 [3] | 0
     if FUSED_RGB_WGRAD and n_images <= 256:
@@ -342,18 +357,19 @@ def rgb_composite_backward(points, z_vals, depth_fac, sdf, grad, feat, v_pack, d
         stride = int(lib.sc_rgb_composite_backward_fused_partial_floats(c_int(n_images)))
         partial = torch.empty(parts * stride, **f32)
         args = (_lib.ptr(points), _lib.ptr(z_vals), _lib.ptr(depth_fac), _lib.ptr(sdf), _lib.ptr(grad), _lib.ptr(feat),
-                _lib.ptr(v_pack), _lib.ptr(dbias), _lib.ptr(beta_param), _lib.ptr(rgb_flat), c_int(n_rays),
+                _lib.ptr(v_pack), _lib.ptr(dbias), _lib.ptr(beta_param), _lib.ptr(rgb_flat), c_int(n_rays), *_entry(lib, "sc_rgb_composite_backward_fused", S)[1],
                 c_int(rays_per_image), c_int(n_images), c_int(1 if symmetric else 0), ctypes.c_float(beta_min),
                 ctypes.c_float(bgcolor), ctypes.c_float(normal_pow), _lib.ptr(G_rgb), _lib.ptr(G_mask), _lib.ptr(G_depth),
                 _lib.ptr(G_normal), _lib.ptr(g["sdf"]), _lib.ptr(g["grad"]), _lib.ptr(g["feat"]), _lib.ptr(g["points"]),
                 _lib.ptr(g["z_vals"]), _lib.ptr(g["depth_fac"]), _lib.ptr(g["beta"]), _lib.ptr(partial), _lib.ptr(v3_part))
         if rr is not None:      # the forward parked r0..r2: no recomputation of the forward chain
             if RGB_BWD_SPLIT:      # round 6: the reverse chain's transposed products from pre-split bf16x3 fragments (`--hip.rgb_bwd_split!`: fp32 MFMA)
-                _lib.check(lib.sc_rgb_composite_backward_fused_split(*args, _lib.ptr(rr), _lib.stream()), "sc_rgb_composite_backward_fused_split")
+                name, tail = "sc_rgb_composite_backward_fused_split", (_lib.ptr(rr),)
             else:
-                _lib.check(lib.sc_rgb_composite_backward_fused_stash(*args, _lib.ptr(rr), _lib.stream()), "sc_rgb_composite_backward_fused_stash")
+                name, tail = "sc_rgb_composite_backward_fused_stash", (_lib.ptr(rr),)
         else:
-            _lib.check(lib.sc_rgb_composite_backward_fused(*args, _lib.stream()), "sc_rgb_composite_backward_fused")
+            name, tail = "sc_rgb_composite_backward_fused", ()
+        _lib.check(_entry(lib, name, S)[0](*args, *tail, _lib.stream()), name)
         g_all = _partial_reduce(lib, partial, parts, stride, stride, torch.empty(stride, **f32))
         g_v = torch.empty(RGB_PACK_FLOATS, **f32)
         g_v[:RGB_OFF["V3"]] = g_all[:RGB_OFF["V3"]]
@@ -365,9 +381,10 @@ def rgb_composite_backward(points, z_vals, depth_fac, sdf, grad, feat, v_pack, d
         return g
     gy = torch.empty(3 * T, **f32)
     rr = torch.empty(2 * T, **f32)         # r0, r1 (operands of dV1 / dV2); r2 and gy3 only feed the output layer's gradient, formed in the kernel:
-    code = lib.sc_rgb_composite_backward_v3(
+    bwd, ns = _entry(lib, "sc_rgb_composite_backward_v3", S)
+    code = bwd(
         _lib.ptr(points), _lib.ptr(z_vals), _lib.ptr(depth_fac), _lib.ptr(sdf), _lib.ptr(grad), _lib.ptr(feat),
-        _lib.ptr(v_pack), _lib.ptr(dbias), _lib.ptr(beta_param), _lib.ptr(rgb_flat), c_int(n_rays),
+        _lib.ptr(v_pack), _lib.ptr(dbias), _lib.ptr(beta_param), _lib.ptr(rgb_flat), c_int(n_rays), *ns,
         c_int(rays_per_image), c_int(n_images), c_int(1 if symmetric else 0), ctypes.c_float(beta_min),
         ctypes.c_float(bgcolor), ctypes.c_float(normal_pow), _lib.ptr(G_rgb), _lib.ptr(G_mask), _lib.ptr(G_depth),
         _lib.ptr(G_normal), _lib.ptr(g["sdf"]), _lib.ptr(g["grad"]), _lib.ptr(g["feat"]), _lib.ptr(g["points"]),
@@ -381,7 +398,7 @@ def rgb_composite_backward(points, z_vals, depth_fac, sdf, grad, feat, v_pack, d
     partial = torch.empty(WGRAD_PARTS * stride, **f32)
     common = (points, None, None, P, symmetric)
     # per-image sums of Gy_l (gradient of the per-image biases d_l) are produced by the launch that streams Gy_l
-    npi = rays_per_image * 64
+    npi = rays_per_image * S
     g_d3 = torch.empty(3, n_images, 64, **f32)
     rs = lambda l: (g_d3[l], npi, n_images)
     # V0 = [PE 48 | sdf feature 64]: one launch (Gy0 is streamed once, 7 N tiles)
@@ -425,29 +442,32 @@ def loss_fused_forward(rgb, rgb_t, mask, mask_t, normal, normal_t, eik, normal_l
     return out[:4], (g_rgb, g_mask, g_normal, g_eik, g_normal_t)
 
 
-def ray_sample_forward(cam_loc, ray_dirs, scale_dist, u, rays_per_image, cam_dist):
-    """-> z_vals [n_rays,64], points [n_rays*64,3]  (u = None: evaluation linspace)."""
+def ray_sample_forward(cam_loc, ray_dirs, scale_dist, u, rays_per_image, cam_dist, n_samples=64):
+    """-> z_vals [n_rays,S], points [n_rays*S,3]  (u [n_rays,S], or None: evaluation linspace; S = n_samples)."""
     lib = _lib.load()
-    n_rays = ray_dirs.shape[0]
-    z = torch.empty(n_rays, 64, device=ray_dirs.device, dtype=torch.float32)
-    pts = torch.empty(n_rays * 64, 3, device=ray_dirs.device, dtype=torch.float32)
-    code = lib.sc_ray_sample_forward(_lib.ptr(cam_loc), _lib.ptr(ray_dirs), _lib.ptr(scale_dist), _lib.ptr(u), c_int(n_rays),
-                                     c_int(rays_per_image), c_int(scale_dist.shape[0]), ctypes.c_float(cam_dist),
-                                     _lib.ptr(z), _lib.ptr(pts), _lib.stream())
+    n_rays, S = ray_dirs.shape[0], int(n_samples)
+    assert u is None or tuple(u.shape) == (n_rays, S), (None if u is None else tuple(u.shape), n_rays, S)
+    z = torch.empty(n_rays, S, device=ray_dirs.device, dtype=torch.float32)
+    pts = torch.empty(n_rays * S, 3, device=ray_dirs.device, dtype=torch.float32)
+    fn, ns = _entry(lib, "sc_ray_sample_forward", S)
+    code = fn(_lib.ptr(cam_loc), _lib.ptr(ray_dirs), _lib.ptr(scale_dist), _lib.ptr(u), c_int(n_rays), *ns, c_int(rays_per_image),
+              c_int(scale_dist.shape[0]), ctypes.c_float(cam_dist), _lib.ptr(z), _lib.ptr(pts), _lib.stream())
     _lib.check(code, "sc_ray_sample_forward")
     return z, pts
 
 
-def ray_sample_forward_eik(cam_loc, ray_dirs, scale_dist, u, eik_idx, eik_uniform, rays_per_image, cam_dist):
+def ray_sample_forward_eik(cam_loc, ray_dirs, scale_dist, u, eik_idx, eik_uniform, rays_per_image, cam_dist, n_samples=64):
     """ray_sample_forward + the eikonal sample points of the render [B, 2 R, 3] (uniform block | near-surface block) in the same launch."""
     lib = _lib.load()
     n_rays, B = ray_dirs.shape[0], scale_dist.shape[0]
-    z = torch.empty(n_rays, 64, device=ray_dirs.device, dtype=torch.float32)
-    pts = torch.empty(n_rays * 64, 3, device=ray_dirs.device, dtype=torch.float32)
+    S = u.shape[1] if u is not None else int(n_samples)
+    z = torch.empty(n_rays, S, device=ray_dirs.device, dtype=torch.float32)
+    pts = torch.empty(n_rays * S, 3, device=ray_dirs.device, dtype=torch.float32)
     eik = torch.empty(B, 2 * rays_per_image, 3, device=ray_dirs.device, dtype=torch.float32)
-    code = lib.sc_ray_sample_forward_eik(_lib.ptr(cam_loc), _lib.ptr(ray_dirs), _lib.ptr(scale_dist), _lib.ptr(u), _lib.ptr(eik_idx), _lib.ptr(eik_uniform),
-                                         c_int(n_rays), c_int(rays_per_image), c_int(B), ctypes.c_float(cam_dist), _lib.ptr(z), _lib.ptr(pts),
-                                         _lib.ptr(eik), _lib.stream())
+    fn, ns = _entry(lib, "sc_ray_sample_forward_eik", S)
+    code = fn(_lib.ptr(cam_loc), _lib.ptr(ray_dirs), _lib.ptr(scale_dist), _lib.ptr(u), _lib.ptr(eik_idx), _lib.ptr(eik_uniform),
+              c_int(n_rays), *ns, c_int(rays_per_image), c_int(B), ctypes.c_float(cam_dist), _lib.ptr(z), _lib.ptr(pts), _lib.ptr(eik),
+              _lib.stream())
     _lib.check(code, "sc_ray_sample_forward_eik")
     return z, pts, eik
 
@@ -459,9 +479,9 @@ def ray_sample_backward_eik(ray_dirs, z_vals, g_points, g_z, eik_idx, g_eik, ray
     g_o = torch.empty(n_rays, 3, device=dev, dtype=torch.float32)
     g_d = torch.empty(n_rays, 3, device=dev, dtype=torch.float32)
     g_sd = torch.empty(n_rays, device=dev, dtype=torch.float32)
-    code = lib.sc_ray_sample_backward_eik(_lib.ptr(ray_dirs), _lib.ptr(z_vals), _lib.ptr(g_points), _lib.ptr(g_z), _lib.ptr(eik_idx), _lib.ptr(g_eik),
-                                          c_int(n_rays), c_int(rays_per_image), c_int(n_images), ctypes.c_float(cam_dist), _lib.ptr(g_o),
-                                          _lib.ptr(g_d), _lib.ptr(g_sd), _lib.stream())
+    fn, ns = _entry(lib, "sc_ray_sample_backward_eik", z_vals.shape[1])
+    code = fn(_lib.ptr(ray_dirs), _lib.ptr(z_vals), _lib.ptr(g_points), _lib.ptr(g_z), _lib.ptr(eik_idx), _lib.ptr(g_eik), c_int(n_rays), *ns,
+              c_int(rays_per_image), c_int(n_images), ctypes.c_float(cam_dist), _lib.ptr(g_o), _lib.ptr(g_d), _lib.ptr(g_sd), _lib.stream())
     _lib.check(code, "sc_ray_sample_backward_eik")
     return g_o, g_d, g_sd.view(n_images, rays_per_image).sum(dim=1)
 
@@ -473,9 +493,9 @@ def ray_sample_backward(ray_dirs, z_vals, g_points, g_z, rays_per_image, n_image
     g_o = torch.empty(n_rays, 3, device=dev, dtype=torch.float32)
     g_d = torch.empty(n_rays, 3, device=dev, dtype=torch.float32)
     g_sd = torch.empty(n_rays, device=dev, dtype=torch.float32)
-    code = lib.sc_ray_sample_backward(_lib.ptr(ray_dirs), _lib.ptr(z_vals), _lib.ptr(g_points), _lib.ptr(g_z), c_int(n_rays),
-                                      c_int(rays_per_image), c_int(n_images), ctypes.c_float(cam_dist), _lib.ptr(g_o),
-                                      _lib.ptr(g_d), _lib.ptr(g_sd), _lib.stream())
+    fn, ns = _entry(lib, "sc_ray_sample_backward", z_vals.shape[1])
+    code = fn(_lib.ptr(ray_dirs), _lib.ptr(z_vals), _lib.ptr(g_points), _lib.ptr(g_z), c_int(n_rays), *ns, c_int(rays_per_image),
+              c_int(n_images), ctypes.c_float(cam_dist), _lib.ptr(g_o), _lib.ptr(g_d), _lib.ptr(g_sd), _lib.stream())
     _lib.check(code, "sc_ray_sample_backward")
     return g_o, g_d, g_sd.view(n_images, rays_per_image).sum(dim=1)
 
