@@ -11,11 +11,18 @@ HIP training renders of 512 rays x 64 samples per image incl. the eikonal branch
 backward (hand-written HIP backward kernels) -> one flat RCCL all-reduce of all gradients (N > 1) ->
 Adam.  Batch = 32 images per GPU (BASELINE.json configs[1]/[2]/[3]; weak scaling).
 
-One JSON line on rank 0; see the repository prompt for the contract.  Extras:
+One JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints
+the line; besides the headline it only reports what the timed region recorded anyway:
   roofline      dominant hand-written kernel: achieved = algorithmic FLOPs / mean
                 launch duration measured with events on the launch stream inside the timed region
-  cpu_baseline  the CPU oracle (pure PyTorch restatement of the reference, oracle/reference_ops.py) timed
-                on this box's host cores on a bounded sample (hot path only)
+Everything that takes runs of its own is measured with --full only:
+  sustained               further steps after the K-step region
+  fp32_mfma_convolutions  the same step with --hip.conv3x3_split! (N = 1)
+  config1_bs16            BASELINE config[1]: the step at bs16 on a runner of its own (N = 1, bs32)
+  allreduce               the flat gradient all-reduce timed alone (N > 1)
+  cpu_baseline            the CPU oracle (pure PyTorch restatement of the reference, oracle/reference_ops.py) timed
+                          on the host cores on a bounded sample (hot path only; N = 1)
+  workloads               the other SURVEY 8(d) workloads (tools/workloads.py; N = 1)
 """
 import argparse
 import json
@@ -51,21 +58,34 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-batch", type=int, default=0, help="images of the CPU baseline step (0: 8 of the batch: 1 warm-up + 3 timed steps inside ~30 s)")
-    ap.add_argument("--sustained", type=int, default=200, help="extra steps timed after the K-step region (0: off)")
-    ap.add_argument("--no-workloads", action="store_true", help="skip the other SURVEY 8(d) workloads (tools/workloads.py)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline that takes runs of its own (module "
+                    "docstring); a plain run does only what the headline needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-batch", type=int, default=0, help="--full: images of the CPU baseline step (0: 8 of the batch: 1 warm-up + 3 timed "
+                    "steps inside ~30 s)")
+    ap.add_argument("--sustained", type=int, default=None, help="--full: extra steps timed after the K-step region (default 200, 0: off)")
+    ap.add_argument("--no-workloads", action="store_true", help="--full: skip the other SURVEY 8(d) workloads (tools/workloads.py)")
     ap.add_argument("--with-reference-gpu", action="store_true", help="Chamfer workloads: also time the reference's own extension built for "
                     "gfx950 (oracle/_ref; maps a binary built from the reference's sources into this process -- off by default)")
     ap.add_argument("--workloads-only", action="store_true", help="only those workloads (the rocprofv3 command of profiles/)")
-    ap.add_argument("--no-alt", action="store_true", help="skip the second measurement with --hip.conv3x3_split! (fp32-MFMA convolutions)")
-    ap.add_argument("--alt-steps", type=int, default=60)
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the second measurement with --hip.conv3x3_split! (fp32-MFMA "
+                    "convolutions) and the bs16 leg")
+    ap.add_argument("--alt-steps", type=int, default=None, help="--full: timed steps of those two (default 60)")
     ap.add_argument("--opt", action="append", default=[], help="extra option override(s), e.g. --opt=--hip.fused_backward!")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (losses, the forward's "
                     "outputs, a fixed sample of the weights, buffers and gradients after it) as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    # a measurement a plain run does not make is asked for: refuse rather than print a line without it
+    if not a.full and not a.workloads_only:
+        asked = [flag for flag, v in (("--sustained", a.sustained), ("--alt-steps", a.alt_steps), ("--cpu-batch", a.cpu_batch),
+                                      ("--with-reference-gpu", a.with_reference_gpu)) if v]
+        if asked:
+            ap.error("%s: measured with --full only" % ", ".join(asked))
+    if a.sustained is None:
+        a.sustained = 200 if a.full else 0
+    a.alt_steps = 60 if a.alt_steps is None else a.alt_steps
     return a
 
 
@@ -447,7 +467,7 @@ def main():
     alt = None
     from shapeclipper_amd.model import resnet
     split_default = bool(resnet.HIP_CONV3X3_SPLIT)
-    if world == 1 and not a.no_alt and split_default:
+    if a.full and world == 1 and not a.no_alt and split_default:
         resnet.HIP_CONV3X3_SPLIT = False
         try:
             for _ in range(5):
@@ -467,7 +487,7 @@ def main():
     # step is GPU-bound at this size too (2 ms less host work per step did not move it: DESIGN.md section 6); what does not shrink with the
     # batch is the fixed part of every launch (~33 us per convolution outside its K loop), which is what the object says.
     config1 = None
-    if world == 1 and not a.no_alt and a.batch == 32:
+    if a.full and world == 1 and not a.no_alt and a.batch == 32:
         import gc
         r16, o16, b16 = build_runner(16, rank, local, world, a.opt)
         from shapeclipper_amd.utils.util import EasyDict as _ed
@@ -490,7 +510,7 @@ def main():
         gc.collect()
         torch.cuda.empty_cache()
     allreduce = None
-    if world > 1 and runner.reducer is not None:      # the step's only exchange: one flat all-reduce
+    if a.full and world > 1 and runner.reducer is not None:      # the step's only exchange: one flat all-reduce
         flat = runner.reducer.flat
         for _ in range(2):
             torch.distributed.all_reduce(flat)
@@ -546,9 +566,9 @@ def main():
             out["config1_bs16"] = config1
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if not a.no_cpu_baseline and world == 1:      # reported at N = 1 only (the other ranks must not wait for rank 0)
+        if a.full and not a.no_cpu_baseline and world == 1:      # reported at N = 1 only (the other ranks must not wait for rank 0)
             out["cpu_baseline"] = _guarded(lambda: cpu_baseline(a.cpu_batch or a.batch, explicit=bool(a.cpu_batch)))
-        if not a.no_workloads and world == 1:
+        if a.full and not a.no_workloads and world == 1:
             out["workloads"] = _guarded(lambda: _workloads().run_all(with_cpu=not a.no_cpu_baseline, with_reference_gpu=a.with_reference_gpu))
         print(json.dumps(out))
     if world > 1:

@@ -1,5 +1,6 @@
-"""bench.py prints ONE JSON line with the driver's contract fields plus `roofline`, `sustained` and (with the CPU legs switched
-off here for speed) no `cpu_baseline`; `--workloads-only` prints the other SURVEY 8(d) workloads."""
+"""bench.py prints ONE JSON line with the driver's contract fields plus `roofline`; a plain run measures nothing else, `--full` adds
+`sustained` and the other secondary objects (with the CPU legs switched off here for speed: no `cpu_baseline`); `--workloads-only` prints
+the other SURVEY 8(d) workloads."""
 import json
 import os
 import subprocess
@@ -19,7 +20,7 @@ def _last_json(out):
 
 def test_bench_line_contract():
     env = dict(os.environ, MIOPEN_LOG_LEVEL="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2", "--sustained", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2", "--full", "--sustained", "2",
                         "--alt-steps", "2", "--no-cpu-baseline", "--no-workloads"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -38,6 +39,24 @@ def test_bench_line_contract():
     assert abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3 and rf["peak"] == 157.3
     assert d["sustained"]["steps"] == 2 and d["sustained"]["ms_per_step"] > 0
     assert "sc_sdf_forward" in d["hip_ms_per_step"] and "sc_rgb_composite_backward" in d["hip_ms_per_step"]
+
+
+def test_bench_plain_run_measures_only_the_headline():
+    """`bench.py --steps K --warmup W` without --full, at the headline batch: the contract fields and what the timed region recorded,
+    none of the secondary measurements that take runs of their own."""
+    env = dict(os.environ, MIOPEN_LOG_LEVEL="1")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len([l for l in r.stdout.splitlines() if l.startswith("{")]) == 1
+    d = _last_json(r.stdout)
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["config"]["global_batch"] == 32
+    assert d["metric"] == "train-step images/sec (Pix3D cfg, bs32/GPU)" and d["unit"] == "images/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32 (bf16x3-split MFMA, fp32 accumulate)" and abs(d["value"] - 32 / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
+    assert d["roofline"]["kernel"] == "sc_sdf_backward_fused" and "sc_sdf_forward" in d["hip_ms_per_step"]
+    assert d["sustained"] is None
+    for k in ("fp32_mfma_convolutions", "config1_bs16", "allreduce", "cpu_baseline", "workloads"):
+        assert k not in d, k
 
 
 def test_bench_dump_outputs_are_reproducible(tmp_path):
@@ -68,7 +87,7 @@ def test_bench_dump_outputs_are_reproducible(tmp_path):
 def test_bench_default_batch_reports_config1_beside_the_headline():
     """At the headline batch (bs32) the line also carries BASELINE config[1] (bs16 on one GPU) as a secondary object; contract keys unchanged."""
     env = dict(os.environ, MIOPEN_LOG_LEVEL="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--sustained", "0", "--alt-steps", "3",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--sustained", "0", "--alt-steps", "3",
                         "--no-cpu-baseline", "--no-workloads"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -87,7 +106,7 @@ def test_bench_two_ranks_through_the_launcher():
     env = dict(os.environ, MIOPEN_LOG_LEVEL="1", SC_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--sustained", "2"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--full", "--sustained", "2"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     assert len([l for l in r.stdout.splitlines() if l.startswith("{")]) == 1
     d = _last_json(r.stdout)
@@ -104,7 +123,7 @@ def test_bench_self_launches_its_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MIOPEN_LOG_LEVEL="1", SC_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--sustained", "0", "--opt=--hip.reserve_cus=16"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--full", "--sustained", "0", "--opt=--hip.reserve_cus=16"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     assert len([l for l in r.stdout.splitlines() if l.startswith("{")]) == 1
     d = _last_json(r.stdout)
@@ -160,7 +179,7 @@ def test_bench_eight_ranks_config3_code_path():
     env = dict(os.environ, MIOPEN_LOG_LEVEL="1", SC_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--batch", "1",
-                        "--sustained", "0"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
+                        "--full", "--sustained", "0"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     assert len([l for l in r.stdout.splitlines() if l.startswith("{")]) == 1
     d = _last_json(r.stdout)

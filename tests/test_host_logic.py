@@ -423,6 +423,29 @@ def test_bench_dump_outputs_writes_the_step_and_samples_at_fixed_positions(tmp_p
             assert bench.parse().steps == 3 and bench.parse().dump_outputs is None
 
 
+def test_bench_plain_and_full_options(monkeypatch):
+    """A plain `bench.py` run times no extra steps; `--full` turns the secondary measurements on with their defaults, and an option that
+    asks for one of them without `--full` is refused instead of being dropped."""
+    import sys
+    bench = _load_bench()
+
+    def parse(*args):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + list(args))
+        return bench.parse()
+    a = parse("--gpus", "1", "--steps", "5", "--warmup", "2")
+    assert not a.full and a.sustained == 0
+    a = parse("--full")
+    assert a.full and a.sustained == 200 and a.alt_steps == 60 and a.cpu_batch == 0
+    a = parse("--full", "--sustained", "0", "--alt-steps", "3", "--cpu-batch", "4")
+    assert a.sustained == 0 and a.alt_steps == 3 and a.cpu_batch == 4
+    a = parse("--sustained", "0", "--no-alt", "--no-cpu-baseline", "--no-workloads")        # switching extras off is harmless
+    assert not a.full and a.sustained == 0
+    assert parse("--workloads-only", "--with-reference-gpu").with_reference_gpu
+    for extra in (["--sustained", "2"], ["--alt-steps", "3"], ["--cpu-batch", "4"], ["--with-reference-gpu"]):
+        with pytest.raises(SystemExit):
+            parse(*extra)
+
+
 def test_gpu_suite_runs_parity_tests_before_subprocess_tests():
     """VERDICT r05 #1c: the driver runs `pytest -m gpu -x`; a timing-dependent subprocess test must never stand in front of a kernel-vs-oracle
     test.  Every test_gpu_*.py file is placed by tests/conftest.py::suite_order_key; files that launch other processes sort last."""

@@ -31,6 +31,6 @@ python tools/summarize_pmc.py $(find /tmp/p_sq -name "*counter_collection.csv" |
 grep "^{" $O/bench_under_rocprof.log | tail -1 > $O/bench_line_under_rocprof.json; rm -f $O/bench_under_rocprof.log
 grep "^{" $O/workloads_under_rocprof.log | tail -1 > $O/workloads_line_under_rocprof.json; rm -f $O/workloads_under_rocprof.log
 bash tools/prof_clip_pmc.sh > /dev/null 2>&1; cp gpurun_out/clip_pmc/pmc_clip_sq.txt $O/pmc_clip_sq.txt 2>/dev/null
-timeout 900 python bench.py > $O/bench_full.log 2>&1
+timeout 900 python bench.py --full > $O/bench_full.log 2>&1
 grep "^{" $O/bench_full.log | tail -1 > $O/bench_line.json; rm -f $O/bench_full.log
 cat $O/gputest.log; cat $O/overlap_1rank.txt; head -c 600 $O/bench_line.json; du -sh $O

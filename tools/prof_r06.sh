@@ -23,6 +23,6 @@ python tools/make_traffic_json.py $O/pmc_fetch_size.txt $O/pmc_write_size.txt > 
 grep "^{" $O/bench_under_rocprof.log | tail -1 > $O/bench_line_under_rocprof.json; rm -f $O/bench_under_rocprof.log
 grep "^{" $O/workloads_under_rocprof.log | tail -1 > $O/workloads_line_under_rocprof.json; rm -f $O/workloads_under_rocprof.log
 bash tools/prof_clip_pmc.sh > /dev/null 2>&1; cp gpurun_out/clip_pmc/pmc_clip_sq.txt $O/pmc_clip_sq.txt 2>/dev/null
-timeout 900 python bench.py > $O/bench_full.log 2>&1
+timeout 900 python bench.py --full > $O/bench_full.log 2>&1
 grep "^{" $O/bench_full.log | tail -1 > $O/bench_line.json; tail -5 $O/bench_full.log | grep -v "^{" | head -3; rm -f $O/bench_full.log
 head -c 700 $O/bench_line.json; echo; head -30 $O/bench_bs32_summary.txt; cat $O/traffic.json | head -40; du -sh $O

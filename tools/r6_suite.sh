@@ -10,6 +10,6 @@ for i in $(seq 1 $REPS); do
   timeout 900 python -m pytest tests/test_gpu_bench_contract.py -q -p no:cacheprovider -k "eight_ranks or two_ranks_through" 2>&1 | tail -1 >> $OUT/eight_ranks.log
 done
 cat $OUT/eight_ranks.log
-timeout 900 python bench.py > $OUT/bench.log 2>&1
+timeout 900 python bench.py --full > $OUT/bench.log 2>&1
 grep "^{" $OUT/bench.log | tail -1 > $OUT/bench.json
 head -c 1200 $OUT/bench.json
