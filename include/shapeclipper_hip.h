@@ -543,6 +543,32 @@ int sc_marching_cubes_block_count_masks(const float* level, int n_images, int n_
 int sc_marching_cubes_block_emit_masks(const float* level, int n_images, int n_axis, float iso, const long long* block_offsets,
                                        const unsigned char* masks, float* tris, void* stream);
 
+/* Indexed marching-cubes mesh (what ops.isosurface_mesh runs; the reference's `mcubes.marching_cubes` returns this form).  Vertices: one
+ * per grid edge (p, p + e_axis) whose end values lie on different sides of iso (inside = value < iso), owned by its lower end p =
+ * (x, y, z), axis 0/1/2 = +x/+y/+z; per image ordered by the linear index (x*n_axis + y)*n_axis + z of p, then by axis; position in
+ * grid-index units, the soup's interpolation of the same edge bit for bit.  Faces: triangle f of image b is triangle f of the soup of
+ * sc_marching_cubes_block_count_masks / _emit_masks for image b, same corner order, as int32 vertex numbers LOCAL to the image.
+ *   sc_marching_cubes_mesh_vertex_blocks_per_image(n_axis)   ceil(n_axis^3 / 1024) workgroups of grid points per image (-1: n_axis
+ *                    outside 2..1024)
+ *   sc_marching_cubes_mesh_vertex_count   block_counts [n_images * vertex blocks per image] int: crossing edges owned by each block
+ *   sc_marching_cubes_mesh_vertex_scan    block_offsets [n_images * vertex blocks per image + 1] int64 exclusive prefix (total last) and
+ *                    per_image [n_images] vertices of each image, as sc_isosurface_block_scan.  The caller reads per_image, sizes verts
+ *                    [total][3] and must refuse an image with more than 2^31 - 1 vertices (its numbers would not fit int32).
+ *   sc_marching_cubes_mesh_vertex_emit    verts at those offsets; vmap [n_images][n_axis^3][3] int32 (caller-allocated, no fill needed:
+ *                    written at crossing edges only) receives each crossing edge's image-local vertex number.
+ *   sc_marching_cubes_mesh_face_emit      faces [triangles][3] int32 at the soup's offsets: block_offsets and masks are the soup's cube
+ *                    scan and case indices (sc_isosurface_block_scan over sc_marching_cubes_block_count_masks), vmap the array above.
+ * Scratch: vmap 12 bytes per grid point (396 MB for 32 images at n_axis 101, 1.6 GB for one at 513), masks 1 byte per cube, 4 + 8
+ * bytes per 1,024-point or 1,024-cube block.                                                                                              */
+int sc_marching_cubes_mesh_vertex_blocks_per_image(int n_axis);
+int sc_marching_cubes_mesh_vertex_count(const float* level, int n_images, int n_axis, float iso, int* block_counts, void* stream);
+int sc_marching_cubes_mesh_vertex_scan(const int* block_counts, int n_images, int n_axis, long long* block_offsets, long long* per_image,
+                                       void* stream);
+int sc_marching_cubes_mesh_vertex_emit(const float* level, int n_images, int n_axis, float iso, const long long* block_offsets, float* verts,
+                                       int* vmap, void* stream);
+int sc_marching_cubes_mesh_face_emit(int n_images, int n_axis, const long long* block_offsets, const unsigned char* masks, const int* vmap,
+                                     int* faces, void* stream);
+
 /* ---- camera algebra of a render -------------------------------------------------------------------
  * sc_camera_rays_*: utils/camera.py:157-196 (get_center_and_ray on the rendered pixels only) + the normalisation of
  * model/renderer.py:69-76.  pose [n_images][3][4] = [R|t] world->camera, intr [n_images][3][3], ray_idx

@@ -362,7 +362,8 @@ class Runner:
     def evaluate_sharded(self, opt, ep=0):
         """Evaluation over all ranks (BASELINE config[4]; the reference evaluates on one GPU, evaluate.py:16-18):
         rank r takes the test samples with index % world == r (eval.batch_size = 1), per-sample records are
-        gathered once, rank 0 writes chamfer.txt / cd_cat.txt / f_score.txt in sample order."""
+        gathered once, rank 0 writes chamfer.txt / cd_cat.txt / f_score.txt in sample order.  Every rank writes the per-sample files of
+        its own samples (dump_visuals: PNGs, mesh and point-cloud PLYs)."""
         from ..parallel import gather_eval_records
         self.graph.eval()
         opt.H, opt.W = opt.eval.image_size
@@ -375,6 +376,7 @@ class Runner:
             batch = {k: ({kk: vv[None] for kk, vv in v.items()} if isinstance(v, dict) else torch.as_tensor(v)[None]) for k, v in sample.items()}
             var = self.evaluate_batch(opt, edict(batch), ep, it, single_gpu=True)
             eval_3D.eval_metrics(opt, var, self.graph.module.sdf_network)
+            self.dump_visuals(opt, var, ep)             # this rank's samples only; rank 0 writes chamfer.txt once below
             recs.append(torch.cat([var.idx.float().view(1), var.cd_acc.view(1), var.cd_comp.view(1), var.f_score.view(-1),
                                    var.category_label.float().view(1)]))
         dev = next(self.graph.parameters()).device
@@ -428,12 +430,30 @@ class Runner:
             self.tb.add_scalar("{0}/{1}".format(split, key), value, step)
 
     @torch.no_grad()
-    def dump_results(self, opt, var, ep, write_new=False, train=False):
+    def dump_visuals(self, opt, var, ep, train=False):
+        """Per-sample files of an evaluated batch: the two PNGs and, outside training, {idx}_mesh.ply (the predicted mesh) and
+        {idx}_pointclouds_comp.ply (the points eval_metrics compared: prediction red, ground truth green).  File names carry the
+        sample index, so the ranks of evaluate_sharded never write the same file."""
         folder = "dump" if not train else "vis_{}".format(ep)
         os.makedirs("{}/{}/".format(opt.output_path, folder), exist_ok=True)
-        if util_vis is not None:
-            util_vis.dump_images(opt, var.idx, "image_recon", var.rgb_recon_map, masks=var.mask_hard_map, folder=folder)
-            util_vis.dump_images(opt, var.idx, "mask_recon", var.mask_recon_map, folder=folder)
+        if util_vis is None:
+            return
+        util_vis.dump_images(opt, var.idx, "image_recon", var.rgb_recon_map, masks=var.mask_hard_map, folder=folder)
+        util_vis.dump_images(opt, var.idx, "mask_recon", var.mask_recon_map, folder=folder)
+        if train:
+            return
+        if eval_3D.HAVE_MESHING:
+            meshes = var.mesh_pred                      # trimesh meshes of the PyMCubes branch
+        else:
+            lo, hi = opt.eval.range
+            meshes = eval_3D.meshes_device(var.level_vox, lo, hi)
+        util_vis.dump_meshes(opt, var.idx, "mesh", meshes, folder=folder)
+        if "dpc" in var:
+            util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_comp", var.dpc_pred, var.dpc.points, folder=folder)
+
+    @torch.no_grad()
+    def dump_results(self, opt, var, ep, write_new=False, train=False):
+        self.dump_visuals(opt, var, ep, train=train)
         if not train:
             with open("{}/chamfer.txt".format(opt.output_path), "w" if write_new else "a") as f:
                 for i, acc, comp in zip(var.idx, var.cd_acc, var.cd_comp):

@@ -696,6 +696,56 @@ def isosurface_triangles(level: torch.Tensor, iso: float = 0.0, method: str = "c
     return tris, per_image
 
 
+def isosurface_mesh(level: torch.Tensor, iso: float = 0.0):
+    """level [B,S,S,S] (device) -> (verts [V,3] fp32, faces [F,3] int32, v_count [B] int64, f_count [B] int64; counts on the host).
+
+    The indexed form of isosurface_triangles(method="cubes"): one vertex per grid edge whose end values lie on different sides of iso,
+    ordered by image, owning grid point (its lower end, linear index) and axis, shared by every triangle around the edge; faces are
+    vertex numbers local to their image, so image b's mesh is verts[vs:ve], faces[fs:fe] with the offsets of the two counts.
+    verts[faces] of an image equals its triangles from isosurface_triangles bit for bit, in the same order.  Two scans with one host
+    read each (faces: the soup's count / scan over 1,024-cube blocks; vertices: 1,024-point blocks), vertex emit, face emit --
+    csrc/isosurface.hip.  Scratch: a vertex-number map of 12 bytes per grid point, written at crossing edges only."""
+    lib = _lib.load()
+    level = level.contiguous().float()
+    B, S = level.shape[0], level.shape[1]
+    assert level.shape[1:] == (S, S, S)
+    bpi = int(lib.sc_isosurface_blocks_per_image(c_int(S)))
+    vbpi = int(lib.sc_marching_cubes_mesh_vertex_blocks_per_image(c_int(S)))
+    if bpi <= 0 or vbpi <= 0:
+        raise RuntimeError("shapeclipper_amd: isosurface_mesh needs 2 <= grid side <= 1024, got %d" % S)
+    dev, c_iso = level.device, ctypes.c_float(iso)
+    counts = torch.empty(B * bpi, device=dev, dtype=torch.int32)                    # triangles per workgroup of 1,024 cubes
+    masks = torch.empty(B * (S - 1) ** 3, device=dev, dtype=torch.uint8)            # case index per cube
+    _lib.check(lib.sc_marching_cubes_block_count_masks(_lib.ptr(level), c_int(B), c_int(S), c_iso, _lib.ptr(counts), _lib.ptr(masks),
+                                                       _lib.stream()), "sc_marching_cubes_block_count_masks")
+    offsets = torch.empty(B * bpi + 1, device=dev, dtype=torch.int64)
+    f_count = torch.empty(B, device=dev, dtype=torch.int64)
+    _lib.check(lib.sc_isosurface_block_scan(_lib.ptr(counts), c_int(B), c_int(S), _lib.ptr(offsets), _lib.ptr(f_count), _lib.stream()),
+               "sc_isosurface_block_scan")
+    vcounts = torch.empty(B * vbpi, device=dev, dtype=torch.int32)                  # crossing edges per workgroup of 1,024 grid points
+    _lib.check(lib.sc_marching_cubes_mesh_vertex_count(_lib.ptr(level), c_int(B), c_int(S), c_iso, _lib.ptr(vcounts), _lib.stream()),
+               "sc_marching_cubes_mesh_vertex_count")
+    voffsets = torch.empty(B * vbpi + 1, device=dev, dtype=torch.int64)
+    v_count = torch.empty(B, device=dev, dtype=torch.int64)
+    _lib.check(lib.sc_marching_cubes_mesh_vertex_scan(_lib.ptr(vcounts), c_int(B), c_int(S), _lib.ptr(voffsets), _lib.ptr(v_count), _lib.stream()),
+               "sc_marching_cubes_mesh_vertex_scan")
+    counts_host = torch.stack([v_count, f_count]).cpu()                             # the one host read: it sizes both outputs
+    v_count, f_count = counts_host[0], counts_host[1]
+    if B and int(v_count.max()) > 2 ** 31 - 1:
+        raise RuntimeError("shapeclipper_amd: isosurface_mesh: image %d has %d vertices; int32 face indices hold at most 2^31 - 1"
+                           % (int(v_count.argmax()), int(v_count.max())))
+    V, F = int(v_count.sum()), int(f_count.sum())
+    verts = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    faces = torch.empty(F, 3, device=dev, dtype=torch.int32)
+    if V > 0:
+        vmap = torch.empty(B * S ** 3 * 3, device=dev, dtype=torch.int32)          # vertex number per (grid point, axis); no fill
+        _lib.check(lib.sc_marching_cubes_mesh_vertex_emit(_lib.ptr(level), c_int(B), c_int(S), c_iso, _lib.ptr(voffsets), _lib.ptr(verts),
+                                                          _lib.ptr(vmap), _lib.stream()), "sc_marching_cubes_mesh_vertex_emit")
+        if F > 0:
+            _lib.check(lib.sc_marching_cubes_mesh_face_emit(c_int(B), c_int(S), _lib.ptr(offsets), _lib.ptr(masks), _lib.ptr(vmap), _lib.ptr(faces),
+                                                            _lib.stream()), "sc_marching_cubes_mesh_face_emit")
+    return verts, faces, v_count, f_count
+
 # ---- camera algebra ------------------------------------------------------------------------------------------------
 def camera_rays_forward(pose, intr, ray_idx, n_rays, width):
     lib = _lib.load()

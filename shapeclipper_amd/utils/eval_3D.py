@@ -8,7 +8,7 @@ Call surface of the reference's utils/eval_3D.py.
   * marching cubes / mesh sampling are third-party in the reference (PyMCubes, trimesh; CPU threads).
     They are used when importable; otherwise the mesh comes from the device marching-cubes kernels (csrc/isosurface.hip: the
     same vertex set, one vertex per sign-changing grid edge) and is sampled area-uniformly like trimesh does -- see DESIGN.md,
-    SURVEY 8f-2.
+    SURVEY 8f-2.  meshes_device gives the same surface as an indexed mesh (shared vertices) for the PLY dumps of the evaluation.
 """
 from __future__ import annotations
 
@@ -130,6 +130,19 @@ def surface_points_device(level, lo, hi, num_points, seed=0, iso=0.0, method="cu
     return torch.where(ok[:, None, None], pts, out), meshes
 
 
+@torch.no_grad()
+def meshes_device(level, lo, hi, iso=0.0):
+    """level [B,S,S,S] on the GPU -> per-image list of (vertices [V,3] float32, faces [F,3] int32), both on the device, vertices in world
+    units: the indexed marching-cubes mesh of ops.isosurface_mesh (the form `mcubes.marching_cubes` returns in the reference), rescaled
+    with surface_points_device's expression, so its de-indexed triangles are exactly the surface the metrics were sampled from."""
+    S = level.shape[1]
+    verts, faces, v_count, f_count = ops.isosurface_mesh(level, iso)
+    verts = verts / S * (hi - lo) + lo
+    v_end, f_end = torch.cumsum(v_count, 0).tolist(), torch.cumsum(f_count, 0).tolist()
+    v_start, f_start = [0] + v_end[:-1], [0] + f_end[:-1]
+    return [(verts[v_start[b]:v_end[b]], faces[f_start[b]:f_end[b]]) for b in range(level.shape[0])]
+
+
 def convert_to_explicit_worker(opt, i, level_vox_i, isoval, meshes, pointclouds=None):
     lo, hi = opt.eval.range
     S = level_vox_i.shape[0]
@@ -187,6 +200,7 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     B = points_3D.shape[0]
     level_vox = compute_level_grid(opt, sdf_network, var.proj_latent_sdf, points_3D)
     var.eval_vox = points_3D.view(B, -1, 3)
+    var.level_vox = level_vox                                           # kept for the mesh dump (meshes_device), not recomputed there
     dev = var.idx.device
     if HAVE_MESHING:
         *level_grids, = level_vox.cpu().numpy()
