@@ -794,6 +794,20 @@ int sc_latent_bias_backward(const float* g, const float* z, const float* lat, co
                             int B, int Z, int L, int NL, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Silhouette ray choice of the Pix3D training loader (csrc/silhouette_rays.hip; reference data/pix3d.py:230-239 ->
+ * utils/util.py:237-248).  One workgroup per mask; 1 <= H, W <= 512, otherwise hipErrorInvalidValue.
+ *   sc_silhouette_distance: masks [n][H][W] fp32 (inside: > 0.5) -> dist [n][H][W] fp32 = Euclidean distance from the pixel
+ *     centre to the nearest pixel centre of the other class minus 0.5 (the image border is no boundary), bit-identical to
+ *     float32(sqrt(float64(dx^2 + dy^2)) - 0.5).  A mask of one class only: dist = 0 everywhere.
+ *   sc_silhouette_rays: dist [n][H][W], seeds [n] int64 -> ray_idx [n][n_rays] int64, 1 <= n_rays <= H*W (else
+ *     hipErrorInvalidValue): the n_rays smallest keys -log(u_i) * (double(dist_i) + uniform_fac) in increasing order, ties to
+ *     the lower index -- a draw without replacement with weights 1 / (dist + uniform_fac) in successive-sampling order.  u_i is
+ *     a splitmix64 hash of (seed, i) in (0, 1] (formula in the source), so a mask's draw depends on its own seed only.            */
+int sc_silhouette_distance(const float* masks, int n, int H, int W, float* dist, void* stream);
+int sc_silhouette_rays(const float* dist, int n, int H, int W, int n_rays, double uniform_fac, const long long* seeds,
+                       long long* ray_idx, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Launch policy (csrc/device.hip) -- the one process-level setting of the library.  The persistent one-workgroup-per-CU grids
  * (stream-K 3x3 convolutions and their weight gradients, stem / 1x1 / stride-2 gradients) are sized for
  * sc_grid_cus() = device CUs - reserved.  Reserve CUs when another stream must make progress beside them: RCCL's

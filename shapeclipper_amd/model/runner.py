@@ -21,6 +21,7 @@ import numpy as np
 import torch
 import tqdm
 
+from ..data.pix3d import sample_rays_device
 from ..parallel import FlatGradAllReduce, ModuleHolder
 from ..utils import eval_3D, util
 from ..utils.util import EasyDict as edict
@@ -170,6 +171,7 @@ class Runner:
             var = edict(next(loader))
             opt.H, opt.W = opt.image_size
             var = util.move_to_device(var, opt.device)
+            var = sample_rays_device(opt, var)        # Pix3D batches with ray_seed (hip.device_rays): silhouette rays drawn on the device
             loss = self.train_iteration(opt, var, progress)
         self.check_finite()                   # the last iteration's deferred NaN/Inf check
         if _rank0(opt) and loss is not None:

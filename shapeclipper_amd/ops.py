@@ -1349,3 +1349,54 @@ def latent_bias_backward(g, z, lat, post, NL, want_z=True):
     _lib.check(_lib.load().sc_latent_bias_backward(_lib.ptr(g), _lib.ptr(z), _lib.ptr(lat), _lib.ptr(post), _lib.ptr(g_z), _lib.ptr(g_lat), _lib.ptr(g_bias),
                                                    c_int(B), c_int(Z), c_int(L), c_int(NL), _lib.stream()), "sc_latent_bias_backward")
     return g_z, g_lat, g_bias
+
+
+# ---- Pix3D loader: silhouette distance and weighted ray draw (csrc/silhouette_rays.hip) ----------------------------------
+SILHOUETTE_MAX_SIDE = 512
+_HIP_ERROR_INVALID_VALUE = 1
+
+
+def _silhouette_shape(t, what):
+    if t.dim() != 3:
+        raise ValueError("shapeclipper_amd: %s takes [N,H,W], got shape %s" % (what, tuple(t.shape)))
+    N, H, W = t.shape
+    if not (1 <= H <= SILHOUETTE_MAX_SIDE and 1 <= W <= SILHOUETTE_MAX_SIDE):
+        raise ValueError("shapeclipper_amd: %s supports 1 <= H, W <= %d, got %dx%d" % (what, SILHOUETTE_MAX_SIDE, H, W))
+    return N, H, W
+
+
+def silhouette_distance(masks: torch.Tensor) -> torch.Tensor:
+    """masks [N,H,W] fp32 (inside: > 0.5) -> [N,H,W] fp32: distance from each pixel centre to the nearest pixel centre of the other
+    class minus 0.5, bit-identical to float32(sqrt(float64(dx^2 + dy^2)) - 0.5); the image border is no boundary; a mask of one class
+    only gives 0 everywhere (a uniform draw).  The boundary distance of the reference's compute_sampling_prob (utils/util.py:237-248)."""
+    N, H, W = _silhouette_shape(masks, "silhouette_distance")
+    masks = masks.contiguous().float()
+    dist = torch.empty(N, H, W, device=masks.device, dtype=torch.float32)
+    code = _lib.load().sc_silhouette_distance(_lib.ptr(masks), c_int(N), c_int(H), c_int(W), _lib.ptr(dist), _lib.stream())
+    if code == _HIP_ERROR_INVALID_VALUE:
+        raise ValueError("shapeclipper_amd: sc_silhouette_distance refused [%d,%d,%d]" % (N, H, W))
+    _lib.check(code, "sc_silhouette_distance")
+    return dist
+
+
+def silhouette_rays(dist: torch.Tensor, n_rays: int, uniform_fac: float, seeds: torch.Tensor) -> torch.Tensor:
+    """dist [N,H,W] fp32, seeds [N] int64 -> ray_idx [N,n_rays] int64: a draw of n_rays pixels without replacement with weights
+    1 / (dist + uniform_fac), in the order of successive sampling (the law of np.random.choice(replace=False, p)).  Exponential race:
+    the n_rays smallest keys -log(u_i) * (float64(dist_i) + uniform_fac), increasing, ties to the lower index; u_i in (0, 1] is a
+    splitmix64 hash of (seed, i) (csrc/silhouette_rays.hip states it), so a mask's draw depends on its own seed only -- not on its
+    place in the batch, N or the rank.  1 <= n_rays <= H*W; n_rays = H*W gives a permutation."""
+    N, H, W = _silhouette_shape(dist, "silhouette_rays")
+    n_rays = int(n_rays)
+    if not 1 <= n_rays <= H * W:
+        raise ValueError("shapeclipper_amd: silhouette_rays draws 1 <= n_rays <= H*W = %d rays without replacement, got %d" % (H * W, n_rays))
+    if seeds.shape != (N,) or seeds.dtype != torch.int64:
+        raise ValueError("shapeclipper_amd: silhouette_rays takes seeds [N] int64, got %s %s" % (tuple(seeds.shape), seeds.dtype))
+    dist = dist.contiguous().float()
+    seeds = seeds.to(dist.device).contiguous()
+    ray_idx = torch.empty(N, n_rays, device=dist.device, dtype=torch.int64)
+    code = _lib.load().sc_silhouette_rays(_lib.ptr(dist), c_int(N), c_int(H), c_int(W), c_int(n_rays), ctypes.c_double(float(uniform_fac)),
+                                          _lib.ptr(seeds), _lib.ptr(ray_idx), _lib.stream())
+    if code == _HIP_ERROR_INVALID_VALUE:
+        raise ValueError("shapeclipper_amd: sc_silhouette_rays refused [%d,%d,%d], n_rays %d" % (N, H, W, n_rays))
+    _lib.check(code, "sc_silhouette_rays")
+    return ray_idx
