@@ -1,4 +1,5 @@
-"""python CLIP_anno.py --yaml=options/clip/pix3d.yaml [--clip_ckpt=<state dict>] [--data.dataset=synthetic]
+"""python CLIP_anno.py --yaml=options/clip/pix3d.yaml [--data.pix3d.root=<tree>] [--clip_ckpt=<state dict>] [--hip.device_clip_preprocess!]
+                      [--data.dataset=synthetic]
 
 Offline CLIP nearest-neighbour annotation (reference CLIP_anno.py): embed every image of a split with
 the CLIP image tower, L2-normalise, cosine k-NN, write `<anno_root>/<cat>_<split>.csv` with the header
@@ -7,7 +8,13 @@ Query,Top_1..Top_{k-1},Top_1_score..  sorted by query (same on-disk format; data
 MI355X build: the tower runs on the HIP kernels (shapeclipper_amd/model/clip_vit.py; --clip_model=ViT-B/32
 (default, BASELINE config[2]) or ViT-L/14 (the model the reference loads, CLIP_anno.py:16)); the O(N^2)
 similarity is ONE GEMM + top-k instead of a Python loop (reference :29-57).  Weights: pass --clip_ckpt (a transformers CLIPVisionModelWithProjection or
-openai/CLIP state dict); without it the tower is randomly initialised (no network here)."""
+openai/CLIP state dict); without it the tower is randomly initialised (no network here).
+
+Pix3D (reference :129-182): the splits val, train, test of data/pix3d.py in its CLIP-annotation mode, in loader order, labelled by
+the dataset's rel_path_list; per split CLIP_NN_{split}.png (save_vis) in opt.output_path and the CSV.  The tower's input is the
+reference's composite + CLIP preprocess (data/clip_preprocess.py): by default computed for each batch on the device from the
+workers' uint8 RGBA images (csrc/clip_preprocess.hip), with --hip.device_clip_preprocess! in the workers on the CPU; both give the
+same bits."""
 import csv
 import importlib
 import os
@@ -38,6 +45,7 @@ class NN_annotator:
                 self.tower.load_state_dict(sd)
         self.tower = self.tower.to(opt.device)
         self.clip_dim = cfg["proj"]
+        self.n_px = cfg["image_size"]
 
     @torch.no_grad()
     def calc_matches(self, opt, features, k_nearest=6):
@@ -71,6 +79,35 @@ class NN_annotator:
     def label2path(self, root, label):
         return os.path.join(root, label), None
 
+    def save_vis(self, opt, label2path, root, labels, ind, values, k_nearest=6, n_vis=15):
+        """CLIP_NN_{split}.png in opt.output_path: n_vis rows (queries N // n_vis * i), each the query and its k_nearest - 1
+        neighbours with their similarity (reference CLIP_anno.py:59-96)."""
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+        from PIL import Image
+        N = len(labels)
+        count = 1
+        fig = plt.figure(figsize=(5 * k_nearest, 5 * n_vis))
+        for i in [N // n_vis * v for v in range(n_vis)]:
+            plt.subplot(n_vis, k_nearest, count)
+            plt.imshow(Image.open(label2path(root, labels[i])[0]).convert("RGB"))
+            plt.xticks([])
+            plt.yticks([])
+            count += 1
+            for j, index in enumerate(ind[i][1:]):
+                plt.subplot(n_vis, k_nearest, count)
+                plt.imshow(Image.open(label2path(root, labels[int(index)])[0]).convert("RGB"))
+                plt.title("{:.3f}".format(values[i, j + 1].item()), fontweight="bold")
+                plt.xticks([])
+                plt.yticks([])
+                count += 1
+        plt.tight_layout()
+        path = os.path.join(opt.output_path, "CLIP_NN_{}.png".format(self.split))
+        plt.savefig(path)
+        plt.close(fig)
+        return path
+
     def save_anno(self, opt, label2path, labels, index_topk, value_topk, k_nearest=6, category_set="all"):
         """`<anno_root>/<category>_<split>.csv`, header Query,Top_1..,Top_1_score.., rows sorted by query
         (reference CLIP_anno.py:98-127; read back by data/pix3d.py:95-108).  self.split names the split."""
@@ -90,9 +127,14 @@ class NN_annotator:
 
     @torch.no_grad()
     def embed_split(self, opt, images):
+        return self.embed_batches(opt, (images[i:i + opt.batch_size] for i in range(0, len(images), opt.batch_size)))
+
+    @torch.no_grad()
+    def embed_batches(self, opt, batches):
+        """L2-normalised embeddings [N,D] of an iterable of image batches [b,3,n_px,n_px]."""
         feats = []
-        for i in range(0, len(images), opt.batch_size):
-            e = self.tower.encode_image(images[i:i + opt.batch_size].to(opt.device)).float()
+        for images in batches:
+            e = self.tower.encode_image(images.to(opt.device)).float()
             feats.append(torch_F.normalize(e, dim=-1))
         feats = torch.cat(feats, dim=0)
         # the small-batch tower reports a cluster-barrier time-out (its members were not co-resident: another kernel held CUs) by poisoning
@@ -104,11 +146,41 @@ class NN_annotator:
         return feats
 
 
+def pix3d_splits(opt, ann):
+    """{split: (embeddings [N,D], labels)} for val, train, test of data/pix3d.py in the CLIP-annotation mode (reference :140-166)."""
+    from shapeclipper_amd.data.clip_preprocess import ClipPreprocess
+    from shapeclipper_amd.data.pix3d import device_clip_preprocess
+    data = importlib.import_module("data.{}".format(opt.data.dataset))
+    pre = ClipPreprocess(ann.n_px, opt.data.bgcolor)
+    on_device = device_clip_preprocess(opt)
+    pin = str(opt.device).startswith("cuda")
+    out = {}
+    for split in ("val", "train", "test"):
+        log.info("loading {} data...".format(split))
+        ds = data.Dataset(opt, split=split, transform=pre)
+        loader = torch.utils.data.DataLoader(ds, batch_size=opt.batch_size, num_workers=opt.data.num_workers, shuffle=False,
+                                             drop_last=False, pin_memory=pin)
+        if on_device:
+            batches = (pre.device(b["rgba_input"].to(opt.device, non_blocking=True)) for b in loader)
+        else:
+            batches = (b["rgb_input"].to(opt.device, non_blocking=True) for b in loader)
+        out[split] = (ann.embed_batches(opt, batches), list(ds.rel_path_list), os.path.join(ds.path, "img_processed"))
+    return out
+
+
 def main():
     log.process(os.getpid())
     log.title("[{}] (compute CLIP-NN)".format(sys.argv[0]))
     opt = options.set(opt_cmd=options.parse_arguments(sys.argv[1:]))
     ann = NN_annotator(opt)
+    if opt.data.dataset.startswith("pix3d"):
+        for split, (feats, labels, root_image) in pix3d_splits(opt, ann).items():
+            idx, val = ann.calc_matches(opt, feats, k_nearest=opt.k_nearest)
+            ann.split = split
+            idx, val = idx.cpu(), val.cpu()
+            print("wrote", ann.save_vis(opt, ann.label2path, root_image, labels, idx, val, k_nearest=opt.k_nearest, n_vis=15))
+            print("wrote", ann.save_anno(opt, ann.label2path, labels, idx, val, k_nearest=opt.k_nearest, category_set="custom"))
+        return
     if opt.data.dataset == "synthetic":
         n = int(opt.data.get("synthetic_len", 256))
         gen = torch.Generator().manual_seed(0)
@@ -116,7 +188,7 @@ def main():
         labels = ["synthetic/img_{:05d}.png".format(i) for i in range(n)]
         splits = {"train": (images, labels)}
     else:
-        raise NotImplementedError("the Pix3D image loader is out of scope of this build (SURVEY 2.1); use --data.dataset=synthetic")
+        raise NotImplementedError("data.dataset '%s' (available: pix3d, synthetic)" % opt.data.dataset)
     for split, (images, labels) in splits.items():
         feats = ann.embed_split(opt, images)
         idx, val = ann.calc_matches(opt, feats, k_nearest=opt.k_nearest)

@@ -808,6 +808,18 @@ int sc_silhouette_rays(const float* dist, int n, int H, int W, int n_rays, doubl
                        long long* ray_idx, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * CLIP preprocessing of Pix3D loader images (csrc/clip_preprocess.hip; reference data/pix3d.py:278-289 in CLIP-annotation mode, then
+ * openai/CLIP's _transform(n_px)).  rgba [n][H][W][4] uint8 (the loader's resized RGBA) -> out [n][3][n_px][n_px] fp32:
+ *   q = alpha >= 128 ? c : bg (bg = -1: no composite, q = c); Pillow's 8-bit bicubic resize, horizontal pass then vertical pass,
+ *   each output value clip8((2^21 + sum q * k) >> 22) with the int32 tables of data/clip_preprocess.py; (v / 255 - mean) / std.
+ * Tables, centre crop included: h_bounds [n_px][2] (first source column, tap count), h_coef [n_px][h_taps]; v_bounds [n_px][2]
+ * (first source row, tap count), v_coef [n_px][v_taps].  tmp: workspace of n * H * n_px * 4 bytes.  rgba, tmp and out 4-byte
+ * aligned.  hipErrorInvalidValue for 1 > H, W > 16384, 1 > n_px > 2048, bg outside [-1, 255], taps outside [1, 1024],
+ * n outside [0, 65535] or a NULL pointer; n = 0 launches nothing.                                                            */
+int sc_clip_preprocess(const unsigned char* rgba, int n, int H, int W, int n_px, int bg, const int* h_bounds, const int* h_coef,
+                       int h_taps, const int* v_bounds, const int* v_coef, int v_taps, unsigned char* tmp, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Launch policy (csrc/device.hip) -- the one process-level setting of the library.  The persistent one-workgroup-per-CU grids
  * (stream-K 3x3 convolutions and their weight gradients, stem / 1x1 / stride-2 gradients) are sized for
  * sc_grid_cus() = device CUs - reserved.  Reserve CUs when another stream must make progress beside them: RCCL's

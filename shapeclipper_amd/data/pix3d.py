@@ -9,6 +9,11 @@ download:
     pointclouds/{model path without "model/", .npy}
     CLIP_NN/{cat}_{split}.csv                query path, then its neighbours (CLIP_anno.py's output)
 
+CLIP-annotation mode (`transform=ClipPreprocess(n_px, bgcolor)`, CLIP_anno.py): no CLIP_NN read; `rel_path_list`, `img_path_list` and
+`pc_path_list` are built instead, and a sample is {idx, rgba_input}: the RGBA image resized to (W, H) as uint8 [H, W, 4], which
+ClipPreprocess.device turns into the tower's input for a whole batch (csrc/clip_preprocess.hip).  With
+`--hip.device_clip_preprocess!` the sample is the reference's {idx, rgb_input}, the fp32 input computed in the worker.
+
 Rays (train split, render.rand_sample): with `hip.device_rays` (default) the workers draw no rays; every sample carries
 `ray_seed [1+K] int64` and `sample_rays_device` draws all B x (1+K) views of a batch on the device (csrc/silhouette_rays.hip).  With
 `--hip.device_rays!` each view's rays come from utils.util.compute_sampling_prob in the worker, the reference's procedure
@@ -24,6 +29,7 @@ import torch.nn.functional as torch_F
 
 from ..utils import camera, util
 from ..utils.util import EasyDict as edict
+from .clip_preprocess import ClipPreprocess
 
 DEFAULT_ROOT = "data/Pix3D"
 _GOLDEN = 0x9E3779B97F4A7C15
@@ -39,6 +45,10 @@ def to_tensor(image):
 
 def device_rays(opt):
     return bool(opt.get("hip", {}).get("device_rays", True))
+
+
+def device_clip_preprocess(opt):
+    return bool(opt.get("hip", {}).get("device_clip_preprocess", True))
 
 
 def ray_seeds(base, idx, n_views):
@@ -57,12 +67,13 @@ class Dataset(torch.utils.data.Dataset):
         self.augment = split == "train" and opt.data.augment
         self.cat_id_all = dict(bed="bed", bookcase="bookcase", chair="chair", desk="desk", misc="misc", sofa="sofa", table="table",
                                tool="tool", wardrobe="wardrobe")                                            # :15-27
-        if transform is not None:
-            # :29-31, :47-48, :117-121: the CLIP-annotation mode needs CLIP's preprocess; the processed download ships the CSVs
-            raise NotImplementedError("data.pix3d: the CLIP-annotation mode (transform is not None, CLIP_anno.py) is not supported; "
-                                      "the processed Pix3D download already ships CLIP_NN/*.csv")
-        self.clip_anno = False
-        self.transform = None
+        # :29-31: a transform puts the dataset in the CLIP-annotation mode (CLIP_anno.py); the transform is the reference's composite
+        # plus CLIP's preprocess, restated as ClipPreprocess
+        if transform is not None and not isinstance(transform, ClipPreprocess):
+            raise NotImplementedError("data.pix3d: the CLIP-annotation mode takes a data.clip_preprocess.ClipPreprocess transform "
+                                      "(CLIP_anno.py), got %r" % (transform,))
+        self.clip_anno = transform is not None
+        self.transform = transform
         self.max_imgs = opt.data.max_img_cat if opt.data.max_img_cat is not None else np.inf
         self.cat2label = {}
         accum_idx = 0
@@ -77,7 +88,10 @@ class Dataset(torch.utils.data.Dataset):
             self.label2cat.append(key)
         self.path = opt.data.pix3d.get("root", None) or DEFAULT_ROOT                                        # :45
         self.list = self.get_list(opt, split)
-        self.NN_dict = self.get_NN_anno(opt)
+        if self.clip_anno:
+            self.get_path_list(opt)                                                                         # :46-49
+        else:
+            self.NN_dict = self.get_NN_anno(opt)
 
     # :51-60 -- [(category, sample name)], at most max_img_cat per category
     def get_list(self, opt, split):
@@ -91,6 +105,14 @@ class Dataset(torch.utils.data.Dataset):
                     break
                 cads.append((c, m))
         return cads
+
+    def get_path_list(self, opt):                                                                          # :62-72
+        self.img_path_list, self.pc_path_list, self.rel_path_list = [], [], []
+        for idx in range(len(self.list)):
+            meta = self.get_metadata(opt, idx)
+            self.pc_path_list.append("{0}/{1}".format(self.path, "pointclouds/" + meta.cad_path[6:]).replace(".obj", ".npy"))
+            self.img_path_list.append("{0}/{1}".format(self.path, meta.img_path))
+            self.rel_path_list.append("/".join(meta.img_path.split("/")[1:]))
 
     def name_from_path(self, opt, relpath):                                                                # :74-77
         c = relpath.split("/")[0]
@@ -127,6 +149,13 @@ class Dataset(torch.utils.data.Dataset):
         opt = self.opt
         sample = dict(idx=idx)
         meta = self.get_metadata(opt, idx)
+        if self.clip_anno:                                                                                  # :117-121
+            image = self.get_image(opt, meta=meta).resize((opt.W, opt.H))
+            if device_clip_preprocess(opt):
+                sample.update(rgba_input=torch.from_numpy(np.array(image, dtype=np.uint8)))      # ClipPreprocess.device on the batch
+            else:
+                sample.update(rgb_input=self.transform(image))
+            return sample
         image = self.get_image(opt, meta=meta)
         cat_label, _ = self.get_category(opt, idx)
         rgb_input_map, mask_input_map = self.preprocess_image(opt, image)

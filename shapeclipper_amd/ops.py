@@ -1400,3 +1400,44 @@ def silhouette_rays(dist: torch.Tensor, n_rays: int, uniform_fac: float, seeds: 
         raise ValueError("shapeclipper_amd: sc_silhouette_rays refused [%d,%d,%d], n_rays %d" % (N, H, W, n_rays))
     _lib.check(code, "sc_silhouette_rays")
     return ray_idx
+
+
+# ---- CLIP annotation: the tower's input from Pix3D loader images (csrc/clip_preprocess.hip) ---------------------------------------
+CLIP_PREPROCESS_MAX_SIDE = 16384
+CLIP_PREPROCESS_MAX_NPX = 2048
+
+
+def clip_preprocess(rgba: torch.Tensor, n_px: int, bgcolor, tables=None) -> torch.Tensor:
+    """rgba [B,H,W,4] uint8 (the loader's resized RGBA images) -> [B,3,n_px,n_px] fp32, the CLIP tower's input: alpha >= 128 keeps the
+    colour, else the background trunc(fp32(bgcolor) * 255) (bgcolor None: no composite); Pillow's bicubic resize of the short side
+    to n_px; centre crop; (v / 255 - mean) / std.  Bit-identical to data/clip_preprocess.ClipPreprocess(n_px, bgcolor) on each image.
+    `tables`: the int32 device tensors of clip_preprocess.kernel_tables(H, W, n_px) (built here when None)."""
+    from .data import clip_preprocess as cp
+    if rgba.dim() != 4 or rgba.shape[3] != 4 or rgba.dtype != torch.uint8:
+        raise ValueError("shapeclipper_amd: clip_preprocess takes [B,H,W,4] uint8, got %s %s" % (tuple(rgba.shape), rgba.dtype))
+    B, H, W, _ = rgba.shape
+    n_px = int(n_px)
+    if not (1 <= H <= CLIP_PREPROCESS_MAX_SIDE and 1 <= W <= CLIP_PREPROCESS_MAX_SIDE and 1 <= n_px <= CLIP_PREPROCESS_MAX_NPX):
+        raise ValueError("shapeclipper_amd: clip_preprocess supports 1 <= H, W <= %d and 1 <= n_px <= %d, got %dx%d -> %d"
+                         % (CLIP_PREPROCESS_MAX_SIDE, CLIP_PREPROCESS_MAX_SIDE, H, W, n_px))
+    if bgcolor is not None and not 0.0 <= float(bgcolor) <= 1.0:
+        raise ValueError("shapeclipper_amd: clip_preprocess takes bgcolor None or in [0, 1], got %r" % (bgcolor,))
+    if tables is None:
+        tables = tuple(torch.from_numpy(a).to(rgba.device) for a in cp.kernel_tables(H, W, n_px))
+    hb, hk, vb, vk = tables
+    if not (hb.shape == (n_px, 2) and vb.shape == (n_px, 2) and hk.dim() == 2 and hk.shape[0] == n_px and vk.dim() == 2
+            and vk.shape[0] == n_px and all(t.dtype == torch.int32 for t in tables)):
+        raise ValueError("shapeclipper_amd: clip_preprocess tables do not match n_px %d" % n_px)
+    rgba = rgba.contiguous()
+    out = torch.empty(B, 3, n_px, n_px, device=rgba.device, dtype=torch.float32)
+    if B == 0:
+        return out
+    tmp = torch.empty(B, H, n_px, 4, device=rgba.device, dtype=torch.uint8)
+    code = _lib.load().sc_clip_preprocess(_lib.ptr(rgba), c_int(B), c_int(H), c_int(W), c_int(n_px), c_int(cp.background_byte(bgcolor)),
+                                          _lib.ptr(hb.contiguous()), _lib.ptr(hk.contiguous()), c_int(hk.shape[1]),
+                                          _lib.ptr(vb.contiguous()), _lib.ptr(vk.contiguous()), c_int(vk.shape[1]),
+                                          _lib.ptr(tmp), _lib.ptr(out), _lib.stream())
+    if code == _HIP_ERROR_INVALID_VALUE:
+        raise ValueError("shapeclipper_amd: sc_clip_preprocess refused [%d,%d,%d,4] -> %d" % (B, H, W, n_px))
+    _lib.check(code, "sc_clip_preprocess")
+    return out
