@@ -820,6 +820,18 @@ int sc_clip_preprocess(const unsigned char* rgba, int n, int H, int W, int n_px,
                        int h_taps, const int* v_bounds, const int* v_coef, int v_taps, unsigned char* tmp, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Turn-table GIF frames (csrc/vis_frames.hip; reference model/runner.py:417-424 -> utils/util_vis.py:35-44,68-80).  x: per-ray outputs
+ * of the render chain, n_pixels rows of `channels` fp32 (the ray order of an image is row-major pixel order) -> out [n_pixels][3]
+ * uint8 in one launch, the bytes the reference hands to PIL:
+ *   kind 0 (RGB, channels 3):    trunc(clamp((x - lo) * scale, 0, 1) * 255)
+ *   kind 1 (mask, channels 1):   i = trunc(clamp((x - lo) * scale, 0, 1) * 256), 256 -> 255, on all three channels (matplotlib's
+ *                                `gray` colormap as get_heatmap applies it; its float64 -> fp32 -> * 255 round trip gives i back)
+ *   kind 2 (normal, channels 3): x * 0.5 + 0.5 first (no contraction), then as kind 0
+ * scale = fp32 1 / (hi - lo).  NaN writes 0.  hipErrorInvalidValue for n_pixels outside [0, 2^40], another kind / channels pair, a NULL
+ * pointer or an out that is not 4-byte aligned; n_pixels = 0 launches nothing.                                                     */
+int sc_vis_frames(const float* x, long long n_pixels, int channels, int kind, float lo, float scale, unsigned char* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Launch policy (csrc/device.hip) -- the one process-level setting of the library.  The persistent one-workgroup-per-CU grids
  * (stream-K 3x3 convolutions and their weight gradients, stem / 1x1 / stride-2 gradients) are sized for
  * sc_grid_cus() = device CUs - reserved.  Reserve CUs when another stream must make progress beside them: RCCL's

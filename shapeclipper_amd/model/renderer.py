@@ -34,6 +34,7 @@ def sample_count_supported(n_samples) -> bool:
 
 UPLOAD_STREAM = True          # `--hip.upload_stream!`: the CPU-generator draws are copied in the render's own stream
 _upload_streams = {}
+VIEWS_MAX_RAYS = 128 * 128 * 32   # rays per pass of render_views: the evaluation render of tools/workloads.py render_eval_128
 
 
 def _upload(x, dev):
@@ -186,6 +187,43 @@ class Renderer(nn.Module):
             return (rgb_output, mask_output, mask_hard_output, depth_output, normal_output, grad_eikonal,
                     pick(points_flat.detach()), pick(transp), pick(rgba))
         return rgb_output, mask_output, mask_hard_output, depth_output, normal_output, grad_eikonal
+
+    @torch.no_grad()
+    def render_views(self, opt, poses, intr, proj_latent_sdf, proj_latent_rgb, max_rays=VIEWS_MAX_RAYS, chunk_views=None):
+        """The B images (intr [B,3,3], latents [B,Z]) seen from each of V poses [V,3,4] with scale_dist 1 (the turn-table of
+        reference runner.py:406-427) -> rgb [V,B,R,3], mask [V,B,R,1], normal [V,B,R,3], R = opt.H * opt.W, in as few passes of the chain
+        CameraRaysFunction -> RaySampleFunction -> SdfFunction -> RgbCompositeFunction (training=False) as max_rays rays per pass allow, or
+        chunk_views views per pass.  The views are laid out as extra images, view-major: image v*B + b has pose v and image b's intrinsics
+        and per-image biases.  A ray's arithmetic does not depend on its batch neighbours, so the result equals the V renders of B images one
+        at a time bit for bit.  Draws nothing from the random generators: Runner.vis_rotate makes the reference's draws."""
+        if self.eager or opt.camera.model != "perspective":
+            raise NotImplementedError("render_views runs on the HIP render chain (perspective camera, compiled architecture and sample count)")
+        V, B = poses.shape[0], intr.shape[0]
+        R, S = opt.H * opt.W, self.N_samples
+        if chunk_views:
+            per = int(chunk_views)
+        else:
+            per = max(1, int(max_rays) // (B * R))
+            per = -(-V // -(-V // per))                 # the same number of passes, the views spread evenly over them
+        sym = bool(self.sdf_network.force_symmetry)
+        w_pack, cbias = self.sdf_network.packed(proj_latent_sdf)
+        v_pack, dbias = self.rgb_network.packed(proj_latent_rgb)
+        dev = poses.device
+        rgb, mask, normal = (torch.empty(V, B, R, c, device=dev) for c in (3, 1, 3))
+        for v0 in range(0, V, per):
+            n = min(per, V - v0)
+            pose = poses[v0:v0 + n].unsqueeze(1).expand(n, B, 3, 4).reshape(n * B, 3, 4)
+            cam_loc, ray_dirs, depth_fac = CameraRaysFunction.apply(pose, intr.repeat(n, 1, 1), None, R, int(opt.W))
+            ones = torch.ones(n * B, device=dev)
+            z_vals, points_flat = RaySampleFunction.apply(cam_loc, ray_dirs, ones, None, R, float(opt.camera.dist), S)
+            sdf, grad, feat = SdfFunction.apply(points_flat, w_pack, cbias.repeat(n, 1, 1), R * S, sym, True, True)
+            outs = RgbCompositeFunction.apply(points_flat, z_vals, depth_fac.contiguous(), sdf, grad, feat, v_pack, dbias.repeat(n, 1, 1),
+                                              self.density.beta, R, sym, float(self.density.beta_min), self.bg_color,
+                                              float(opt.reg.normal_pow), False)
+            rgb[v0:v0 + n] = outs[0].view(n, B, R, 3)
+            mask[v0:v0 + n] = outs[1].view(n, B, R, 1)
+            normal[v0:v0 + n] = outs[4].view(n, B, R, 3)
+        return rgb, mask, normal
 
     def _forward_eager(self, opt, cam_loc, ray_dirs, depth_fac, scale_dist, t_rand, eik_idx, B, R, latent_sdf, latent_rgb, training, visualize,
                        up, rdev, pin):

@@ -39,6 +39,12 @@ def _rank0(opt):
     return opt.device == 0 or opt.device in ("cuda:0", "cpu")
 
 
+def _train_vis(opt):
+    """`--hip.train_vis` (default off): the reference's training-time visualisation on rank 0 -- the visualisation samples, vis_log/iter_{it}/
+    every freq.save_vis iterations and vis_{ep}/ (PNGs, mesh, point cloud, turn-table GIFs) at every training-time evaluation."""
+    return bool(opt.get("hip", {}).get("train_vis", False)) and _rank0(opt)
+
+
 class Runner:
 
     def __init__(self, opt):
@@ -70,6 +76,36 @@ class Runner:
         self.test_data = data.Dataset(opt, split=eval_split)
         self.test_loader = self.test_data.setup_loader(opt, shuffle=False, drop_last=False, batch_size=opt.eval.batch_size)
         self.viz_data = []
+        if _train_vis(opt):
+            # reference runner.py:105-111: a shuffled loader over the evaluation split, iterated here -- its sampler draws from the CPU
+            # generator, which is why nothing of this runs without --hip.train_vis
+            log.info("creating data for visualization...")
+            self.viz_loader = self.test_data.setup_loader(opt, shuffle=True, drop_last=False, batch_size=opt.eval.batch_size)
+            self.viz_loader_iter = iter(self.viz_loader)
+            for _ in range(opt.eval.n_vis):
+                self.append_viz_data(opt)
+
+    def append_viz_data(self, opt):
+        """One sample per category from the visualisation loader until n_vis_classes categories are covered (reference runner.py:60-89);
+        each sample is kept as a batch of one (its tensors [1, ...], nested dictionaries likewise)."""
+        cat_samples = [0] * opt.data.num_classes
+        n_vis_classes = min(opt.eval.n_vis_classes if "n_vis_classes" in opt.eval else opt.data.num_classes, opt.data.num_classes)
+        while sum(cat_samples) < n_vis_classes:
+            batch = next(self.viz_loader_iter)
+            for i, cat in enumerate(batch["category_label"]):
+                c = int(cat)
+                if cat_samples[c] >= 1:
+                    continue
+                cat_samples[c] += 1
+                sample = {}
+                for key, value in batch.items():
+                    if isinstance(value, torch.Tensor):
+                        sample[key] = value[i].unsqueeze(0)
+                    elif isinstance(value, dict):
+                        sample[key] = {k: v[i].unsqueeze(0) for k, v in value.items()}
+                    else:
+                        raise NotImplementedError(key)
+                self.viz_data.append(sample)
 
     # ---- networks / optimisers ------------------------------------------------------------------------
     def build_networks(self, opt):
@@ -227,6 +263,8 @@ class Runner:
             if opt.freq.scalar and self.it % opt.freq.scalar == 0 and self.tb is not None:
                 self.log_scalars(opt, var, loss, step=self.it, split="train")
                 self.tb.add_scalar("train/beta", self.graph.module.renderer.density.beta, global_step=self.it)
+            if _train_vis(opt) and opt.freq.save_vis and self.it % opt.freq.save_vis == 0:
+                self.save_vis(opt)
         self.it += 1
         if loader is not None and hasattr(loader, "set_postfix") and self.it % 10 == 0:
             loader.set_postfix(it=self.it, loss="{:.3f}".format(float(loss.all)))
@@ -339,6 +377,8 @@ class Runner:
             metric["dist_acc"] += dist_acc * len(var.idx)
             metric["dist_cov"] += dist_cov * len(var.idx)
             loader.set_postfix(CD="{:.3f}".format(float((dist_acc + dist_cov) / 2)))
+            if it == 0 and training and _train_vis(opt):
+                self.visualize_samples(opt, ep)
             if not training:
                 self.dump_results(opt, var, ep, write_new=(it == 0))
         if not training:
@@ -409,15 +449,61 @@ class Runner:
         var = util.move_to_device(var, opt.device)
         return self.graph.module(opt, var, training=False, visualize=visualize, get_loss=False)
 
-    def vis_rotate(self, opt, var, n_views=50, vis_NN=False):
+    @torch.no_grad()
+    def save_vis(self, opt):
+        """vis_log/iter_{it}/: the seven PNGs of every visualisation sample (reference runner.py:267-286, every freq.save_vis iterations)."""
+        opt.H, opt.W = opt.eval.image_size
+        self.graph.eval()
+        folder = "vis_log/iter_{}".format(self.it)
+        os.makedirs("{}/{}".format(opt.output_path, folder), exist_ok=True)
+        for sample in self.viz_data:
+            var = util.move_to_device(edict(deepcopy(sample)), opt.device)
+            var = self.graph.module(opt, var, training=False, visualize=False, get_loss=False)
+            if "normal_input_map" not in var:
+                var.normal_input_map = var.normal_gt.view(len(var.idx), opt.image_size[0], opt.image_size[1], 3).permute(0, 3, 1, 2).contiguous()
+            self.dump_vis_images(opt, var, folder, input_pose=False)
+        opt.H, opt.W = opt.image_size
+        self.graph.train()
+
+    @torch.no_grad()
+    def visualize_samples(self, opt, ep, n_views=50):
+        """vis_{ep}/ of every visualisation sample: the `it == 0 and training` block of the reference's evaluate (runner.py:349-357) without
+        its TensorBoard grids -- the visualize=True render, the n_views turn-table (batched on the HIP chain), the mesh and the dumps."""
+        renderer = self.graph.module.renderer
+        batched = not renderer.eager and opt.camera.model == "perspective"
+        for sample in self.viz_data:
+            var = self.evaluate_batch(opt, edict(deepcopy(sample)), ep, 0, single_gpu=True, visualize=True)
+            var = self.graph.module.get_rotate_pose(opt, var, n_views=n_views)
+            self.vis_rotate(opt, var, n_views=n_views, batched=batched)
+            eval_3D.eval_metrics(opt, var, self.graph.module.sdf_network, vis_only=True)
+            self.dump_train_vis(opt, var, ep)
+
+    @torch.no_grad()
+    def vis_rotate(self, opt, var, n_views=50, vis_NN=False, batched=False, chunk_views=None):
+        """The turn-table of reference runner.py:406-427: var.rotating_imgs / rotating_masks / rotating_normals, n_views lists of [B,c,H,W]
+        maps (normals / 2 + 0.5).  batched=False renders the views one after another, the reference's loop.  batched=True makes the same
+        draws of the random generator first (each view's render draws its eikonal sample indices, unused at training=False) and renders
+        every view in as few passes of the HIP chain as memory allows (Renderer.render_views; chunk_views views per pass when given):
+        bit-identical maps, and the per-ray outputs stay in var.rotating_raw = (rgb, mask, normal) [n_views,B,R,c] for ops.vis_frames."""
         B = len(var.idx)
+        renderer = self.graph.module.renderer
+        latent_rgb = var.proj_latent_rgb_NN if vis_NN else var.proj_latent_rgb
+        if batched:
+            rdev = var.intr.device if opt.get("hip", {}).get("device_rng", False) else "cpu"
+            for _ in range(n_views):
+                torch.randint(renderer.N_samples, (B * opt.H * opt.W,), device=rdev)
+            rgb, mask, normal = renderer.render_views(opt, var.vis_pose[:n_views], var.intr, var.proj_latent_sdf, latent_rgb,
+                                                      chunk_views=chunk_views)
+            maps = lambda x: [m.view(B, opt.H, opt.W, -1).permute(0, 3, 1, 2) for m in x.unbind(0)]
+            var.rotating_imgs, var.rotating_masks, var.rotating_normals = maps(rgb), maps(mask), maps(normal / 2 + 0.5)
+            var.rotating_raw = (rgb, mask, normal)
+            return
         imgs, masks, normals = [], [], []
         as_map = lambda x, c: x.view(B, opt.H, opt.W, c).permute(0, 3, 1, 2).contiguous()
         for i in range(n_views):
             pose_i = var.vis_pose[i].unsqueeze(0).expand(B, -1, -1)
-            rgb, mask, _, _, normal, _ = self.graph.module.renderer(
-                opt, pose_i, var.intr, torch.ones_like(var.scale_dist), var.proj_latent_sdf,
-                var.proj_latent_rgb_NN if vis_NN else var.proj_latent_rgb, training=False)
+            rgb, mask, _, _, normal, _ = renderer(opt, pose_i, var.intr, torch.ones_like(var.scale_dist), var.proj_latent_sdf, latent_rgb,
+                                                  training=False)
             imgs.append(as_map(rgb, 3)); masks.append(as_map(mask, 1)); normals.append(as_map(normal, 3) / 2 + 0.5)
         var.rotating_imgs, var.rotating_masks, var.rotating_normals = imgs, masks, normals
 
@@ -444,6 +530,53 @@ class Runner:
         util_vis.dump_images(opt, var.idx, "mask_recon", var.mask_recon_map, folder=folder)
         if train:
             return
+        self.dump_geometry(opt, var, folder)
+
+    @torch.no_grad()
+    def dump_vis_images(self, opt, var, folder, input_pose=True):
+        """The PNGs of a visualisation sample (reference dump_results, runner.py:473-482): input and reconstruction with the pose axes drawn
+        (the input's only when input_pose), masks, and the input, canonical and reconstructed normals."""
+        if util_vis is None:
+            return
+        dump = lambda name, images, **kw: util_vis.dump_images(opt, var.idx, name, images, folder=folder, **kw)
+        dump("image_input", var.rgb_input_map, poses=var.get("pose_gt") if input_pose else None)
+        dump("image_recon", var.rgb_recon_map, masks=var.mask_hard_map, poses=var.pose)
+        dump("mask_recon", var.mask_recon_map)
+        dump("mask_input", var.mask_input_map)
+        for name, key in (("normal_input_viewpoint", "normal_input_map"), ("normal_input_canonical", "normal_transformed_map"),
+                          ("normal_recon", "normal_recon_map")):
+            if key in var:
+                dump(name, var[key], from_range=(-1, 1))
+
+    @torch.no_grad()
+    def dump_train_vis(self, opt, var, ep):
+        """vis_{ep}/ of a visualisation sample (reference dump_results(train=True), runner.py:469-497): the PNGs, {idx}_mesh.ply,
+        {idx}_pointclouds_comp.ply and the rotating GIFs {idx}_image_rotate.gif, _mask_rotate.gif, _normal_rotate.gif."""
+        folder = "vis_{}".format(ep)
+        os.makedirs("{}/{}/".format(opt.output_path, folder), exist_ok=True)
+        if util_vis is None:
+            return
+        self.dump_vis_images(opt, var, folder)
+        self.dump_geometry(opt, var, folder)
+        for name, frames in self.turntable_frames(opt, var).items():
+            util_vis.dump_gifs(opt, var.idx, name, frames, folder=folder)
+
+    @staticmethod
+    def turntable_frames(opt, var):
+        """{gif name: uint8 frames [B, n_views, H, W, 3]} of var's turn-table, by ops.vis_frames: from the per-ray outputs of the batched
+        turn-table (var.rotating_raw), else from the maps of the per-view loop (whose normals are already / 2 + 0.5)."""
+        from .. import ops
+        B = len(var.idx)
+        if "rotating_raw" in var:
+            outs, kinds = var.rotating_raw, ("rgb", "mask", "normal")
+        else:
+            stack = lambda maps: torch.stack(maps).permute(0, 1, 3, 4, 2)          # [V,B,c,H,W] -> [V,B,H,W,c]
+            outs, kinds = (stack(var.rotating_imgs), stack(var.rotating_masks), stack(var.rotating_normals)), ("rgb", "mask", "rgb")
+        return {name: ops.vis_frames(x.reshape(x.shape[0], B, opt.H, opt.W, -1), kind).transpose(0, 1)
+                for name, x, kind in zip(("image_rotate", "mask_rotate", "normal_rotate"), outs, kinds)}
+
+    def dump_geometry(self, opt, var, folder):
+        """{idx}_mesh.ply (the predicted mesh) and {idx}_pointclouds_comp.ply (prediction red, ground truth green) of an evaluated batch."""
         if eval_3D.HAVE_MESHING:
             meshes = var.mesh_pred                      # trimesh meshes of the PyMCubes branch
         else:

@@ -1441,3 +1441,28 @@ def clip_preprocess(rgba: torch.Tensor, n_px: int, bgcolor, tables=None) -> torc
         raise ValueError("shapeclipper_amd: sc_clip_preprocess refused [%d,%d,%d,4] -> %d" % (B, H, W, n_px))
     _lib.check(code, "sc_clip_preprocess")
     return out
+
+
+# ---- training-time visualisation: turn-table GIF frames (csrc/vis_frames.hip) -----------------------------------------------------
+VIS_FRAME_KINDS = dict(rgb=(0, 3), mask=(1, 1), normal=(2, 3))      # kind -> (code, channels per pixel)
+
+
+def vis_frames(x: torch.Tensor, kind: str, from_range=(0, 1)) -> torch.Tensor:
+    """x [..., c] fp32 per-ray outputs of the render chain (c = 3 for "rgb" and "normal", 1 for "mask"; an image's rays in row-major pixel
+    order) -> uint8 [..., 3], the frame bytes the reference's dump_gifs hands to PIL: "rgb" trunc(clamp((x - lo) / (hi - lo), 0, 1) * 255);
+    "normal" the same of x / 2 + 0.5 (vis_rotate's normal maps); "mask" matplotlib's `gray` colormap as get_heatmap applies it, index
+    trunc(v * 256) with 256 -> 255 on all three channels.  NaN gives 0.  One launch."""
+    import numpy as np
+    if kind not in VIS_FRAME_KINDS:
+        raise ValueError("shapeclipper_amd: vis_frames kind is one of %s, got %r" % (sorted(VIS_FRAME_KINDS), kind))
+    code, c = VIS_FRAME_KINDS[kind]
+    if x.dtype != torch.float32 or x.dim() < 1 or x.shape[-1] != c:
+        raise ValueError("shapeclipper_amd: vis_frames(%s) takes [..., %d] fp32, got %s %s" % (kind, c, tuple(x.shape), x.dtype))
+    lo, hi = from_range
+    scale = float(np.float32(1.0) / np.float32(hi - lo))        # torch divides by a Python number as a multiply by its fp32 reciprocal
+    x = x.contiguous()
+    out = torch.empty(*x.shape[:-1], 3, device=x.device, dtype=torch.uint8)
+    code = _lib.load().sc_vis_frames(_lib.ptr(x), ctypes.c_longlong(x.numel() // c), c_int(c), c_int(code), ctypes.c_float(lo),
+                                     ctypes.c_float(scale), _lib.ptr(out), _lib.stream())
+    _lib.check(code, "sc_vis_frames")
+    return out

@@ -1,18 +1,22 @@
-"""Evaluation dumps: PNG images (via PIL when available) and PLY geometry (numpy only) -- the reference's utils/util_vis.py
-dump_images, dump_meshes and dump_pointclouds_compare.  Its TensorBoard grids and rotating GIFs are not reproduced."""
+"""Evaluation and training-time dumps: PNG images with optional pose axes and rotating GIFs (via PIL when available) and PLY geometry
+(numpy only) -- the reference's utils/util_vis.py dump_images, draw_pose, dump_gifs, dump_meshes and dump_pointclouds_compare.  The GIF
+frames arrive as bytes (ops.vis_frames computes the reference's float -> uint8 recipe on the device).  Its TensorBoard grids are not
+reproduced."""
 import os
 
 import numpy as np
 import torch
 
 try:
-    from PIL import Image
+    from PIL import Image, ImageDraw
 except Exception:  # pragma: no cover
-    Image = None
+    Image = ImageDraw = None
 
 
 @torch.no_grad()
 def dump_images(opt, idx, name, images, masks=None, from_range=(0, 1), poses=None, folder="dump"):
+    """{idx}_{name}.png per image of [B,C,H,W] in from_range; masks composite on white.  poses [B,3,4]: the axes of each rotation drawn in
+    the top-left corner (draw_pose, size 20, width 2) on the 8-bit image, which is then saved as RGB."""
     if Image is None:
         return
     lo, hi = from_range
@@ -20,9 +24,41 @@ def dump_images(opt, idx, name, images, masks=None, from_range=(0, 1), poses=Non
     if masks is not None:
         imgs = imgs * masks + (1 - masks)
     imgs = (imgs.cpu().permute(0, 2, 3, 1).numpy() * 255).astype(np.uint8)
-    for i, img in zip(idx, imgs):
+    rots = poses[..., :3].detach().cpu() if poses is not None else None
+    for k, (i, img) in enumerate(zip(idx, imgs)):
         arr = img[..., 0] if img.shape[-1] == 1 else img
-        Image.fromarray(arr).save("{}/{}/{}_{}.png".format(opt.output_path, folder, int(i), name))
+        image = Image.fromarray(arr)
+        if rots is not None:
+            image = draw_pose(image, rots[k], size=20, width=2).convert("RGB")
+        image.save("{}/{}/{}_{}.png".format(opt.output_path, folder, int(i), name))
+
+
+def draw_pose(image, rot, size=15, width=1):
+    """The reference's draw_pose on an 8-bit PIL image: the first two coordinates of each column of rot [3,3] (the rotated x, y, z axes) as
+    red, green and blue lines from (size, size), drawn on a transparent layer and alpha-composited.  -> RGBA image.  (The reference goes
+    float -> mul(255).byte() -> PIL and back through to_tensor; the 8-bit image it draws on is the one dump_images makes.)"""
+    base = image.convert("RGBA")
+    layer = Image.new("RGBA", base.size, (0, 0, 0, 0))
+    draw = ImageDraw.Draw(layer)
+    center = (size, size)
+    endpoint = [(float(size + size * p[0]), float(size + size * p[1])) for p in rot.t()]
+    draw.line([center, endpoint[0]], fill=(255, 0, 0), width=width)
+    draw.line([center, endpoint[1]], fill=(0, 255, 0), width=width)
+    draw.line([center, endpoint[2]], fill=(0, 0, 255), width=width)
+    base.alpha_composite(layer)
+    return base
+
+
+def dump_gifs(opt, idx, name, frames, folder="dump"):
+    """frames: uint8 [B, V, H, W, 3] (ops.vis_frames) -> per sample {idx}_{name}.gif of its V frames, 100 ms each, looping forever
+    (reference dump_gifs: PIL, convert('RGB'), save_all)."""
+    if Image is None:
+        return
+    frames = _numpy(frames)
+    for i, clip in zip(idx, frames):
+        images = [Image.fromarray(f).convert("RGB") for f in clip]
+        fname = "{}/{}/{}_{}.gif".format(opt.output_path, folder, int(i), name)
+        images[0].save(fname, format="GIF", append_images=images[1:], save_all=True, duration=100, loop=0)
 
 
 # ---- PLY (binary_little_endian 1.0): a header, then each element's rows as one packed structured array ----------------------------------
