@@ -831,6 +831,18 @@ int sc_clip_preprocess(const unsigned char* rgba, int n, int H, int W, int n_px,
  * pointer or an out that is not 4-byte aligned; n_pixels = 0 launches nothing.                                                     */
 int sc_vis_frames(const float* x, long long n_pixels, int channels, int kind, float lo, float scale, unsigned char* out, void* stream);
 
+/* Coloured meshes (csrc/rgb_points.hip): RGBNetwork.forward (model/implicit.py:220-239) at arbitrary points, e.g. mesh vertices.
+ * points [n_points][3]; grad [n_points][3] and feat (TBL64, ceil(n_points / 16) tiles) are what sc_sdf_forward / sc_sdf_forward_stream
+ * wrote for those points; v_pack / dbias [n_images][3][64] as sc_rgb_composite_forward.  The image of point i is
+ * min(16 * floor(i / 16) / n_per_image, n_images - 1), as in the SDF kernels; n_per_image must be a positive multiple of 16.
+ * -> rgb [n_points][3] (sigmoid colours; bit-identical to the rgb_flat rows of sc_rgb_composite_forward_split at the same inputs: the
+ *    same pre-split bf16x3 chain) and normal [n_points][3] = grad / max(|grad|, 1e-12).  Either output may be NULL (rgb NULL: feat,
+ *    v_pack and dbias are not read; normal NULL: grad is not read).  Nothing is read or written past n_points.  n_points = 0 launches
+ *    nothing; a negative n_points, n_per_image <= 0, n_per_image % 16 != 0 or n_images <= 0 returns hipErrorInvalidValue.             */
+int sc_rgb_points_forward_split(const float* points, const float* grad, const float* feat, const float* v_pack,
+                                const float* dbias, int n_points, int n_per_image, int n_images, int symmetric,
+                                float* rgb, float* normal, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Launch policy (csrc/device.hip) -- the one process-level setting of the library.  The persistent one-workgroup-per-CU grids
  * (stream-K 3x3 convolutions and their weight gradients, stem / 1x1 / stride-2 gradients) are sized for

@@ -49,6 +49,8 @@ SYMBOLS = (
     "sc_clip_preprocess",
     # training-time visualisation: turn-table GIF frames
     "sc_vis_frames",
+    # coloured meshes: the RGB network and the unit normal at mesh vertices
+    "sc_rgb_points_forward_split",
 )
 # entry points that do not return an int status
 SYMBOLS_OTHER = ("sc_clip_cluster_pack_elems", "sc_render_backward_workspace_bytes", "sc_chamfer3d_grid_workspace_bytes", "sc_clip_vit_workspace_bytes", "sc_conv3x3_pack_floats", "sc_conv3x3_workspace_floats", "sc_conv3x3_wgrad_workspace_floats", "sc_conv3x3_pack_floats_split", "sc_conv3x3_workspace_floats_split", "sc_conv_stem_wgrad_workspace_floats", "sc_conv1x1s2_wgrad_workspace_floats", "sc_conv3x3s2_pack_floats", "sc_conv3x3s2_workspace_floats", "sc_conv3x3s2_bd_pack_floats", "sc_conv3x3s2_bd_workspace_floats")

@@ -12,6 +12,7 @@
 #include "../../include/shapeclipper_hip.h"
 #include "rgb_common.hpp"
 #include "mlp_presplit.hpp"
+#include "rgb_presplit.hpp"
 #include <type_traits>
 
 namespace sc {
@@ -200,16 +201,7 @@ __global__ __launch_bounds__(256) void rgb_composite_fwd_kernel(RgbFwdArgsT<GEN>
 // ([V0 feature | V0 encoding | V1 | V2]), so ONE 8-wave workgroup per CU instead of two 4-wave ones; a wave still owns a ray and walks its
 // four tiles two at a time (a weight fragment read feeds both).  Per tile 144 K = 32 + 24 K = 16 MFMAs + 24 = 2.9 k matrix cycles against
 // 7.7 k of the fp32 form.  Everything behind the chain (density, normal, compositing, the parked activations) is the code above.
-namespace rs {
-using namespace ps;
-constexpr int WAVES = 8;
-constexpr int OFF_V0F = 0;                         // [ks][mt]: feature columns 48..111 of V0
-constexpr int OFF_V0E = OFF_V0F + HID_BYTES;       // [mt]: encoding columns 0..47 of V0
-constexpr int OFF_V1 = OFF_V0E + PE_BYTES;
-constexpr int OFF_V2 = OFF_V1 + HID_BYTES;
-constexpr int OFF_V3 = OFF_V2 + HID_BYTES;         // fp32: [3][64] + b3[3] (+1 pad)
-constexpr int LDS_BYTES = OFF_V3 + (3 * 64 + 4) * 4;
-}  // namespace rs
+// The LDS layout (namespace rs) lives in rgb_presplit.hpp, shared with rgb_points.hip.
 
 template <bool STASH, bool GEN = false>
 __global__ __launch_bounds__(64 * rs::WAVES) void rgb_composite_fwd_split_kernel(RgbFwdArgsT<GEN> a) {

@@ -45,6 +45,12 @@ def _train_vis(opt):
     return bool(opt.get("hip", {}).get("train_vis", False)) and _rank0(opt)
 
 
+def _mesh_color(opt):
+    """`--hip.mesh_color` (default off): every mesh dump also writes {idx}_mesh_color.ply, the same mesh with per-vertex normals and
+    predicted colours (eval_3D.mesh_attributes)."""
+    return bool(opt.get("hip", {}).get("mesh_color", False))
+
+
 class Runner:
 
     def __init__(self, opt):
@@ -576,13 +582,18 @@ class Runner:
                 for name, x, kind in zip(("image_rotate", "mask_rotate", "normal_rotate"), outs, kinds)}
 
     def dump_geometry(self, opt, var, folder):
-        """{idx}_mesh.ply (the predicted mesh) and {idx}_pointclouds_comp.ply (prediction red, ground truth green) of an evaluated batch."""
+        """{idx}_mesh.ply (the predicted mesh) and {idx}_pointclouds_comp.ply (prediction red, ground truth green) of an evaluated batch;
+        with --hip.mesh_color also {idx}_mesh_color.ply (the device mesh with vertex normals and the sample's predicted colours)."""
         if eval_3D.HAVE_MESHING:
             meshes = var.mesh_pred                      # trimesh meshes of the PyMCubes branch
         else:
             lo, hi = opt.eval.range
             meshes = eval_3D.meshes_device(var.level_vox, lo, hi)
         util_vis.dump_meshes(opt, var.idx, "mesh", meshes, folder=folder)
+        if _mesh_color(opt):
+            net = self.graph.module
+            coloured = eval_3D.mesh_attributes(opt, net.sdf_network, net.rgb_network, var.proj_latent_sdf, var.proj_latent_rgb, var.level_vox)
+            util_vis.dump_meshes(opt, var.idx, "mesh_color", coloured, folder=folder)
         if "dpc" in var:
             util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_comp", var.dpc_pred, var.dpc.points, folder=folder)
 

@@ -127,6 +127,31 @@ def rgb_composite_forward(points, z_vals, depth_fac, sdf, grad, feat, v_pack, db
     return out
 
 
+def rgb_points_forward(points, grad, feat, v_pack, dbias, n_per_image: int, symmetric: bool, want_rgb: bool = True,
+                       want_normal: bool = True):
+    """RGBNetwork.forward and the unit SDF normal at arbitrary points (mesh vertices), from the sdf_forward outputs of those points.
+
+    points [N,3], grad [N,3] (read for the normal), feat TBL64 (read for the colour), v_pack / dbias [n_images,3,64] (RGBNetwork.packed);
+    point i belongs to image (16 * (i // 16)) // n_per_image, n_per_image a multiple of 16 (the layout of sdf_forward(n_per_image=...)).
+    -> (rgb [N,3] sigmoid colours | None, normal [N,3] = grad / max(|grad|, 1e-12) | None).  The colours are those of
+    rgb_composite_forward's rgb_flat bit for bit (the same pre-split bf16x3 chain, csrc/rgb_points.hip).  No autograd: inference only."""
+    if n_per_image <= 0 or n_per_image % 16:
+        raise ValueError("shapeclipper_amd: rgb_points_forward needs n_per_image to be a positive multiple of 16, not %d" % n_per_image)
+    n = points.shape[0]
+    if points.shape != (n, 3) or (want_normal and grad.numel() < 3 * n) or (want_rgb and feat.numel() < n_tiles(n) * 1024):
+        raise ValueError("shapeclipper_amd: rgb_points_forward takes points [N,3], grad [N,3] and feat of ceil(N / 16) TBL64 tiles")
+    lib = _lib.load()
+    f32 = dict(device=points.device, dtype=torch.float32)
+    rgb = torch.empty(n, 3, **f32) if want_rgb else None
+    normal = torch.empty(n, 3, **f32) if want_normal else None
+    code = lib.sc_rgb_points_forward_split(
+        _lib.ptr(points), _lib.ptr(grad if want_normal else None), _lib.ptr(feat if want_rgb else None),
+        _lib.ptr(v_pack if want_rgb else None), _lib.ptr(dbias if want_rgb else None), c_int(n), c_int(n_per_image),
+        c_int(dbias.shape[0] if want_rgb else 1), c_int(1 if symmetric else 0), _lib.ptr(rgb), _lib.ptr(normal), _lib.stream())
+    _lib.check(code, "sc_rgb_points_forward_split")
+    return rgb, normal
+
+
 def _entry(lib, name, S):
     """The entry point `name` for S samples per ray and the sample-count argument it takes after n_rays: S = 64 calls the symbol
     without the count (the kernels of the default, and the names bench.py and profiles know), any other S its _ns twin."""

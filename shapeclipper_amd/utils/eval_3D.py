@@ -143,6 +143,53 @@ def meshes_device(level, lo, hi, iso=0.0):
     return [(verts[v_start[b]:v_end[b]], faces[f_start[b]:f_end[b]]) for b in range(level.shape[0])]
 
 
+@torch.no_grad()
+def mesh_attributes(opt, sdf_network, rgb_network, proj_latent_sdf, proj_latent_rgb, level_vox):
+    """level_vox [B,S,S,S] (compute_level_grid) -> per image (vertices [V,3] fp32, faces [F,3] int32, normals [V,3] fp32 unit,
+    colours [V,3] uint8), on the device: the mesh of meshes_device, written the same way, with the predicted colour and the unit SDF
+    normal of every vertex.
+
+    Query positions: colours and normals are evaluated where the level grid was sampled, lo + v (hi - lo) / (S - 1) with v in grid-index
+    units.  The written vertices keep the reference's v / S (hi - lo) + lo rescale (meshes_device), which moves each vertex toward the
+    grid's lower corner by (p - lo) / S, p its true position -- up to (hi - lo) / S per axis, off the zero level set; querying there would
+    colour the wrong point.
+
+    One ops.sdf_forward (with d sdf/dx and the feature) and one ops.rgb_points_forward serve all images: image b's vertices sit at rows
+    [b P, b P + V_b), P = 16 ceil(max V_b / 16), padding rows repeat the image's first vertex and are dropped.  Colours are
+    trunc(clamp(c, 0, 1) * 255), the recipe of util_vis.dump_images.  Architectures outside the compiled family (sdf_network.eager) run
+    the same steps on stock operators (model/eager_path.py)."""
+    lo, hi = opt.eval.range
+    B, S = level_vox.shape[0], level_vox.shape[1]
+    dev = level_vox.device
+    verts, faces, v_count, f_count = ops.isosurface_mesh(level_vox)
+    written = verts / S * (hi - lo) + lo                                # meshes_device's expression: the same bytes as {idx}_mesh.ply
+    v_end, f_end = torch.cumsum(v_count, 0).tolist(), torch.cumsum(f_count, 0).tolist()
+    v_start, f_start = [0] + v_end[:-1], [0] + f_end[:-1]
+    V = v_count.tolist()
+    P = 16 * ((max(V, default=0) + 15) // 16)
+    if P == 0:
+        empty = (torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.int32, device=dev),
+                 torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.uint8, device=dev))
+        return [empty] * B
+    start = torch.tensor(v_start, device=dev).clamp_max(verts.shape[0] - 1)
+    j = torch.arange(P, device=dev)
+    rows = torch.where(j[None] < v_count.to(dev)[:, None], start[:, None] + j[None], start[:, None]).reshape(-1)
+    query = (lo + verts[rows] * ((hi - lo) / (S - 1))).contiguous()    # [B P, 3]
+    if sdf_network.eager or rgb_network.eager:
+        from ..model import eager_path
+        _, feat, grad = eager_path.sdf_conditional_output(sdf_network, B, query, proj_latent_sdf, compute_grad=True)
+        rgb = eager_path.rgb_mlp(rgb_network, query.view(B, P, 3), proj_latent_rgb, feat.detach().view(B, P, -1)).reshape(-1, 3)
+        normal = torch.nn.functional.normalize(grad.detach(), dim=1, eps=1e-12)
+    else:
+        w_pack, cbias = sdf_network.packed(proj_latent_sdf)
+        _, grad, feat = ops.sdf_forward(query, w_pack, cbias, P, symmetric=bool(sdf_network.force_symmetry), want_grad=True, want_feat=True)
+        v_pack, dbias = rgb_network.packed(proj_latent_rgb)
+        rgb, normal = ops.rgb_points_forward(query, grad, feat, v_pack, dbias, P, symmetric=bool(rgb_network.force_symmetry))
+    colours = (rgb.clamp(0, 1) * 255).to(torch.uint8)
+    return [(written[v_start[b]:v_end[b]], faces[f_start[b]:f_end[b]], normal[b * P:b * P + V[b]], colours[b * P:b * P + V[b]])
+            for b in range(B)]
+
+
 def convert_to_explicit_worker(opt, i, level_vox_i, isoval, meshes, pointclouds=None):
     lo, hi = opt.eval.range
     S = level_vox_i.shape[0]

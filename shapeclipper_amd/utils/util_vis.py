@@ -67,9 +67,11 @@ PLY_FACE = np.dtype([("n", "u1"), ("vertex_indices", "<i4", (3,))])
 PLY_COLOURED_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
 
 
-def _ply_header(n_vertices, n_faces=None, colours=False):
+def _ply_header(n_vertices, n_faces=None, colours=False, normals=False):
     lines = ["ply", "format binary_little_endian 1.0", "element vertex %d" % n_vertices,
              "property float x", "property float y", "property float z"]
+    if normals:
+        lines += ["property float nx", "property float ny", "property float nz"]
     if colours:
         lines += ["property uchar red", "property uchar green", "property uchar blue"]
     if n_faces is not None:
@@ -81,15 +83,27 @@ def _numpy(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
 
-def write_ply_mesh(fname, vertices, faces):
-    """vertices [V,3] float, faces [F,3] int (tensors or arrays) -> binary PLY with `element vertex` and `element face`."""
+def write_ply_mesh(fname, vertices, faces, normals=None, colours=None):
+    """vertices [V,3] float, faces [F,3] int (tensors or arrays) -> binary PLY with `element vertex` and `element face`.  The vertex
+    element is x y z, then nx ny nz (float) when normals [V,3] are given, then red green blue (uchar) when colours [V,3] uint8 are."""
     v, f = _numpy(vertices).reshape(-1, 3), _numpy(faces).reshape(-1, 3)
-    vert = np.empty(len(v), PLY_VERTEX)
+    fields = list(PLY_VERTEX.descr)
+    if normals is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if colours is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    vert = np.empty(len(v), np.dtype(fields))
     vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        n = _numpy(normals).reshape(-1, 3)
+        vert["nx"], vert["ny"], vert["nz"] = n[:, 0], n[:, 1], n[:, 2]
+    if colours is not None:
+        c = _numpy(colours).reshape(-1, 3)
+        vert["red"], vert["green"], vert["blue"] = c[:, 0], c[:, 1], c[:, 2]
     face = np.empty(len(f), PLY_FACE)
     face["n"], face["vertex_indices"] = 3, f
     with open(fname, "wb") as fh:
-        fh.write(_ply_header(len(vert), len(face)) + vert.tobytes() + face.tobytes())
+        fh.write(_ply_header(len(vert), len(face), colours=colours is not None, normals=normals is not None) + vert.tobytes() + face.tobytes())
 
 
 def write_ply_pointcloud(fname, points, colours):
@@ -103,8 +117,9 @@ def write_ply_pointcloud(fname, points, colours):
 
 
 def dump_meshes(opt, idx, name, meshes, folder="dump"):
-    """meshes: per sample a (vertices, faces) pair (eval_3D.meshes_device) or an object with .export (trimesh, when PyMCubes/trimesh are
-    importable).  An empty mesh writes no file and prints one line, as the reference does."""
+    """meshes: per sample a (vertices, faces) pair (eval_3D.meshes_device), a (vertices, faces, normals, colours) tuple
+    (eval_3D.mesh_attributes) or an object with .export (trimesh, when PyMCubes/trimesh are importable).  An empty mesh writes no file and
+    prints one line, as the reference does."""
     for i, mesh in zip(idx, meshes):
         fname = "{}/{}/{}_{}.ply".format(opt.output_path, folder, int(i), name)
         if hasattr(mesh, "export"):
@@ -113,11 +128,11 @@ def dump_meshes(opt, idx, name, meshes, folder="dump"):
             except Exception:
                 print("Mesh is empty!")
             continue
-        vertices, faces = mesh
+        vertices, faces, *attributes = mesh
         if len(faces) == 0:
             print("Mesh is empty!")
             continue
-        write_ply_mesh(fname, vertices, faces)
+        write_ply_mesh(fname, vertices, faces, *attributes)
 
 
 def dump_pointclouds_compare(opt, idx, name, preds, gts, folder="dump"):
