@@ -14,7 +14,6 @@ chamfer_grid.hip (exact uniform-grid search, same results bit for bit, used for 
 through the C ABI (include/shapeclipper_hip.h); there is no CPU fallback.  SEARCH = "brute" (or the environment
 variable SHAPECLIPPER_CHAMFER_SEARCH=brute) keeps every call on the all-pairs kernels.
 """
-import ctypes
 import os
 
 import torch
@@ -61,11 +60,9 @@ def _forward(lib, b, n, m, xyz1, xyz2, dist1, dist2, idx1, idx2):
     if SEARCH not in ("grid", "brute"):
         raise ValueError("chamfer_3D.SEARCH must be 'grid' or 'brute', got %r" % (SEARCH,))
     if SEARCH == "grid" and min(n, m) >= GRID_MIN_POINTS:
-        ws = torch.empty(int(lib.sc_chamfer3d_grid_workspace_bytes(ctypes.c_int(b), ctypes.c_int(n), ctypes.c_int(m))),
-                         dtype=torch.uint8, device=xyz1.device)
+        ws = torch.empty(lib.sc_chamfer3d_grid_workspace_bytes(b, n, m), dtype=torch.uint8, device=xyz1.device)
         code = lib.sc_chamfer3d_forward_grid(_lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(dist1), _lib.ptr(dist2), _lib.ptr(idx1),
-                                             _lib.ptr(idx2), ctypes.c_int(b), ctypes.c_int(n), ctypes.c_int(m), _lib.ptr(ws),
-                                             _lib.stream())
+                                             _lib.ptr(idx2), b, n, m, _lib.ptr(ws), _lib.stream())
         _lib.check(code, "sc_chamfer3d_forward_grid")
         return 1
     if max(n, m) >= 4096:
@@ -73,13 +70,11 @@ def _forward(lib, b, n, m, xyz1, xyz2, dist1, dist2, idx1, idx2):
         # library chooses per direction; evaluation at b = 1: 13 slices -> one round; b = 32: 2 slices -> 4.9 rounds instead of 2.45)
         ws = torch.empty(b * (n + m), dtype=torch.int64, device=xyz1.device)
         code = lib.sc_chamfer3d_forward_split(_lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(dist1), _lib.ptr(dist2),
-                                              _lib.ptr(idx1), _lib.ptr(idx2), ctypes.c_int(b), ctypes.c_int(n),
-                                              ctypes.c_int(m), ctypes.c_int(NSPLIT), _lib.ptr(ws), _lib.stream())
+                                              _lib.ptr(idx1), _lib.ptr(idx2), b, n, m, NSPLIT, _lib.ptr(ws), _lib.stream())
         _lib.check(code, "sc_chamfer3d_forward_split")
         return 1
     code = lib.sc_chamfer3d_forward(_lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(dist1), _lib.ptr(dist2),
-                                    _lib.ptr(idx1), _lib.ptr(idx2), ctypes.c_int(b), ctypes.c_int(n),
-                                    ctypes.c_int(m), _lib.stream())
+                                    _lib.ptr(idx1), _lib.ptr(idx2), b, n, m, _lib.stream())
     _lib.check(code, "sc_chamfer3d_forward")
     return 1
 
@@ -94,6 +89,6 @@ def backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2):
     with torch.cuda.device(xyz1.device):
         code = lib.sc_chamfer3d_backward(_lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(gradxyz1), _lib.ptr(gradxyz2),
                                          _lib.ptr(graddist1), _lib.ptr(graddist2), _lib.ptr(idx1), _lib.ptr(idx2),
-                                         ctypes.c_int(b), ctypes.c_int(n), ctypes.c_int(m), _lib.stream())
+                                         b, n, m, _lib.stream())
     _lib.check(code, "sc_chamfer3d_backward")
     return 1

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import threading
 from typing import Optional
 
@@ -17,43 +18,39 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SHAPECLIPPER_HIP_LIB: load another build of the same C ABI (tuning / A-B experiments, e.g. tools/micro variants)
 LIB_PATH = os.environ.get("SHAPECLIPPER_HIP_LIB") or os.path.join(_HERE, "lib", "libshapeclipper_hip.so")
 
-SYMBOLS = (
-    "sc_chamfer3d_forward", "sc_chamfer3d_forward_split", "sc_chamfer3d_forward_grid", "sc_chamfer3d_backward", "sc_sdf_forward", "sc_rgb_composite_forward",
-    "sc_rgb_composite_backward", "sc_sdf_backward", "sc_wgrad", "sc_partial_reduce", "sc_tbl_sum", "sc_loss_fused_forward",
-    "sc_clip_vit_forward", "sc_gemm_bf16", "sc_f32_to_bf16", "sc_clip_vit_forward_f16", "sc_gemm_f16", "sc_f32_to_f16",
-    "sc_clip_cluster_supported", "sc_clip_cluster_pack", "sc_clip_vit_forward_packed", "sc_clip_cluster_set_batch_range",
-    "sc_ray_sample_forward", "sc_ray_sample_backward", "sc_ray_sample_forward_eik", "sc_ray_sample_backward_eik", "sc_render_forward", "sc_sdf_grid_forward", "sc_sdf_grid_forward_split", "sc_sdf_value_forward_split", "sc_sdf_stream_pack_bytes", "sc_sdf_stream_pack", "sc_sdf_forward_stream", "sc_loss_fused_backward",
-    "sc_bn_splits", "sc_bn_act_forward", "sc_bn_act_backward", "sc_bn_relu_pool_forward", "sc_bn_relu_pool_backward",
-    "sc_isosurface_count", "sc_isosurface_emit", "sc_marching_cubes_count", "sc_marching_cubes_emit",
-    "sc_isosurface_blocks_per_image", "sc_isosurface_block_scan", "sc_isosurface_block_count", "sc_isosurface_block_emit", "sc_marching_cubes_block_count",
-    "sc_marching_cubes_block_emit", "sc_marching_cubes_block_count_masks", "sc_marching_cubes_block_emit_masks",
-    "sc_marching_cubes_mesh_vertex_blocks_per_image", "sc_marching_cubes_mesh_vertex_count", "sc_marching_cubes_mesh_vertex_scan",
-    "sc_marching_cubes_mesh_vertex_emit", "sc_marching_cubes_mesh_face_emit",
-    "sc_camera_rays_forward", "sc_camera_rays_backward", "sc_pose_from_trig_forward", "sc_pose_from_trig_backward",
-    "sc_estimator_head_forward", "sc_estimator_head_backward", "sc_camera_prior_forward", "sc_camera_prior_backward",
-    "sc_camera_prior_max_images", "sc_transform_normal_forward", "sc_transform_normal_backward", "sc_loss_total_forward",
-    "sc_loss_total_backward",
-    "sc_render_backward", "sc_sdf_backward_fused", "sc_sdf_backward_fused_parts", "sc_sdf_backward_fused_partial_floats", "sc_tbl_sum_blocks", "sc_conv3x3_pack", "sc_conv3x3_forward", "sc_conv3x3_pack_multi", "sc_conv3x3_pack_multi_units", "sc_conv3x3_tile_channels", "sc_conv3x3_wgrad", "sc_conv3x3_wgrad_split", "sc_conv3x3_forward_split", "sc_conv3x3_forward_add", "sc_conv3x3_tile_channels_split", "sc_conv_stem_forward", "sc_conv_stem_wgrad", "sc_conv1x1s2_forward", "sc_conv1x1s2_backward_data", "sc_conv1x1s2_wgrad", "sc_conv3x3s2_forward", "sc_conv3x3s2_bd_pack", "sc_conv3x3s2_backward_data", "sc_conv3x3s2_wgrad",
-    "sc_basic_block_forward", "sc_basic_block_backward", "sc_rgb_composite_backward_v3", "sc_set_reserved_cus", "sc_grid_cus", "sc_conv3x3_release_tables",
-    "sc_linear_bn_supported", "sc_linear_bn_forward", "sc_linear_bn_backward", "sc_linear_backward_data",
-    "sc_latent_bias_forward", "sc_latent_bias_backward", "sc_rgb_composite_backward_fused", "sc_rgb_composite_backward_fused_stash", "sc_rgb_composite_backward_fused_split", "sc_rgb_composite_forward_stash", "sc_rgb_composite_forward_split", "sc_rgb_composite_backward_fused_parts",
-    "sc_rgb_composite_backward_fused_partial_floats",
-    # S != 64 samples per ray (SC_N_SAMPLES_SUPPORTED)
-    "sc_ray_sample_forward_ns", "sc_ray_sample_backward_ns", "sc_ray_sample_forward_eik_ns", "sc_ray_sample_backward_eik_ns",
-    "sc_rgb_composite_forward_ns", "sc_rgb_composite_forward_stash_ns", "sc_rgb_composite_forward_split_ns",
-    "sc_rgb_composite_backward_v3_ns", "sc_rgb_composite_backward_fused_ns", "sc_rgb_composite_backward_fused_stash_ns",
-    "sc_rgb_composite_backward_fused_split_ns",
-    # Pix3D loader: silhouette distance and weighted ray draw
-    "sc_silhouette_distance", "sc_silhouette_rays",
-    # CLIP annotation: the tower's input from loader images
-    "sc_clip_preprocess",
-    # training-time visualisation: turn-table GIF frames
-    "sc_vis_frames",
-    # coloured meshes: the RGB network and the unit normal at mesh vertices
-    "sc_rgb_points_forward_split",
-)
-# entry points that do not return an int status
-SYMBOLS_OTHER = ("sc_clip_cluster_pack_elems", "sc_render_backward_workspace_bytes", "sc_chamfer3d_grid_workspace_bytes", "sc_clip_vit_workspace_bytes", "sc_conv3x3_pack_floats", "sc_conv3x3_workspace_floats", "sc_conv3x3_wgrad_workspace_floats", "sc_conv3x3_pack_floats_split", "sc_conv3x3_workspace_floats_split", "sc_conv_stem_wgrad_workspace_floats", "sc_conv1x1s2_wgrad_workspace_floats", "sc_conv3x3s2_pack_floats", "sc_conv3x3s2_workspace_floats", "sc_conv3x3s2_bd_pack_floats", "sc_conv3x3s2_bd_workspace_floats")
+HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "shapeclipper_hip.h")
+_CTYPES = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def read_signatures(text):
+    """{name: (restype, [argtypes])} of every `sc_*` function the header text declares.  A reader for this one regular header, not a C
+    parser: comments, preprocessor lines, the extern "C" braces and the sc_block_args struct body go, the rest is split on `;` and
+    every piece must be `(int|long long) sc_name(params)`.  A parameter with a `*` is a c_void_p (device pointers, `void* stream`,
+    host pointer arrays, `const sc_block_args*`); anything that is not understood raises."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r"typedef struct sc_block_args \{.*?\} sc_block_args", " ", text, flags=re.S)
+    text = re.sub(r'extern "C" \{|\}', " ", text)
+    sigs = {}
+    for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
+        m = re.fullmatch(r"(int|long long) (sc_\w+)\((.*)\)", decl)
+        if m is None:
+            raise RuntimeError("shapeclipper_amd: include/shapeclipper_hip.h: unrecognised declaration %r" % decl)
+        params = [] if m.group(3) == "void" else m.group(3).split(",")
+        try:        # `const float* x` -> pointer; `const int n` / `long long n` -> the type without qualifier and name
+            args = [ctypes.c_void_p if "*" in p else _CTYPES[" ".join(w for w in p.split()[:-1] if w != "const")] for p in params]
+        except KeyError:
+            raise RuntimeError("shapeclipper_amd: include/shapeclipper_hip.h: unrecognised parameter type in %r" % decl) from None
+        sigs[m.group(2)] = (_CTYPES[m.group(1)], args)
+    return sigs
+
+
+with open(HEADER_PATH) as _f:
+    SIGNATURES = read_signatures(_f.read())
+# derived from the header: the `int` returners (hipError_t status; wrapped by _Timed unless TIMING_SKIP names them) / the host-only
+# `long long` size queries (never wrapped)
+SYMBOLS = tuple(n for n, (res, _) in SIGNATURES.items() if res is ctypes.c_int)
+SYMBOLS_OTHER = tuple(n for n, (res, _) in SIGNATURES.items() if res is ctypes.c_longlong)
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -74,7 +71,7 @@ class _Timed:
         self.name, self.fn = name, fn
 
     def __call__(self, *args):
-        if TIMING is None or self.name in TIMING_SKIP:
+        if TIMING is None:
             return self.fn(*args)
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
@@ -85,16 +82,17 @@ class _Timed:
 
 
 class _LibProxy:
+    """The one table of bound functions: every declared entry point with the header's restype and argtypes, so plain ints, floats,
+    None and data_ptr() integers go in as they are and a wrong argument kind raises ctypes.ArgumentError before the call.  Status
+    entry points are wrapped by _Timed unless TIMING_SKIP names them; those and the size queries are the ctypes functions themselves
+    (no Python frame between the ~270 BatchNorm / block / convolution calls of a step and the library)."""
+
     def __init__(self, cdll):
         self._cdll = cdll
-        for name in SYMBOLS:
+        for name, (restype, argtypes) in SIGNATURES.items():
             fn = getattr(cdll, name)
-            fn.restype = ctypes.c_int
-            setattr(self, name, _Timed(name, fn))
-        for name in SYMBOLS_OTHER:          # size queries: long long result, host-only
-            fn = getattr(cdll, name)
-            fn.restype = ctypes.c_longlong
-            setattr(self, name, fn)
+            fn.restype, fn.argtypes = restype, argtypes
+            setattr(self, name, _Timed(name, fn) if restype is ctypes.c_int and name not in TIMING_SKIP else fn)
 
 
 class HipLibraryMissing(RuntimeError):
@@ -113,6 +111,7 @@ def load():
     return _lib
 
 
+NO_CPU = "shapeclipper_amd: HIP kernels need device tensors (got a CPU tensor); the product path has no CPU fallback"
 _tls = threading.local()    # .dev: device index of the tensor ptr() saw last ON THIS THREAD (autograd and side-stream threads have their own)
 
 
@@ -121,8 +120,7 @@ def ptr(t: Optional[torch.Tensor]):
     if t is None:
         return ctypes.c_void_p(0)
     if not t.is_cuda:
-        raise RuntimeError("shapeclipper_amd: HIP kernels need device tensors (got a CPU tensor); "
-                           "the product path has no CPU fallback")
+        raise RuntimeError(NO_CPU)
     if not t.is_contiguous():
         raise RuntimeError("shapeclipper_amd: tensor must be contiguous")
     _tls.dev = t.get_device()
@@ -135,7 +133,7 @@ def raw_stream(device: Optional[int] = None) -> int:
 
     Device guard: the kernels are launched on the CURRENT device's stream, so a tensor that lives on another device
     (rank != device index, a stray `cuda:0` default in a multi-GPU process) would be dereferenced by the wrong GPU.  `device` = the
-    device index of the call's tensors: callers that take raw data_ptr()s (BatchNorm, block and workspace paths) pass it explicitly;
+    device index of the call's tensors: callers that take raw data_ptr()s (BatchNorm and block paths) pass it explicitly;
     entry points that pass their tensors through ptr() leave it None and the device of the last ptr() of THIS thread is checked.  The
     remembered device is consumed by the check, so a later, unrelated call is never judged by a stale tensor."""
     cur = torch._C._cuda_getDevice()

@@ -9,8 +9,6 @@ Compute: 16-bit MFMA GEMMs with fp32 accumulation, fp32 LayerNorm / softmax stat
 activations with fp32 LayerNorm, CLIP_anno.py:16); `dtype="bf16"`: bf16 operands (8-bit mantissa, fp32's range)."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.nn as nn
 
@@ -93,20 +91,16 @@ class ClipVisionTower(nn.Module):
         w_cluster = None
         lib = _lib.load()
         T = (c["image_size"] // c["patch"]) ** 2 + 1
-        if w_bf16.is_cuda and lib.sc_clip_cluster_supported(ctypes.c_int(c["width"]), ctypes.c_int(c["mlp"]), ctypes.c_int(c["heads"]), ctypes.c_int(T)):
-            lib.sc_clip_cluster_pack_elems.restype = ctypes.c_longlong
-            n = int(lib.sc_clip_cluster_pack_elems(ctypes.c_int(c["layers"])))
-            w_cluster = torch.empty(n, device=w_bf16.device, dtype=w_bf16.dtype)
+        if w_bf16.is_cuda and lib.sc_clip_cluster_supported(c["width"], c["mlp"], c["heads"], T):
+            w_cluster = torch.empty(lib.sc_clip_cluster_pack_elems(c["layers"]), device=w_bf16.device, dtype=w_bf16.dtype)
             with torch.cuda.device(w_bf16.device):
-                _lib.check(lib.sc_clip_cluster_pack(_lib.ptr(w_bf16), ctypes.c_int(mats[0].shape[1]), ctypes.c_int(c["layers"]), _lib.ptr(w_cluster),
+                _lib.check(lib.sc_clip_cluster_pack(_lib.ptr(w_bf16), mats[0].shape[1], c["layers"], _lib.ptr(w_cluster),
                                                     _lib.stream()), "sc_clip_cluster_pack")
         return w_bf16, w_f32, w_cluster
 
     def workspace_bytes(self, B):
         c = self.cfg
-        return int(_lib.load().sc_clip_vit_workspace_bytes(ctypes.c_int(B), ctypes.c_int(c["channels"]), ctypes.c_int(c["image_size"]),
-                                                           ctypes.c_int(c["image_size"]), ctypes.c_int(c["patch"]),
-                                                           ctypes.c_int(c["width"]), ctypes.c_int(c["mlp"])))
+        return _lib.load().sc_clip_vit_workspace_bytes(B, c["channels"], c["image_size"], c["image_size"], c["patch"], c["width"], c["mlp"])
 
     @torch.no_grad()
     def encode_image(self, image: torch.Tensor) -> torch.Tensor:
@@ -122,13 +116,10 @@ class ClipVisionTower(nn.Module):
         out = torch.empty(B, c["proj"], device=image.device, dtype=torch.float32)
         nbytes = self.workspace_bytes(B)
         ws = torch.empty(nbytes, device=image.device, dtype=torch.uint8)
-        code = lib.sc_clip_vit_forward_packed(_lib.ptr(image), ctypes.c_int(B), ctypes.c_int(c["channels"]),
-                                              ctypes.c_int(c["image_size"]), ctypes.c_int(c["image_size"]), ctypes.c_int(c["patch"]),
-                                              ctypes.c_int(c["width"]), ctypes.c_int(c["mlp"]), ctypes.c_int(c["layers"]),
-                                              ctypes.c_int(c["heads"]), ctypes.c_int(c["proj"]), _lib.ptr(w_bf16), _lib.ptr(w_f32),
-                                              _lib.ptr(w_cluster) if w_cluster is not None else ctypes.c_void_p(0),
-                                              ctypes.c_int(1 if self.dtype16 == "fp16" else 0),
-                                              ctypes.c_float(1e-5), _lib.ptr(out), _lib.ptr(ws), ctypes.c_longlong(nbytes), _lib.stream())
+        code = lib.sc_clip_vit_forward_packed(_lib.ptr(image), B, c["channels"], c["image_size"], c["image_size"], c["patch"], c["width"],
+                                              c["mlp"], c["layers"], c["heads"], c["proj"], _lib.ptr(w_bf16), _lib.ptr(w_f32),
+                                              _lib.ptr(w_cluster), 1 if self.dtype16 == "fp16" else 0, 1e-5, _lib.ptr(out), _lib.ptr(ws),
+                                              nbytes, _lib.stream())
         _lib.check(code, "sc_clip_vit_forward")
         return out
 

@@ -2,45 +2,49 @@
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+import weakref
 
 import torch
 
 from . import _lib
 from .packing import n_tiles
 
-c_int = ctypes.c_int
+_SCRATCH = {}       # (tag, device index, raw stream) -> fp32 buffer; every cached device scratch of this module lives here
 
 
-_SCRATCH = {}
+def _scratch(tag, dev, n_floats):
+    """The fp32 scratch buffer `tag` of at least n_floats for torch's current stream on `dev`: one per (tag, device, stream) -- calls on
+    a stream are ordered, so they can share it -- grown on demand, never shrunk.  Uses that were separate buffers carry separate tags;
+    the tags of buffers whose size follows the convolution grid start with "conv" (set_reserved_cus drops those).  The stream is read
+    without touching the device ptr() remembers, so the device guard of the launch itself judges the call's tensors."""
+    if dev.type != "cuda":
+        raise RuntimeError(_lib.NO_CPU)
+    key = (tag, dev.index, torch._C._cuda_getCurrentRawStream(dev.index))
+    buf = _SCRATCH.get(key)
+    if buf is None or buf.numel() < n_floats:
+        buf = _SCRATCH[key] = torch.empty(n_floats, device=dev, dtype=torch.float32)
+    return buf
 
 
-def _sdf_scratch(dev):
-    """[256 workgroups x 8 waves][5][1024] floats (42 MB), one per (device, stream): calls on a stream are ordered."""
-    key = (dev.type, dev.index, _lib.raw_stream(dev.index) if dev.type == "cuda" else 0)
-    if key not in _SCRATCH:
-        _SCRATCH[key] = torch.empty(256 * 8 * 5 * 1024, device=dev, dtype=torch.float32)
-    return _SCRATCH[key]
-
-
-_STREAM_IMG = {}
+SDF_SCRATCH_FLOATS = 256 * 8 * 5 * 1024     # sc_sdf_forward's parked pre-activations: [256 workgroups x 8 waves][5][1024] floats (42 MB)
+_stream_imgs = {}                           # id(w_pack) -> (weak reference to w_pack, its _version, raw stream, image)
 
 
 def _sdf_stream_image(w_pack):
     """The pre-split fragment image of sc_sdf_forward_stream for this packed weight tensor.  The four SDF calls of a training step (two renders,
     two eikonal batches) share ONE w_pack tensor (SDFNetwork.packed): the image is built once for it.  A hit needs the SAME tensor object at
-    the same version on the same stream -- the entry keeps the tensor alive, so its address cannot be handed to another tensor meanwhile."""
-    dev = w_pack.device
+    the same version on the same stream.  The entry holds the pack weakly and goes when the pack does (its address is a key only while
+    it lives), so neither the pack nor the graph behind it is kept alive, and packs that alternate on a stream each keep their image.
+    A pack must NOT be rewritten in place through raw pointers (the C ABI): that does not bump _version and would leave a stale image."""
     _lib.ptr(w_pack)                    # (a CPU tensor is refused here with the product's own message: there is no CPU fallback)
-    key = (dev.index, _lib.raw_stream(dev.index))
-    hit = _STREAM_IMG.get(key)
-    if hit is not None and hit[0] is w_pack and hit[1] == w_pack._version:
-        return hit[2]
+    key, st = id(w_pack), _lib.raw_stream()
+    hit = _stream_imgs.get(key)
+    if hit is not None and hit[0]() is w_pack and hit[1:3] == (w_pack._version, st):
+        return hit[3]
     lib = _lib.load()
-    lib.sc_sdf_stream_pack_bytes.restype = ctypes.c_longlong
-    img = torch.empty(int(lib.sc_sdf_stream_pack_bytes()), device=dev, dtype=torch.uint8)
+    img = torch.empty(lib.sc_sdf_stream_pack_bytes(), device=w_pack.device, dtype=torch.uint8)
     _lib.check(lib.sc_sdf_stream_pack(_lib.ptr(w_pack), _lib.ptr(img), _lib.stream()), "sc_sdf_stream_pack")
-    _STREAM_IMG[key] = (w_pack, w_pack._version, img)
+    _stream_imgs[key] = (weakref.ref(w_pack, lambda _, key=key: _stream_imgs.pop(key, None)), w_pack._version, st, img)
     return img
 
 
@@ -62,8 +66,8 @@ def sdf_forward(points: torch.Tensor, w_pack: torch.Tensor, cbias: torch.Tensor,
     if SDF_VALUE_SPLIT and not (want_grad or want_feat or stash):
         # the value alone (compute_level_grid): the chain in the exact bf16x3 split arithmetic with pre-split weights, 1.6x the fp32-MFMA
         # chain (csrc/sdf_value_split.hip, profiles/r06_value_chain_split_ab.txt)
-        _lib.check(lib.sc_sdf_value_forward_split(_lib.ptr(points), _lib.ptr(w_pack), _lib.ptr(cbias), c_int(n), c_int(n_per_image),
-                                                  c_int(cbias.shape[0]), c_int(1 if symmetric else 0), _lib.ptr(sdf), _lib.stream()),
+        _lib.check(lib.sc_sdf_value_forward_split(_lib.ptr(points), _lib.ptr(w_pack), _lib.ptr(cbias), n, n_per_image,
+                                                  cbias.shape[0], 1 if symmetric else 0, _lib.ptr(sdf), _lib.stream()),
                    "sc_sdf_value_forward_split")
         return sdf, None, None
     grad = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_grad else None
@@ -71,19 +75,17 @@ def sdf_forward(points: torch.Tensor, w_pack: torch.Tensor, cbias: torch.Tensor,
     sa = torch.empty(5 * nt * 1024, device=dev, dtype=torch.float32) if stash else None
     sp = torch.empty(4 * nt * 1024, device=dev, dtype=torch.float32) if (stash and want_grad) else None
     # gradient kernel without a training stash: per-wave scratch for the parked pre-activations (L2-resident)
-    scratch = _sdf_scratch(dev) if (want_grad and not stash) else None
+    scratch = _scratch("sdf", dev, SDF_SCRATCH_FLOATS) if (want_grad and not stash) else None
     if SDF_FWD_STREAM and want_grad and (not stash or (want_feat and sp is not None)):
-        # value + feature + d sdf/dx from pre-split bf16x3 fragments streamed through LDS (csrc/sdf_fwd_stream.hip)
-        img = _sdf_stream_image(w_pack)
-        code = lib.sc_sdf_forward_stream(_lib.ptr(points), _lib.ptr(img), _lib.ptr(w_pack), _lib.ptr(cbias), c_int(n), c_int(n_per_image),
-                                         c_int(cbias.shape[0]), c_int(1 if symmetric else 0), _lib.ptr(sdf), _lib.ptr(grad),
-                                         _lib.ptr(feat), _lib.ptr(sa), _lib.ptr(sp), _lib.ptr(scratch), _lib.stream())
-        _lib.check(code, "sc_sdf_forward_stream")
+        # value + feature + d sdf/dx from pre-split bf16x3 fragments streamed through LDS (csrc/sdf_fwd_stream.hip): the same arguments
+        # with the fragment image after the points
+        name, img = "sc_sdf_forward_stream", (_lib.ptr(_sdf_stream_image(w_pack)),)
     else:
-        code = lib.sc_sdf_forward(_lib.ptr(points), _lib.ptr(w_pack), _lib.ptr(cbias), c_int(n), c_int(n_per_image),
-                                  c_int(cbias.shape[0]), c_int(1 if symmetric else 0), _lib.ptr(sdf), _lib.ptr(grad),
-                                  _lib.ptr(feat), _lib.ptr(sa), _lib.ptr(sp), _lib.ptr(scratch), _lib.stream())
-        _lib.check(code, "sc_sdf_forward")
+        name, img = "sc_sdf_forward", ()
+    code = getattr(lib, name)(_lib.ptr(points), *img, _lib.ptr(w_pack), _lib.ptr(cbias), n, n_per_image, cbias.shape[0],
+                              1 if symmetric else 0, _lib.ptr(sdf), _lib.ptr(grad), _lib.ptr(feat), _lib.ptr(sa), _lib.ptr(sp),
+                              _lib.ptr(scratch), _lib.stream())
+    _lib.check(code, name)
     if stash:
         return sdf, grad, feat, sa, sp
     return sdf, grad, feat
@@ -118,9 +120,9 @@ def rgb_composite_forward(points, z_vals, depth_fac, sdf, grad, feat, v_pack, db
     fwd, ns = _entry(lib, name, S)
     code = fwd(
         _lib.ptr(points), _lib.ptr(z_vals), _lib.ptr(depth_fac), _lib.ptr(sdf), _lib.ptr(grad), _lib.ptr(feat),
-        _lib.ptr(v_pack), _lib.ptr(dbias), _lib.ptr(beta_param), c_int(n_rays), *ns, c_int(rays_per_image),
-        c_int(dbias.shape[0]), c_int(1 if symmetric else 0), ctypes.c_float(beta_min), ctypes.c_float(bgcolor),
-        ctypes.c_float(normal_pow), _lib.ptr(out["rgb"]), _lib.ptr(out["mask"]), _lib.ptr(out["mask_hard"]),
+        _lib.ptr(v_pack), _lib.ptr(dbias), _lib.ptr(beta_param), n_rays, *ns, rays_per_image,
+        dbias.shape[0], 1 if symmetric else 0, beta_min, bgcolor,
+        normal_pow, _lib.ptr(out["rgb"]), _lib.ptr(out["mask"]), _lib.ptr(out["mask_hard"]),
         _lib.ptr(out["depth"]), _lib.ptr(out["normal"]), _lib.ptr(out.get("weights")), _lib.ptr(out.get("alpha")),
         _lib.ptr(out.get("rgb_flat")), _lib.ptr(out.get("rr")), _lib.stream())
     _lib.check(code, name)
@@ -146,8 +148,8 @@ def rgb_points_forward(points, grad, feat, v_pack, dbias, n_per_image: int, symm
     normal = torch.empty(n, 3, **f32) if want_normal else None
     code = lib.sc_rgb_points_forward_split(
         _lib.ptr(points), _lib.ptr(grad if want_normal else None), _lib.ptr(feat if want_rgb else None),
-        _lib.ptr(v_pack if want_rgb else None), _lib.ptr(dbias if want_rgb else None), c_int(n), c_int(n_per_image),
-        c_int(dbias.shape[0] if want_rgb else 1), c_int(1 if symmetric else 0), _lib.ptr(rgb), _lib.ptr(normal), _lib.stream())
+        _lib.ptr(v_pack if want_rgb else None), _lib.ptr(dbias if want_rgb else None), n, n_per_image,
+        dbias.shape[0] if want_rgb else 1, 1 if symmetric else 0, _lib.ptr(rgb), _lib.ptr(normal), _lib.stream())
     _lib.check(code, "sc_rgb_points_forward_split")
     return rgb, normal
 
@@ -155,7 +157,7 @@ def rgb_points_forward(points, grad, feat, v_pack, dbias, n_per_image: int, symm
 def _entry(lib, name, S):
     """The entry point `name` for S samples per ray and the sample-count argument it takes after n_rays: S = 64 calls the symbol
     without the count (the kernels of the default, and the names bench.py and profiles know), any other S its _ns twin."""
-    return (getattr(lib, name), ()) if S == 64 else (getattr(lib, name + "_ns"), (c_int(S),))
+    return (getattr(lib, name), ()) if S == 64 else (getattr(lib, name + "_ns"), (S,))
 
 
 def sample_count_supported(n_samples: int) -> bool:
@@ -172,16 +174,9 @@ RGB_BWD_BETA_PARTS = 2048      # SC_RGB_BWD_BETA_PARTS (include/shapeclipper_hip
 
 def _partial_reduce(lib, partial, nparts, stride, n, out):
     """out[:n] = sum over the parts in a fixed order (csrc/wgrad.hip partial_reduce_kernel: no atomics)."""
-    _lib.check(lib.sc_partial_reduce(_lib.ptr(partial), c_int(nparts), c_int(stride), c_int(n), _lib.ptr(out), _lib.stream()),
+    _lib.check(lib.sc_partial_reduce(_lib.ptr(partial), nparts, stride, n, _lib.ptr(out), _lib.stream()),
                "sc_partial_reduce")
     return out
-
-
-def _rowsum_scratch(dev, n_floats):
-    key = ("rowsum", dev.type, dev.index, _lib.raw_stream(dev.index) if dev.type == "cuda" else 0)
-    if key not in _SCRATCH or _SCRATCH[key].numel() < n_floats:
-        _SCRATCH[key] = torch.empty(n_floats, device=dev, dtype=torch.float32)
-    return _SCRATCH[key]
 
 
 def _wgrad(lib, terms, points, g_grad, w5row, n_points, symmetric, nb0, nb1, partial, stride, out_offset, out_ld,
@@ -192,12 +187,12 @@ def _wgrad(lib, terms, points, g_grad, w5row, n_points, symmetric, nb0, nb1, par
     t = list(terms) + [(None, None, OP_NONE, None, OP_NONE, None, OP_NONE)] * (2 - len(terms))
     args = []
     for (a0, a1, aop, b0, bop0, b1, bop1) in t:
-        args += [_lib.ptr(a0), _lib.ptr(a1), c_int(aop), _lib.ptr(b0), c_int(bop0), _lib.ptr(b1), c_int(bop1)]
-    rs_part = _rowsum_scratch(points.device, WGRAD_PARTS * 4 * n_images * 64) if rowsum is not None else None
-    code = lib.sc_wgrad(c_int(len(terms)), *args, _lib.ptr(points), _lib.ptr(g_grad), _lib.ptr(w5row),
-                        c_int(n_points), c_int(1 if symmetric else 0), c_int(nb0), c_int(nb1), _lib.ptr(partial),
-                        c_int(WGRAD_PARTS), c_int(stride), c_int(out_offset), c_int(out_ld), _lib.ptr(rs_part),
-                        c_int(n_per_image), c_int(n_images), _lib.stream())
+        args += [_lib.ptr(a0), _lib.ptr(a1), aop, _lib.ptr(b0), bop0, _lib.ptr(b1), bop1]
+    rs_part = _scratch("rowsum", points.device, WGRAD_PARTS * 4 * n_images * 64) if rowsum is not None else None
+    code = lib.sc_wgrad(len(terms), *args, _lib.ptr(points), _lib.ptr(g_grad), _lib.ptr(w5row),
+                        n_points, 1 if symmetric else 0, nb0, nb1, _lib.ptr(partial),
+                        WGRAD_PARTS, stride, out_offset, out_ld, _lib.ptr(rs_part),
+                        n_per_image, n_images, _lib.stream())
     _lib.check(code, "sc_wgrad")
     if rowsum is not None:
         _partial_reduce(lib, rs_part, WGRAD_PARTS * 4, n_images * 64, n_images * 64, rowsum)
@@ -212,16 +207,16 @@ def tbl_sum_multi(xs, n_points, n_per_image, n_images, coef=None):
     dev = xs[0].device
     PtrArr = ctypes.c_void_p * n
     xp = PtrArr(*[x.data_ptr() for x in xs])
-    blocks = int(lib.sc_tbl_sum_blocks(c_int(n_points)))
+    blocks = int(lib.sc_tbl_sum_blocks(n_points))
     fixed = n_per_image % 16 == 0 and blocks * n * n_images * K * 64 <= (1 << 26)     # partial images of at most 256 MB
     if fixed:       # fixed summation order: per-block partial images + an ordered sum
         out = torch.empty(n, n_images, K, 64, device=dev, dtype=torch.float32)
-        part = _rowsum_scratch(dev, blocks * n * n_images * K * 64)
+        part = _scratch("rowsum", dev, blocks * n * n_images * K * 64)
     else:           # images that are not whole tiles (per-point latents) or too many of them: float atomics
         out = torch.zeros(n, n_images, K, 64, device=dev, dtype=torch.float32)
         part = None
     op = PtrArr(*[out[i].data_ptr() for i in range(n)])
-    code = lib.sc_tbl_sum(xp, c_int(n), _lib.ptr(coef), c_int(n_points), c_int(n_per_image), c_int(n_images), op, _lib.ptr(part),
+    code = lib.sc_tbl_sum(xp, n, _lib.ptr(coef), n_points, n_per_image, n_images, op, _lib.ptr(part),
                           _lib.stream())
     _lib.check(code, "sc_tbl_sum")
     return out
@@ -229,14 +224,6 @@ def tbl_sum_multi(xs, n_points, n_per_image, n_images, coef=None):
 
 def tbl_sum(x, n_points, n_per_image, n_images, coef=None):
     return tbl_sum_multi([x], n_points, n_per_image, n_images, coef)[0]
-
-
-def _park_scratch(dev, n_floats):
-    """Per-(device, stream) scratch of the fused backward (parked second-order terms; L2-resident)."""
-    key = ("park", dev.type, dev.index, _lib.raw_stream(dev.index) if dev.type == "cuda" else 0)
-    if key not in _SCRATCH or _SCRATCH[key].numel() < n_floats:
-        _SCRATCH[key] = torch.empty(n_floats, device=dev, dtype=torch.float32)
-    return _SCRATCH[key]
 
 
 def sdf_backward_fused(points, w_pack, n_per_image, n_images, symmetric, stash_a, stash_p, g_sdf, g_grad, g_feat,
@@ -252,15 +239,15 @@ def sdf_backward_fused(points, w_pack, n_per_image, n_images, symmetric, stash_a
     for t in (g_sdf, g_grad, g_feat):
         if t is not None and not (t.is_contiguous() and t.dtype == torch.float32):
             raise RuntimeError("shapeclipper_amd: sc_sdf_backward_fused needs contiguous fp32 upstream gradients")
-    parts = int(lib.sc_sdf_backward_fused_parts(c_int(n)))
-    stride = int(lib.sc_sdf_backward_fused_partial_floats(c_int(n_images)))
+    parts = int(lib.sc_sdf_backward_fused_parts(n))
+    stride = int(lib.sc_sdf_backward_fused_partial_floats(n_images))
     dense = stride > SDF_PACK_FLOATS                  # per-image bias gradients ride in the partial images (fixed summation order)
-    park = _park_scratch(dev, 256 * 4 * 4 * 1024)
+    park = _scratch("park", dev, 256 * 4 * 4 * 1024)      # the parked second-order terms (L2-resident)
     partial = torch.empty(parts * stride, **f32)
     g_c = None if dense else torch.zeros(n_images, 5, 64, **f32)
     g_points = torch.empty(n, 3, **f32) if want_points_grad else None
-    code = lib.sc_sdf_backward_fused(_lib.ptr(points), _lib.ptr(w_pack), c_int(n), c_int(n_per_image), c_int(n_images),
-                                     c_int(1 if symmetric else 0), _lib.ptr(stash_a), _lib.ptr(stash_p), _lib.ptr(g_sdf),
+    code = lib.sc_sdf_backward_fused(_lib.ptr(points), _lib.ptr(w_pack), n, n_per_image, n_images,
+                                     1 if symmetric else 0, _lib.ptr(stash_a), _lib.ptr(stash_p), _lib.ptr(g_sdf),
                                      _lib.ptr(g_grad), _lib.ptr(g_feat), _lib.ptr(g_points), _lib.ptr(park),
                                      _lib.ptr(partial), _lib.ptr(g_c), _lib.stream())
     _lib.check(code, "sc_sdf_backward_fused")
@@ -289,7 +276,7 @@ def sdf_backward(points, w_pack, n_per_image, n_images, symmetric, stash_a, stas
     gp = torch.empty(4 * T, **f32) if g_grad is not None else None
     r0 = torch.empty(T, **f32)
     g_points = torch.empty(n, 3, **f32) if want_points_grad else None
-    code = lib.sc_sdf_backward(_lib.ptr(points), _lib.ptr(w_pack), c_int(n), c_int(1 if symmetric else 0),
+    code = lib.sc_sdf_backward(_lib.ptr(points), _lib.ptr(w_pack), n, 1 if symmetric else 0,
                                _lib.ptr(stash_a), _lib.ptr(stash_p), _lib.ptr(g_sdf), _lib.ptr(g_grad),
                                _lib.ptr(g_feat), _lib.ptr(g_points), _lib.ptr(ga), _lib.ptr(gp), _lib.ptr(r0),
                                _lib.stream())
@@ -375,26 +362,24 @@ def rgb_composite_backward(points, z_vals, depth_fac, sdf, grad, feat, v_pack, d
              points=torch.empty(P, 3, **f32), z_vals=torch.empty(n_rays, S, **f32),
              depth_fac=torch.empty(n_rays, **f32), beta=torch.empty(RGB_BWD_BETA_PARTS, **f32))
     v3_part = torch.empty(RGB_BWD_BETA_PARTS * 196, **f32)     # per-wave partial sums of dV3 [3][64] | db3 [3] | 0
+    # the arguments every reverse entry point starts with (S != 64: the sample count after n_rays, see _entry)
+    head = (_lib.ptr(points), _lib.ptr(z_vals), _lib.ptr(depth_fac), _lib.ptr(sdf), _lib.ptr(grad), _lib.ptr(feat), _lib.ptr(v_pack),
+            _lib.ptr(dbias), _lib.ptr(beta_param), _lib.ptr(rgb_flat), n_rays, *(() if S == 64 else (S,)), rays_per_image, n_images,
+            1 if symmetric else 0, beta_min, bgcolor, normal_pow, _lib.ptr(G_rgb), _lib.ptr(G_mask), _lib.ptr(G_depth), _lib.ptr(G_normal),
+            _lib.ptr(g["sdf"]), _lib.ptr(g["grad"]), _lib.ptr(g["feat"]), _lib.ptr(g["points"]), _lib.ptr(g["z_vals"]),
+            _lib.ptr(g["depth_fac"]), _lib.ptr(g["beta"]))
     if FUSED_RGB_WGRAD and n_images <= 256:
         # round 5: the gradients of V0, V1, V2 and of the per-image biases are formed inside the kernel by four weight-gradient waves (the scheme
         # of sc_sdf_backward_fused): no Gy_l / r_l hand-off tensors (1.6 GB per bs32 render) and no sc_wgrad launches
-        parts = int(lib.sc_rgb_composite_backward_fused_parts(c_int(n_rays)))
-        stride = int(lib.sc_rgb_composite_backward_fused_partial_floats(c_int(n_images)))
+        parts = int(lib.sc_rgb_composite_backward_fused_parts(n_rays))
+        stride = int(lib.sc_rgb_composite_backward_fused_partial_floats(n_images))
         partial = torch.empty(parts * stride, **f32)
-        args = (_lib.ptr(points), _lib.ptr(z_vals), _lib.ptr(depth_fac), _lib.ptr(sdf), _lib.ptr(grad), _lib.ptr(feat),
-                _lib.ptr(v_pack), _lib.ptr(dbias), _lib.ptr(beta_param), _lib.ptr(rgb_flat), c_int(n_rays), *_entry(lib, "sc_rgb_composite_backward_fused", S)[1],
-                c_int(rays_per_image), c_int(n_images), c_int(1 if symmetric else 0), ctypes.c_float(beta_min),
-                ctypes.c_float(bgcolor), ctypes.c_float(normal_pow), _lib.ptr(G_rgb), _lib.ptr(G_mask), _lib.ptr(G_depth),
-                _lib.ptr(G_normal), _lib.ptr(g["sdf"]), _lib.ptr(g["grad"]), _lib.ptr(g["feat"]), _lib.ptr(g["points"]),
-                _lib.ptr(g["z_vals"]), _lib.ptr(g["depth_fac"]), _lib.ptr(g["beta"]), _lib.ptr(partial), _lib.ptr(v3_part))
         if rr is not None:      # the forward parked r0..r2: no recomputation of the forward chain
-            if RGB_BWD_SPLIT:      # round 6: the reverse chain's transposed products from pre-split bf16x3 fragments (`--hip.rgb_bwd_split!`: fp32 MFMA)
-                name, tail = "sc_rgb_composite_backward_fused_split", (_lib.ptr(rr),)
-            else:
-                name, tail = "sc_rgb_composite_backward_fused_stash", (_lib.ptr(rr),)
+            # round 6: the reverse chain's transposed products from pre-split bf16x3 fragments (`--hip.rgb_bwd_split!`: fp32 MFMA)
+            name, tail = "sc_rgb_composite_backward_fused_" + ("split" if RGB_BWD_SPLIT else "stash"), (_lib.ptr(rr),)
         else:
             name, tail = "sc_rgb_composite_backward_fused", ()
-        _lib.check(_entry(lib, name, S)[0](*args, *tail, _lib.stream()), name)
+        _lib.check(_entry(lib, name, S)[0](*head, _lib.ptr(partial), _lib.ptr(v3_part), *tail, _lib.stream()), name)
         g_all = _partial_reduce(lib, partial, parts, stride, stride, torch.empty(stride, **f32))
         g_v = torch.empty(RGB_PACK_FLOATS, **f32)
         g_v[:RGB_OFF["V3"]] = g_all[:RGB_OFF["V3"]]
@@ -406,15 +391,7 @@ def rgb_composite_backward(points, z_vals, depth_fac, sdf, grad, feat, v_pack, d
         return g
     gy = torch.empty(3 * T, **f32)
     rr = torch.empty(2 * T, **f32)         # r0, r1 (operands of dV1 / dV2); r2 and gy3 only feed the output layer's gradient, formed in the kernel:
-    bwd, ns = _entry(lib, "sc_rgb_composite_backward_v3", S)
-    code = bwd(
-        _lib.ptr(points), _lib.ptr(z_vals), _lib.ptr(depth_fac), _lib.ptr(sdf), _lib.ptr(grad), _lib.ptr(feat),
-        _lib.ptr(v_pack), _lib.ptr(dbias), _lib.ptr(beta_param), _lib.ptr(rgb_flat), c_int(n_rays), *ns,
-        c_int(rays_per_image), c_int(n_images), c_int(1 if symmetric else 0), ctypes.c_float(beta_min),
-        ctypes.c_float(bgcolor), ctypes.c_float(normal_pow), _lib.ptr(G_rgb), _lib.ptr(G_mask), _lib.ptr(G_depth),
-        _lib.ptr(G_normal), _lib.ptr(g["sdf"]), _lib.ptr(g["grad"]), _lib.ptr(g["feat"]), _lib.ptr(g["points"]),
-        _lib.ptr(g["z_vals"]), _lib.ptr(g["depth_fac"]), _lib.ptr(g["beta"]), _lib.ptr(gy), _lib.ptr(rr),
-        None, _lib.ptr(v3_part), _lib.stream())
+    code = _entry(lib, "sc_rgb_composite_backward_v3", S)[0](*head, _lib.ptr(gy), _lib.ptr(rr), None, _lib.ptr(v3_part), _lib.stream())
     _lib.check(code, "sc_rgb_composite_backward_v3")
 
     GY = lambda l: gy[l * T:(l + 1) * T]
@@ -459,8 +436,8 @@ def loss_fused_forward(rgb, rgb_t, mask, mask_t, normal, normal_t, eik, normal_l
     g_normal_t = torch.empty(B, R, 3, **f32) if want_target_grad else None
     ws = torch.empty(B * R + 4 * B, **f32)
     code = lib.sc_loss_fused_forward(_lib.ptr(rgb), _lib.ptr(rgb_t), _lib.ptr(mask), _lib.ptr(mask_t), _lib.ptr(normal),
-                                     _lib.ptr(normal_t), _lib.ptr(eik), c_int(B), c_int(R), c_int(E),
-                                     ctypes.c_float(normal_l1), ctypes.c_float(mask_mse), ctypes.c_double(keep_frac),
+                                     _lib.ptr(normal_t), _lib.ptr(eik), B, R, E,
+                                     normal_l1, mask_mse, keep_frac,
                                      _lib.ptr(out), _lib.ptr(g_rgb), _lib.ptr(g_mask), _lib.ptr(g_normal),
                                      _lib.ptr(g_eik), _lib.ptr(g_normal_t), _lib.ptr(ws), _lib.stream())
     _lib.check(code, "sc_loss_fused_forward")
@@ -475,8 +452,8 @@ def ray_sample_forward(cam_loc, ray_dirs, scale_dist, u, rays_per_image, cam_dis
     z = torch.empty(n_rays, S, device=ray_dirs.device, dtype=torch.float32)
     pts = torch.empty(n_rays * S, 3, device=ray_dirs.device, dtype=torch.float32)
     fn, ns = _entry(lib, "sc_ray_sample_forward", S)
-    code = fn(_lib.ptr(cam_loc), _lib.ptr(ray_dirs), _lib.ptr(scale_dist), _lib.ptr(u), c_int(n_rays), *ns, c_int(rays_per_image),
-              c_int(scale_dist.shape[0]), ctypes.c_float(cam_dist), _lib.ptr(z), _lib.ptr(pts), _lib.stream())
+    code = fn(_lib.ptr(cam_loc), _lib.ptr(ray_dirs), _lib.ptr(scale_dist), _lib.ptr(u), n_rays, *ns, rays_per_image,
+              scale_dist.shape[0], cam_dist, _lib.ptr(z), _lib.ptr(pts), _lib.stream())
     _lib.check(code, "sc_ray_sample_forward")
     return z, pts
 
@@ -491,58 +468,44 @@ def ray_sample_forward_eik(cam_loc, ray_dirs, scale_dist, u, eik_idx, eik_unifor
     eik = torch.empty(B, 2 * rays_per_image, 3, device=ray_dirs.device, dtype=torch.float32)
     fn, ns = _entry(lib, "sc_ray_sample_forward_eik", S)
     code = fn(_lib.ptr(cam_loc), _lib.ptr(ray_dirs), _lib.ptr(scale_dist), _lib.ptr(u), _lib.ptr(eik_idx), _lib.ptr(eik_uniform),
-              c_int(n_rays), *ns, c_int(rays_per_image), c_int(B), ctypes.c_float(cam_dist), _lib.ptr(z), _lib.ptr(pts), _lib.ptr(eik),
+              n_rays, *ns, rays_per_image, B, cam_dist, _lib.ptr(z), _lib.ptr(pts), _lib.ptr(eik),
               _lib.stream())
     _lib.check(code, "sc_ray_sample_forward_eik")
     return z, pts, eik
 
 
-def ray_sample_backward_eik(ray_dirs, z_vals, g_points, g_z, eik_idx, g_eik, rays_per_image, n_images, cam_dist):
+def _ray_sample_backward(name, eik, ray_dirs, z_vals, g_points, g_z, rays_per_image, n_images, cam_dist):
+    """`eik`: the (eik_idx, g_eik) pair the _eik entry points take after g_z, () for the plain ones."""
     lib = _lib.load()
     n_rays = ray_dirs.shape[0]
     dev = ray_dirs.device
     g_o = torch.empty(n_rays, 3, device=dev, dtype=torch.float32)
     g_d = torch.empty(n_rays, 3, device=dev, dtype=torch.float32)
     g_sd = torch.empty(n_rays, device=dev, dtype=torch.float32)
-    fn, ns = _entry(lib, "sc_ray_sample_backward_eik", z_vals.shape[1])
-    code = fn(_lib.ptr(ray_dirs), _lib.ptr(z_vals), _lib.ptr(g_points), _lib.ptr(g_z), _lib.ptr(eik_idx), _lib.ptr(g_eik), c_int(n_rays), *ns,
-              c_int(rays_per_image), c_int(n_images), ctypes.c_float(cam_dist), _lib.ptr(g_o), _lib.ptr(g_d), _lib.ptr(g_sd), _lib.stream())
-    _lib.check(code, "sc_ray_sample_backward_eik")
+    fn, ns = _entry(lib, name, z_vals.shape[1])
+    code = fn(_lib.ptr(ray_dirs), _lib.ptr(z_vals), _lib.ptr(g_points), _lib.ptr(g_z), *[_lib.ptr(t) for t in eik], n_rays, *ns,
+              rays_per_image, n_images, cam_dist, _lib.ptr(g_o), _lib.ptr(g_d), _lib.ptr(g_sd), _lib.stream())
+    _lib.check(code, name)
     return g_o, g_d, g_sd.view(n_images, rays_per_image).sum(dim=1)
+
+
+def ray_sample_backward_eik(ray_dirs, z_vals, g_points, g_z, eik_idx, g_eik, rays_per_image, n_images, cam_dist):
+    return _ray_sample_backward("sc_ray_sample_backward_eik", (eik_idx, g_eik), ray_dirs, z_vals, g_points, g_z, rays_per_image, n_images, cam_dist)
 
 
 def ray_sample_backward(ray_dirs, z_vals, g_points, g_z, rays_per_image, n_images, cam_dist):
-    lib = _lib.load()
-    n_rays = ray_dirs.shape[0]
-    dev = ray_dirs.device
-    g_o = torch.empty(n_rays, 3, device=dev, dtype=torch.float32)
-    g_d = torch.empty(n_rays, 3, device=dev, dtype=torch.float32)
-    g_sd = torch.empty(n_rays, device=dev, dtype=torch.float32)
-    fn, ns = _entry(lib, "sc_ray_sample_backward", z_vals.shape[1])
-    code = fn(_lib.ptr(ray_dirs), _lib.ptr(z_vals), _lib.ptr(g_points), _lib.ptr(g_z), c_int(n_rays), *ns, c_int(rays_per_image),
-              c_int(n_images), ctypes.c_float(cam_dist), _lib.ptr(g_o), _lib.ptr(g_d), _lib.ptr(g_sd), _lib.stream())
-    _lib.check(code, "sc_ray_sample_backward")
-    return g_o, g_d, g_sd.view(n_images, rays_per_image).sum(dim=1)
+    return _ray_sample_backward("sc_ray_sample_backward", (), ray_dirs, z_vals, g_points, g_z, rays_per_image, n_images, cam_dist)
 
 
 def sdf_grid_forward(w_pack, cbias, lo, hi, n_axis, symmetric=True, split=None):
     """compute_level_grid in one call: -> level [n_images, n_axis, n_axis, n_axis]."""
     lib = _lib.load()
-    if SDF_VALUE_SPLIT if split is None else split:
-        B, dev = cbias.shape[0], cbias.device
-        ws = torch.empty(B * n_axis ** 3, 3, device=dev, dtype=torch.float32)
-        level = torch.empty(B, n_axis, n_axis, n_axis, device=dev, dtype=torch.float32)
-        _lib.check(lib.sc_sdf_grid_forward_split(_lib.ptr(w_pack), _lib.ptr(cbias), ctypes.c_float(lo), ctypes.c_float(hi), c_int(n_axis),
-                                                 c_int(B), c_int(1 if symmetric else 0), _lib.ptr(ws), _lib.ptr(level), _lib.stream()),
-                   "sc_sdf_grid_forward_split")
-        return level
-    B = cbias.shape[0]
-    dev = cbias.device
+    name = "sc_sdf_grid_forward_split" if (SDF_VALUE_SPLIT if split is None else split) else "sc_sdf_grid_forward"
+    B, dev = cbias.shape[0], cbias.device
     ws = torch.empty(B * n_axis ** 3, 3, device=dev, dtype=torch.float32)
     level = torch.empty(B, n_axis, n_axis, n_axis, device=dev, dtype=torch.float32)
-    code = lib.sc_sdf_grid_forward(_lib.ptr(w_pack), _lib.ptr(cbias), ctypes.c_float(lo), ctypes.c_float(hi), c_int(n_axis),
-                                   c_int(B), c_int(1 if symmetric else 0), _lib.ptr(ws), _lib.ptr(level), _lib.stream())
-    _lib.check(code, "sc_sdf_grid_forward")
+    _lib.check(getattr(lib, name)(_lib.ptr(w_pack), _lib.ptr(cbias), lo, hi, n_axis, B, 1 if symmetric else 0, _lib.ptr(ws),
+                                  _lib.ptr(level), _lib.stream()), name)
     return level
 
 
@@ -560,52 +523,27 @@ def render_forward(cam_loc, ray_dirs, depth_fac, scale_dist, u, sdf_pack, sdf_cb
     grad = torch.empty(P, 3, **f32); feat = torch.empty(n_tiles(P) * 1024, **f32)
     code = lib.sc_render_forward(
         _lib.ptr(cam_loc), _lib.ptr(ray_dirs), _lib.ptr(depth_fac), _lib.ptr(scale_dist), _lib.ptr(u), _lib.ptr(sdf_pack),
-        _lib.ptr(sdf_cbias), _lib.ptr(rgb_pack), _lib.ptr(rgb_dbias), _lib.ptr(beta_param), c_int(n_rays), c_int(rays_per_image),
-        c_int(scale_dist.shape[0]), c_int(1 if symmetric else 0), ctypes.c_float(cam_dist), ctypes.c_float(beta_min),
-        ctypes.c_float(bgcolor), ctypes.c_float(normal_pow), _lib.ptr(out["rgb"]), _lib.ptr(out["mask"]), _lib.ptr(out["mask_hard"]),
+        _lib.ptr(sdf_cbias), _lib.ptr(rgb_pack), _lib.ptr(rgb_dbias), _lib.ptr(beta_param), n_rays, rays_per_image,
+        scale_dist.shape[0], 1 if symmetric else 0, cam_dist, beta_min,
+        bgcolor, normal_pow, _lib.ptr(out["rgb"]), _lib.ptr(out["mask"]), _lib.ptr(out["mask_hard"]),
         _lib.ptr(out["depth"]), _lib.ptr(out["normal"]), _lib.ptr(z), _lib.ptr(pts), _lib.ptr(sdf), _lib.ptr(grad), _lib.ptr(feat),
-        _lib.ptr(_sdf_scratch(dev)), None, None, None, _lib.stream())
+        _lib.ptr(_scratch("sdf", dev, SDF_SCRATCH_FLOATS)), None, None, None, _lib.stream())
     _lib.check(code, "sc_render_forward")
     out.update(z_vals=z, points=pts)
     return out
 
 
 # ---- encoder glue: fused BatchNorm2d (+ residual, ReLU, stem max-pool) -------------------------------------------
-# ~270 of these calls per step: the binding is kept lean (argtypes declared once so plain ints go through ctypes,
-# one persistent partial-sum buffer per device -- calls on a stream are ordered, so it can be shared).
-_VP, _CI, _CF = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-_BN_SIG = dict(
-    sc_bn_act_forward=[_VP] * 11 + [_CI] * 6 + [_CF, _CF, _VP],
-    sc_bn_act_backward=[_VP] * 12 + [_CI] * 6 + [_VP],
-    sc_bn_relu_pool_forward=[_VP] * 11 + [_CI] * 6 + [_CF, _CF, _VP],
-    sc_bn_relu_pool_backward=[_VP] * 11 + [_CI] * 6 + [_VP],
-)
-_bn_fn = {}
-_bn_ws = {}
-
-
-def _bn(name):
-    fn = _bn_fn.get(name)
-    if fn is None:
-        fn = getattr(_lib.load()._cdll, name)
-        fn.argtypes, fn.restype = _BN_SIG[name], ctypes.c_int
-        _bn_fn[name] = fn
-    return fn
-
-
+# ~270 of these calls per step: the binding is kept lean (plain ints and data_ptr()s through the bound argtypes, no Python frame
+# around the ctypes function, one persistent partial-sum buffer per stream).
 def _bn_partial(x, groups=1):
     """Workspace for the per-(channel, group) partial sums: at most 2*(2048 + C*G) floats."""
-    key = (x.device.index, _lib.raw_stream(x.device.index))      # one per stream: calls on a stream are ordered
-    need = 2 * (2048 + x.shape[1] * groups)
-    ws = _bn_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _bn_ws[key] = torch.empty(max(need, 1 << 16), device=x.device, dtype=torch.float32)
-    return ws.data_ptr()
+    return _scratch("bn", x.device, max(2 * (2048 + x.shape[1] * groups), 1 << 16)).data_ptr()
 
 
 def _aligned(t):
     if not t.is_cuda:
-        raise RuntimeError("shapeclipper_amd: HIP kernels need device tensors (got a CPU tensor); the product path has no CPU fallback")
+        raise RuntimeError(_lib.NO_CPU)
     if not t.is_contiguous():
         t = t.contiguous()
     return t if (t.storage_offset() & 3) == 0 else t.clone()
@@ -615,20 +553,16 @@ def _p(t):
     return t.data_ptr() if t is not None else None
 
 
-def _stream():
-    return _lib.raw_stream()
-
-
 def bn_act_forward(x, res, gamma, beta, running_mean, running_var, n_tracked, training, momentum, eps, relu, groups=1):
     """x [N,C,H,W] (+ res) -> y, stats [2,G,C] (save_mean, save_rstd); running statistics updated in place when training."""
     N, C, H, W = x.shape
     y = torch.empty_like(x)
     stats = torch.empty(2, groups, C, device=x.device, dtype=torch.float32)
     sp = stats.data_ptr()
-    code = _bn("sc_bn_act_forward")(x.data_ptr(), _p(res), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), sp,
-                                    sp + 4 * C * groups, _p(running_mean), _p(running_var), _p(n_tracked),
-                                    _bn_partial(x, groups), N, C, H * W, 1 if relu else 0, 1 if training else 0, groups,
-                                    eps, momentum, _stream())
+    code = _lib.load().sc_bn_act_forward(x.data_ptr(), _p(res), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), sp,
+                                         sp + 4 * C * groups, _p(running_mean), _p(running_var), _p(n_tracked),
+                                         _bn_partial(x, groups), N, C, H * W, 1 if relu else 0, 1 if training else 0, groups,
+                                         eps, momentum, _lib.raw_stream(x.get_device()))
     if code:
         _lib.check(code, "sc_bn_act_forward")
     return y, stats
@@ -640,9 +574,9 @@ def bn_act_backward(dy, x, y, gamma, beta, stats, training, relu, want_dx, want_
     dres = torch.empty_like(x) if want_dres else None
     dgb = torch.empty(2, C, device=x.device, dtype=torch.float32)
     sp, gp = stats.data_ptr(), dgb.data_ptr()
-    code = _bn("sc_bn_act_backward")(dy.data_ptr(), x.data_ptr(), _p(y), gamma.data_ptr(), beta.data_ptr(), sp,
-                                     sp + 4 * C * groups, _bn_partial(x, groups), _p(dx), _p(dres), gp, gp + 4 * C, N, C,
-                                     H * W, 1 if relu else 0, 1 if training else 0, groups, _stream())
+    code = _lib.load().sc_bn_act_backward(dy.data_ptr(), x.data_ptr(), _p(y), gamma.data_ptr(), beta.data_ptr(), sp,
+                                          sp + 4 * C * groups, _bn_partial(x, groups), _p(dx), _p(dres), gp, gp + 4 * C, N, C,
+                                          H * W, 1 if relu else 0, 1 if training else 0, groups, _lib.raw_stream(x.get_device()))
     if code:
         _lib.check(code, "sc_bn_act_backward")
     return dx, dres, dgb[0], dgb[1]
@@ -655,10 +589,10 @@ def bn_relu_pool_forward(x, gamma, beta, running_mean, running_var, n_tracked, t
     idx = torch.empty(N, C, Ho, Wo, device=x.device, dtype=torch.int32)
     stats = torch.empty(2, groups, C, device=x.device, dtype=torch.float32)
     sp = stats.data_ptr()
-    code = _bn("sc_bn_relu_pool_forward")(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), idx.data_ptr(),
-                                          sp, sp + 4 * C * groups, _p(running_mean), _p(running_var), _p(n_tracked),
-                                          _bn_partial(x, groups), N, C, H, W, 1 if training else 0, groups, eps, momentum,
-                                          _stream())
+    code = _lib.load().sc_bn_relu_pool_forward(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), idx.data_ptr(),
+                                               sp, sp + 4 * C * groups, _p(running_mean), _p(running_var), _p(n_tracked),
+                                               _bn_partial(x, groups), N, C, H, W, 1 if training else 0, groups, eps, momentum,
+                                               _lib.raw_stream(x.get_device()))
     if code:
         _lib.check(code, "sc_bn_relu_pool_forward")
     return y, idx, stats
@@ -669,9 +603,9 @@ def bn_relu_pool_backward(dy, idx, x, gamma, beta, stats, training, groups=1):
     dx = torch.empty_like(x)
     dgb = torch.empty(2, C, device=x.device, dtype=torch.float32)
     sp, gp = stats.data_ptr(), dgb.data_ptr()
-    code = _bn("sc_bn_relu_pool_backward")(dy.data_ptr(), idx.data_ptr(), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                           sp, sp + 4 * C * groups, _bn_partial(x, groups), dx.data_ptr(), gp, gp + 4 * C,
-                                           N, C, H, W, 1 if training else 0, groups, _stream())
+    code = _lib.load().sc_bn_relu_pool_backward(dy.data_ptr(), idx.data_ptr(), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                                sp, sp + 4 * C * groups, _bn_partial(x, groups), dx.data_ptr(), gp, gp + 4 * C,
+                                                N, C, H, W, 1 if training else 0, groups, _lib.raw_stream(x.get_device()))
     if code:
         _lib.check(code, "sc_bn_relu_pool_backward")
     return dx, dgb[0], dgb[1]
@@ -694,29 +628,29 @@ def isosurface_triangles(level: torch.Tensor, iso: float = 0.0, method: str = "c
     level = level.contiguous().float()
     B, S = level.shape[0], level.shape[1]
     assert level.shape[1:] == (S, S, S)
-    bpi = int(lib.sc_isosurface_blocks_per_image(c_int(S)))
+    bpi = int(lib.sc_isosurface_blocks_per_image(S))
     if bpi <= 0:
         raise RuntimeError("shapeclipper_amd: isosurface_triangles needs 2 <= grid side <= 1024, got %d" % S)
     counts = torch.empty(B * bpi, device=level.device, dtype=torch.int32)           # triangles per workgroup of 1,024 cubes
     masks = None
     if method == "cubes":       # the case index of every cube goes from the count pass to the emit pass (1 byte per cube)
         masks = torch.empty(B * (S - 1) ** 3, device=level.device, dtype=torch.uint8)
-        _lib.check(lib.sc_marching_cubes_block_count_masks(_lib.ptr(level), c_int(B), c_int(S), ctypes.c_float(iso), _lib.ptr(counts), _lib.ptr(masks),
+        _lib.check(lib.sc_marching_cubes_block_count_masks(_lib.ptr(level), B, S, iso, _lib.ptr(counts), _lib.ptr(masks),
                                                            _lib.stream()), "sc_marching_cubes_block_count_masks")
     else:
-        _lib.check(count_fn(_lib.ptr(level), c_int(B), c_int(S), ctypes.c_float(iso), _lib.ptr(counts), _lib.stream()), "sc_isosurface_block_count")
+        _lib.check(count_fn(_lib.ptr(level), B, S, iso, _lib.ptr(counts), _lib.stream()), "sc_isosurface_block_count")
     offsets = torch.empty(B * bpi + 1, device=level.device, dtype=torch.int64)      # exclusive prefix, the total last
     per_image = torch.empty(B, device=level.device, dtype=torch.int64)
-    _lib.check(lib.sc_isosurface_block_scan(_lib.ptr(counts), c_int(B), c_int(S), _lib.ptr(offsets), _lib.ptr(per_image), _lib.stream()),
+    _lib.check(lib.sc_isosurface_block_scan(_lib.ptr(counts), B, S, _lib.ptr(offsets), _lib.ptr(per_image), _lib.stream()),
                "sc_isosurface_block_scan")
     per_image = per_image.cpu()                                                       # the one host read: it sizes the output
     total = int(per_image.sum())
     tris = torch.empty(total, 3, 3, device=level.device, dtype=torch.float32)
     if total > 0 and masks is not None:
-        _lib.check(lib.sc_marching_cubes_block_emit_masks(_lib.ptr(level), c_int(B), c_int(S), ctypes.c_float(iso), _lib.ptr(offsets), _lib.ptr(masks),
+        _lib.check(lib.sc_marching_cubes_block_emit_masks(_lib.ptr(level), B, S, iso, _lib.ptr(offsets), _lib.ptr(masks),
                                                           _lib.ptr(tris), _lib.stream()), "sc_marching_cubes_block_emit_masks")
     elif total > 0:
-        _lib.check(emit_fn(_lib.ptr(level), c_int(B), c_int(S), ctypes.c_float(iso), _lib.ptr(offsets), _lib.ptr(tris), _lib.stream()),
+        _lib.check(emit_fn(_lib.ptr(level), B, S, iso, _lib.ptr(offsets), _lib.ptr(tris), _lib.stream()),
                    "sc_isosurface_block_emit / sc_marching_cubes_block_emit")
     return tris, per_image
 
@@ -734,25 +668,25 @@ def isosurface_mesh(level: torch.Tensor, iso: float = 0.0):
     level = level.contiguous().float()
     B, S = level.shape[0], level.shape[1]
     assert level.shape[1:] == (S, S, S)
-    bpi = int(lib.sc_isosurface_blocks_per_image(c_int(S)))
-    vbpi = int(lib.sc_marching_cubes_mesh_vertex_blocks_per_image(c_int(S)))
+    bpi = int(lib.sc_isosurface_blocks_per_image(S))
+    vbpi = int(lib.sc_marching_cubes_mesh_vertex_blocks_per_image(S))
     if bpi <= 0 or vbpi <= 0:
         raise RuntimeError("shapeclipper_amd: isosurface_mesh needs 2 <= grid side <= 1024, got %d" % S)
-    dev, c_iso = level.device, ctypes.c_float(iso)
+    dev = level.device
     counts = torch.empty(B * bpi, device=dev, dtype=torch.int32)                    # triangles per workgroup of 1,024 cubes
     masks = torch.empty(B * (S - 1) ** 3, device=dev, dtype=torch.uint8)            # case index per cube
-    _lib.check(lib.sc_marching_cubes_block_count_masks(_lib.ptr(level), c_int(B), c_int(S), c_iso, _lib.ptr(counts), _lib.ptr(masks),
+    _lib.check(lib.sc_marching_cubes_block_count_masks(_lib.ptr(level), B, S, iso, _lib.ptr(counts), _lib.ptr(masks),
                                                        _lib.stream()), "sc_marching_cubes_block_count_masks")
     offsets = torch.empty(B * bpi + 1, device=dev, dtype=torch.int64)
     f_count = torch.empty(B, device=dev, dtype=torch.int64)
-    _lib.check(lib.sc_isosurface_block_scan(_lib.ptr(counts), c_int(B), c_int(S), _lib.ptr(offsets), _lib.ptr(f_count), _lib.stream()),
+    _lib.check(lib.sc_isosurface_block_scan(_lib.ptr(counts), B, S, _lib.ptr(offsets), _lib.ptr(f_count), _lib.stream()),
                "sc_isosurface_block_scan")
     vcounts = torch.empty(B * vbpi, device=dev, dtype=torch.int32)                  # crossing edges per workgroup of 1,024 grid points
-    _lib.check(lib.sc_marching_cubes_mesh_vertex_count(_lib.ptr(level), c_int(B), c_int(S), c_iso, _lib.ptr(vcounts), _lib.stream()),
+    _lib.check(lib.sc_marching_cubes_mesh_vertex_count(_lib.ptr(level), B, S, iso, _lib.ptr(vcounts), _lib.stream()),
                "sc_marching_cubes_mesh_vertex_count")
     voffsets = torch.empty(B * vbpi + 1, device=dev, dtype=torch.int64)
     v_count = torch.empty(B, device=dev, dtype=torch.int64)
-    _lib.check(lib.sc_marching_cubes_mesh_vertex_scan(_lib.ptr(vcounts), c_int(B), c_int(S), _lib.ptr(voffsets), _lib.ptr(v_count), _lib.stream()),
+    _lib.check(lib.sc_marching_cubes_mesh_vertex_scan(_lib.ptr(vcounts), B, S, _lib.ptr(voffsets), _lib.ptr(v_count), _lib.stream()),
                "sc_marching_cubes_mesh_vertex_scan")
     counts_host = torch.stack([v_count, f_count]).cpu()                             # the one host read: it sizes both outputs
     v_count, f_count = counts_host[0], counts_host[1]
@@ -764,10 +698,10 @@ def isosurface_mesh(level: torch.Tensor, iso: float = 0.0):
     faces = torch.empty(F, 3, device=dev, dtype=torch.int32)
     if V > 0:
         vmap = torch.empty(B * S ** 3 * 3, device=dev, dtype=torch.int32)          # vertex number per (grid point, axis); no fill
-        _lib.check(lib.sc_marching_cubes_mesh_vertex_emit(_lib.ptr(level), c_int(B), c_int(S), c_iso, _lib.ptr(voffsets), _lib.ptr(verts),
+        _lib.check(lib.sc_marching_cubes_mesh_vertex_emit(_lib.ptr(level), B, S, iso, _lib.ptr(voffsets), _lib.ptr(verts),
                                                           _lib.ptr(vmap), _lib.stream()), "sc_marching_cubes_mesh_vertex_emit")
         if F > 0:
-            _lib.check(lib.sc_marching_cubes_mesh_face_emit(c_int(B), c_int(S), _lib.ptr(offsets), _lib.ptr(masks), _lib.ptr(vmap), _lib.ptr(faces),
+            _lib.check(lib.sc_marching_cubes_mesh_face_emit(B, S, _lib.ptr(offsets), _lib.ptr(masks), _lib.ptr(vmap), _lib.ptr(faces),
                                                             _lib.stream()), "sc_marching_cubes_mesh_face_emit")
     return verts, faces, v_count, f_count
 
@@ -779,7 +713,7 @@ def camera_rays_forward(pose, intr, ray_idx, n_rays, width):
     cam_loc = torch.empty(B * n_rays, 3, **f32)
     dirs = torch.empty(B * n_rays, 3, **f32)
     depth_fac = torch.empty(B * n_rays, **f32)
-    _lib.check(lib.sc_camera_rays_forward(_lib.ptr(pose), _lib.ptr(intr), _lib.ptr(ray_idx), c_int(B), c_int(n_rays), c_int(width),
+    _lib.check(lib.sc_camera_rays_forward(_lib.ptr(pose), _lib.ptr(intr), _lib.ptr(ray_idx), B, n_rays, width,
                                           _lib.ptr(cam_loc), _lib.ptr(dirs), _lib.ptr(depth_fac), _lib.stream()),
                "sc_camera_rays_forward")
     return cam_loc, dirs, depth_fac
@@ -789,7 +723,7 @@ def camera_rays_backward(pose, intr, ray_idx, n_rays, width, g_cam_loc, g_dirs, 
     lib = _lib.load()
     B = pose.shape[0]
     g_pose, g_intr = torch.empty_like(pose), torch.empty_like(intr)
-    _lib.check(lib.sc_camera_rays_backward(_lib.ptr(pose), _lib.ptr(intr), _lib.ptr(ray_idx), c_int(B), c_int(n_rays), c_int(width),
+    _lib.check(lib.sc_camera_rays_backward(_lib.ptr(pose), _lib.ptr(intr), _lib.ptr(ray_idx), B, n_rays, width,
                                            _lib.ptr(g_cam_loc), _lib.ptr(g_dirs), _lib.ptr(g_depth_fac), _lib.ptr(g_pose),
                                            _lib.ptr(g_intr), _lib.stream()), "sc_camera_rays_backward")
     return g_pose, g_intr
@@ -801,8 +735,8 @@ def pose_from_trig_forward(azim, elev, theta, scale_focal, scale_dist, cam_dist,
     pose = torch.empty(B, 3, 4, device=azim.device, dtype=torch.float32)
     intr = torch.empty(B, 3, 3, device=azim.device, dtype=torch.float32)
     _lib.check(lib.sc_pose_from_trig_forward(_lib.ptr(azim), _lib.ptr(elev), _lib.ptr(theta), _lib.ptr(scale_focal),
-                                             _lib.ptr(scale_dist), c_int(B), ctypes.c_float(cam_dist), ctypes.c_float(focal),
-                                             c_int(width), c_int(height), _lib.ptr(pose), _lib.ptr(intr), _lib.stream()),
+                                             _lib.ptr(scale_dist), B, cam_dist, focal,
+                                             width, height, _lib.ptr(pose), _lib.ptr(intr), _lib.stream()),
                "sc_pose_from_trig_forward")
     return pose, intr
 
@@ -813,8 +747,8 @@ def pose_from_trig_backward(azim, elev, theta, scale_focal, scale_dist, cam_dist
     g = torch.empty(8, B, device=azim.device, dtype=torch.float32)      # azim[B,2] | elev[B,2] | theta[B,2] | sf[B] | sd[B]
     ga, ge, gt = g[0:2].view(B, 2), g[2:4].view(B, 2), g[4:6].view(B, 2)
     _lib.check(lib.sc_pose_from_trig_backward(_lib.ptr(azim), _lib.ptr(elev), _lib.ptr(theta), _lib.ptr(scale_focal),
-                                              _lib.ptr(scale_dist), c_int(B), ctypes.c_float(cam_dist), ctypes.c_float(focal),
-                                              c_int(width), c_int(height), _lib.ptr(g_pose), _lib.ptr(g_intr), _lib.ptr(ga),
+                                              _lib.ptr(scale_dist), B, cam_dist, focal,
+                                              width, height, _lib.ptr(g_pose), _lib.ptr(g_intr), _lib.ptr(ga),
                                               _lib.ptr(ge), _lib.ptr(gt), _lib.ptr(g[6]), _lib.ptr(g[7]), _lib.stream()),
                "sc_pose_from_trig_backward")
     return ga, ge, gt, g[6], g[7]
@@ -822,9 +756,6 @@ def pose_from_trig_backward(azim, elev, theta, scale_focal, scale_dist, cam_dist
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # the [B]-sized arithmetic around the view estimator (csrc/camera_prior.hip)
-c_float = ctypes.c_float
-
-
 def _ptr_array(tensors):
     """HOST array of device pointers (NULL for None) for the entry points that take `const float* const*`."""
     return (ctypes.c_void_p * max(len(tensors), 1))(*[_lib.ptr(t).value for t in tensors])
@@ -841,8 +772,8 @@ def estimator_head_forward(trig, size_lin, persp_lin, size_range, persp_range):
     lib = _lib.load()
     N = trig.shape[0]
     o = torch.empty(8 * N, device=trig.device, dtype=torch.float32)
-    _lib.check(lib.sc_estimator_head_forward(_lib.ptr(trig), _lib.ptr(size_lin), _lib.ptr(persp_lin), c_int(N), c_float(size_range),
-                                             c_float(persp_range), _lib.ptr(o[0:2 * N]), _lib.ptr(o[2 * N:4 * N]), _lib.ptr(o[4 * N:6 * N]),
+    _lib.check(lib.sc_estimator_head_forward(_lib.ptr(trig), _lib.ptr(size_lin), _lib.ptr(persp_lin), N, size_range,
+                                             persp_range, _lib.ptr(o[0:2 * N]), _lib.ptr(o[2 * N:4 * N]), _lib.ptr(o[4 * N:6 * N]),
                                              _lib.ptr(o[6 * N:7 * N]), _lib.ptr(o[7 * N:8 * N]), _lib.stream()), "sc_estimator_head_forward")
     return o
 
@@ -853,8 +784,8 @@ def estimator_head_backward(trig, size_lin, persp_lin, size_range, persp_range, 
     N = trig.shape[0]
     g = torch.empty(8 * N, device=trig.device, dtype=torch.float32)
     grads = [_f32c(t) for t in grads]
-    _lib.check(lib.sc_estimator_head_backward(_lib.ptr(trig), _lib.ptr(size_lin), _lib.ptr(persp_lin), c_int(N), c_float(size_range),
-                                              c_float(persp_range), _ptr_array(grads), c_int(n_groups), _lib.ptr(g[:6 * N]),
+    _lib.check(lib.sc_estimator_head_backward(_lib.ptr(trig), _lib.ptr(size_lin), _lib.ptr(persp_lin), N, size_range,
+                                              persp_range, _ptr_array(grads), n_groups, _lib.ptr(g[:6 * N]),
                                               _lib.ptr(g[6 * N:7 * N]), _lib.ptr(g[7 * N:]), _lib.stream()), "sc_estimator_head_backward")
     return g[:6 * N].view(N, 6), g[6 * N:7 * N], g[7 * N:]
 
@@ -876,8 +807,8 @@ def camera_prior_forward(azim, elev, theta, f_azim, f_elev, f_theta, elev_range,
     out = torch.empty(3, device=azim.device, dtype=torch.float32)
     grads = torch.empty(6, B, 2, device=azim.device, dtype=torch.float32)
     _lib.check(lib.sc_camera_prior_forward(_lib.ptr(azim), _lib.ptr(elev), _lib.ptr(theta), _lib.ptr(f_azim), _lib.ptr(f_elev),
-                                           _lib.ptr(f_theta), c_int(B), c_float(elev_range[0]), c_float(elev_range[1]),
-                                           c_float(theta_range[0]), c_float(theta_range[1]), c_float(margin_eps), c_int(emd_p),
+                                           _lib.ptr(f_theta), B, elev_range[0], elev_range[1],
+                                           theta_range[0], theta_range[1], margin_eps, emd_p,
                                            _lib.ptr(out), _lib.ptr(grads), _lib.stream()), "sc_camera_prior_forward")
     return out, grads
 
@@ -887,7 +818,7 @@ def camera_prior_backward(grads, G_margin, G_uniform, G_sym):
     lib = _lib.load()
     B = grads.shape[1]
     g = torch.empty(6, B, 2, device=grads.device, dtype=torch.float32)
-    _lib.check(lib.sc_camera_prior_backward(_lib.ptr(grads), c_int(B), _lib.ptr(_f32c(G_margin)), _lib.ptr(_f32c(G_uniform)),
+    _lib.check(lib.sc_camera_prior_backward(_lib.ptr(grads), B, _lib.ptr(_f32c(G_margin)), _lib.ptr(_f32c(G_uniform)),
                                             _lib.ptr(_f32c(G_sym)), *[_lib.ptr(g[k]) for k in range(6)], _lib.stream()),
                "sc_camera_prior_backward")
     return g
@@ -897,7 +828,7 @@ def transform_normal_forward(normals, pose):
     lib = _lib.load()
     B, R = normals.shape[0], normals.shape[1]
     out = torch.empty(B, R, 3, device=normals.device, dtype=torch.float32)
-    _lib.check(lib.sc_transform_normal_forward(_lib.ptr(normals), _lib.ptr(pose), c_int(B), c_int(R), _lib.ptr(out), _lib.stream()),
+    _lib.check(lib.sc_transform_normal_forward(_lib.ptr(normals), _lib.ptr(pose), B, R, _lib.ptr(out), _lib.stream()),
                "sc_transform_normal_forward")
     return out
 
@@ -906,7 +837,7 @@ def transform_normal_backward(normals, g_out):
     lib = _lib.load()
     B, R = normals.shape[0], normals.shape[1]
     g_pose = torch.empty(B, 3, 4, device=normals.device, dtype=torch.float32)
-    _lib.check(lib.sc_transform_normal_backward(_lib.ptr(normals), _lib.ptr(g_out), c_int(B), c_int(R), _lib.ptr(g_pose), _lib.stream()),
+    _lib.check(lib.sc_transform_normal_backward(_lib.ptr(normals), _lib.ptr(g_out), B, R, _lib.ptr(g_pose), _lib.stream()),
                "sc_transform_normal_backward")
     return g_pose
 
@@ -920,8 +851,8 @@ def loss_total_forward(values, weights):
     dev = values[0].device
     total = torch.empty((), device=dev, dtype=torch.float32)
     bad = torch.empty((), device=dev, dtype=torch.bool)
-    w = (c_float * len(weights))(*weights)
-    _lib.check(lib.sc_loss_total_forward(_ptr_array(values), w, c_int(len(values)), _lib.ptr(total), _lib.ptr(bad), _lib.stream()),
+    w = (ctypes.c_float * len(weights))(*weights)
+    _lib.check(lib.sc_loss_total_forward(_ptr_array(values), w, len(values), _lib.ptr(total), _lib.ptr(bad), _lib.stream()),
                "sc_loss_total_forward")
     return total, bad
 
@@ -929,8 +860,8 @@ def loss_total_forward(values, weights):
 def loss_total_backward(weights, G):
     lib = _lib.load()
     g = torch.empty(len(weights), device=G.device, dtype=torch.float32)
-    w = (c_float * len(weights))(*weights)
-    _lib.check(lib.sc_loss_total_backward(w, c_int(len(weights)), _lib.ptr(_f32c(G)), _lib.ptr(g), _lib.stream()), "sc_loss_total_backward")
+    w = (ctypes.c_float * len(weights))(*weights)
+    _lib.check(lib.sc_loss_total_backward(w, len(weights), _lib.ptr(_f32c(G)), _lib.ptr(g), _lib.stream()), "sc_loss_total_backward")
     return g
 
 
@@ -961,9 +892,6 @@ def conv3x3_pack(w, side, transpose_flip=False, split=False):
     return w_pack
 
 
-_conv_ws = {}
-
-
 def set_reserved_cus(n: int) -> int:
     """Size the persistent convolution grids for (device CUs - n) compute units (sc_set_reserved_cus; `--hip.reserve_cus`): leaves n CUs
     to concurrently running kernels of other streams (RCCL's all-reduce in a multi-GPU step).  Returns the resulting grid size.  The cached
@@ -973,19 +901,16 @@ def set_reserved_cus(n: int) -> int:
     _lib.check(lib.sc_set_reserved_cus(int(n)), "sc_set_reserved_cus")
     after = lib.sc_grid_cus()
     if after != before:
-        _conv_ws.clear()
+        for key in [k for k in _SCRATCH if k[0].startswith("conv")]:
+            del _SCRATCH[key]
     return after
 
 
 def _conv_workspace(dev, side, split=False):
-    """Scratch for the partial tiles of sc_conv3x3_forward, one per (device, stream, map side): calls on a stream are ordered."""
-    key = (dev.index, _lib.raw_stream(dev.index), side, split)
-    ws = _conv_ws.get(key)
-    if ws is None:
-        lib = _lib.load()
-        n = (lib.sc_conv3x3_workspace_floats_split if split else lib.sc_conv3x3_workspace_floats)(side)
-        ws = _conv_ws[key] = torch.empty(n, device=dev, dtype=torch.float32)
-    return ws
+    """Scratch for the partial tiles of sc_conv3x3_forward, one per (device, stream, map side, arithmetic)."""
+    lib = _lib.load()
+    n = (lib.sc_conv3x3_workspace_floats_split if split else lib.sc_conv3x3_workspace_floats)(side)
+    return _scratch("conv3x3 %d %d" % (side, split), dev, n)
 
 
 def conv3x3_apply(x, w_pack, cout, split=False):
@@ -1029,10 +954,7 @@ def conv3x3_backward_weight(gy, x, split=False):
     n = lib.sc_conv3x3_wgrad_workspace_floats(cin, cout)
     if n < 0 or H not in CONV3X3_SIDES or x.shape[0] != B or tuple(x.shape[2:]) != (H, H):
         raise RuntimeError("shapeclipper_amd: sc_conv3x3_wgrad does not take gy %s with x %s" % (tuple(gy.shape), tuple(x.shape)))
-    key = (x.device.index, _lib.raw_stream(x.device.index), "wgrad")
-    ws = _conv_ws.get(key)
-    if ws is None or ws.numel() < n:
-        ws = _conv_ws[key] = torch.empty(n, device=x.device, dtype=torch.float32)
+    ws = _scratch("conv wgrad", x.device, n)
     dw = torch.empty(cout, cin, 3, 3, device=x.device, dtype=torch.float32)
     fn = lib.sc_conv3x3_wgrad_split if split else lib.sc_conv3x3_wgrad
     _lib.check(fn(_lib.ptr(gy), _lib.ptr(x), _lib.ptr(dw), _lib.ptr(ws), B, cin, cout, H, _lib.stream()), "sc_conv3x3_wgrad")
@@ -1040,37 +962,17 @@ def conv3x3_backward_weight(gy, x, split=False):
 
 
 # ---- one C call per BasicBlock (csrc/block.hip; include/shapeclipper_hip.h: sc_block_args) ---------------------------------------------
-_P = ctypes.c_void_p
-
-
 class BlockArgs(ctypes.Structure):
     """ctypes mirror of sc_block_args (field order and types of include/shapeclipper_hip.h)."""
-    _fields_ = ([(n, _P) for n in ("x", "pf1", "pf2", "pb1", "pb2", "g1", "b1", "g2", "b2", "rm1", "rv1", "rm2", "rv2", "nt1", "nt2",
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("x", "pf1", "pf2", "pb1", "pb2", "g1", "b1", "g2", "b2", "rm1", "rv1", "rm2", "rv2", "nt1", "nt2",
                                    "y1", "a1", "y2", "out", "st1", "st2", "conv_ws", "bn_ws", "wgrad_ws", "d_out",
                                    "dy2", "dres", "da1", "dy1", "dx", "gw1", "gw2", "dgb1", "dgb2")]
                 + [(n, ctypes.c_int) for n in ("batch", "channels", "hw", "groups", "training", "split", "need_dx")]
                 + [(n, ctypes.c_float) for n in ("mom1", "eps1", "mom2", "eps2")])
 
 
-_block_fn = {}
-
-
-def _block(name):
-    fn = _block_fn.get(name)
-    if fn is None:
-        fn = getattr(_lib.load()._cdll, name)
-        fn.argtypes, fn.restype = (ctypes.POINTER(BlockArgs), ctypes.c_void_p), ctypes.c_int
-        _block_fn[name] = fn
-    return fn
-
-
 def _wgrad_workspace(x, cin, cout):
-    n = _lib.load().sc_conv3x3_wgrad_workspace_floats(cin, cout)
-    key = (x.device.index, _lib.raw_stream(x.device.index), "wgrad")
-    ws = _conv_ws.get(key)
-    if ws is None or ws.numel() < n:
-        ws = _conv_ws[key] = torch.empty(n, device=x.device, dtype=torch.float32)
-    return ws
+    return _scratch("conv wgrad", x.device, _lib.load().sc_conv3x3_wgrad_workspace_floats(cin, cout))
 
 
 def basic_block_forward(x, pf1, pf2, g1, b1, g2, b2, bn1_state, bn2_state, split, groups):
@@ -1082,7 +984,6 @@ def basic_block_forward(x, pf1, pf2, g1, b1, g2, b2, bn1_state, bn2_state, split
     rm2, rv2, nt2, _, mom2, eps2 = bn2_state
     y1, a1, y2, out = (torch.empty_like(x) for _ in range(4))
     st = torch.empty(2, 2, groups, C, device=x.device, dtype=torch.float32)
-    stream = _lib.raw_stream(x.get_device())
     a = BlockArgs()
     a.x, a.pf1, a.pf2 = x.data_ptr(), pf1.data_ptr(), pf2.data_ptr()
     a.g1, a.b1, a.g2, a.b2 = g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), b2.data_ptr()
@@ -1092,7 +993,7 @@ def basic_block_forward(x, pf1, pf2, g1, b1, g2, b2, bn1_state, bn2_state, split
     a.conv_ws, a.bn_ws = _conv_workspace(x.device, H, split).data_ptr(), _bn_partial(x, groups)
     a.batch, a.channels, a.hw, a.groups, a.training, a.split = B, C, H, groups, 1 if training else 0, 1 if split else 0
     a.mom1, a.eps1, a.mom2, a.eps2 = mom1, eps1, mom2, eps2
-    code = _block("sc_basic_block_forward")(ctypes.byref(a), stream)
+    code = _lib.load().sc_basic_block_forward(ctypes.byref(a), _lib.raw_stream(x.get_device()))
     if code:
         _lib.check(code, "sc_basic_block_forward")
     return out, (y1, a1, y2, st[0], st[1])
@@ -1108,7 +1009,6 @@ def basic_block_backward(d_out, x, saved, out, pb1, pb2, g1, b1, g2, b2, trainin
     gw1 = torch.empty(C, C, 3, 3, device=x.device, dtype=torch.float32) if need_w1 else None
     gw2 = torch.empty(C, C, 3, 3, device=x.device, dtype=torch.float32) if need_w2 else None
     dgb = torch.empty(2, 2, C, device=x.device, dtype=torch.float32)
-    stream = _lib.raw_stream(x.get_device())
     a = BlockArgs()
     a.x, a.pb1, a.pb2, a.d_out = x.data_ptr(), pb1.data_ptr(), pb2.data_ptr(), d_out.data_ptr()
     a.g1, a.b1, a.g2, a.b2 = g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), b2.data_ptr()
@@ -1118,7 +1018,7 @@ def basic_block_backward(d_out, x, saved, out, pb1, pb2, g1, b1, g2, b2, trainin
     a.conv_ws, a.bn_ws = _conv_workspace(x.device, H, split).data_ptr(), _bn_partial(x, groups)
     a.wgrad_ws = _wgrad_workspace(x, C, C).data_ptr() if (need_w1 or need_w2) else None
     a.batch, a.channels, a.hw, a.groups, a.training, a.split, a.need_dx = B, C, H, groups, 1 if training else 0, 1 if split else 0, 1 if need_dx else 0
-    code = _block("sc_basic_block_backward")(ctypes.byref(a), stream)
+    code = _lib.load().sc_basic_block_backward(ctypes.byref(a), _lib.raw_stream(x.get_device()))
     if code:
         _lib.check(code, "sc_basic_block_backward")
     return dx, gw1, dgb[0, 0], dgb[0, 1], gw2, dgb[1, 0], dgb[1, 1]
@@ -1140,10 +1040,7 @@ def conv_stem_forward(x, w):
 def conv_stem_backward_weight(gy, x):
     lib = _lib.load()
     gy, x = _aligned(gy), _aligned(x)
-    key = (x.device.index, _lib.raw_stream(x.device.index), "stem")
-    ws = _conv_ws.get(key)
-    if ws is None:
-        ws = _conv_ws[key] = torch.empty(lib.sc_conv_stem_wgrad_workspace_floats(), device=x.device, dtype=torch.float32)
+    ws = _scratch("conv stem", x.device, lib.sc_conv_stem_wgrad_workspace_floats())
     dw = torch.empty(64, 3, 7, 7, device=x.device, dtype=torch.float32)
     _lib.check(lib.sc_conv_stem_wgrad(_lib.ptr(gy), _lib.ptr(x), _lib.ptr(dw), _lib.ptr(ws), x.shape[0], _lib.stream()), "sc_conv_stem_wgrad")
     return dw
@@ -1180,10 +1077,7 @@ def conv1x1s2_backward_weight(gy, x):
     B, cin, H, _ = x.shape
     cout = gy.shape[1]
     n = lib.sc_conv1x1s2_wgrad_workspace_floats(cin, cout)
-    key = (x.device.index, _lib.raw_stream(x.device.index), "1x1s2")
-    ws = _conv_ws.get(key)
-    if ws is None or ws.numel() < n:
-        ws = _conv_ws[key] = torch.empty(n, device=x.device, dtype=torch.float32)
+    ws = _scratch("conv 1x1s2", x.device, n)
     dw = torch.empty(cout, cin, 1, 1, device=x.device, dtype=torch.float32)
     _lib.check(lib.sc_conv1x1s2_wgrad(_lib.ptr(gy), _lib.ptr(x), _lib.ptr(dw), _lib.ptr(ws), B, cin, cout, H, _lib.stream()), "sc_conv1x1s2_wgrad")
     return dw
@@ -1206,10 +1100,7 @@ def conv3x3s2_forward(x, w):
         raise RuntimeError("shapeclipper_amd: sc_conv3x3s2 does not take [%d, %d, %d, %d] * %s" % (B, cin, H, H, tuple(w.shape)))
     w_pack = torch.empty(n, device=x.device, dtype=torch.float32)
     _lib.check(lib.sc_conv3x3_pack(_lib.ptr(w), _lib.ptr(w_pack), cin, cout, H, 4, _lib.stream()), "sc_conv3x3_pack")
-    key = (x.device.index, _lib.raw_stream(x.device.index), H, "s2")
-    ws = _conv_ws.get(key)
-    if ws is None:
-        ws = _conv_ws[key] = torch.empty(lib.sc_conv3x3s2_workspace_floats(H), device=x.device, dtype=torch.float32)
+    ws = _scratch("conv s2 %d" % H, x.device, lib.sc_conv3x3s2_workspace_floats(H))
     out = torch.empty(B, cout, H // 2, H // 2, device=x.device, dtype=torch.float32)
     _lib.check(lib.sc_conv3x3s2_forward(_lib.ptr(x), _lib.ptr(w_pack), _lib.ptr(out), _lib.ptr(ws), B, cin, cout, H, _lib.stream()),
                "sc_conv3x3s2_forward")
@@ -1232,10 +1123,7 @@ def conv3x3s2_backward_data(gy, w, hw):
         raise RuntimeError("shapeclipper_amd: sc_conv3x3s2_backward_data does not take gy %s with w %s" % (tuple(gy.shape), tuple(w.shape)))
     w_pack = torch.empty(n, device=gy.device, dtype=torch.float32)
     _lib.check(lib.sc_conv3x3s2_bd_pack(_lib.ptr(w), _lib.ptr(w_pack), cin, cout, hw, _lib.stream()), "sc_conv3x3s2_bd_pack")
-    key = (gy.device.index, _lib.raw_stream(gy.device.index), hw, "s2bd")
-    ws = _conv_ws.get(key)
-    if ws is None:
-        ws = _conv_ws[key] = torch.empty(lib.sc_conv3x3s2_bd_workspace_floats(hw), device=gy.device, dtype=torch.float32)
+    ws = _scratch("conv s2bd %d" % hw, gy.device, lib.sc_conv3x3s2_bd_workspace_floats(hw))
     gx = torch.empty(B, cin, hw, hw, device=gy.device, dtype=torch.float32)
     _lib.check(lib.sc_conv3x3s2_backward_data(_lib.ptr(gy), _lib.ptr(w_pack), _lib.ptr(gx), _lib.ptr(ws), B, cin, cout, hw, _lib.stream()),
                "sc_conv3x3s2_backward_data")
@@ -1251,10 +1139,7 @@ def conv3x3s2_backward_weight(gy, x):
     n = lib.sc_conv3x3_wgrad_workspace_floats(cin, cout)
     if n < 0 or hw not in (56, 28, 14) or tuple(gy.shape) != (B, cout, hw // 2, hw // 2):
         raise RuntimeError("shapeclipper_amd: sc_conv3x3s2_wgrad does not take gy %s with x %s" % (tuple(gy.shape), tuple(x.shape)))
-    key = (x.device.index, _lib.raw_stream(x.device.index), "wgrad")
-    ws = _conv_ws.get(key)
-    if ws is None or ws.numel() < n:
-        ws = _conv_ws[key] = torch.empty(n, device=x.device, dtype=torch.float32)
+    ws = _scratch("conv wgrad", x.device, n)
     dw = torch.empty(cout, cin, 3, 3, device=x.device, dtype=torch.float32)
     _lib.check(lib.sc_conv3x3s2_wgrad(_lib.ptr(gy), _lib.ptr(x), _lib.ptr(dw), _lib.ptr(ws), B, cin, cout, hw, _lib.stream()), "sc_conv3x3s2_wgrad")
     return dw
@@ -1309,7 +1194,7 @@ class Conv3x3PackSet:
 
 # ---- fused 1x1 bottleneck blocks (csrc/bottleneck.hip) ----------------------------------------------------------------------------------
 def linear_bn_supported(N, Cin, Cout, groups) -> bool:
-    return bool(_lib.load().sc_linear_bn_supported(c_int(N), c_int(Cin), c_int(Cout), c_int(groups)))
+    return bool(_lib.load().sc_linear_bn_supported(N, Cin, Cout, groups))
 
 
 def linear_bn_forward(x, w, gamma, beta, res, running_mean, running_var, n_tracked, training, momentum, eps, relu, groups):
@@ -1320,8 +1205,8 @@ def linear_bn_forward(x, w, gamma, beta, res, running_mean, running_var, n_track
     stats = torch.empty(2, groups, Cout, device=x.device, dtype=torch.float32)
     code = _lib.load().sc_linear_bn_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(res), _lib.ptr(y), _lib.ptr(out),
                                             _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.ptr(running_mean), _lib.ptr(running_var), _lib.ptr(n_tracked),
-                                            c_int(N), c_int(Cin), c_int(Cout), c_int(groups), c_int(1 if training else 0), c_int(1 if relu else 0),
-                                            ctypes.c_float(eps), ctypes.c_float(momentum), _lib.stream())
+                                            N, Cin, Cout, groups, 1 if training else 0, 1 if relu else 0,
+                                            eps, momentum, _lib.stream())
     _lib.check(code, "sc_linear_bn_forward")
     return out, y, stats
 
@@ -1337,10 +1222,10 @@ def linear_bn_backward(g_out, gy_next, w_next, g_add, out, y, stats, gamma, x, w
     dw = torch.empty(Cout, Cin, **f32)
     dgb = torch.empty(2, Cout, **f32)
     code = _lib.load().sc_linear_bn_backward(_lib.ptr(g_out), _lib.ptr(gy_next), _lib.ptr(w_next), _lib.ptr(g_add),
-                                             c_int(gy_next.shape[1] if gy_next is not None else 0), _lib.ptr(out), _lib.ptr(y), _lib.ptr(stats[0]),
+                                             gy_next.shape[1] if gy_next is not None else 0, _lib.ptr(out), _lib.ptr(y), _lib.ptr(stats[0]),
                                              _lib.ptr(stats[1]), _lib.ptr(gamma), _lib.ptr(x), _lib.ptr(gy), _lib.ptr(g_res), _lib.ptr(dw),
-                                             _lib.ptr(dgb[0]), _lib.ptr(dgb[1]), c_int(N), c_int(Cin), c_int(Cout), c_int(groups),
-                                             c_int(1 if training else 0), c_int(1 if relu else 0), _lib.stream())
+                                             _lib.ptr(dgb[0]), _lib.ptr(dgb[1]), N, Cin, Cout, groups,
+                                             1 if training else 0, 1 if relu else 0, _lib.stream())
     _lib.check(code, "sc_linear_bn_backward")
     return gy, g_res, dw, dgb[0], dgb[1]
 
@@ -1350,7 +1235,7 @@ def linear_backward_data(gy, w, g_add):
     N, Cout = gy.shape
     Cin = w.shape[1]
     dx = torch.empty(N, Cin, device=gy.device, dtype=torch.float32)
-    _lib.check(_lib.load().sc_linear_backward_data(_lib.ptr(gy), _lib.ptr(w), _lib.ptr(g_add), _lib.ptr(dx), c_int(N), c_int(Cin), c_int(Cout),
+    _lib.check(_lib.load().sc_linear_backward_data(_lib.ptr(gy), _lib.ptr(w), _lib.ptr(g_add), _lib.ptr(dx), N, Cin, Cout,
                                                    _lib.stream()), "sc_linear_backward_data")
     return dx
 
@@ -1360,8 +1245,8 @@ def latent_bias_forward(z, lat, bias, post):
     B, Z = z.shape
     L, NL = lat.shape[0] // 64, bias.shape[0]
     out = torch.empty(B, NL, 64, device=z.device, dtype=torch.float32)
-    _lib.check(_lib.load().sc_latent_bias_forward(_lib.ptr(z), _lib.ptr(lat), _lib.ptr(bias), _lib.ptr(post), _lib.ptr(out), c_int(B), c_int(Z), c_int(L),
-                                                  c_int(NL), _lib.stream()), "sc_latent_bias_forward")
+    _lib.check(_lib.load().sc_latent_bias_forward(_lib.ptr(z), _lib.ptr(lat), _lib.ptr(bias), _lib.ptr(post), _lib.ptr(out), B, Z, L,
+                                                  NL, _lib.stream()), "sc_latent_bias_forward")
     return out
 
 
@@ -1372,7 +1257,7 @@ def latent_bias_backward(g, z, lat, post, NL, want_z=True):
     g_z = torch.empty(B, Z, **f32) if want_z else None
     g_lat, g_bias = torch.empty(L * 64, Z, **f32), torch.empty(NL, 64, **f32)
     _lib.check(_lib.load().sc_latent_bias_backward(_lib.ptr(g), _lib.ptr(z), _lib.ptr(lat), _lib.ptr(post), _lib.ptr(g_z), _lib.ptr(g_lat), _lib.ptr(g_bias),
-                                                   c_int(B), c_int(Z), c_int(L), c_int(NL), _lib.stream()), "sc_latent_bias_backward")
+                                                   B, Z, L, NL, _lib.stream()), "sc_latent_bias_backward")
     return g_z, g_lat, g_bias
 
 
@@ -1397,7 +1282,7 @@ def silhouette_distance(masks: torch.Tensor) -> torch.Tensor:
     N, H, W = _silhouette_shape(masks, "silhouette_distance")
     masks = masks.contiguous().float()
     dist = torch.empty(N, H, W, device=masks.device, dtype=torch.float32)
-    code = _lib.load().sc_silhouette_distance(_lib.ptr(masks), c_int(N), c_int(H), c_int(W), _lib.ptr(dist), _lib.stream())
+    code = _lib.load().sc_silhouette_distance(_lib.ptr(masks), N, H, W, _lib.ptr(dist), _lib.stream())
     if code == _HIP_ERROR_INVALID_VALUE:
         raise ValueError("shapeclipper_amd: sc_silhouette_distance refused [%d,%d,%d]" % (N, H, W))
     _lib.check(code, "sc_silhouette_distance")
@@ -1419,7 +1304,7 @@ def silhouette_rays(dist: torch.Tensor, n_rays: int, uniform_fac: float, seeds: 
     dist = dist.contiguous().float()
     seeds = seeds.to(dist.device).contiguous()
     ray_idx = torch.empty(N, n_rays, device=dist.device, dtype=torch.int64)
-    code = _lib.load().sc_silhouette_rays(_lib.ptr(dist), c_int(N), c_int(H), c_int(W), c_int(n_rays), ctypes.c_double(float(uniform_fac)),
+    code = _lib.load().sc_silhouette_rays(_lib.ptr(dist), N, H, W, n_rays, float(uniform_fac),
                                           _lib.ptr(seeds), _lib.ptr(ray_idx), _lib.stream())
     if code == _HIP_ERROR_INVALID_VALUE:
         raise ValueError("shapeclipper_amd: sc_silhouette_rays refused [%d,%d,%d], n_rays %d" % (N, H, W, n_rays))
@@ -1458,9 +1343,9 @@ def clip_preprocess(rgba: torch.Tensor, n_px: int, bgcolor, tables=None) -> torc
     if B == 0:
         return out
     tmp = torch.empty(B, H, n_px, 4, device=rgba.device, dtype=torch.uint8)
-    code = _lib.load().sc_clip_preprocess(_lib.ptr(rgba), c_int(B), c_int(H), c_int(W), c_int(n_px), c_int(cp.background_byte(bgcolor)),
-                                          _lib.ptr(hb.contiguous()), _lib.ptr(hk.contiguous()), c_int(hk.shape[1]),
-                                          _lib.ptr(vb.contiguous()), _lib.ptr(vk.contiguous()), c_int(vk.shape[1]),
+    code = _lib.load().sc_clip_preprocess(_lib.ptr(rgba), B, H, W, n_px, cp.background_byte(bgcolor),
+                                          _lib.ptr(hb.contiguous()), _lib.ptr(hk.contiguous()), hk.shape[1],
+                                          _lib.ptr(vb.contiguous()), _lib.ptr(vk.contiguous()), vk.shape[1],
                                           _lib.ptr(tmp), _lib.ptr(out), _lib.stream())
     if code == _HIP_ERROR_INVALID_VALUE:
         raise ValueError("shapeclipper_amd: sc_clip_preprocess refused [%d,%d,%d,4] -> %d" % (B, H, W, n_px))
@@ -1487,7 +1372,7 @@ def vis_frames(x: torch.Tensor, kind: str, from_range=(0, 1)) -> torch.Tensor:
     scale = float(np.float32(1.0) / np.float32(hi - lo))        # torch divides by a Python number as a multiply by its fp32 reciprocal
     x = x.contiguous()
     out = torch.empty(*x.shape[:-1], 3, device=x.device, dtype=torch.uint8)
-    code = _lib.load().sc_vis_frames(_lib.ptr(x), ctypes.c_longlong(x.numel() // c), c_int(c), c_int(code), ctypes.c_float(lo),
-                                     ctypes.c_float(scale), _lib.ptr(out), _lib.stream())
+    code = _lib.load().sc_vis_frames(_lib.ptr(x), x.numel() // c, c, code, lo,
+                                     scale, _lib.ptr(out), _lib.stream())
     _lib.check(code, "sc_vis_frames")
     return out

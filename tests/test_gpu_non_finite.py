@@ -516,8 +516,9 @@ def test_rgb_composite_ignores_nan_padding_and_poisoned_blocks(split, n_images, 
 # the SDF backward (fused and non-fused) and ray sampling on NaN-padded inputs, NaN blocks waiting for their outputs and scratch
 # ---------------------------------------------------------------------------------------------------------------------------------
 def _poison_scratch():
-    """NaN into every cached scratch buffer of ops (forward scratch, parked second-order terms, partial images of the row sums and
-    of tbl_sum): each must be written before it is read."""
+    """NaN into every cached scratch buffer of ops -- ops._SCRATCH holds them all: forward scratch, parked second-order terms, partial
+    images of the row sums and of tbl_sum, and whatever BatchNorm / convolution workspaces earlier tests of the process left there:
+    each must be written before it is read."""
     from shapeclipper_amd import ops
     for v in ops._SCRATCH.values():
         v.fill_(float("nan"))
