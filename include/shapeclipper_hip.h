@@ -56,6 +56,26 @@ int sc_chamfer3d_backward(const float* xyz1, const float* xyz2, float* gradxyz1,
                           const float* graddist1, const float* graddist2, const int32_t* idx1,
                           const int32_t* idx2, int b, int n, int m, void* stream);
 
+/* The same gradient without float atomics, bitwise reproducible (csrc/chamfer_bwd.hip).  gradxyz1 / gradxyz2 are OVERWRITTEN:
+ * unlike sc_chamfer3d_backward there is no zero-fill contract, whatever they held on entry is gone.  Either may be NULL: that
+ * cloud's gradient is not formed and its passes are skipped.  Indices must satisfy 0 <= idx1 < m, 0 <= idx2 < n (what the
+ * forward entry points write).
+ * The term of source j of cloud 1 with k = idx1[b,j] is t = (2 * graddist1[b,j]) * (xyz1[b,j] - xyz2[b,k]), per component, every
+ * operation rounded to fp32 on its own (no fused multiply-add); direction 2 is the mirror image with idx2 / graddist2.
+ * Summation order, a function of the inputs only (not of b, the chip, the stream or sc_set_reserved_cus):
+ *   row gradxyz1[b,j] = t(j) + S, where S sums the terms -t(i) of the sources i of cloud 2 with idx2[b,i] == j (gradxyz2 alike);
+ *   the sources of a row are taken in ASCENDING source index and cut into chunks of C = sc_chamfer3d_backward_ordered_chunk()
+ *   consecutive list entries (the last one shorter); a chunk's partial sum is P = ((+0 + u0) + u1) + ... over its entries in
+ *   order, and S = ((+0 + P0) + P1) + ... over the chunks in order (S = +0 for a row nobody points at).
+ * b <= 0 returns 0 and writes nothing; n == 0 or m == 0 writes zeros to the non-empty gradient that was given (an empty opposite
+ * cloud gives no terms).  workspace: sc_chamfer3d_backward_ordered_workspace_bytes(b, n, m) bytes of device scratch, contents
+ * irrelevant on entry, the same size whichever gradients are asked for; nothing is allocated inside.  Launches on `stream`.  */
+long long sc_chamfer3d_backward_ordered_workspace_bytes(int b, int n, int m);
+int sc_chamfer3d_backward_ordered_chunk(void);
+int sc_chamfer3d_backward_ordered(const float* xyz1, const float* xyz2, float* gradxyz1, float* gradxyz2,
+                                  const float* graddist1, const float* graddist2, const int32_t* idx1,
+                                  const int32_t* idx2, int b, int n, int m, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Conditional SDF MLP, shipped architecture only (options/pix3d/config.yaml: 5 hidden x 64,
  * softplus(100), skips at layers 1,2, pos_enc 6, force_symmetry).

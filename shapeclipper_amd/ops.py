@@ -1376,3 +1376,20 @@ def vis_frames(x: torch.Tensor, kind: str, from_range=(0, 1)) -> torch.Tensor:
                                      scale, _lib.ptr(out), _lib.stream())
     _lib.check(code, "sc_vis_frames")
     return out
+
+
+# ---- Chamfer3D backward in a fixed summation order (csrc/chamfer_bwd.hip) -----------------------------------------------------------
+def chamfer_backward_ordered(xyz1, xyz2, graddist1, graddist2, idx1, idx2, want1=True, want2=True):
+    """-> (gradxyz1 [b,n,3] or None, gradxyz2 [b,m,3] or None): sc_chamfer3d_backward_ordered on torch's current stream; the gradient
+    that is not wanted is not formed.  Inputs fp32 / int32, contiguous, on one device (the caller checks); the workspace is the
+    "chamfer bwd" buffer of the scratch cache."""
+    lib = _lib.load()
+    b, n, m = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
+    g1 = torch.empty_like(xyz1) if want1 else None
+    g2 = torch.empty_like(xyz2) if want2 else None
+    words = (lib.sc_chamfer3d_backward_ordered_workspace_bytes(b, n, m) + 3) // 4
+    ws = _scratch("chamfer bwd", xyz1.device, words) if words else None
+    code = lib.sc_chamfer3d_backward_ordered(_lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(g1), _lib.ptr(g2), _lib.ptr(graddist1),
+                                             _lib.ptr(graddist2), _lib.ptr(idx1), _lib.ptr(idx2), b, n, m, _lib.ptr(ws), _lib.stream())
+    _lib.check(code, "sc_chamfer3d_backward_ordered")
+    return g1, g2
