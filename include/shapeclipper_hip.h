@@ -864,6 +864,27 @@ int sc_rgb_points_forward_split(const float* points, const float* grad, const fl
                                 float* rgb, float* normal, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Largest connected component of the solid of a level grid (csrc/level_components.hip): the stage between the level grid and the
+ * sc_marching_cubes_* / sc_isosurface_* entry points, for dropping detached "floaters".  level [n_images][S][S][S] fp32, S = n_axis.
+ *   inside:      a voxel is inside iff level < iso, the corner predicate of the meshers (NaN and +Inf are outside, -Inf is inside).
+ *   components:  of the inside voxels of ONE image under 6-connectivity (two voxels are joined iff they share a face; an edge or a
+ *                corner is not enough); never across images.
+ *   label:       the smallest linear index (x * S + y) * S + z of the component's voxels;  size: its voxel count.
+ *   kept:        the component of the largest size; among components of equal size the one with the smallest label.
+ *   level_out [n_images][S][S][S]: the bits of level everywhere (NaN payloads included), except at the inside voxels of components
+ *                that are not kept, which hold iso + (iso - level) -- the value reflected to the outside, one fp32 subtraction and one
+ *                fp32 addition (an exact sign flip for iso = 0).  level_out may be level itself.
+ *   n_components, inside_voxels, kept_voxels [n_images] int32: components, inside voxels and voxels of the kept component of each
+ *                image (0, 0, 0 without an inside voxel).  An image with no or one component comes back bit-identical.
+ * Integer atomics only: the same bits from run to run, whatever n_images, the stream or sc_set_reserved_cus.  Five launches on `stream`,
+ * no host synchronisation.  scratch: sc_level_largest_component_scratch_bytes(n_images, n_axis) bytes of device memory, 16-byte
+ * aligned, contents irrelevant on entry (the query gives 0 for sizes the entry point refuses).  n_images <= 0 returns 0 and launches
+ * nothing; hipErrorInvalidValue for n_images > 65535, n_axis outside [2, 1024], a NULL pointer or a misaligned scratch.            */
+long long sc_level_largest_component_scratch_bytes(int n_images, int n_axis);
+int sc_level_largest_component(const float* level, int n_images, int n_axis, float iso, float* level_out, int32_t* n_components,
+                               int32_t* inside_voxels, int32_t* kept_voxels, void* scratch, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Launch policy (csrc/device.hip) -- the one process-level setting of the library.  The persistent one-workgroup-per-CU grids
  * (stream-K 3x3 convolutions and their weight gradients, stem / 1x1 / stride-2 gradients) are sized for
  * sc_grid_cus() = device CUs - reserved.  Reserve CUs when another stream must make progress beside them: RCCL's

@@ -51,6 +51,11 @@ def _mesh_color(opt):
     return bool(opt.get("hip", {}).get("mesh_color", False))
 
 
+def _component_counts(var):
+    """(n_components, inside_voxels, kept_voxels) [B] of var.component_stats (eval_3D.eval_metrics with `--hip.largest_component`)."""
+    return tuple(var.component_stats[k] for k in ("n_components", "inside_voxels", "kept_voxels"))
+
+
 class Runner:
 
     def __init__(self, opt):
@@ -410,15 +415,16 @@ class Runner:
     def evaluate_sharded(self, opt, ep=0):
         """Evaluation over all ranks (BASELINE config[4]; the reference evaluates on one GPU, evaluate.py:16-18):
         rank r takes the test samples with index % world == r (eval.batch_size = 1), per-sample records are
-        gathered once, rank 0 writes chamfer.txt / cd_cat.txt / f_score.txt in sample order.  Every rank writes the per-sample files of
-        its own samples (dump_visuals: PNGs, mesh and point-cloud PLYs)."""
+        gathered once, rank 0 writes chamfer.txt / cd_cat.txt / f_score.txt in sample order (with --hip.largest_component also
+        components.txt, from a second gather of the per-sample counts).  Every rank writes the per-sample files of its own samples
+        (dump_visuals: PNGs, mesh and point-cloud PLYs)."""
         from ..parallel import gather_eval_records
         self.graph.eval()
         opt.H, opt.W = opt.eval.image_size
         # the reference's single-node convention is rank == device index; the process group's rank is the same number there and stays
         # right when ranks and devices are numbered differently (several nodes; tests/test_gpu_two_ranks.py: two ranks on one GPU)
         rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else util.get_rank(opt)
-        recs = []
+        recs, comps = [], []
         for it in range(rank, len(self.test_data), opt.world_size):
             sample = self.test_data[it]
             batch = {k: ({kk: vv[None] for kk, vv in v.items()} if isinstance(v, dict) else torch.as_tensor(v)[None]) for k, v in sample.items()}
@@ -427,10 +433,20 @@ class Runner:
             self.dump_visuals(opt, var, ep)             # this rank's samples only; rank 0 writes chamfer.txt once below
             recs.append(torch.cat([var.idx.float().view(1), var.cd_acc.view(1), var.cd_comp.view(1), var.f_score.view(-1),
                                    var.category_label.float().view(1)]))
+            if "component_stats" in var:                # --hip.largest_component: (idx, n_components, inside_voxels, kept_voxels), exact in float64
+                comps.append(torch.cat([t.view(1).double() for t in (var.idx, *_component_counts(var))]))
         dev = next(self.graph.parameters()).device
         records = torch.stack(recs) if recs else torch.zeros(0, 10, device=dev)
         allr = gather_eval_records(records.to(dev), opt.world_size).cpu()
+        allc = None
+        if eval_3D.largest_component_enabled(opt):      # every rank joins the second gather, also one that evaluated no sample
+            allc = gather_eval_records(torch.stack(comps).to(dev) if comps else torch.zeros(0, 4, device=dev, dtype=torch.float64),
+                                       opt.world_size).cpu()
         opt.H, opt.W = opt.image_size
+        if rank == 0 and allc is not None:
+            with open("{}/components.txt".format(opt.output_path), "w") as f:
+                for r in allc:
+                    f.write("{} {} {} {}\n".format(*(int(x) for x in r)))
         if rank == 0:
             with open("{}/chamfer.txt".format(opt.output_path), "w") as f:
                 for r in allr:
@@ -604,6 +620,10 @@ class Runner:
             with open("{}/chamfer.txt".format(opt.output_path), "w" if write_new else "a") as f:
                 for i, acc, comp in zip(var.idx, var.cd_acc, var.cd_comp):
                     f.write("{} {:.8f} {:.8f}\n".format(i, acc, comp))
+            if "component_stats" in var:                # --hip.largest_component: idx n_components inside_voxels kept_voxels
+                with open("{}/components.txt".format(opt.output_path), "w" if write_new else "a") as f:
+                    for row in zip(var.idx.tolist(), *(c.tolist() for c in _component_counts(var))):
+                        f.write("{} {} {} {}\n".format(*row))
 
     def save_checkpoint(self, opt, ep=0, it=0, best_val=np.inf, latest=False, best=False):
         assert _rank0(opt)

@@ -1,6 +1,7 @@
 """Thin Python wrappers over the C ABI (allocation + pointer plumbing only; no arithmetic here)."""
 from __future__ import annotations
 
+import collections
 import ctypes
 import weakref
 
@@ -704,6 +705,42 @@ def isosurface_mesh(level: torch.Tensor, iso: float = 0.0):
             _lib.check(lib.sc_marching_cubes_mesh_face_emit(B, S, _lib.ptr(offsets), _lib.ptr(masks), _lib.ptr(vmap), _lib.ptr(faces),
                                                             _lib.stream()), "sc_marching_cubes_mesh_face_emit")
     return verts, faces, v_count, f_count
+
+
+# ---- evaluation: the largest connected component of a level grid's solid (csrc/level_components.hip) -------------------------------
+LEVEL_COMPONENTS_MAX_IMAGES = 65535
+ComponentStats = collections.namedtuple("ComponentStats", ["n_components", "inside_voxels", "kept_voxels"])
+
+
+def level_largest_component(level: torch.Tensor, iso: float = 0.0):
+    """level [B,S,S,S] fp32 (device) -> (level_out [B,S,S,S], ComponentStats of int32 [B] tensors n_components, inside_voxels, kept_voxels).
+
+    The inside voxels (level < iso; NaN is outside) of each image fall into components under 6-connectivity; the largest one is kept,
+    among equals the one whose smallest linear index (x S + y) S + z is smallest.  level_out holds level's bits except at the inside voxels
+    of the other components, which hold iso + (iso - level), outside.  sc_level_largest_component (include/shapeclipper_hip.h states the
+    definition): integer atomics only, bit-reproducible, no host synchronisation; its labels live in the "level components" buffer of
+    the scratch cache.  ValueError for a grid that is not [B,S,S,S], not fp32, S outside 2..1024 or B > 65535."""
+    if level.dim() != 4 or not (level.shape[1] == level.shape[2] == level.shape[3]):
+        raise ValueError("shapeclipper_amd: level_largest_component takes a cubic grid [B,S,S,S], got shape %s" % (tuple(level.shape),))
+    if level.dtype != torch.float32:
+        raise ValueError("shapeclipper_amd: level_largest_component takes an fp32 grid, got %s" % level.dtype)
+    B, S = level.shape[0], level.shape[1]
+    if not 2 <= S <= 1024:
+        raise ValueError("shapeclipper_amd: level_largest_component needs 2 <= grid side <= 1024, got %d" % S)
+    if B > LEVEL_COMPONENTS_MAX_IMAGES:
+        raise ValueError("shapeclipper_amd: level_largest_component takes at most %d images per call, got %d" % (LEVEL_COMPONENTS_MAX_IMAGES, B))
+    if not level.is_cuda:
+        raise RuntimeError(_lib.NO_CPU)
+    lib = _lib.load()
+    level = level.contiguous()
+    out = torch.empty_like(level)
+    stats = torch.empty(3, B, device=level.device, dtype=torch.int32)
+    if B > 0:
+        ws = _scratch("level components", level.device, (lib.sc_level_largest_component_scratch_bytes(B, S) + 3) // 4)
+        code = lib.sc_level_largest_component(_lib.ptr(level), B, S, float(iso), _lib.ptr(out), _lib.ptr(stats[0]), _lib.ptr(stats[1]),
+                                              _lib.ptr(stats[2]), _lib.ptr(ws), _lib.stream())
+        _lib.check(code, "sc_level_largest_component")
+    return out, ComponentStats(stats[0], stats[1], stats[2])
 
 # ---- camera algebra ------------------------------------------------------------------------------------------------
 def camera_rays_forward(pose, intr, ray_idx, n_rays, width):

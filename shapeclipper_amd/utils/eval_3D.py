@@ -237,6 +237,13 @@ def compute_fscore(dist1, dist2, thresholds=[0.005, 0.01, 0.02, 0.05, 0.1, 0.2])
     return torch.where(torch.isnan(f), torch.zeros_like(f), f)
 
 
+def largest_component_enabled(opt):
+    """`--hip.largest_component` (default off): eval_metrics keeps only the largest 6-connected component of the solid {level < 0}
+    (ops.level_largest_component) -- var.level_vox is the filtered grid, var.component_stats the per-image counts -- so the metrics,
+    the mesh and point-cloud dumps and the training-time visualisation all see the solid without its detached floaters."""
+    return bool(opt.get("hip", {}).get("largest_component", False))
+
+
 _FLIP_PRED = [[1, 0, 0], [0, -1, 0], [0, 0, -1]]
 _FLIP_GT = [[-1, 0, 0], [0, 1, 0], [0, 0, 1]]
 
@@ -246,6 +253,9 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     points_3D = get_dense_3D_grid(opt, var)
     B = points_3D.shape[0]
     level_vox = compute_level_grid(opt, sdf_network, var.proj_latent_sdf, points_3D)
+    if largest_component_enabled(opt):      # detached floaters leave the solid before anything is meshed, sampled or dumped from it
+        level_vox, stats = ops.level_largest_component(level_vox.contiguous(), 0.0)
+        var.component_stats = stats._asdict()               # (var keeps a dict with attribute access; a tuple would become a plain list)
     var.eval_vox = points_3D.view(B, -1, 3)
     var.level_vox = level_vox                                           # kept for the mesh dump (meshes_device), not recomputed there
     dev = var.idx.device
