@@ -885,6 +885,43 @@ int sc_level_largest_component(const float* level, int n_images, int n_axis, flo
                                int32_t* inside_voxels, int32_t* kept_voxels, void* scratch, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Surface render (csrc/surface_hit.hip): the per-ray root finder between a value-only SDF pass over the S uniform samples of every ray
+ * and the colour / normal evaluation at the surface point (Renderer.render_surface, `--hip.surface_render`).  All arithmetic is fp32,
+ * every operation rounded once (no contraction), every comparison a true comparison (false when an operand is NaN).
+ *
+ * sc_ray_first_crossing: z_vals [n_rays][S], sdf [n_rays * S] (sample i of ray r at r * S + i), S = n_samples with
+ * SC_N_SAMPLES_SUPPORTED, f_i = sdf_i - iso.  Per ray r:
+ *   hit = 2  if f_0 <= 0 (the near end of the ray is already inside):  t_lo = t_hi = z_0, f_lo = f_hi = f_0;
+ *   hit = 1  otherwise, at the SMALLEST i in [0, S - 2] with f_i > 0 and f_{i+1} <= 0 (outside -> inside; a NaN on either side never
+ *            forms a bracket, inside -> outside pairs are passed over, a pair that lies across two 64-sample chunks counts like any
+ *            other):  t_lo = z_i, f_lo = f_i, t_hi = z_{i+1}, f_hi = f_{i+1};
+ *   hit = 0  otherwise:  t_lo = t_hi = z_0, f_lo = f_hi = f_0 (a NaN f_0 is written as it is; t stays finite).
+ * Outputs t_lo, t_hi, f_lo, f_hi [n_rays] fp32 and hit [n_rays] int32, every element overwritten.  One 64-lane wave per ray, one
+ * ballot per chunk of 64 samples, one pass over the ray, no atomics.
+ *
+ * sc_ray_bracket_step: one lane per ray; the bracket arrays are read and updated in place.  cam_loc, ray_dirs [n_rays][3] as
+ * sc_camera_rays_forward writes them.
+ *   update (only when f_new != NULL and hit == 1), with f = f_new[r] - iso the value at the previous query t_prev[r]:
+ *            f > 0:  t_lo = t_prev, f_lo = f;      f <= 0:  t_hi = t_prev, f_hi = f;      f NaN: nothing changes.
+ *   query, hit == 1:  d = f_lo - f_hi;  w = f_lo / d;  if !(d <= FLT_MAX) or !(w >= 0 && w <= 1) then w = 0.5 (d overflowed to Inf
+ *            or a value is NaN: bisect);  x = t_lo + w * (t_hi - t_lo);  if !(x >= t_lo) then x = t_lo;  if !(x <= t_hi) then
+ *            x = t_hi;  t = x.            hit != 1:  t = t_lo.
+ *   t [n_rays] and points [n_rays][3] = cam_loc + t * ray_dirs (one multiplication, one addition: the ray sampler's expression) are
+ *   overwritten for every ray, so a ray that misses still gets a finite point.  t_prev may be t itself; it is not read when f_new is
+ *   NULL (and may then be NULL).
+ * With f_lo > 0 >= f_hi on entry (what sc_ray_first_crossing leaves) the update keeps f_lo > 0 >= f_hi and t_lo <= t <= t_hi, and the
+ * bracket never widens: regula falsi with a safeguard, K updates cost K value-only SDF evaluations of n_rays points.
+ *
+ * Plain vector stores, no atomics: the same bits run to run, whatever the batch or the stream.  n_rays <= 0 returns 0 and launches
+ * nothing; hipErrorInvalidValue for an unsupported n_samples, n_rays > SC_SURFACE_HIT_MAX_RAYS or a NULL pointer (f_new / t_prev
+ * excepted as above).                                                                                                          */
+#define SC_SURFACE_HIT_MAX_RAYS (1 << 30)
+int sc_ray_first_crossing(const float* z_vals, const float* sdf, int n_rays, int n_samples, float iso, float* t_lo, float* t_hi,
+                          float* f_lo, float* f_hi, int32_t* hit, void* stream);
+int sc_ray_bracket_step(const float* cam_loc, const float* ray_dirs, const float* f_new, const float* t_prev, int n_rays, float iso,
+                        float* t_lo, float* t_hi, float* f_lo, float* f_hi, const int32_t* hit, float* t, float* points, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Launch policy (csrc/device.hip) -- the one process-level setting of the library.  The persistent one-workgroup-per-CU grids
  * (stream-K 3x3 convolutions and their weight gradients, stem / 1x1 / stride-2 gradients) are sized for
  * sc_grid_cus() = device CUs - reserved.  Reserve CUs when another stream must make progress beside them: RCCL's

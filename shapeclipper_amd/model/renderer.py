@@ -15,6 +15,8 @@ Random numbers: exactly the reference's CPU-generator draws, in its order (rand 
 """
 from __future__ import annotations
 
+import collections
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as torch_F
@@ -48,6 +50,11 @@ def _upload(x, dev):
     main.wait_stream(side)
     d.record_stream(main)                       # allocated on the upload stream, used on the render's
     return d
+
+
+SurfaceRender = collections.namedtuple("SurfaceRender", ["rgb", "mask", "depth", "normal", "hit"])
+SURFACE_REFINE_MAX = 16       # `--hip.surface_refine` 0..16
+SURFACE_SCALE_MAX = 4         # `--hip.surface_scale` 1..4
 
 
 class UniformSampler(nn.Module):
@@ -189,16 +196,38 @@ class Renderer(nn.Module):
         return rgb_output, mask_output, mask_hard_output, depth_output, normal_output, grad_eikonal
 
     @torch.no_grad()
-    def render_views(self, opt, poses, intr, proj_latent_sdf, proj_latent_rgb, max_rays=VIEWS_MAX_RAYS, chunk_views=None):
+    def render_views(self, opt, poses, intr, proj_latent_sdf, proj_latent_rgb, max_rays=VIEWS_MAX_RAYS, chunk_views=None, surface=False,
+                     n_refine=3, scale=1):
         """The B images (intr [B,3,3], latents [B,Z]) seen from each of V poses [V,3,4] with scale_dist 1 (the turn-table of
         reference runner.py:406-427) -> rgb [V,B,R,3], mask [V,B,R,1], normal [V,B,R,3], R = opt.H * opt.W, in as few passes of the chain
         CameraRaysFunction -> RaySampleFunction -> SdfFunction -> RgbCompositeFunction (training=False) as max_rays rays per pass allow, or
         chunk_views views per pass.  The views are laid out as extra images, view-major: image v*B + b has pose v and image b's intrinsics
         and per-image biases.  A ray's arithmetic does not depend on its batch neighbours, so the result equals the V renders of B images one
-        at a time bit for bit.  Draws nothing from the random generators: Runner.vis_rotate makes the reference's draws."""
+        at a time bit for bit.  Draws nothing from the random generators: Runner.vis_rotate makes the reference's draws.
+        surface=True: the surface render of every view instead (render_surface with n_refine and scale, scale_dist 1) -> a SurfaceRender
+        of rgb [V,B,R,3], mask, depth [V,B,R,1], normal [V,B,R,3], hit [V,B,R], R = scale^2 opt.H opt.W, laid out and batched the same
+        way and equal to the V calls of render_surface bit for bit."""
         if self.eager or opt.camera.model != "perspective":
             raise NotImplementedError("render_views runs on the HIP render chain (perspective camera, compiled architecture and sample count)")
         V, B = poses.shape[0], intr.shape[0]
+        if surface:
+            k, n_refine, R = self._surface_args(opt, n_refine, scale)
+            if chunk_views:
+                per = int(chunk_views)
+            else:
+                per = max(1, int(max_rays) // (B * R))
+                per = -(-V // -(-V // per))
+            packs = self.sdf_network.packed(proj_latent_sdf) + self.rgb_network.packed(proj_latent_rgb)
+            dev = poses.device
+            out = SurfaceRender(*(torch.empty(V, B, R, c, device=dev) for c in (3, 1, 1, 3)), torch.empty(V, B, R, device=dev, dtype=torch.int32))
+            ones = torch.ones(B, device=dev)
+            for v0 in range(0, V, per):
+                n = min(per, V - v0)
+                pose = poses[v0:v0 + n].unsqueeze(1).expand(n, B, 3, 4).reshape(n * B, 3, 4)
+                part = self._surface_chain(opt, pose, intr.repeat(n, 1, 1), ones.repeat(n), packs, B, n_refine, k, max_rays)
+                for dst, src in zip(out, part):
+                    dst[v0:v0 + n] = src.view(n, *dst.shape[1:])
+            return out
         R, S = opt.H * opt.W, self.N_samples
         if chunk_views:
             per = int(chunk_views)
@@ -224,6 +253,96 @@ class Renderer(nn.Module):
             mask[v0:v0 + n] = outs[1].view(n, B, R, 1)
             normal[v0:v0 + n] = outs[4].view(n, B, R, 3)
         return rgb, mask, normal
+
+    def _surface_args(self, opt, n_refine, scale):
+        """(scale, n_refine, rays per image) of a surface render, or the error it must raise -- before anything touches the device."""
+        if self.eager or opt.camera.model != "perspective":
+            raise NotImplementedError("render_surface runs on the HIP render chain (perspective camera, compiled architecture and sample count)")
+        if isinstance(scale, bool) or not isinstance(scale, int) or not 1 <= scale <= SURFACE_SCALE_MAX:
+            raise ValueError("shapeclipper_amd: render_surface takes an integer scale in 1..%d, got %r" % (SURFACE_SCALE_MAX, scale))
+        if isinstance(n_refine, bool) or not isinstance(n_refine, int) or not 0 <= n_refine <= SURFACE_REFINE_MAX:
+            raise ValueError("shapeclipper_amd: render_surface takes an integer n_refine in 0..%d, got %r" % (SURFACE_REFINE_MAX, n_refine))
+        R = scale * scale * int(opt.H) * int(opt.W)
+        if R % 16:
+            raise ValueError("shapeclipper_amd: render_surface needs a multiple of 16 rays per image (the point layout of sdf_forward and "
+                             "rgb_points_forward), got %d x %d" % (scale * int(opt.H), scale * int(opt.W)))
+        return scale, n_refine, R
+
+    @torch.no_grad()
+    def render_surface(self, opt, pose, intr, scale_dist, proj_latent_sdf, proj_latent_rgb, n_refine=3, scale=1):
+        """The sharp render of `--hip.surface_render`: every ray is shot at the solid {sdf < 0}, stops at the first place it enters it, and
+        the colour and the unit normal are evaluated at that one point.  Inference only (no autograd, no random draws).
+
+        pose [B,3,4], intr [B,3,3], scale_dist [B], latents [B,Z] as forward takes them.  scale = k in 1..4 renders k opt.H x k opt.W pixels
+        of the same view (intrinsics diag(k, k, 1) intr, width k opt.W; at k = 1 the rays are those of the evaluation render bit for bit).
+        -> SurfaceRender, R = k^2 opt.H opt.W rays per image in row-major pixel order:
+             rgb    [B,R,3]  predicted colour where the ray hits, data.bgcolor where it misses
+             mask   [B,R,1]  1 where hit != 0, else 0
+             depth  [B,R,1]  t * depth_fac where it hits (t: distance along the unit ray), else 0
+             normal [B,R,3]  unit SDF gradient at the surface point where it hits, else 0
+             hit    [B,R]    int32: 1 a crossing was bracketed, 2 the ray starts inside the solid (the near sample stands in), 0 miss
+        The chain: rays -> the S evaluation samples (linspace) -> value-only SDF at the R S points -> ops.ray_first_crossing -> n_refine
+        rounds of (ops.ray_bracket_step, value-only SDF at its R points) -> a last ops.ray_bracket_step for the surface point ->
+        SDF with gradient and feature and ops.rgb_points_forward at those R points.  Images go through it at most VIEWS_MAX_RAYS rays at a
+        time; a ray does not depend on its batch neighbours.  NotImplementedError for eager architectures, unsupported sample counts and
+        the orthographic camera (as render_views); ValueError for R % 16 != 0 and for scale / n_refine out of range."""
+        k, n_refine, _ = self._surface_args(opt, n_refine, scale)
+        packs = self.sdf_network.packed(proj_latent_sdf) + self.rgb_network.packed(proj_latent_rgb)
+        return self._surface_chain(opt, pose, intr, scale_dist, packs, pose.shape[0], n_refine, k, VIEWS_MAX_RAYS)
+
+    @torch.no_grad()
+    def surface_depth_grey(self, opt, out, pose, intr, scale_dist, scale=1):
+        """The grey picture of a SurfaceRender's depth, [B,R,1] in [0, 1]: the samples of a ray span t in [near, far] = camera.dist
+        scale_dist -+ 0.7, i.e. depths [near, far] depth_fac of that pixel, and the picture is (depth - near depth_fac) / (1.4 depth_fac)
+        clamped to [0, 1] -- 0 (black) at the near sample plane, 1 (white) at the far one -- and 1 where the ray misses."""
+        k, _, R = self._surface_args(opt, 0, scale)
+        intr = intr.contiguous().float()
+        if k != 1:
+            intr = intr * torch.tensor([float(k), float(k), 1.0], device=intr.device).view(1, 3, 1)
+        depth_fac = CameraRaysFunction.apply(pose, intr, None, R, k * int(opt.W))[2].view(-1, R, 1)
+        near = (float(opt.camera.dist) * scale_dist.float() - 0.7).view(-1, 1, 1)
+        grey = ((out.depth - near * depth_fac) / (1.4 * depth_fac)).clamp(0, 1)
+        return torch.where(out.hit.unsqueeze(-1) != 0, grey, torch.ones_like(grey))
+
+    def _surface_chain(self, opt, pose, intr, scale_dist, packs, n_bias, n_refine, k, max_rays):
+        """render_surface of N = pose.shape[0] images whose image i takes the per-image biases i % n_bias (render_views lays V views of B
+        images out view-major), in passes of whole images and at most max_rays rays (one image at least)."""
+        w_pack, cbias, v_pack, dbias = packs
+        N, S, W = pose.shape[0], self.N_samples, k * int(opt.W)
+        R = k * k * int(opt.H) * int(opt.W)
+        sym = bool(self.sdf_network.force_symmetry)
+        pose, intr = pose.contiguous().float(), intr.contiguous().float()
+        if k != 1:      # diag(k, k, 1) @ intr: the first two rows times k, exact in fp32
+            intr = intr * torch.tensor([float(k), float(k), 1.0], device=intr.device).view(1, 3, 1)
+        dev = pose.device
+        out = SurfaceRender(*(torch.empty(N, R, c, device=dev) for c in (3, 1, 1, 3)), torch.empty(N, R, device=dev, dtype=torch.int32))
+        per = max(1, int(max_rays) // R)
+        for i0 in range(0, N, per):
+            n = min(per, N - i0)
+            cb, db = cbias, dbias
+            if (i0, n) != (0, n_bias):
+                which = torch.arange(i0, i0 + n, device=dev) % n_bias
+                cb, db = cbias.index_select(0, which), dbias.index_select(0, which)
+            cam_loc, ray_dirs, depth_fac = CameraRaysFunction.apply(pose[i0:i0 + n], intr[i0:i0 + n], None, R, W)
+            z_vals, points = RaySampleFunction.apply(cam_loc, ray_dirs, scale_dist[i0:i0 + n].contiguous().float(), None, R, float(opt.camera.dist), S)
+            sdf = ops.sdf_forward(points, w_pack, cb, R * S, symmetric=sym, want_grad=False, want_feat=False)[0]
+            del points
+            br = ops.ray_first_crossing(z_vals, sdf, 0.0)
+            del sdf, z_vals
+            t, p = ops.ray_bracket_step(br, cam_loc, ray_dirs)
+            for _ in range(n_refine):
+                f = ops.sdf_forward(p, w_pack, cb, R, symmetric=sym, want_grad=False, want_feat=False)[0]
+                t, p = ops.ray_bracket_step(br, cam_loc, ray_dirs, f, t)
+            _, grad, feat = ops.sdf_forward(p, w_pack, cb, R, symmetric=sym, want_grad=True, want_feat=True)
+            rgb, normal = ops.rgb_points_forward(p, grad, feat, v_pack, db, R, sym)
+            hit = (br.hit != 0).unsqueeze(-1)
+            sl = slice(i0, i0 + n)
+            out.rgb[sl] = torch.where(hit, rgb, torch.full_like(rgb, self.bg_color)).view(n, R, 3)
+            out.mask[sl] = hit.float().view(n, R, 1)
+            out.depth[sl] = torch.where(hit, (t * depth_fac).unsqueeze(-1), torch.zeros_like(hit, dtype=torch.float32)).view(n, R, 1)
+            out.normal[sl] = torch.where(hit, normal, torch.zeros_like(normal)).view(n, R, 3)
+            out.hit[sl] = br.hit.view(n, R)
+        return out
 
     def _forward_eager(self, opt, cam_loc, ray_dirs, depth_fac, scale_dist, t_rand, eik_idx, B, R, latent_sdf, latent_rgb, training, visualize,
                        up, rdev, pin):

@@ -51,6 +51,13 @@ def _mesh_color(opt):
     return bool(opt.get("hip", {}).get("mesh_color", False))
 
 
+def _surface_render(opt):
+    """`--hip.surface_render` (default off): every per-sample dump also gets the sharp surface render of the sample's view
+    (Renderer.render_surface with `--hip.surface_refine` rounds at `--hip.surface_scale` times the evaluation resolution):
+    {idx}_image_surface.png, _mask_surface.png, _normal_surface.png, _depth_surface.png and _depth_surface.npy."""
+    return bool(opt.get("hip", {}).get("surface_render", False))
+
+
 def _component_counts(var):
     """(n_components, inside_voxels, kept_voxels) [B] of var.component_stats (eval_3D.eval_metrics with `--hip.largest_component`)."""
     return tuple(var.component_stats[k] for k in ("n_components", "inside_voxels", "kept_voxels"))
@@ -553,6 +560,8 @@ class Runner:
         if train:
             return
         self.dump_geometry(opt, var, folder)
+        if _surface_render(opt):
+            self.dump_surface(opt, var, folder)
 
     @torch.no_grad()
     def dump_vis_images(self, opt, var, folder, input_pose=True):
@@ -582,6 +591,8 @@ class Runner:
         self.dump_geometry(opt, var, folder)
         for name, frames in self.turntable_frames(opt, var).items():
             util_vis.dump_gifs(opt, var.idx, name, frames, folder=folder)
+        if _surface_render(opt):
+            self.dump_surface(opt, var, folder, rotate=True)
 
     @staticmethod
     def turntable_frames(opt, var):
@@ -596,6 +607,41 @@ class Runner:
             outs, kinds = (stack(var.rotating_imgs), stack(var.rotating_masks), stack(var.rotating_normals)), ("rgb", "mask", "rgb")
         return {name: ops.vis_frames(x.reshape(x.shape[0], B, opt.H, opt.W, -1), kind).transpose(0, 1)
                 for name, x, kind in zip(("image_rotate", "mask_rotate", "normal_rotate"), outs, kinds)}
+
+    @torch.no_grad()
+    def dump_surface(self, opt, var, folder, rotate=False):
+        """The files of `--hip.surface_render` for an evaluated batch, k = hip.surface_scale times opt.H x opt.W pixels each:
+        {idx}_image_surface.png (predicted colour at the surface point, data.bgcolor where the ray misses), {idx}_mask_surface.png (1 where
+        the ray meets the solid {sdf < 0}), {idx}_normal_surface.png (the unit normal in the encoding of the other normal PNGs,
+        (n + 1) / 2; misses are mid-grey), {idx}_depth_surface.png (Renderer.surface_depth_grey: black at the near sample plane, white at
+        the far one and where the ray misses) and {idx}_depth_surface.npy (the raw fp32 depth [k H, k W], 0 where the ray misses).
+        rotate=True (the vis_{ep}/ dump of --hip.train_vis): also {idx}_image_surface_rotate.gif and {idx}_normal_surface_rotate.gif, the
+        surface render from every pose of var.vis_pose (Renderer.render_views(surface=True), frames by ops.vis_frames).
+        The surface render shows the raw network: --hip.largest_component filters the level grid, not the MLP.  var.surface keeps the
+        SurfaceRender as a dict."""
+        if util_vis is None:
+            return
+        from .. import ops
+        hip = opt.get("hip", {})
+        k, n_refine = int(hip.get("surface_scale", 1)), int(hip.get("surface_refine", 3))
+        renderer = self.graph.module.renderer
+        B, H, W = len(var.idx), k * opt.H, k * opt.W
+        out = renderer.render_surface(opt, var.pose, var.intr, var.scale_dist, var.proj_latent_sdf, var.proj_latent_rgb, n_refine=n_refine, scale=k)
+        var.surface = out._asdict()
+        as_map = lambda x: x.view(B, H, W, -1).permute(0, 3, 1, 2)
+        grey = renderer.surface_depth_grey(opt, out, var.pose, var.intr, var.scale_dist, scale=k)
+        dump = lambda name, images, **kw: util_vis.dump_images(opt, var.idx, name, images, folder=folder, **kw)
+        dump("image_surface", as_map(out.rgb))
+        dump("mask_surface", as_map(out.mask))
+        dump("normal_surface", as_map(out.normal), from_range=(-1, 1))
+        dump("depth_surface", as_map(grey))
+        util_vis.dump_arrays(opt, var.idx, "depth_surface", out.depth.view(B, H, W), folder=folder)
+        if rotate and "vis_pose" in var:
+            views = renderer.render_views(opt, var.vis_pose, var.intr, var.proj_latent_sdf, var.proj_latent_rgb, surface=True,
+                                          n_refine=n_refine, scale=k)
+            for name, x, kind in (("image_surface_rotate", views.rgb, "rgb"), ("normal_surface_rotate", views.normal, "normal")):
+                frames = ops.vis_frames(x.reshape(x.shape[0], B, H, W, 3), kind).transpose(0, 1)
+                util_vis.dump_gifs(opt, var.idx, name, frames, folder=folder)
 
     def dump_geometry(self, opt, var, folder):
         """{idx}_mesh.ply (the predicted mesh) and {idx}_pointclouds_comp.ply (prediction red, ground truth green) of an evaluated batch;

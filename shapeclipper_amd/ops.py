@@ -742,6 +742,82 @@ def level_largest_component(level: torch.Tensor, iso: float = 0.0):
         _lib.check(code, "sc_level_largest_component")
     return out, ComponentStats(stats[0], stats[1], stats[2])
 
+# ---- surface render: the per-ray root finder (csrc/surface_hit.hip) -----------------------------------------------------------------
+SURFACE_HIT_MAX_RAYS = 1 << 30          # SC_SURFACE_HIT_MAX_RAYS (include/shapeclipper_hip.h)
+RayBracket = collections.namedtuple("RayBracket", ["t_lo", "t_hi", "f_lo", "f_hi", "hit"])
+
+
+def _surface_arg(name, t, shape, dtype=torch.float32):
+    """ValueError unless t is a device tensor of this dtype and shape (the two surface ops refuse everything else before any launch)."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError("shapeclipper_amd: %s must be a %s tensor of shape %s, got %s" % (
+            name, str(dtype).replace("torch.", ""), tuple(shape), "%s %s" % (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__))
+    if not t.is_cuda:
+        raise ValueError(_lib.NO_CPU)
+    return t.contiguous()
+
+
+def ray_first_crossing(z_vals: torch.Tensor, sdf: torch.Tensor, iso: float = 0.0) -> RayBracket:
+    """z_vals [n_rays,S], sdf [n_rays*S] fp32 (device; sample i of ray r at r S + i, the layout of sdf_forward on ray_sample_forward's
+    points) -> RayBracket(t_lo, t_hi, f_lo, f_hi fp32 [n_rays], hit int32 [n_rays]).
+
+    With f_i = sdf_i - iso: hit 2 where f_0 <= 0 (the ray starts inside; bracket = sample 0 twice), else hit 1 at the first pair with
+    f_i > 0 and f_{i+1} <= 0 (bracket = that pair), else hit 0 (bracket = sample 0 twice).  sc_ray_first_crossing
+    (include/shapeclipper_hip.h states the definition): no atomics, no scratch, no host synchronisation.  ValueError for CPU tensors,
+    another dtype or shape, or an S outside sample_count_supported."""
+    if not isinstance(z_vals, torch.Tensor) or z_vals.dim() != 2:
+        raise ValueError("shapeclipper_amd: ray_first_crossing takes z_vals [n_rays,S], got %s" % (tuple(z_vals.shape) if isinstance(z_vals, torch.Tensor) else type(z_vals).__name__,))
+    n, S = z_vals.shape
+    if not sample_count_supported(S):
+        raise ValueError("shapeclipper_amd: ray_first_crossing takes S %% 32 == 0, 32 <= S <= 256 samples per ray, not %d" % S)
+    if n > SURFACE_HIT_MAX_RAYS:
+        raise ValueError("shapeclipper_amd: ray_first_crossing takes at most %d rays per call, got %d" % (SURFACE_HIT_MAX_RAYS, n))
+    z_vals = _surface_arg("z_vals", z_vals, (n, S))
+    sdf = _surface_arg("sdf", sdf, (n * S,))
+    lib = _lib.load()
+    f = torch.empty(4, n, device=z_vals.device, dtype=torch.float32)
+    hit = torch.empty(n, device=z_vals.device, dtype=torch.int32)
+    code = lib.sc_ray_first_crossing(_lib.ptr(z_vals), _lib.ptr(sdf), n, S, float(iso), _lib.ptr(f[0]), _lib.ptr(f[1]), _lib.ptr(f[2]),
+                                     _lib.ptr(f[3]), _lib.ptr(hit), _lib.stream())
+    _lib.check(code, "sc_ray_first_crossing")
+    return RayBracket(f[0], f[1], f[2], f[3], hit)
+
+
+def ray_bracket_step(bracket: RayBracket, cam_loc: torch.Tensor, ray_dirs: torch.Tensor, f_new: torch.Tensor = None,
+                     t_prev: torch.Tensor = None, iso: float = 0.0):
+    """One step of the safeguarded regula falsi on every ray -> (t [n_rays], points [n_rays,3] = cam_loc + t * ray_dirs).
+
+    bracket: a RayBracket of contiguous tensors, UPDATED IN PLACE on its hit == 1 rays when f_new is given: f_new [n_rays] is the SDF at
+    the previous query t_prev [n_rays] (the t this function returned last); f_new - iso > 0 moves the lower end there, <= 0 the upper
+    end, NaN nothing.  Then the query: t_lo + w (t_hi - t_lo) with w = f_lo / (f_lo - f_hi), w = 0.5 when that is not a number in
+    [0, 1] or the difference overflowed, clamped to the bracket; t_lo on rays with hit != 1.  cam_loc, ray_dirs [n_rays,3] as
+    camera_rays_forward returns them.  sc_ray_bracket_step (include/shapeclipper_hip.h): one launch, no scratch, no host
+    synchronisation.  ValueError for CPU tensors, another dtype or shape, or f_new without t_prev."""
+    if not isinstance(bracket, RayBracket) or not isinstance(bracket.hit, torch.Tensor) or bracket.hit.dim() != 1:
+        raise ValueError("shapeclipper_amd: ray_bracket_step takes the RayBracket of ray_first_crossing")
+    n = bracket.hit.shape[0]
+    if n > SURFACE_HIT_MAX_RAYS:
+        raise ValueError("shapeclipper_amd: ray_bracket_step takes at most %d rays per call, got %d" % (SURFACE_HIT_MAX_RAYS, n))
+    for name, x in zip(RayBracket._fields, bracket):
+        _surface_arg("bracket.%s" % name, x, (n,), torch.int32 if name == "hit" else torch.float32)
+        if not x.is_contiguous():
+            raise ValueError("shapeclipper_amd: bracket.%s must be contiguous (it is updated in place)" % name)
+    cam_loc = _surface_arg("cam_loc", cam_loc, (n, 3))
+    ray_dirs = _surface_arg("ray_dirs", ray_dirs, (n, 3))
+    if (f_new is None) != (t_prev is None):
+        raise ValueError("shapeclipper_amd: ray_bracket_step takes f_new and t_prev together (the SDF value at the previous query)")
+    if f_new is not None:
+        f_new, t_prev = _surface_arg("f_new", f_new, (n,)), _surface_arg("t_prev", t_prev, (n,))
+    lib = _lib.load()
+    t = torch.empty(n, device=cam_loc.device, dtype=torch.float32)
+    points = torch.empty(n, 3, device=cam_loc.device, dtype=torch.float32)
+    code = lib.sc_ray_bracket_step(_lib.ptr(cam_loc), _lib.ptr(ray_dirs), _lib.ptr(f_new), _lib.ptr(t_prev), n, float(iso),
+                                   _lib.ptr(bracket.t_lo), _lib.ptr(bracket.t_hi), _lib.ptr(bracket.f_lo), _lib.ptr(bracket.f_hi),
+                                   _lib.ptr(bracket.hit), _lib.ptr(t), _lib.ptr(points), _lib.stream())
+    _lib.check(code, "sc_ray_bracket_step")
+    return t, points
+
+
 # ---- camera algebra ------------------------------------------------------------------------------------------------
 def camera_rays_forward(pose, intr, ray_idx, n_rays, width):
     lib = _lib.load()

@@ -22,7 +22,7 @@ torch.backends.cudnn.benchmark = False
 # defaults for keys this build adds (a reference YAML without them still loads)
 # deterministic_conv: the reference sets cudnn.deterministic=True globally (utils/options.py:14); on ROCm that
 # restricts MIOpen to GEMM-based backward solvers (measured 437 ms of 640 ms per bs32 step), so it is opt-in here.
-HIP_DEFAULTS = dict(hip=dict(device_rng=False, device_choice=True, device_rays=True, device_clip_preprocess=True, fused_backward=True, deterministic_conv=False, fused_loss=True, fused_adam=True, guarded_step=True, batched_encoders=True, two_streams=True, overlap_allreduce=False, reserve_cus=0, fused_block=True, fused_bottleneck=True, fused_rgb_wgrad=True, rgb_stash=True, value_split=True, rgb_split=True, rgb_bwd_split=True, sdf_stream=True, upload_stream=True, rocblas=True, conv3x3=True, conv3x3_split=True, conv_stem=True, conv1x1=True, conv3x3s2=True, conv3x3s2_grads=True, train_vis=False, mesh_color=False, largest_component=False))
+HIP_DEFAULTS = dict(hip=dict(device_rng=False, device_choice=True, device_rays=True, device_clip_preprocess=True, fused_backward=True, deterministic_conv=False, fused_loss=True, fused_adam=True, guarded_step=True, batched_encoders=True, two_streams=True, overlap_allreduce=False, reserve_cus=0, fused_block=True, fused_bottleneck=True, fused_rgb_wgrad=True, rgb_stash=True, value_split=True, rgb_split=True, rgb_bwd_split=True, sdf_stream=True, upload_stream=True, rocblas=True, conv3x3=True, conv3x3_split=True, conv_stem=True, conv1x1=True, conv3x3s2=True, conv3x3s2_grads=True, train_vis=False, mesh_color=False, largest_component=False, surface_render=False, surface_refine=3, surface_scale=1))
 
 
 def parse_arguments(args):
@@ -109,6 +109,11 @@ def process_options(opt):
     opt.H, opt.W = opt.image_size
     if "data" in opt and "dataset" in opt.data and opt.data.dataset not in opt.data and "pix3d" in opt.data:
         opt.data[opt.data.dataset] = opt.data.pix3d      # e.g. --data.dataset=synthetic reuses the Pix3D camera ranges
+    # the surface render of `--hip.surface_render` (Renderer.render_surface): refinement rounds 0..16, pixels per pixel side 1..4
+    for key, lo, hi in (("surface_refine", 0, 16), ("surface_scale", 1, 4)):
+        v = opt.get("hip", {}).get(key, lo)
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError("hip.%s must be an integer in %d..%d, got %r" % (key, lo, hi, v))
     torch.backends.cudnn.deterministic = bool(opt.get("hip", {}).get("deterministic_conv", False))
     from ..model import resnet
     resnet.HIP_CONV3X3 = bool(opt.get("hip", {}).get("conv3x3", True))

@@ -33,6 +33,13 @@ def dump_images(opt, idx, name, images, masks=None, from_range=(0, 1), poses=Non
         image.save("{}/{}/{}_{}.png".format(opt.output_path, folder, int(i), name))
 
 
+def dump_arrays(opt, idx, name, arrays, folder="dump"):
+    """{idx}_{name}.npy per sample: arrays [B, ...] (tensor or numpy) saved as they are, one numpy file each (raw per-pixel quantities a PNG
+    would quantise, e.g. the depth map of the surface render)."""
+    for i, a in zip(idx, _numpy(arrays)):
+        np.save("{}/{}/{}_{}.npy".format(opt.output_path, folder, int(i), name), a)
+
+
 def draw_pose(image, rot, size=15, width=1):
     """The reference's draw_pose on an 8-bit PIL image: the first two coordinates of each column of rot [3,3] (the rotated x, y, z axes) as
     red, green and blue lines from (size, size), drawn on a transparent layer and alpha-composited.  -> RGBA image.  (The reference goes
