@@ -27,7 +27,7 @@ import PIL.Image
 import torch
 import torch.nn.functional as torch_F
 
-from ..utils import camera, util
+from ..utils import camera, options, util
 from ..utils.util import EasyDict as edict
 from .clip_preprocess import ClipPreprocess
 
@@ -44,11 +44,11 @@ def to_tensor(image):
 
 
 def device_rays(opt):
-    return bool(opt.get("hip", {}).get("device_rays", True))
+    return bool(options.hip(opt, "device_rays"))
 
 
 def device_clip_preprocess(opt):
-    return bool(opt.get("hip", {}).get("device_clip_preprocess", True))
+    return bool(options.hip(opt, "device_clip_preprocess"))
 
 
 def ray_seeds(base, idx, n_views):

@@ -60,7 +60,7 @@ class RgbCompositeFunction(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         need = any(ctx.needs_input_grad[:9])
         beta1 = beta.reshape(1).contiguous()
-        stash = need and ops.RGB_STASH and ops.FUSED_RGB_WGRAD and dbias.shape[0] <= 256      # what the fused backward takes
+        stash = need and ops.rgb_forward_parks(dbias.shape[0])
         out = ops.rgb_composite_forward(points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta1,
                                         rays_per_image, symmetric, beta_min, bgcolor, normal_pow,
                                         keep_samples=keep_samples, keep_rgb_flat=need, keep_rr=stash)
@@ -242,6 +242,14 @@ def _bn_fusable(bn, x):
             and (bn.training or bn.track_running_stats))
 
 
+def _bn_state(bn):
+    """(running_mean, running_var, num_batches_tracked, training, momentum, eps) as the fused BatchNorm entry points take them."""
+    training = bn.training or not bn.track_running_stats
+    track = bn.track_running_stats
+    return (bn.running_mean if track else None, bn.running_var if track else None,
+            bn.num_batches_tracked if (track and training) else None, training, float(bn.momentum), float(bn.eps))
+
+
 def bn_act(bn, x, residual=None, relu=True, groups=1):
     """nn.BatchNorm2d `bn` applied to x, then `+ residual`, then ReLU.  Device tensors take the fused HIP path (raises
     if the library is missing); host tensors use the stock torch operators (pretrain plumbing on CPU, config[0]).
@@ -252,19 +260,7 @@ def bn_act(bn, x, residual=None, relu=True, groups=1):
         if residual is not None:
             out = out + residual
         return torch.relu_(out) if relu else out
-    training = bn.training or not bn.track_running_stats
-    track = bn.track_running_stats
-    return BnActFunction.apply(x, residual, bn.weight, bn.bias, bn.running_mean if track else None,
-                               bn.running_var if track else None,
-                               bn.num_batches_tracked if (track and training) else None,
-                               training, float(bn.momentum), float(bn.eps), relu, groups)
-
-
-def _bn_state(bn):
-    training = bn.training or not bn.track_running_stats
-    track = bn.track_running_stats
-    return (bn.running_mean if track else None, bn.running_var if track else None,
-            bn.num_batches_tracked if (track and training) else None, training, float(bn.momentum), float(bn.eps))
+    return BnActFunction.apply(x, residual, bn.weight, bn.bias, *_bn_state(bn), relu, groups)
 
 
 def bottleneck_linear(x, conv1, bn1, conv2, bn2, groups=1):
@@ -286,12 +282,7 @@ def bn_relu_maxpool(bn, x, groups=1):
     if not _bn_fusable(bn, x):
         out = bn(x) if groups == 1 else torch.cat([bn(c) for c in x.chunk(groups)], 0)
         return torch.nn.functional.max_pool2d(torch.relu_(out), 3, 2, 1)
-    training = bn.training or not bn.track_running_stats
-    track = bn.track_running_stats
-    return BnReluPoolFunction.apply(x, bn.weight, bn.bias, bn.running_mean if track else None,
-                                    bn.running_var if track else None,
-                                    bn.num_batches_tracked if (track and training) else None,
-                                    training, float(bn.momentum), float(bn.eps), groups)
+    return BnReluPoolFunction.apply(x, bn.weight, bn.bias, *_bn_state(bn), groups)
 
 
 class Conv3x3Function(torch.autograd.Function):
@@ -468,13 +459,6 @@ class BasicBlockFunction(torch.autograd.Function):
             ops._aligned(d_out), x, (y1, a1, y2, st1, st2), out, pb1, pb2, g1, b1, g2, b2, training, split, groups,
             ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[4])
         return dx, gw1, dg1, db1, gw2, dg2, db2, None, None, None, None, None, None, None, None
-
-
-def _bn_state(bn):
-    training = bn.training or not bn.track_running_stats
-    track = bn.track_running_stats
-    return (bn.running_mean if track else None, bn.running_var if track else None,
-            bn.num_batches_tracked if (track and training) else None, training, float(bn.momentum), float(bn.eps))
 
 
 def basic_block_takes(block, x, packs):

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as torch_F
 
-from ..utils import camera
+from ..utils import camera, options
 from ..utils.util import EasyDict as edict
 from . import loss, resnet
 from .implicit import RGBNetwork, SDFNetwork
@@ -104,7 +104,7 @@ class Graph(nn.Module):
             var.pop(stale, None)
         idx_NN = self.select_neighbours(opt, var) if use_NN else None
         views = self.gather_neighbour_views(opt, var, idx_NN, sampled) if use_NN else []
-        if use_NN and "latent" not in var and opt.get("hip", {}).get("batched_encoders", True):
+        if use_NN and "latent" not in var and options.hip(opt, "batched_encoders"):
             self.encode_all_views(opt, var, views)
 
         # always (re)written, as in the reference (graph.py:73): a second forward of the same `var` after an optimiser
@@ -118,7 +118,7 @@ class Graph(nn.Module):
         # neighbours' latents are already known (batched encoders) all of them go through it ONCE, stacked, with per-set BatchNorm
         # statistics updated in the reference's call order -- one set of launches and one gradient per shared weight instead of one per view.
         nn_lat = [nn_in.latent_raw[:, opt.arch.latent_dim_shape:] for nn_in in views if "latent_raw" in nn_in] if use_NN else []
-        if nn_lat and len(nn_lat) == len(views) and var.latent_rgb.is_cuda and opt.get("hip", {}).get("batched_encoders", True):
+        if nn_lat and len(nn_lat) == len(views) and var.latent_rgb.is_cuda and options.hip(opt, "batched_encoders"):
             G = 1 + len(nn_lat)
             proj = self._project_stacked(self.latent_proj_rgb, torch.cat([var.latent_rgb] + nn_lat, 0), G)
             pieces = proj.reshape(G, B, proj.shape[1]).unbind(0)
@@ -174,7 +174,7 @@ class Graph(nn.Module):
         union = (nn_masks + inp - nn_masks * inp + 1.e-8).sum(dim=1)
         probs = torch_F.normalize((1 - inter / union) ** opt.reg.sample_temp, dim=-1, p=1)
         dev = var.rgb_input_map.device
-        if opt.reg.n_views == 1 and opt.get("hip", {}).get("device_choice", True):
+        if opt.reg.n_views == 1 and options.hip(opt, "device_choice"):
             u = torch.from_numpy(np.random.random_sample(B))
             if probs.is_cuda:
                 u = u.pin_memory().to(probs.device, non_blocking=True)
@@ -229,7 +229,7 @@ class Graph(nn.Module):
         # The two networks are independent: the estimator pass runs on a second HIP stream next to the encoder pass
         # (HBM-bound BatchNorm of one overlaps MFMA-bound convolutions of the other; autograd replays the backward of
         # every operator on the stream of its forward, so the backward passes overlap the same way).
-        side = self._side_stream(est_in.device) if (est_in.is_cuda and opt.get("hip", {}).get("two_streams", True)) else None
+        side = self._side_stream(est_in.device) if (est_in.is_cuda and options.hip(opt, "two_streams")) else None
         if side is not None:
             main = torch.cuda.current_stream()
             side.wait_stream(main)
@@ -307,7 +307,7 @@ class Graph(nn.Module):
         lw, fns = opt.loss_weight, self.loss_fns
         mask_gt = var.mask_gt if "mask_gt" in var else var.mask_input
         fused = (w3 is None and var.rgb_recon.is_cuda and lw.render is not None and lw.mask is not None
-                 and lw.normal is not None and var.rgb_recon.dim() == 3 and opt.get("hip", {}).get("fused_loss", True))
+                 and lw.normal is not None and var.rgb_recon.dim() == 3 and options.hip(opt, "fused_loss"))
         if fused:
             return self.compute_loss_fused(opt, var, training, mask_gt)
         if lw.render is not None:

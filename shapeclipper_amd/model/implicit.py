@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from .. import packing
 from ..functional import SdfFunction
+from ..utils import options
 from . import eager_path
 
 
@@ -184,7 +185,7 @@ class SDFNetwork(nn.Module):
             proj_latent = proj_latent.detach()
         w_pack, cbias = self.packed(proj_latent)
         sdf, grad, feat = SdfFunction.apply(points_flat, w_pack, cbias, n // batch_size, bool(self.force_symmetry),
-                                            bool(compute_grad), True, bool(opt.get("hip", {}).get("fused_backward", True)))
+                                            bool(compute_grad), True, bool(options.hip(opt, "fused_backward")))
         return sdf[:, None], packing.tbl_to_rows(feat, n)[:, :self.n_channel], (grad if compute_grad else None)
 
 

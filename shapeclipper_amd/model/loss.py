@@ -11,6 +11,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as torch_F
 
+from ..utils import options
+
 
 class Loss(nn.Module):
 
@@ -107,7 +109,7 @@ class Loss(nn.Module):
         lw = opt.loss_weight
         trig = var.trig_azim
         if (trig.is_cuda and lw.cam_margin is not None and lw.cam_uniform is not None and lw.cam_sym is not None
-                and "_estim_flip" in var and opt.get("hip", {}).get("fused_loss", True)):
+                and "_estim_flip" in var and options.hip(opt, "fused_loss")):
             from .. import ops
             if ops.camera_prior_supported(trig.shape[0], opt.reg.emd_p):
                 from ..functional import CameraPriorLossFunction

@@ -23,16 +23,13 @@ import torch.nn.functional as torch_F
 
 from .. import ops
 from ..functional import CameraRaysFunction, RaySampleEikFunction, RaySampleFunction, RgbCompositeFunction, SdfFunction
-from ..utils import camera
+from ..utils import camera, options
 from .implicit import LaplaceDensity
 
 
-def sample_count_supported(n_samples) -> bool:
-    """render.n_samples_uniform values the HIP render kernels take: multiples of 32 from 32 to 256 (1 to 4 chunks of 64 samples per
-    ray).  Any other value renders on model/eager_path.py."""
-    return ops.sample_count_supported(n_samples)
-
-
+# render.n_samples_uniform values the HIP render kernels take (pure host logic; importing ops loads no library); any other value renders
+# on model/eager_path.py
+sample_count_supported = ops.sample_count_supported
 
 UPLOAD_STREAM = True          # `--hip.upload_stream!`: the CPU-generator draws are copied in the render's own stream
 _upload_streams = {}
@@ -129,8 +126,8 @@ class Renderer(nn.Module):
             depth_fac = depth_fac.reshape(-1)
 
         # reference CPU-generator draws, in its order (renderer.py:29,33): jitter then the eikonal sample index
-        dev_rng = bool(opt.get("hip", {}).get("device_rng", False))   # True: draw on the GPU (no 4 MB H2D copy per render,
-        rdev = ray_dirs.device if dev_rng else "cpu"                   # but a different random stream than the reference)
+        dev_rng = bool(options.hip(opt, "device_rng"))       # True: draw on the GPU (no 4 MB H2D copy per render,
+        rdev = ray_dirs.device if dev_rng else "cpu"         # but a different random stream than the reference)
         # CPU draws land in pinned memory and are copied asynchronously: a pageable H2D copy would drain the stream
         # (one host sync per draw, three per render) and let the GPU idle while the host catches up.
         pin = (not dev_rng) and ray_dirs.is_cuda
@@ -159,7 +156,7 @@ class Renderer(nn.Module):
 
         # fused SDF value + feature + d(sdf)/dx, then RGB MLP + density + compositing
         w_pack, cbias = self.sdf_network.packed(proj_latent_sdf)
-        fused_bwd = bool(opt.get("hip", {}).get("fused_backward", True))
+        fused_bwd = bool(options.hip(opt, "fused_backward"))
         sdf, grad, feat = SdfFunction.apply(points_flat, w_pack, cbias, R * S, sym, True, True, fused_bwd)
         v_pack, dbias = self.rgb_network.packed(proj_latent_rgb)
         outs = RgbCompositeFunction.apply(points_flat, z_vals, depth_fac.contiguous(), sdf, grad, feat,

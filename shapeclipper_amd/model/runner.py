@@ -23,7 +23,7 @@ import tqdm
 
 from ..data.pix3d import sample_rays_device
 from ..parallel import FlatGradAllReduce, ModuleHolder
-from ..utils import eval_3D, util
+from ..utils import eval_3D, options, util
 from ..utils.util import EasyDict as edict
 from ..utils.util import cleanup, log, setup
 
@@ -42,20 +42,20 @@ def _rank0(opt):
 def _train_vis(opt):
     """`--hip.train_vis` (default off): the reference's training-time visualisation on rank 0 -- the visualisation samples, vis_log/iter_{it}/
     every freq.save_vis iterations and vis_{ep}/ (PNGs, mesh, point cloud, turn-table GIFs) at every training-time evaluation."""
-    return bool(opt.get("hip", {}).get("train_vis", False)) and _rank0(opt)
+    return bool(options.hip(opt, "train_vis")) and _rank0(opt)
 
 
 def _mesh_color(opt):
     """`--hip.mesh_color` (default off): every mesh dump also writes {idx}_mesh_color.ply, the same mesh with per-vertex normals and
     predicted colours (eval_3D.mesh_attributes)."""
-    return bool(opt.get("hip", {}).get("mesh_color", False))
+    return bool(options.hip(opt, "mesh_color"))
 
 
 def _surface_render(opt):
     """`--hip.surface_render` (default off): every per-sample dump also gets the sharp surface render of the sample's view
     (Renderer.render_surface with `--hip.surface_refine` rounds at `--hip.surface_scale` times the evaluation resolution):
     {idx}_image_surface.png, _mask_surface.png, _normal_surface.png, _depth_surface.png and _depth_surface.npy."""
-    return bool(opt.get("hip", {}).get("surface_render", False))
+    return bool(options.hip(opt, "surface_render"))
 
 
 def _component_counts(var):
@@ -134,7 +134,7 @@ class Runner:
         # `--hip.reserve_cus=N` (default 0): in a multi-GPU step the persistent one-workgroup-per-CU grids of the trunk convolutions are sized
         # for (CUs - N), leaving N compute units to RCCL's all-reduce kernels.  Set before any workspace is sized;
         # single-GPU runs keep every CU.
-        reserve = int(opt.get("hip", {}).get("reserve_cus", 0) or 0)
+        reserve = int(options.hip(opt, "reserve_cus") or 0)
         if dev.type == "cuda":
             from .. import ops
             ops.set_reserved_cus(reserve if opt.world_size > 1 else 0)
@@ -145,13 +145,13 @@ class Runner:
             # juggling cost 1.1 ms of host time per step more than the single collective (profiles/r04_overlap_1rank.txt) on a step that
             # is host-paced, against ~0.7-1 ms of xGMI time it could hide: not the default until a multi-GPU run says otherwise.
             self.reducer = FlatGradAllReduce(self.graph.module, opt.world_size,
-                                             overlap=None if opt.get("hip", {}).get("overlap_allreduce", False) else False)
+                                             overlap=None if options.hip(opt, "overlap_allreduce") else False)
 
     def setup_optimizer(self, opt):
         if _rank0(opt): log.info("setting up optimizers...")
         kwargs = {k: (tuple(v) if k == "betas" else v) for k, v in opt.optim.params.items()}
         on_gpu = next(self.graph.parameters()).is_cuda
-        if on_gpu and self.optimizer in (torch.optim.Adam, torch.optim.AdamW) and opt.get("hip", {}).get("fused_adam", True):
+        if on_gpu and self.optimizer in (torch.optim.Adam, torch.optim.AdamW) and options.hip(opt, "fused_adam"):
             kwargs.setdefault("fused", True)       # one multi-tensor kernel instead of ~90 foreach launches per step
         full, view = [], []
         for k, v in self.graph.named_parameters():
@@ -162,7 +162,7 @@ class Runner:
         self.optim_V = self.optimizer([dict(params=view, lr=opt.optim.lr)], **kwargs)
         # hip.guarded_step: the fused optimizer takes the step's NaN / Inf flag as its `found_inf` tensor (the hook torch's GradScaler uses) and
         # skips the update ON THE DEVICE; the host then reads the flag one step late instead of waiting for it before every optim.step()
-        self._guarded_step = bool(kwargs.get("fused")) and bool(opt.get("hip", {}).get("guarded_step", True))
+        self._guarded_step = bool(kwargs.get("fused")) and bool(options.hip(opt, "guarded_step"))
 
     def restore_checkpoint(self, opt, best=False, evaluate=False):
         epoch_start, iter_start = None, None
@@ -518,7 +518,7 @@ class Runner:
         renderer = self.graph.module.renderer
         latent_rgb = var.proj_latent_rgb_NN if vis_NN else var.proj_latent_rgb
         if batched:
-            rdev = var.intr.device if opt.get("hip", {}).get("device_rng", False) else "cpu"
+            rdev = var.intr.device if options.hip(opt, "device_rng") else "cpu"
             for _ in range(n_views):
                 torch.randint(renderer.N_samples, (B * opt.H * opt.W,), device=rdev)
             rgb, mask, normal = renderer.render_views(opt, var.vis_pose[:n_views], var.intr, var.proj_latent_sdf, latent_rgb,
@@ -622,8 +622,7 @@ class Runner:
         if util_vis is None:
             return
         from .. import ops
-        hip = opt.get("hip", {})
-        k, n_refine = int(hip.get("surface_scale", 1)), int(hip.get("surface_refine", 3))
+        k, n_refine = int(options.hip(opt, "surface_scale")), int(options.hip(opt, "surface_refine"))
         renderer = self.graph.module.renderer
         B, H, W = len(var.idx), k * opt.H, k * opt.W
         out = renderer.render_surface(opt, var.pose, var.intr, var.scale_dist, var.proj_latent_sdf, var.proj_latent_rgb, n_refine=n_refine, scale=k)

@@ -53,6 +53,32 @@ RGB_BWD_SPLIT = True      # reverse chain of the RGB network (fused form that re
 RGB_FWD_SPLIT = True      # RGB network of the forward pass from pre-split bf16x3 fragments (csrc/rgb_fwd.hip, mlp_presplit.hpp); False: fp32 MFMA
 SDF_FWD_STREAM = True     # sdf_forward with d sdf/dx from streamed pre-split fragments (csrc/sdf_fwd_stream.hip); False: sdf_fwd.hip (fp32 MFMA)
 SDF_VALUE_SPLIT = True    # value-only SDF calls (no gradient, no feature, no stash) take csrc/sdf_value_split.hip; False: sdf_fwd.hip (fp32 MFMA)
+FUSED_RGB_WGRAD = True    # `--hip.fused_rgb_wgrad!`: Gy_l / r_l through HBM and three sc_wgrad launches (the round-4 path)
+RGB_STASH = True          # `--hip.rgb_stash!`: the backward recomputes the RGB forward chain instead of loading r0..r2 parked by the forward
+
+
+def sdf_forward_entry(want_grad: bool, want_feat: bool, stash: bool) -> str:
+    """The entry point sdf_forward calls for these outputs under the switches above.  Pure host logic."""
+    if SDF_VALUE_SPLIT and not (want_grad or want_feat or stash):
+        return "sc_sdf_value_forward_split"
+    if SDF_FWD_STREAM and want_grad and (not stash or want_feat):
+        return "sc_sdf_forward_stream"
+    return "sc_sdf_forward"
+
+
+def rgb_reverse_form(n_images: int, parked: bool) -> str:
+    """The entry-point stem of rgb_composite_backward (_entry adds _ns for S != 64) for a batch of n_images, `parked`: the forward kept
+    r0..r2.  The fused kernels take at most 256 images (csrc/rgb_bwd.hip).  Pure host logic."""
+    if not (FUSED_RGB_WGRAD and n_images <= 256):
+        return "sc_rgb_composite_backward_v3"
+    if not parked:
+        return "sc_rgb_composite_backward_fused"
+    return "sc_rgb_composite_backward_fused_" + ("split" if RGB_BWD_SPLIT else "stash")
+
+
+def rgb_forward_parks(n_images: int) -> bool:
+    """Whether a forward that needs gradients parks r0..r2 (805 MB per bs32 render): only when the reverse pass will load them."""
+    return bool(RGB_STASH) and rgb_reverse_form(n_images, True) != "sc_rgb_composite_backward_v3"
 
 
 def sdf_forward(points: torch.Tensor, w_pack: torch.Tensor, cbias: torch.Tensor, n_per_image: int,
@@ -64,7 +90,8 @@ def sdf_forward(points: torch.Tensor, w_pack: torch.Tensor, cbias: torch.Tensor,
     dev = points.device
     nt = n_tiles(n)
     sdf = torch.empty(n, device=dev, dtype=torch.float32)
-    if SDF_VALUE_SPLIT and not (want_grad or want_feat or stash):
+    name = sdf_forward_entry(want_grad, want_feat, stash)
+    if name == "sc_sdf_value_forward_split":
         # the value alone (compute_level_grid): the chain in the exact bf16x3 split arithmetic with pre-split weights, 1.6x the fp32-MFMA
         # chain (csrc/sdf_value_split.hip, profiles/r06_value_chain_split_ab.txt)
         _lib.check(lib.sc_sdf_value_forward_split(_lib.ptr(points), _lib.ptr(w_pack), _lib.ptr(cbias), n, n_per_image,
@@ -77,12 +104,9 @@ def sdf_forward(points: torch.Tensor, w_pack: torch.Tensor, cbias: torch.Tensor,
     sp = torch.empty(4 * nt * 1024, device=dev, dtype=torch.float32) if (stash and want_grad) else None
     # gradient kernel without a training stash: per-wave scratch for the parked pre-activations (L2-resident)
     scratch = _scratch("sdf", dev, SDF_SCRATCH_FLOATS) if (want_grad and not stash) else None
-    if SDF_FWD_STREAM and want_grad and (not stash or (want_feat and sp is not None)):
-        # value + feature + d sdf/dx from pre-split bf16x3 fragments streamed through LDS (csrc/sdf_fwd_stream.hip): the same arguments
-        # with the fragment image after the points
-        name, img = "sc_sdf_forward_stream", (_lib.ptr(_sdf_stream_image(w_pack)),)
-    else:
-        name, img = "sc_sdf_forward", ()
+    # sc_sdf_forward_stream: value + feature + d sdf/dx from pre-split bf16x3 fragments streamed through LDS (csrc/sdf_fwd_stream.hip),
+    # the same arguments with the fragment image after the points
+    img = (_lib.ptr(_sdf_stream_image(w_pack)),) if name == "sc_sdf_forward_stream" else ()
     code = getattr(lib, name)(_lib.ptr(points), *img, _lib.ptr(w_pack), _lib.ptr(cbias), n, n_per_image, cbias.shape[0],
                               1 if symmetric else 0, _lib.ptr(sdf), _lib.ptr(grad), _lib.ptr(feat), _lib.ptr(sa), _lib.ptr(sp),
                               _lib.ptr(scratch), _lib.stream())
@@ -342,10 +366,6 @@ def sdf_backward(points, w_pack, n_per_image, n_images, symmetric, stash_a, stas
     return g_points, g_w, g_c
 
 
-FUSED_RGB_WGRAD = True      # `--hip.fused_rgb_wgrad!`: Gy_l / r_l through HBM and three sc_wgrad launches (the round-4 path)
-RGB_STASH = True            # `--hip.rgb_stash!`: the backward recomputes the RGB forward chain instead of loading r0..r2 parked by the forward
-
-
 def rgb_composite_backward(points, z_vals, depth_fac, sdf, grad, feat, v_pack, dbias, beta_param, rgb_flat,
                            rays_per_image, symmetric, beta_min, bgcolor, normal_pow,
                            G_rgb, G_mask, G_depth, G_normal, rr=None):
@@ -369,17 +389,16 @@ def rgb_composite_backward(points, z_vals, depth_fac, sdf, grad, feat, v_pack, d
             1 if symmetric else 0, beta_min, bgcolor, normal_pow, _lib.ptr(G_rgb), _lib.ptr(G_mask), _lib.ptr(G_depth), _lib.ptr(G_normal),
             _lib.ptr(g["sdf"]), _lib.ptr(g["grad"]), _lib.ptr(g["feat"]), _lib.ptr(g["points"]), _lib.ptr(g["z_vals"]),
             _lib.ptr(g["depth_fac"]), _lib.ptr(g["beta"]))
-    if FUSED_RGB_WGRAD and n_images <= 256:
+    name = rgb_reverse_form(n_images, rr is not None)
+    if name != "sc_rgb_composite_backward_v3":
         # round 5: the gradients of V0, V1, V2 and of the per-image biases are formed inside the kernel by four weight-gradient waves (the scheme
         # of sc_sdf_backward_fused): no Gy_l / r_l hand-off tensors (1.6 GB per bs32 render) and no sc_wgrad launches
         parts = int(lib.sc_rgb_composite_backward_fused_parts(n_rays))
         stride = int(lib.sc_rgb_composite_backward_fused_partial_floats(n_images))
         partial = torch.empty(parts * stride, **f32)
-        if rr is not None:      # the forward parked r0..r2: no recomputation of the forward chain
-            # round 6: the reverse chain's transposed products from pre-split bf16x3 fragments (`--hip.rgb_bwd_split!`: fp32 MFMA)
-            name, tail = "sc_rgb_composite_backward_fused_" + ("split" if RGB_BWD_SPLIT else "stash"), (_lib.ptr(rr),)
-        else:
-            name, tail = "sc_rgb_composite_backward_fused", ()
+        # the forward parked r0..r2: no recomputation of the forward chain (_split: the reverse chain's transposed products from pre-split
+        # bf16x3 fragments, `--hip.rgb_bwd_split!`: fp32 MFMA)
+        tail = (_lib.ptr(rr),) if rr is not None else ()
         _lib.check(_entry(lib, name, S)[0](*head, _lib.ptr(partial), _lib.ptr(v3_part), *tail, _lib.stream()), name)
         g_all = _partial_reduce(lib, partial, parts, stride, stride, torch.empty(stride, **f32))
         g_v = torch.empty(RGB_PACK_FLOATS, **f32)
@@ -392,8 +411,8 @@ def rgb_composite_backward(points, z_vals, depth_fac, sdf, grad, feat, v_pack, d
         return g
     gy = torch.empty(3 * T, **f32)
     rr = torch.empty(2 * T, **f32)         # r0, r1 (operands of dV1 / dV2); r2 and gy3 only feed the output layer's gradient, formed in the kernel:
-    code = _entry(lib, "sc_rgb_composite_backward_v3", S)[0](*head, _lib.ptr(gy), _lib.ptr(rr), None, _lib.ptr(v3_part), _lib.stream())
-    _lib.check(code, "sc_rgb_composite_backward_v3")
+    code = _entry(lib, name, S)[0](*head, _lib.ptr(gy), _lib.ptr(rr), None, _lib.ptr(v3_part), _lib.stream())
+    _lib.check(code, name)
 
     GY = lambda l: gy[l * T:(l + 1) * T]
     RR = lambda l: rr[l * T:(l + 1) * T]

@@ -20,6 +20,7 @@ import torch
 import chamfer_3D
 
 from .. import ops, packing
+from . import options
 
 try:
     import mcubes
@@ -241,7 +242,7 @@ def largest_component_enabled(opt):
     """`--hip.largest_component` (default off): eval_metrics keeps only the largest 6-connected component of the solid {level < 0}
     (ops.level_largest_component) -- var.level_vox is the filtered grid, var.component_stats the per-image counts -- so the metrics,
     the mesh and point-cloud dumps and the training-time visualisation all see the solid without its detached floaters."""
-    return bool(opt.get("hip", {}).get("largest_component", False))
+    return bool(options.hip(opt, "largest_component"))
 
 
 _FLIP_PRED = [[1, 0, 0], [0, -1, 0], [0, 0, -1]]

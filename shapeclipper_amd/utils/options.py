@@ -4,6 +4,8 @@ utils/options.py (parse_arguments :16-34, set :36-44, _parent_ inheritance :46-6
 options.yaml never block on input() unless stdin is a TTY (benchmarks / CI must not hang)."""
 from __future__ import annotations
 
+import collections
+import importlib
 import os
 import random
 import string
@@ -19,10 +21,69 @@ from .util import log
 
 torch.backends.cudnn.benchmark = False
 
-# defaults for keys this build adds (a reference YAML without them still loads)
-# deterministic_conv: the reference sets cudnn.deterministic=True globally (utils/options.py:14); on ROCm that
-# restricts MIOpen to GEMM-based backward solvers (measured 437 ms of 640 ms per bs32 step), so it is opt-in here.
-HIP_DEFAULTS = dict(hip=dict(device_rng=False, device_choice=True, device_rays=True, device_clip_preprocess=True, fused_backward=True, deterministic_conv=False, fused_loss=True, fused_adam=True, guarded_step=True, batched_encoders=True, two_streams=True, overlap_allreduce=False, reserve_cus=0, fused_block=True, fused_bottleneck=True, fused_rgb_wgrad=True, rgb_stash=True, value_split=True, rgb_split=True, rgb_bwd_split=True, sdf_stream=True, upload_stream=True, rocblas=True, conv3x3=True, conv3x3_split=True, conv_stem=True, conv1x1=True, conv3x3s2=True, conv3x3s2_grads=True, train_vis=False, mesh_color=False, largest_component=False, surface_render=False, surface_refine=3, surface_scale=1))
+# The `hip.*` switches of this build, one row each: (key, default, kind, what it selects, the (module, attribute) it drives | None).
+# kind is bool, or (lo, hi) for an integer in lo..hi (hi None: no upper bound here).  A reference YAML without these keys still loads:
+# `set` fills in the defaults, and `hip(opt, key)` answers with them for an option tree that has no `hip` node.  Modules are named
+# relative to the package; process_options writes bool(value) into every attribute named here.
+Switch = collections.namedtuple("Switch", ["key", "default", "kind", "text", "drives"])
+HIP_TABLE = tuple(Switch(*row) for row in (
+    ("device_rng", False, bool, "draw the render's jitter on the GPU (no 4 MB upload per render, another random stream than the reference)", None),
+    ("device_choice", True, bool, "pick the regularisation view on the device (reg.n_views = 1)", None),
+    ("device_rays", True, bool, "Pix3D: silhouette-weighted ray choice for the whole batch on the GPU (csrc/silhouette_rays.hip)", None),
+    ("device_clip_preprocess", True, bool, "Pix3D: CLIP preprocessing on the GPU (csrc/clip_preprocess.hip)", None),
+    ("fused_backward", True, bool, "SDF reverse pass with the weight gradients formed in the kernel (sc_sdf_backward_fused)", None),
+    # the reference sets cudnn.deterministic=True globally (utils/options.py:14); on ROCm that restricts MIOpen to GEMM-based backward
+    # solvers (measured 437 ms of 640 ms per bs32 step), so it is opt-in here
+    ("deterministic_conv", False, bool, "torch.backends.cudnn.deterministic, process-global", None),
+    ("fused_loss", True, bool, "the render losses of one render in a single launch (csrc/loss.hip)", None),
+    ("fused_adam", True, bool, "torch's fused Adam on the device", None),
+    ("guarded_step", True, bool, "a non-finite loss skips the update on the device; the host raises one step later", None),
+    ("batched_encoders", True, bool, "one grouped encoder pass and one grouped estimator pass per step", None),
+    ("two_streams", True, bool, "the view estimator runs on a side stream next to the encoders", None),
+    ("overlap_allreduce", False, bool, "multi-GPU: the early gradient segment is all-reduced from inside backward", None),
+    ("reserve_cus", 0, (0, None), "multi-GPU: persistent convolution grids sized for the device's CUs minus this many", None),
+    ("fused_block", True, bool, "one autograd node per stride-1 BasicBlock", ("model.resnet", "FUSED_BLOCK")),
+    ("fused_bottleneck", True, bool, "1x1 Bottleneck_Linear blocks as fused launches (csrc/bottleneck.hip)", ("model.view_estimator", "HIP_BOTTLENECK")),
+    ("fused_rgb_wgrad", True, bool, "RGB reverse pass forms the weight gradients in the kernel; off: Gy_l / r_l through HBM and sc_wgrad",
+     ("ops", "FUSED_RGB_WGRAD")),
+    ("rgb_stash", True, bool, "RGB forward parks its hidden activations for the reverse pass; off: the reverse pass recomputes them",
+     ("ops", "RGB_STASH")),
+    ("value_split", True, bool, "value-only SDF calls (evaluation grid) on the pre-split bf16x3 chain; off: fp32 MFMA", ("ops", "SDF_VALUE_SPLIT")),
+    ("rgb_split", True, bool, "RGB network of the forward pass from pre-split bf16x3 fragments; off: fp32 MFMA", ("ops", "RGB_FWD_SPLIT")),
+    ("rgb_bwd_split", True, bool, "RGB reverse chain from pre-split transposed fragments; off: fp32 MFMA (see HIP_REQUIRES)",
+     ("ops", "RGB_BWD_SPLIT")),
+    ("sdf_stream", True, bool, "SDF forward (value, feature, d sdf/dx) from streamed pre-split fragments; off: fp32 MFMA", ("ops", "SDF_FWD_STREAM")),
+    ("upload_stream", True, bool, "the CPU-generator draws are copied on a stream of their own, ahead of the render",
+     ("model.renderer", "UPLOAD_STREAM")),
+    # (the bottleneck blocks and the per-image latent biases no longer go through a BLAS at all -- csrc/bottleneck.hip, latent_bias.hip --
+    # so what this switch still touches are the ~20 remaining small products of a step: final projector / head Linears.)  rocBLAS instead
+    # of torch's default hipBLASLt: 7 instead of 18 us of host time per call (a host-paced B=8 step 16.3 -> 14.9 ms)
+    ("rocblas", True, bool, "the small fp32 GEMMs left to torch go through rocBLAS, process-global; off leaves torch's choice alone", None),
+    ("conv3x3", True, bool, "3x3 stride-1 trunk convolutions on csrc/conv3x3.hip", ("model.resnet", "HIP_CONV3X3")),
+    ("conv3x3_split", True, bool, "... as exact three-piece bf16 operand splits; off: fp32 MFMA throughout", ("model.resnet", "HIP_CONV3X3_SPLIT")),
+    ("conv_stem", True, bool, "the 7x7 stride-2 stem convolution on its HIP kernel", ("model.resnet", "HIP_CONV_STEM")),
+    ("conv1x1", True, bool, "the 1x1 stride-2 shortcut convolutions on their HIP kernels", ("model.resnet", "HIP_CONV_1X1")),
+    ("conv3x3s2", True, bool, "the 3x3 stride-2 convolutions' forward on its HIP kernel", ("model.resnet", "HIP_CONV3X3_S2")),
+    ("conv3x3s2_grads", True, bool, "... and their backward-data / weight gradient", ("model.resnet", "HIP_CONV3X3_S2_GRADS")),
+    ("train_vis", False, bool, "training-time visualisation on rank 0: turn-table GIFs and periodic dumps", None),
+    ("mesh_color", False, bool, "every mesh dump also writes a coloured PLY with vertex normals", None),
+    ("largest_component", False, bool, "evaluation keeps the largest connected component of the level grid", None),
+    ("surface_render", False, bool, "every per-sample dump also gets a render at the SDF zero crossing (Renderer.render_surface)", None),
+    ("surface_refine", 3, (0, 16), "... refinement rounds of the crossing", None),
+    ("surface_scale", 1, (1, 4), "... pixels per pixel side", None),
+))
+HIP = {row.key: row for row in HIP_TABLE}
+# a switch that only counts while others are on: the split reverse chain is a form of the fused kernel that reads the parked activations
+HIP_REQUIRES = {"rgb_bwd_split": ("rgb_stash", "fused_rgb_wgrad")}
+HIP_DEFAULTS = dict(hip={row.key: row.default for row in HIP_TABLE})
+_PACKAGE = __name__.rsplit(".", 2)[0]
+
+
+def hip(opt, key):
+    """opt.hip[key] where the option tree has it, else the table's default (trees built by hand need no `hip` node).  A key the table
+    does not have is a KeyError: a mistake at the call site, not user input."""
+    default = HIP[key].default
+    return opt.get("hip", {}).get(key, default)
 
 
 def parse_arguments(args):
@@ -109,37 +170,18 @@ def process_options(opt):
     opt.H, opt.W = opt.image_size
     if "data" in opt and "dataset" in opt.data and opt.data.dataset not in opt.data and "pix3d" in opt.data:
         opt.data[opt.data.dataset] = opt.data.pix3d      # e.g. --data.dataset=synthetic reuses the Pix3D camera ranges
-    # the surface render of `--hip.surface_render` (Renderer.render_surface): refinement rounds 0..16, pixels per pixel side 1..4
-    for key, lo, hi in (("surface_refine", 0, 16), ("surface_scale", 1, 4)):
-        v = opt.get("hip", {}).get(key, lo)
-        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
-            raise ValueError("hip.%s must be an integer in %d..%d, got %r" % (key, lo, hi, v))
-    torch.backends.cudnn.deterministic = bool(opt.get("hip", {}).get("deterministic_conv", False))
-    from ..model import resnet
-    resnet.HIP_CONV3X3 = bool(opt.get("hip", {}).get("conv3x3", True))
-    resnet.HIP_CONV3X3_SPLIT = bool(opt.get("hip", {}).get("conv3x3_split", True))
-    resnet.HIP_CONV_STEM = bool(opt.get("hip", {}).get("conv_stem", True))
-    resnet.HIP_CONV_1X1 = bool(opt.get("hip", {}).get("conv1x1", True))
-    resnet.HIP_CONV3X3_S2 = bool(opt.get("hip", {}).get("conv3x3s2", True))
-    resnet.HIP_CONV3X3_S2_GRADS = bool(opt.get("hip", {}).get("conv3x3s2_grads", True))
-    resnet.FUSED_BLOCK = bool(opt.get("hip", {}).get("fused_block", True))
-    from .. import ops as _ops
-    _ops.FUSED_RGB_WGRAD = bool(opt.get("hip", {}).get("fused_rgb_wgrad", True))
-    _ops.RGB_STASH = bool(opt.get("hip", {}).get("rgb_stash", True))
-    _ops.SDF_FWD_STREAM = bool(opt.get("hip", {}).get("sdf_stream", True))       # SDF forward (value, feature, d sdf/dx) from streamed pre-split fragments
-    _ops.RGB_BWD_SPLIT = bool(opt.get("hip", {}).get("rgb_bwd_split", True)) and _ops.RGB_STASH and _ops.FUSED_RGB_WGRAD
-    _ops.RGB_FWD_SPLIT = bool(opt.get("hip", {}).get("rgb_split", True))         # forward RGB network from pre-split bf16x3 fragments
-    _ops.SDF_VALUE_SPLIT = bool(opt.get("hip", {}).get("value_split", True))     # evaluation grid: the pre-split bf16x3 value chain
-    from ..model import renderer as _renderer
-    _renderer.UPLOAD_STREAM = bool(opt.get("hip", {}).get("upload_stream", True))
-    from ..model import view_estimator
-    view_estimator.HIP_BOTTLENECK = bool(opt.get("hip", {}).get("fused_bottleneck", True))
-    # (Round 5: the bottleneck blocks and the per-image latent biases no longer go through a BLAS at all -- csrc/bottleneck.hip,
-    # latent_bias.hip -- so what this switch still touches are the ~20 remaining small products of a step: final projector / head Linears.)
-    # The ~83 small fp32 GEMMs of a step (estimator heads, latent projectors: [B..3B, 256..512] x [C, C]) through rocBLAS instead of torch's
-    # default hipBLASLt: 7 instead of 18 us of host time per call (a host-paced B=8 step 16.3 -> 14.9 ms); process-global
-    # like cudnn.deterministic above, `--hip.rocblas!` leaves torch's choice alone.
-    if bool(opt.get("hip", {}).get("rocblas", True)) and torch.cuda.is_available():
+    for row in HIP_TABLE:
+        if row.kind is not bool and None not in row.kind:
+            (lo, hi), v = row.kind, hip(opt, row.key)
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError("hip.%s must be an integer in %d..%d, got %r" % (row.key, lo, hi, v))
+    torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
+    for row in HIP_TABLE:
+        if row.drives is not None:
+            module, attr = row.drives
+            on = all(bool(hip(opt, k)) for k in (row.key,) + HIP_REQUIRES.get(row.key, ()))
+            setattr(importlib.import_module("%s.%s" % (_PACKAGE, module)), attr, on)
+    if bool(hip(opt, "rocblas")) and torch.cuda.is_available():
         try:
             torch.backends.cuda.preferred_blas_library("cublas")
         except Exception:       # noqa: BLE001  (older torch: no such switch)

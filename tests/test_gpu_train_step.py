@@ -1,5 +1,6 @@
 """Full training iterations through Runner.train_iteration on the GPU (synthetic batch): every loss key the
 reference produces is present and finite, parameters of every trainable child move, consecutive steps work."""
+import math
 import os
 import time
 
@@ -270,3 +271,52 @@ def test_fused_loss_carries_the_normal_target_gradient_into_the_estimator():
     assert (num / den) ** 0.5 < 2e-3
     for n in ("sdf_network.lin3.weight", "renderer.density.beta"):
         assert float((got[n] - ref[n]).norm() / ref[n].norm().clamp_min(1e-20)) < 2e-3, n
+
+
+@pytest.mark.parametrize("flag, ran, not_ran", [
+    (None, ["sc_sdf_forward_stream", "sc_sdf_backward_fused", "sc_rgb_composite_forward_split", "sc_rgb_composite_backward_fused_split"], ["sc_wgrad"]),
+    ("--hip.sdf_stream!", ["sc_sdf_forward"], ["sc_sdf_forward_stream"]),
+    ("--hip.rgb_split!", ["sc_rgb_composite_forward_stash"], []),
+    ("--hip.rgb_bwd_split!", ["sc_rgb_composite_backward_fused_stash"], []),
+    ("--hip.rgb_stash!", ["sc_rgb_composite_backward_fused"], []),
+    ("--hip.fused_rgb_wgrad!", ["sc_rgb_composite_backward_v3", "sc_wgrad"], []),
+    ("--hip.fused_backward!", ["sc_sdf_backward", "sc_wgrad"], []),
+], ids=["default", "sdf_stream", "rgb_split", "rgb_bwd_split", "rgb_stash", "fused_rgb_wgrad", "fused_backward"])
+def test_render_switches_select_their_entry_points(flag, ran, not_ran):
+    """The render switches decide which entry points of the library a training step calls: one batch-2 step (the step of the alternate-path
+    test above) with the per-entry-point timing table on, which records every call outside _lib.TIMING_SKIP by name."""
+    import importlib
+    import numpy as np
+    from shapeclipper_amd import _lib, synthetic
+    from shapeclipper_amd.model.runner import Runner
+    from shapeclipper_amd.utils import options, util
+    from shapeclipper_amd.utils.util import EasyDict as edict
+    driven = [(importlib.import_module("shapeclipper_amd." + row.drives[0]), row.drives[1]) for row in options.HIP_TABLE if row.drives]
+    before, timing = [getattr(m, a) for m, a in driven], _lib.TIMING
+    try:
+        opt = options.set(options.parse_arguments(["--yaml=options/pix3d/config.yaml", "--name=pytest_entry", "--output_root=/tmp/sc_pytest",
+                                                   "--batch_size=2", "--tb!", "--arch.enc_pretrained!"] + ([flag] if flag else [])), verbose=False)
+        opt.device, opt.world_size, opt.port = 0, 1, 0
+        opt.freq.scalar, opt.freq.ckpt_latest = 0, 10 ** 9
+        torch.manual_seed(0)
+        np.random.seed(0)
+        runner = Runner(opt)
+        runner.build_networks(opt)
+        runner.setup_optimizer(opt)
+        runner.graph.train()
+        runner.it, runner.ep, runner.best_val = 1, 0, 0.0
+        runner.timer = edict(start=time.time(), it_mean=None)
+        batch = util.move_to_device(synthetic.make_batch(opt, 2, seed=0), "cuda:0")
+        opt.H, opt.W = opt.image_size
+        _lib.TIMING = {}
+        loss = runner.train_iteration(opt, edict(batch), None)
+        torch.cuda.synchronize()
+        called = set(_lib.TIMING)
+    finally:
+        _lib.TIMING = timing
+        for (m, a), v in zip(driven, before):
+            setattr(m, a, v)
+    assert math.isfinite(float(loss.all.detach()))
+    print(flag, sorted(called))
+    assert set(ran) <= called, sorted(set(ran) - called)
+    assert not set(not_ran) & called, sorted(set(not_ran) & called)

@@ -464,3 +464,105 @@ def test_gpu_suite_runs_parity_tests_before_subprocess_tests():
         assert suite_order_key(f)[0] == 2, "%s runs after a subprocess test but is not in the last group" % f
     for f in ordered[:first_launcher]:
         assert not launches.search(open(os.path.join(here, f)).read())
+
+
+# ---- the hip.* switch table (utils/options.py) and the render-path choice (ops.py) ---------------------------------------------------------
+def test_hip_defaults_are_the_35_known_switches():
+    assert options.HIP_DEFAULTS == dict(hip=dict(
+        device_rng=False, device_choice=True, device_rays=True, device_clip_preprocess=True, fused_backward=True, deterministic_conv=False,
+        fused_loss=True, fused_adam=True, guarded_step=True, batched_encoders=True, two_streams=True, overlap_allreduce=False, reserve_cus=0,
+        fused_block=True, fused_bottleneck=True, fused_rgb_wgrad=True, rgb_stash=True, value_split=True, rgb_split=True, rgb_bwd_split=True,
+        sdf_stream=True, upload_stream=True, rocblas=True, conv3x3=True, conv3x3_split=True, conv_stem=True, conv1x1=True, conv3x3s2=True,
+        conv3x3s2_grads=True, train_vis=False, mesh_color=False, largest_component=False, surface_render=False, surface_refine=3,
+        surface_scale=1))
+    assert len(options.HIP_DEFAULTS["hip"]) == 35 == len(options.HIP_TABLE)
+    assert list(options.HIP_DEFAULTS["hip"]) == [row.key for row in options.HIP_TABLE]
+    for row in options.HIP_TABLE:
+        assert row.text and (row.kind is bool) == isinstance(row.default, bool), row.key
+    assert options.HIP["surface_refine"].kind == (0, 16) and options.HIP["surface_scale"].kind == (1, 4)
+
+
+def test_hip_accessor_answers_with_the_table_default_and_refuses_unknown_keys():
+    for row in options.HIP_TABLE:
+        assert options.hip(edict(), row.key) == row.default and type(options.hip(edict(), row.key)) is type(row.default)
+        assert options.hip(edict(hip=edict()), row.key) == row.default
+    o = edict(hip=edict(fused_loss=False, surface_refine=7))
+    assert options.hip(o, "fused_loss") is False and options.hip(o, "surface_refine") == 7 and options.hip(o, "fused_adam") is True
+    for tree in (edict(), o, _opt()):
+        with pytest.raises(KeyError):
+            options.hip(tree, "no_such")
+    assert _opt(["--hip.no_such=3"]).hip.no_such == 3            # an unknown flag on the command line is tolerated, as before
+
+
+def test_each_switch_drives_exactly_its_module_attribute():
+    import importlib
+    driven = {row.key: row.drives for row in options.HIP_TABLE if row.drives is not None}
+    assert driven == dict(
+        fused_block=("model.resnet", "FUSED_BLOCK"), fused_bottleneck=("model.view_estimator", "HIP_BOTTLENECK"),
+        fused_rgb_wgrad=("ops", "FUSED_RGB_WGRAD"), rgb_stash=("ops", "RGB_STASH"), value_split=("ops", "SDF_VALUE_SPLIT"),
+        rgb_split=("ops", "RGB_FWD_SPLIT"), rgb_bwd_split=("ops", "RGB_BWD_SPLIT"), sdf_stream=("ops", "SDF_FWD_STREAM"),
+        upload_stream=("model.renderer", "UPLOAD_STREAM"), conv3x3=("model.resnet", "HIP_CONV3X3"),
+        conv3x3_split=("model.resnet", "HIP_CONV3X3_SPLIT"), conv_stem=("model.resnet", "HIP_CONV_STEM"),
+        conv1x1=("model.resnet", "HIP_CONV_1X1"), conv3x3s2=("model.resnet", "HIP_CONV3X3_S2"),
+        conv3x3s2_grads=("model.resnet", "HIP_CONV3X3_S2_GRADS"))
+    read = lambda: {d: getattr(importlib.import_module("shapeclipper_amd." + d[0]), d[1]) for d in driven.values()}
+    try:
+        _opt()
+        base = read()
+        assert base == {d: True for d in driven.values()}
+        for key, target in driven.items():
+            assert options.HIP[key].default is True
+            _opt(["--hip.%s!" % key])
+            want = dict(base)
+            want[target] = False
+            if key in ("rgb_stash", "fused_rgb_wgrad"):         # the one derived rule: the split reverse chain needs both
+                want[("ops", "RGB_BWD_SPLIT")] = False
+            assert read() == want, key
+            _opt(["--hip.%s" % key])                             # stated explicitly: the default again
+            assert read() == base, key
+            _opt(["--hip.%s!" % key])
+            _opt()                                               # a default set restores every attribute
+            assert read() == base, key
+    finally:
+        _opt()
+    assert options.HIP_REQUIRES == {"rgb_bwd_split": ("rgb_stash", "fused_rgb_wgrad")}
+
+
+def test_render_entry_points_follow_the_switches(monkeypatch):
+    """ops.sdf_forward_entry / rgb_reverse_form / rgb_forward_parks against tables written out from the inline conditions they replaced:
+    sdf_forward took the value chain for SDF_VALUE_SPLIT and not (want_grad or want_feat or stash), the streamed kernel for SDF_FWD_STREAM
+    and want_grad and (not stash or want_feat), else sc_sdf_forward; rgb_composite_backward took the fused family for FUSED_RGB_WGRAD and
+    n_images <= 256 (_split / _stash with parked activations by RGB_BWD_SPLIT), else _v3; the forward parked for RGB_STASH and
+    FUSED_RGB_WGRAD and n_images <= 256."""
+    import itertools
+    from shapeclipper_amd import ops
+    tf = (False, True)
+    V, S, P = "sc_sdf_value_forward_split", "sc_sdf_forward_stream", "sc_sdf_forward"
+    sdf_want = {     # (SDF_VALUE_SPLIT, SDF_FWD_STREAM) -> (want_grad, want_feat, stash) = FFF FFT FTF FTT TFF TFT TTF TTT
+        (True, True): (V, P, P, P, S, P, S, S),
+        (True, False): (V, P, P, P, P, P, P, P),
+        (False, True): (P, P, P, P, S, P, S, S),
+        (False, False): (P, P, P, P, P, P, P, P)}
+    for (vs, st), row in sdf_want.items():
+        monkeypatch.setattr(ops, "SDF_VALUE_SPLIT", vs)
+        monkeypatch.setattr(ops, "SDF_FWD_STREAM", st)
+        for args, want in zip(itertools.product(tf, tf, tf), row):
+            assert ops.sdf_forward_entry(*args) == want, (vs, st, args)
+    stem = "sc_rgb_composite_backward_"
+    v3, fu, sp, sh = stem + "v3", stem + "fused", stem + "fused_split", stem + "fused_stash"
+    rgb_want = {     # (FUSED_RGB_WGRAD, RGB_BWD_SPLIT) -> (n_images, parked) = (1,F) (1,T) (256,F) (256,T) (257,F) (257,T); RGB_STASH: no part
+        (True, True): (fu, sp, fu, sp, v3, v3),
+        (True, False): (fu, sh, fu, sh, v3, v3),
+        (False, True): (v3, v3, v3, v3, v3, v3),
+        (False, False): (v3, v3, v3, v3, v3, v3)}
+    parks_want = {   # (RGB_STASH, FUSED_RGB_WGRAD) -> n_images = 1, 256, 257; RGB_BWD_SPLIT: no part
+        (True, True): (True, True, False), (True, False): (False, False, False),
+        (False, True): (False, False, False), (False, False): (False, False, False)}
+    for stash, fused, bwd in itertools.product(tf, tf, tf):
+        monkeypatch.setattr(ops, "RGB_STASH", stash)
+        monkeypatch.setattr(ops, "FUSED_RGB_WGRAD", fused)
+        monkeypatch.setattr(ops, "RGB_BWD_SPLIT", bwd)
+        for (n, parked), want in zip(itertools.product((1, 256, 257), tf), rgb_want[fused, bwd]):
+            assert ops.rgb_reverse_form(n, parked) == want, (stash, fused, bwd, n, parked)
+        for n, want in zip((1, 256, 257), parks_want[stash, fused]):
+            assert ops.rgb_forward_parks(n) is want, (stash, fused, bwd, n)
