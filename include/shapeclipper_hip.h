@@ -589,6 +589,54 @@ int sc_marching_cubes_mesh_vertex_emit(const float* level, int n_images, int n_a
 int sc_marching_cubes_mesh_face_emit(int n_images, int n_axis, const long long* block_offsets, const unsigned char* masks, const int* vmap,
                                      int* faces, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dual contouring of the level grid (csrc/dual_contour.hip; what ops.dual_contour_mesh runs).  It works on the state of the indexed
+ * marching-cubes mesh above -- masks (the case byte of every cube, sc_marching_cubes_block_count_masks), verts and vmap
+ * (sc_marching_cubes_mesh_vertex_emit), vertex_block_offsets (sc_marching_cubes_mesh_vertex_scan) -- plus normals [vertices][3] fp32, one
+ * per crossing vertex in the order of verts.  A crossing vertex with its normal is Hermite data (p_i, n_i).  "Inside" is value < iso, the
+ * rule that wrote masks; a NaN is outside.  Corner v of a cube is its lower corner + (v & 1, (v >> 1) & 1, (v >> 2) & 1).
+ *
+ * Cells.  A cell is a cube of 8 grid points with lower corner g = (x, y, z), 0 <= x, y, z <= n_axis - 2.  It owns one dual vertex iff its
+ * case byte is neither 0 nor 255; an image's dual vertices are numbered in ascending linear cell index (x (n_axis-1) + y)(n_axis-1) + z.
+ * The cell reads its crossings through vmap in the order of its 12 edges e = 0..11 = (corner, corner): (0,1) (0,2) (0,4) (1,3) (1,5)
+ * (2,3) (2,6) (3,7) (4,5) (4,6) (5,7) (6,7); edge e is a crossing iff its corners' bits of the case byte differ.  All arithmetic is
+ * fp32, every operation rounded once (no contraction), every comparison a true comparison (false when an operand is NaN):
+ *   s = (0,0,0), k = 0;  for e ascending, crossings only:  s_j = s_j + p_e,j (j = 0, 1, 2),  k = k + 1
+ *   c_j = s_j / (float)k
+ *   a00 = a01 = a02 = a11 = a12 = a22 = 0, b = (0,0,0);  for e ascending, crossings whose three normal components all have
+ *   |n_j| <= FLT_MAX only (a normal with a NaN or Inf component counts for c and k and for nothing else), n = n_e:
+ *       d_j = p_e,j - c_j;   w = (n_0 d_0 + n_1 d_1) + n_2 d_2;   a_ij = a_ij + n_i n_j  (i <= j);   b_j = b_j + n_j w
+ *   r = reg * (float)k;   a00 = a00 + r,  a11 = a11 + r,  a22 = a22 + r          -- (sum n n^T + reg k I) y = sum n (n . (p - c))
+ *   LDL^T, divisions only:   l10 = a01 / a00;   l20 = a02 / a00;   e1 = a11 - l10 a01;   t21 = a12 - l20 a01;   l21 = t21 / e1;
+ *       e2 = (a22 - l20 a02) - l21 t21;   z1 = b_1 - l10 b_0;   z2 = (b_2 - l20 b_0) - l21 z1;
+ *       y_2 = z2 / e2;   y_1 = z1 / e1 - l21 y_2;   y_0 = (b_0 / a00 - l10 y_1) - l20 y_2
+ *   x_j = c_j + y_j;   if !(x_j >= (float)g_j) then x_j = (float)g_j;   if !(x_j <= (float)(g_j + 1)) then x_j = (float)(g_j + 1)
+ * so every dual vertex lies in its own cell's unit box, and a NaN (from a NaN level value at an end of a crossing) lands on g_j.
+ * With reg > 0 the matrix is positive definite: a00 >= r > 0, and e1, e2 > 0 up to rounding.
+ *
+ * Faces.  One quad, as two triangles, per crossing grid edge that has four cells around it: for the edge from grid point P along axis
+ * a with (a, b, c) a cyclic permutation of (x, y, z), both P_b and P_c lie in 1..n_axis-2 (edges on the faces of the grid emit nothing:
+ * the surface is open there, as the marching-cubes surface is).  Its cells, all at P_a along a, are q0 = (P_b - 1, P_c - 1),
+ * q1 = (P_b, P_c - 1), q2 = (P_b, P_c), q3 = (P_b - 1, P_c); the triangles are (q0, q1, q2), (q0, q2, q3) when P is inside (the quad's
+ * normal then points along +a, out of the solid, the orientation of the marching-cubes faces) and (q0, q2, q1), (q0, q3, q2) otherwise.
+ * Faces are ordered by owning edge -- image, linear index of P, axis: the order of the crossing vertices -- and hold int32 dual vertex
+ * numbers LOCAL to the image.
+ *   sc_dual_contour_count      cell_block_counts, face_block_counts [n_images * sc_isosurface_blocks_per_image(n_axis)] int: owning
+ *                    cells and triangles (2 per quad) of every block of 1,024 consecutive cubes; sc_isosurface_block_scan turns each
+ *                    into int64 offsets and per-image totals.  The caller reads the totals and sizes dual_verts [cells][3] and faces
+ *                    [triangles][3] (a cell count fits int32 because a cube count does).
+ *   sc_dual_contour_cell_emit  dual_verts at the cell offsets; cell_map [n_images][(n_axis-1)^3] int32 (caller-allocated, no fill
+ *                    needed: written at owning cells only) receives each owning cell's image-local dual vertex number.
+ *   sc_dual_contour_face_emit  faces at the face offsets, from masks and cell_map.
+ * Plain vector stores, no atomics: the same bits from run to run, whatever n_images or the stream.  n_images <= 0 returns 0 and launches
+ * nothing; hipErrorInvalidValue for n_axis outside [2, 1024], a NULL pointer, or a reg that is not a finite number > 0.               */
+int sc_dual_contour_count(const unsigned char* masks, int n_images, int n_axis, int* cell_block_counts, int* face_block_counts, void* stream);
+int sc_dual_contour_cell_emit(const unsigned char* masks, const float* verts, const float* normals, const int* vmap,
+                              const long long* vertex_block_offsets, int n_images, int n_axis, float reg, const long long* cell_block_offsets,
+                              float* dual_verts, int* cell_map, void* stream);
+int sc_dual_contour_face_emit(const unsigned char* masks, const int* cell_map, int n_images, int n_axis, const long long* face_block_offsets,
+                              int* faces, void* stream);
+
 /* ---- camera algebra of a render -------------------------------------------------------------------
  * sc_camera_rays_*: utils/camera.py:157-196 (get_center_and_ray on the rendered pixels only) + the normalisation of
  * model/renderer.py:69-76.  pose [n_images][3][4] = [R|t] world->camera, intr [n_images][3][3], ray_idx

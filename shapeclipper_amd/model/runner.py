@@ -644,7 +644,8 @@ class Runner:
 
     def dump_geometry(self, opt, var, folder):
         """{idx}_mesh.ply (the predicted mesh) and {idx}_pointclouds_comp.ply (prediction red, ground truth green) of an evaluated batch;
-        with --hip.mesh_color also {idx}_mesh_color.ply (the device mesh with vertex normals and the sample's predicted colours)."""
+        with --hip.mesh_color also {idx}_mesh_color.ply (the device mesh with vertex normals and the sample's predicted colours); with
+        --eval.dual_mesh also {idx}_mesh_dual.ply (eval_3D.meshes_dual: the dual-contouring mesh of the same grid, positions and faces)."""
         if eval_3D.HAVE_MESHING:
             meshes = var.mesh_pred                      # trimesh meshes of the PyMCubes branch
         else:
@@ -655,6 +656,11 @@ class Runner:
             net = self.graph.module
             coloured = eval_3D.mesh_attributes(opt, net.sdf_network, net.rgb_network, var.proj_latent_sdf, var.proj_latent_rgb, var.level_vox)
             util_vis.dump_meshes(opt, var.idx, "mesh_color", coloured, folder=folder)
+        reg = options.dual_mesh_reg(opt)
+        if reg is not None:
+            net = self.graph.module
+            dual = eval_3D.meshes_dual(opt, net.sdf_network, var.proj_latent_sdf, var.level_vox, reg)
+            util_vis.dump_meshes(opt, var.idx, "mesh_dual", dual, folder=folder)
         if "dpc" in var:
             util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_comp", var.dpc_pred, var.dpc.points, folder=folder)
 

@@ -675,15 +675,13 @@ def isosurface_triangles(level: torch.Tensor, iso: float = 0.0, method: str = "c
     return tris, per_image
 
 
-def isosurface_mesh(level: torch.Tensor, iso: float = 0.0):
-    """level [B,S,S,S] (device) -> (verts [V,3] fp32, faces [F,3] int32, v_count [B] int64, f_count [B] int64; counts on the host).
+_MeshState = collections.namedtuple("_MeshState", ["level", "masks", "offsets", "voffsets", "verts", "vmap", "v_count", "f_count"])
 
-    The indexed form of isosurface_triangles(method="cubes"): one vertex per grid edge whose end values lie on different sides of iso,
-    ordered by image, owning grid point (its lower end, linear index) and axis, shared by every triangle around the edge; faces are
-    vertex numbers local to their image, so image b's mesh is verts[vs:ve], faces[fs:fe] with the offsets of the two counts.
-    verts[faces] of an image equals its triangles from isosurface_triangles bit for bit, in the same order.  Two scans with one host
-    read each (faces: the soup's count / scan over 1,024-cube blocks; vertices: 1,024-point blocks), vertex emit, face emit --
-    csrc/isosurface.hip.  Scratch: a vertex-number map of 12 bytes per grid point, written at crossing edges only."""
+
+def _mesh_state(level, iso, who):
+    """What the indexed marching-cubes mesh and the dual mesh share, up to and including the vertex emit: the contiguous fp32 grid, the
+    case byte of every cube, the triangle block offsets, the vertex block offsets, the crossing vertices verts [V,3] (grid-index units),
+    the vertex-number map (None when V == 0) and the two per-image counts on the host.  `who` names the caller in the refusals."""
     lib = _lib.load()
     level = level.contiguous().float()
     B, S = level.shape[0], level.shape[1]
@@ -691,7 +689,7 @@ def isosurface_mesh(level: torch.Tensor, iso: float = 0.0):
     bpi = int(lib.sc_isosurface_blocks_per_image(S))
     vbpi = int(lib.sc_marching_cubes_mesh_vertex_blocks_per_image(S))
     if bpi <= 0 or vbpi <= 0:
-        raise RuntimeError("shapeclipper_amd: isosurface_mesh needs 2 <= grid side <= 1024, got %d" % S)
+        raise RuntimeError("shapeclipper_amd: %s needs 2 <= grid side <= 1024, got %d" % (who, S))
     dev = level.device
     counts = torch.empty(B * bpi, device=dev, dtype=torch.int32)                    # triangles per workgroup of 1,024 cubes
     masks = torch.empty(B * (S - 1) ** 3, device=dev, dtype=torch.uint8)            # case index per cube
@@ -711,18 +709,91 @@ def isosurface_mesh(level: torch.Tensor, iso: float = 0.0):
     counts_host = torch.stack([v_count, f_count]).cpu()                             # the one host read: it sizes both outputs
     v_count, f_count = counts_host[0], counts_host[1]
     if B and int(v_count.max()) > 2 ** 31 - 1:
-        raise RuntimeError("shapeclipper_amd: isosurface_mesh: image %d has %d vertices; int32 face indices hold at most 2^31 - 1"
-                           % (int(v_count.argmax()), int(v_count.max())))
-    V, F = int(v_count.sum()), int(f_count.sum())
+        raise RuntimeError("shapeclipper_amd: %s: image %d has %d vertices; int32 face indices hold at most 2^31 - 1"
+                           % (who, int(v_count.argmax()), int(v_count.max())))
+    V = int(v_count.sum())
     verts = torch.empty(V, 3, device=dev, dtype=torch.float32)
-    faces = torch.empty(F, 3, device=dev, dtype=torch.int32)
+    vmap = None
     if V > 0:
         vmap = torch.empty(B * S ** 3 * 3, device=dev, dtype=torch.int32)          # vertex number per (grid point, axis); no fill
         _lib.check(lib.sc_marching_cubes_mesh_vertex_emit(_lib.ptr(level), B, S, iso, _lib.ptr(voffsets), _lib.ptr(verts),
                                                           _lib.ptr(vmap), _lib.stream()), "sc_marching_cubes_mesh_vertex_emit")
-        if F > 0:
-            _lib.check(lib.sc_marching_cubes_mesh_face_emit(B, S, _lib.ptr(offsets), _lib.ptr(masks), _lib.ptr(vmap), _lib.ptr(faces),
-                                                            _lib.stream()), "sc_marching_cubes_mesh_face_emit")
+    return _MeshState(level, masks, offsets, voffsets, verts, vmap, v_count, f_count)
+
+
+def isosurface_mesh(level: torch.Tensor, iso: float = 0.0):
+    """level [B,S,S,S] (device) -> (verts [V,3] fp32, faces [F,3] int32, v_count [B] int64, f_count [B] int64; counts on the host).
+
+    The indexed form of isosurface_triangles(method="cubes"): one vertex per grid edge whose end values lie on different sides of iso,
+    ordered by image, owning grid point (its lower end, linear index) and axis, shared by every triangle around the edge; faces are
+    vertex numbers local to their image, so image b's mesh is verts[vs:ve], faces[fs:fe] with the offsets of the two counts.
+    verts[faces] of an image equals its triangles from isosurface_triangles bit for bit, in the same order.  Two scans with one host
+    read each (faces: the soup's count / scan over 1,024-cube blocks; vertices: 1,024-point blocks), vertex emit, face emit --
+    csrc/isosurface.hip.  Scratch: a vertex-number map of 12 bytes per grid point, written at crossing edges only."""
+    st = _mesh_state(level, iso, "isosurface_mesh")
+    B, S = st.level.shape[0], st.level.shape[1]
+    F = int(st.f_count.sum())
+    faces = torch.empty(F, 3, device=st.level.device, dtype=torch.int32)
+    if st.vmap is not None and F > 0:
+        _lib.check(_lib.load().sc_marching_cubes_mesh_face_emit(B, S, _lib.ptr(st.offsets), _lib.ptr(st.masks), _lib.ptr(st.vmap),
+                                                                _lib.ptr(faces), _lib.stream()), "sc_marching_cubes_mesh_face_emit")
+    return st.verts, faces, st.v_count, st.f_count
+
+
+def dual_contour_mesh(level: torch.Tensor, normals: torch.Tensor, iso: float = 0.0, reg: float = 0.05):
+    """level [B,S,S,S] (device), normals [V,3] fp32 (device) -> (verts [Vd,3] fp32 in grid-index units, faces [Fd,3] int32, v_count [B]
+    int64, f_count [B] int64; counts on the host): the dual-contouring mesh of the grid.
+
+    normals belong to the vertices of isosurface_mesh(level, iso), in their order (V of them).  One vertex per cell whose corners lie
+    on both sides of iso, where the tangent planes of the cell's crossings meet: the minimiser of sum (n_i . (x - p_i))^2 +
+    reg k |x - c|^2 over the cell's k crossings (c their mean), clamped into the cell; per image in ascending cell index.  One quad
+    (two triangles) per crossing grid edge with four cells around it, in the order of the crossing vertices, oriented as the faces
+    of isosurface_mesh; indices are local to the image.  include/shapeclipper_hip.h states the arithmetic operation by operation
+    (csrc/dual_contour.hip; bit-reproducible, no atomics).  On top of isosurface_mesh's launches: count, two scans, one more host read
+    to size the outputs, cell emit, face emit.  Scratch: the cell-to-vertex map, 4 bytes per cube, in the scratch cache ("dual contour").
+    ValueError for normals that are not fp32 [*,3] on level's device or a reg that is not a finite number > 0, before any launch, and
+    for a row count other than V once the crossing vertices are counted (before any dual-contouring launch); isosurface_mesh's refusals
+    otherwise."""
+    reg = float(reg)
+    if not 0.0 < reg < float("inf"):
+        raise ValueError("shapeclipper_amd: dual_contour_mesh needs a finite reg > 0, got %r" % reg)
+    if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or normals.dim() != 2 or normals.shape[1] != 3:
+        raise ValueError("shapeclipper_amd: dual_contour_mesh takes normals [V,3] fp32, got %s" % (
+            "%s %s" % (tuple(normals.shape), normals.dtype) if isinstance(normals, torch.Tensor) else type(normals).__name__))
+    if normals.device != level.device:
+        raise ValueError("shapeclipper_amd: dual_contour_mesh: normals on %s, level on %s" % (normals.device, level.device))
+    lib = _lib.load()
+    st = _mesh_state(level, iso, "dual_contour_mesh")
+    B, S = st.level.shape[0], st.level.shape[1]
+    dev = st.level.device
+    if normals.shape[0] != st.verts.shape[0]:
+        raise ValueError("shapeclipper_amd: dual_contour_mesh: %d normals for the %d crossing vertices of isosurface_mesh(level, iso)"
+                         % (normals.shape[0], st.verts.shape[0]))
+    if st.vmap is None:                                                             # no crossing edge: no image has a surface
+        return (torch.empty(0, 3, device=dev, dtype=torch.float32), torch.empty(0, 3, device=dev, dtype=torch.int32),
+                torch.zeros(B, dtype=torch.int64), torch.zeros(B, dtype=torch.int64))
+    normals = normals.contiguous()
+    bpi = int(lib.sc_isosurface_blocks_per_image(S))
+    counts = torch.empty(2, B * bpi, device=dev, dtype=torch.int32)                 # owning cells / triangles per 1,024-cube block
+    _lib.check(lib.sc_dual_contour_count(_lib.ptr(st.masks), B, S, _lib.ptr(counts[0]), _lib.ptr(counts[1]), _lib.stream()),
+               "sc_dual_contour_count")
+    offsets = torch.empty(2, B * bpi + 1, device=dev, dtype=torch.int64)
+    totals = torch.empty(2, B, device=dev, dtype=torch.int64)
+    for k in range(2):
+        _lib.check(lib.sc_isosurface_block_scan(_lib.ptr(counts[k]), B, S, _lib.ptr(offsets[k]), _lib.ptr(totals[k]), _lib.stream()),
+                   "sc_isosurface_block_scan")
+    totals = totals.cpu()                                                           # the one host read: it sizes both outputs
+    v_count, f_count = totals[0], totals[1]
+    Vd, Fd = int(v_count.sum()), int(f_count.sum())
+    verts = torch.empty(Vd, 3, device=dev, dtype=torch.float32)
+    faces = torch.empty(Fd, 3, device=dev, dtype=torch.int32)
+    cell_map = _scratch("dual contour", dev, B * (S - 1) ** 3).view(torch.int32)   # dual vertex number per cube; written at owning cells only
+    _lib.check(lib.sc_dual_contour_cell_emit(_lib.ptr(st.masks), _lib.ptr(st.verts), _lib.ptr(normals), _lib.ptr(st.vmap),
+                                             _lib.ptr(st.voffsets), B, S, reg, _lib.ptr(offsets[0]), _lib.ptr(verts), _lib.ptr(cell_map),
+                                             _lib.stream()), "sc_dual_contour_cell_emit")
+    if Fd > 0:
+        _lib.check(lib.sc_dual_contour_face_emit(_lib.ptr(st.masks), _lib.ptr(cell_map), B, S, _lib.ptr(offsets[1]), _lib.ptr(faces),
+                                                 _lib.stream()), "sc_dual_contour_face_emit")
     return verts, faces, v_count, f_count
 
 

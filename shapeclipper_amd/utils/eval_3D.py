@@ -9,6 +9,8 @@ Call surface of the reference's utils/eval_3D.py.
     They are used when importable; otherwise the mesh comes from the device marching-cubes kernels (csrc/isosurface.hip: the
     same vertex set, one vertex per sign-changing grid edge) and is sampled area-uniformly like trimesh does -- see DESIGN.md,
     SURVEY 8f-2.  meshes_device gives the same surface as an indexed mesh (shared vertices) for the PLY dumps of the evaluation.
+  * meshes_dual (`--eval.dual_mesh`): the dual-contouring mesh of the same grid from the SDF gradients at the crossings
+    (csrc/dual_contour.hip), which keeps corners and creases that marching cubes chamfers at the grid pitch.
 """
 from __future__ import annotations
 
@@ -144,6 +146,20 @@ def meshes_device(level, lo, hi, iso=0.0):
     return [(verts[v_start[b]:v_end[b]], faces[f_start[b]:f_end[b]]) for b in range(level.shape[0])]
 
 
+def _padded_vertex_queries(verts, v_count, v_start, lo, hi, S):
+    """The one-launch layout of the per-vertex network queries: (P, query [B P, 3]) with P = 16 ceil(max V_b / 16) rows per image, image
+    b's vertices at rows [b P, b P + V_b), padding rows repeating the image's first vertex; positions are where the level grid was sampled,
+    lo + v (hi - lo) / (S - 1) with v in grid-index units.  (0, None) when no image has a vertex."""
+    dev = verts.device
+    P = 16 * ((max(v_count.tolist(), default=0) + 15) // 16)
+    if P == 0:
+        return 0, None
+    start = torch.tensor(v_start, device=dev).clamp_max(verts.shape[0] - 1)
+    j = torch.arange(P, device=dev)
+    rows = torch.where(j[None] < v_count.to(dev)[:, None], start[:, None] + j[None], start[:, None]).reshape(-1)
+    return P, (lo + verts[rows] * ((hi - lo) / (S - 1))).contiguous()
+
+
 @torch.no_grad()
 def mesh_attributes(opt, sdf_network, rgb_network, proj_latent_sdf, proj_latent_rgb, level_vox):
     """level_vox [B,S,S,S] (compute_level_grid) -> per image (vertices [V,3] fp32, faces [F,3] int32, normals [V,3] fp32 unit,
@@ -167,15 +183,11 @@ def mesh_attributes(opt, sdf_network, rgb_network, proj_latent_sdf, proj_latent_
     v_end, f_end = torch.cumsum(v_count, 0).tolist(), torch.cumsum(f_count, 0).tolist()
     v_start, f_start = [0] + v_end[:-1], [0] + f_end[:-1]
     V = v_count.tolist()
-    P = 16 * ((max(V, default=0) + 15) // 16)
+    P, query = _padded_vertex_queries(verts, v_count, v_start, lo, hi, S)
     if P == 0:
         empty = (torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.int32, device=dev),
                  torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.uint8, device=dev))
         return [empty] * B
-    start = torch.tensor(v_start, device=dev).clamp_max(verts.shape[0] - 1)
-    j = torch.arange(P, device=dev)
-    rows = torch.where(j[None] < v_count.to(dev)[:, None], start[:, None] + j[None], start[:, None]).reshape(-1)
-    query = (lo + verts[rows] * ((hi - lo) / (S - 1))).contiguous()    # [B P, 3]
     if sdf_network.eager or rgb_network.eager:
         from ..model import eager_path
         _, feat, grad = eager_path.sdf_conditional_output(sdf_network, B, query, proj_latent_sdf, compute_grad=True)
@@ -189,6 +201,41 @@ def mesh_attributes(opt, sdf_network, rgb_network, proj_latent_sdf, proj_latent_
     colours = (rgb.clamp(0, 1) * 255).to(torch.uint8)
     return [(written[v_start[b]:v_end[b]], faces[f_start[b]:f_end[b]], normal[b * P:b * P + V[b]], colours[b * P:b * P + V[b]])
             for b in range(B)]
+
+
+@torch.no_grad()
+def meshes_dual(opt, sdf_network, proj_latent_sdf, level_vox, reg):
+    """level_vox [B,S,S,S] (compute_level_grid) -> per image (vertices [Vd,3] fp32, faces [Fd,3] int32) on the device: the dual-contouring
+    mesh of ops.dual_contour_mesh (`--eval.dual_mesh`, {idx}_mesh_dual.ply), which puts one vertex INSIDE every surface cell, where the
+    tangent planes of the cell's crossings meet, so corners and creases narrower than the grid pitch survive; `reg` holds the vertex near
+    the mean of the crossings.
+
+    The normals are the unit SDF gradients at the crossing vertices of ops.isosurface_mesh, queried at mesh_attributes' positions in its
+    padded one-launch layout (one ops.sdf_forward with d sdf/dx; sdf_network.eager: stock operators, model/eager_path.py).  The written
+    vertices take meshes_device's v / S (hi - lo) + lo, so the mesh overlays {idx}_mesh.ply.  The crossing vertices are extracted twice,
+    here for the queries and again inside dual_contour_mesh, whose public form takes the grid and the normals."""
+    lo, hi = opt.eval.range
+    B, S = level_vox.shape[0], level_vox.shape[1]
+    dev = level_vox.device
+    verts, _, v_count, _ = ops.isosurface_mesh(level_vox)
+    v_end = torch.cumsum(v_count, 0).tolist()
+    v_start = [0] + v_end[:-1]
+    P, query = _padded_vertex_queries(verts, v_count, v_start, lo, hi, S)
+    if P == 0:
+        return [(torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.int32, device=dev))] * B
+    if sdf_network.eager:
+        from ..model import eager_path
+        _, _, grad = eager_path.sdf_conditional_output(sdf_network, B, query, proj_latent_sdf, compute_grad=True)
+    else:
+        w_pack, cbias = sdf_network.packed(proj_latent_sdf)
+        _, grad, _ = ops.sdf_forward(query, w_pack, cbias, P, symmetric=bool(sdf_network.force_symmetry), want_grad=True, want_feat=False)
+    normal = torch.nn.functional.normalize(grad.detach(), dim=1, eps=1e-12)
+    normals = torch.cat([normal[b * P:b * P + n] for b, n in enumerate(v_count.tolist())])
+    dverts, dfaces, dv_count, df_count = ops.dual_contour_mesh(level_vox, normals, 0.0, reg)
+    dverts = dverts / S * (hi - lo) + lo
+    dv_end, df_end = torch.cumsum(dv_count, 0).tolist(), torch.cumsum(df_count, 0).tolist()
+    dv_start, df_start = [0] + dv_end[:-1], [0] + df_end[:-1]
+    return [(dverts[dv_start[b]:dv_end[b]], dfaces[df_start[b]:df_end[b]]) for b in range(B)]
 
 
 def convert_to_explicit_worker(opt, i, level_vox_i, isoval, meshes, pointclouds=None):

@@ -86,6 +86,17 @@ def hip(opt, key):
     return opt.get("hip", {}).get(key, default)
 
 
+def dual_mesh_reg(opt):
+    """The evaluation's dual-contouring dump: None unless `--eval.dual_mesh` is set (absent means off), else `--eval.dual_reg` (default
+    0.05), the weight that holds a cell's vertex near the mean of its crossings (ops.dual_contour_mesh).  An evaluation setting beside
+    eval.vox_res, not a hip.* switch.  A dual_reg that is not a real number in (0, 1] is a ValueError, whether or not the dump is on."""
+    ev = opt.get("eval", None) or {}
+    reg = ev.get("dual_reg", 0.05)
+    if isinstance(reg, bool) or not isinstance(reg, (int, float)) or not 0.0 < reg <= 1.0:
+        raise ValueError("eval.dual_reg must be a float in (0, 1], got %r" % (reg,))
+    return float(reg) if ev.get("dual_mesh", False) else None
+
+
 def parse_arguments(args):
     """--key1.key2=value ; --flag (true) ; --flag! (false)"""
     opt_cmd = {}
@@ -175,6 +186,7 @@ def process_options(opt):
             (lo, hi), v = row.kind, hip(opt, row.key)
             if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
                 raise ValueError("hip.%s must be an integer in %d..%d, got %r" % (row.key, lo, hi, v))
+    dual_mesh_reg(opt)
     torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
     for row in HIP_TABLE:
         if row.drives is not None:
