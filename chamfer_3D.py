@@ -56,19 +56,38 @@ def forward(xyz1, xyz2, dist1, dist2, idx1, idx2):
         return _forward(lib, b, n, m, xyz1, xyz2, dist1, dist2, idx1, idx2)
 
 
-def _forward(lib, b, n, m, xyz1, xyz2, dist1, dist2, idx1, idx2):
+def _path(n, m):
+    """Which forward serves an [*, n, 3] x [*, m, 3] call under the current SEARCH: "grid", "split" or "plain"."""
     if SEARCH not in ("grid", "brute"):
         raise ValueError("chamfer_3D.SEARCH must be 'grid' or 'brute', got %r" % (SEARCH,))
     if SEARCH == "grid" and min(n, m) >= GRID_MIN_POINTS:
-        ws = torch.empty(lib.sc_chamfer3d_grid_workspace_bytes(b, n, m), dtype=torch.uint8, device=xyz1.device)
+        return "grid"
+    return "split" if max(n, m) >= 4096 else "plain"
+
+
+def _workspace(lib, b, n, m, device):
+    """The scratch the chosen forward needs (None for the plain all-pairs kernel); its contents are irrelevant on entry, so a caller
+    that searches the same shapes repeatedly (ops.icp_align) allocates it once and hands it to every _forward."""
+    path = _path(n, m)
+    if path == "grid":
+        return torch.empty(lib.sc_chamfer3d_grid_workspace_bytes(b, n, m), dtype=torch.uint8, device=device)
+    if path == "split":
+        return torch.empty(b * (n + m), dtype=torch.int64, device=device)
+    return None
+
+
+def _forward(lib, b, n, m, xyz1, xyz2, dist1, dist2, idx1, idx2, ws=None):
+    path = _path(n, m)
+    if ws is None:
+        ws = _workspace(lib, b, n, m, xyz1.device)
+    if path == "grid":
         code = lib.sc_chamfer3d_forward_grid(_lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(dist1), _lib.ptr(dist2), _lib.ptr(idx1),
                                              _lib.ptr(idx2), b, n, m, _lib.ptr(ws), _lib.stream())
         _lib.check(code, "sc_chamfer3d_forward_grid")
         return 1
-    if max(n, m) >= 4096:
+    if path == "split":
         # all pairs with the target cloud cut into slices so that the launch is a whole number of full rounds of the chip (nsplit 0: the
         # library chooses per direction; evaluation at b = 1: 13 slices -> one round; b = 32: 2 slices -> 4.9 rounds instead of 2.45)
-        ws = torch.empty(b * (n + m), dtype=torch.int64, device=xyz1.device)
         code = lib.sc_chamfer3d_forward_split(_lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(dist1), _lib.ptr(dist2),
                                               _lib.ptr(idx1), _lib.ptr(idx2), b, n, m, NSPLIT, _lib.ptr(ws), _lib.stream())
         _lib.check(code, "sc_chamfer3d_forward_split")

@@ -637,6 +637,52 @@ int sc_dual_contour_cell_emit(const unsigned char* masks, const float* verts, co
 int sc_dual_contour_face_emit(const unsigned char* masks, const int* cell_map, int n_images, int n_axis, const long long* face_block_offsets,
                               int* faces, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Similarity ICP of the evaluation (csrc/icp.hip; what ops.icp_fit / icp_apply / icp_align run).  The search between two fits is
+ * sc_chamfer3d_forward* above; these are the fit, the apply and the objective around it.  src [n_images][n][3] and dst [n_images][m][3]
+ * fp32; idx1 [n_images][n] int32 = nearest dst point of each CURRENT (transformed) source point, idx2 [n_images][m] int32 = nearest
+ * current source point of each dst point, as sc_chamfer3d_forward* writes them.  transform [n_images][4][4] and scale [n_images] float64.
+ * The file is built without contraction: every operation below rounds once, in float64 unless it says fp32.
+ *
+ * Pairs.  Image b has two halves of pairs (p, q), p always an ORIGINAL source point (the fit is absolute, not incremental):
+ *   half 1: (src[i], dst[idx1[i]]) for i = 0..n-1, weight 1/n each;   half 2: (src[idx2[j]], dst[j]) for j = 0..m-1, weight 1/m each.
+ * An index outside its cloud turns the pair into NaNs (no read out of bounds); the image then keeps its previous transform.
+ *
+ * Sums.  For a per-pair term f, <f> = (S1(f) / n + S2(f) / m) / 2, S1 and S2 the sums of f over the two halves: the weight is applied to
+ * the half's sum, not to each term (so equal points average to themselves exactly).  Each half is cut into chunks of SC_ICP_CHUNK =
+ * 1,024 consecutive pairs, one workgroup of 256 threads per chunk, and a half's sum is formed in this order:
+ *   thread t adds its chunk's pairs t, t + 256, t + 512, t + 768, ascending (pairs past the end of the half add nothing);
+ *   each wave folds its 64 lanes by v += v[lane + 32], then + 16, + 8, + 4, + 2, + 1; the workgroup adds its four wave sums in wave order;
+ *   the chunk partials are added in ascending chunk number.
+ * No float atomics anywhere: partials are plain stores, read by a later launch.  The same bits from run to run, on any stream, and for an
+ * image whatever else is in the batch.
+ *
+ * sc_icp_fit (Umeyama): pm = <p>, qm = <q>; with dp = p - pm, dq = q - qm:  H = <dq dp^T> (H_rc = <dq_r dp_c>),
+ *   var_p = <(dp_0 dp_0 + dp_1 dp_1) + dp_2 dp_2>.  H = U D V^T by one-sided Jacobi in one thread per image: A = H, V = I; sweeps over the
+ *   column pairs (0,1), (0,2), (1,2) rotate A's and V's columns from the right until every pair of A's columns is orthogonal to 1e-16 of
+ *   the product of their norms (at most 30 sweeps); D = the column norms, sorted descending with the columns, u_k = a_k / d_k.
+ *   R = U diag(1, 1, det U det V) V^T, formed as u_0 v_0^T + u_1 v_1^T + (u_0 x u_1)(v_0 x v_1)^T (the same matrix, and defined when
+ *   d_2 = 0);  s = ((d_0 + d_1) + sigma d_2) / var_p with sigma = det U det V = sign((a_2 . (u_0 x u_1)) (v_2 . (v_0 x v_1))), or s = 1
+ *   when with_scale == 0;  M = s R;  t_r = qm_r - ((M_r0 pm_0 + M_r1 pm_1) + M_r2 pm_2).
+ *   transform = [M t; 0 0 0 1], scale = s.  The image keeps its previous transform and scale -- prev_transform / prev_scale, both NULL
+ *   for the identity and 1; they may be transform / scale themselves -- when a sum is not finite, var_p <= 0, d_1 <= 1e-12 d_0 (rank
+ *   <= 1: the rotation is undetermined), or s or an entry of M or t is not finite.  Three launches: means per chunk, centred sums per
+ *   chunk (each workgroup first adds the mean partials in the stated order), solve.
+ * sc_icp_apply: out[i][r] = fp32(((M_r0 x + M_r1 y) + M_r2 z) + t_r), (x, y, z) = src[i] widened to float64; one rounding to fp32.
+ * sc_icp_objective: objective[b * objective_stride] = S1(dist1) / n + S2(dist2) / m in float64, the sums in the order above (dist1
+ *   [n_images][n], dist2 [n_images][m] fp32, the squared distances of the search).  Two launches.
+ * workspace: sc_icp_workspace_bytes(n_images, n, m) bytes (128 per chunk), contents irrelevant on entry; fit and objective may share it
+ *   on one stream.  -1 for sizes the entry points refuse.
+ * n_images <= 0 returns 0 and launches nothing; hipErrorInvalidValue for a NULL pointer (prev_* aside, which must be NULL together),
+ * n or m < 1, n_images > 65535 or objective_stride < 1.                                                                                */
+#define SC_ICP_CHUNK 1024
+long long sc_icp_workspace_bytes(int n_images, int n, int m);
+int sc_icp_fit(const float* src, const float* dst, const int* idx1, const int* idx2, int n_images, int n, int m, int with_scale,
+               const double* prev_transform, const double* prev_scale, double* workspace, double* transform, double* scale, void* stream);
+int sc_icp_apply(const float* src, const double* transform, int n_images, int n, float* out, void* stream);
+int sc_icp_objective(const float* dist1, const float* dist2, int n_images, int n, int m, double* workspace, double* objective,
+                     long long objective_stride, void* stream);
+
 /* ---- camera algebra of a render -------------------------------------------------------------------
  * sc_camera_rays_*: utils/camera.py:157-196 (get_center_and_ray on the rendered pixels only) + the normalisation of
  * model/renderer.py:69-76.  pose [n_images][3][4] = [R|t] world->camera, intr [n_images][3][3], ray_idx

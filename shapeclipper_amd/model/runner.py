@@ -384,6 +384,7 @@ class Runner:
         metric = dict(dist_acc=0., dist_cov=0.)
         C = opt.data.num_classes
         acc_cat, comp_cat, counts = [0.] * C, [0.] * C, [0.001] * C
+        f_scores_icp, acc_cat_icp, comp_cat_icp = [], [0.] * C, [0.] * C     # --eval.icp: the same tallies of the ICP-aligned metrics
         loader = tqdm.tqdm(self.test_loader, desc="evaluating", leave=False)
         for it, batch in enumerate(loader):
             var = self.evaluate_batch(opt, edict(batch), ep, it, single_gpu=True)
@@ -392,6 +393,10 @@ class Runner:
             for i in range(len(var.idx)):
                 c = var.category_label[i].item()
                 counts[c] += 1; acc_cat[c] += var.cd_acc[i].item(); comp_cat[c] += var.cd_comp[i].item()
+                if "icp" in var:
+                    acc_cat_icp[c] += var.cd_acc_icp[i].item(); comp_cat_icp[c] += var.cd_comp_icp[i].item()
+            if "icp" in var:
+                f_scores_icp.append(var.f_score_icp)
             metric["dist_acc"] += dist_acc * len(var.idx)
             metric["dist_cov"] += dist_cov * len(var.idx)
             loader.set_postfix(CD="{:.3f}".format(float((dist_acc + dist_cov) / 2)))
@@ -411,6 +416,16 @@ class Runner:
                 for i, th in enumerate(opt.eval.f_thresholds):
                     line = "F-score @ %.2f: %.4f" % (th * 100, fs[i].item())
                     print(line); f.write(line + "\n")
+            if f_scores_icp:                            # cd_cat_icp.txt / f_score_icp.txt, in the formats of their namesakes
+                with open(os.path.join(opt.output_path, "cd_cat_icp.txt"), "w") as f:
+                    f.write("CD     Acc    Comp   Count Cat\n")
+                    for i in range(C):
+                        a, c = acc_cat_icp[i] / counts[i], comp_cat_icp[i] / counts[i]
+                        f.write("%.4f %.4f %.4f %5d %s\n" % ((a + c) / 2, a, c, counts[i], names[i]))
+                fs = torch.cat(f_scores_icp, dim=0).mean(dim=0)
+                with open(os.path.join(opt.output_path, "f_score_icp.txt"), "w") as f:
+                    for i, th in enumerate(opt.eval.f_thresholds):
+                        f.write("F-score @ %.2f: %.4f\n" % (th * 100, fs[i].item()))
         n = max(len(self.test_data), 1)
         for k in metric:
             metric[k] /= n
@@ -423,15 +438,16 @@ class Runner:
         """Evaluation over all ranks (BASELINE config[4]; the reference evaluates on one GPU, evaluate.py:16-18):
         rank r takes the test samples with index % world == r (eval.batch_size = 1), per-sample records are
         gathered once, rank 0 writes chamfer.txt / cd_cat.txt / f_score.txt in sample order (with --hip.largest_component also
-        components.txt, from a second gather of the per-sample counts).  Every rank writes the per-sample files of its own samples
-        (dump_visuals: PNGs, mesh and point-cloud PLYs)."""
+        components.txt, from a second gather of the per-sample counts; with --eval.icp also chamfer_icp.txt / cd_cat_icp.txt /
+        f_score_icp.txt / icp.txt, from one more gather of the ICP-aligned records).  The value returned is the raw one.  Every rank
+        writes the per-sample files of its own samples (dump_visuals: PNGs, mesh and point-cloud PLYs)."""
         from ..parallel import gather_eval_records
         self.graph.eval()
         opt.H, opt.W = opt.eval.image_size
         # the reference's single-node convention is rank == device index; the process group's rank is the same number there and stays
         # right when ranks and devices are numbered differently (several nodes; tests/test_gpu_two_ranks.py: two ranks on one GPU)
         rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else util.get_rank(opt)
-        recs, comps = [], []
+        recs, comps, icps = [], [], []
         for it in range(rank, len(self.test_data), opt.world_size):
             sample = self.test_data[it]
             batch = {k: ({kk: vv[None] for kk, vv in v.items()} if isinstance(v, dict) else torch.as_tensor(v)[None]) for k, v in sample.items()}
@@ -442,6 +458,9 @@ class Runner:
                                    var.category_label.float().view(1)]))
             if "component_stats" in var:                # --hip.largest_component: (idx, n_components, inside_voxels, kept_voxels), exact in float64
                 comps.append(torch.cat([t.view(1).double() for t in (var.idx, *_component_counts(var))]))
+            if "icp" in var:                            # --eval.icp: the record above of the aligned metrics, then icp.txt's five numbers
+                icps.append(torch.cat([t.double().view(-1).cpu() for t in (var.idx, var.cd_acc_icp, var.cd_comp_icp, var.f_score_icp,
+                                                                           var.category_label, eval_3D.icp_summary(var))]))
         dev = next(self.graph.parameters()).device
         records = torch.stack(recs) if recs else torch.zeros(0, 10, device=dev)
         allr = gather_eval_records(records.to(dev), opt.world_size).cpu()
@@ -449,30 +468,44 @@ class Runner:
         if eval_3D.largest_component_enabled(opt):      # every rank joins the second gather, also one that evaluated no sample
             allc = gather_eval_records(torch.stack(comps).to(dev) if comps else torch.zeros(0, 4, device=dev, dtype=torch.float64),
                                        opt.world_size).cpu()
+        alli = None
+        if options.icp_settings(opt) is not None:       # likewise: every rank joins
+            alli = gather_eval_records(torch.stack(icps).to(dev) if icps else torch.zeros(0, 15, device=dev, dtype=torch.float64),
+                                       opt.world_size).cpu()
         opt.H, opt.W = opt.image_size
+        if rank == 0 and alli is not None:
+            self._write_gathered(opt, alli[:, :10].float(), "_icp")     # the metrics are fp32 values: tallied as the raw records are
+            with open("{}/icp.txt".format(opt.output_path), "w") as f:
+                for r in alli:
+                    f.write("%d %.8f %.8f %.8f %.8f %.8f\n" % (int(r[0]), *(float(x) for x in r[10:15])))
         if rank == 0 and allc is not None:
             with open("{}/components.txt".format(opt.output_path), "w") as f:
                 for r in allc:
                     f.write("{} {} {} {}\n".format(*(int(x) for x in r)))
         if rank == 0:
-            with open("{}/chamfer.txt".format(opt.output_path), "w") as f:
-                for r in allr:
-                    f.write("{} {:.8f} {:.8f}\n".format(int(r[0]), r[1], r[2]))
-            C = opt.data.num_classes
-            names = getattr(self.test_data, "label2cat", {i: str(i) for i in range(C)})
-            with open(os.path.join(opt.output_path, "cd_cat.txt"), "w") as f:
-                f.write("CD     Acc    Comp   Count Cat\n")
-                for c in range(C):
-                    sel = allr[allr[:, 9] == c]
-                    n = sel.shape[0] + 0.001
-                    a_, c_ = float(sel[:, 1].sum()) / n, float(sel[:, 2].sum()) / n
-                    f.write("%.4f %.4f %.4f %5d %s\n" % ((a_ + c_) / 2, a_, c_, n, names[c]))
-            fs = allr[:, 3:9].mean(dim=0)
-            with open(os.path.join(opt.output_path, "f_score.txt"), "w") as f:
-                for i, th in enumerate(opt.eval.f_thresholds):
-                    f.write("F-score @ %.2f: %.4f\n" % (th * 100, fs[i].item()))
+            self._write_gathered(opt, allr)
             log.loss_eval(opt, loss=None, chamfer=(allr[:, 1].mean(), allr[:, 2].mean()))
         return float((allr[:, 1].mean() + allr[:, 2].mean()) / 2) if allr.shape[0] else float("nan")
+
+    def _write_gathered(self, opt, allr, suffix=""):
+        """chamfer{suffix}.txt, cd_cat{suffix}.txt and f_score{suffix}.txt from gathered records [N,10] = (idx, cd_acc, cd_comp, f_score[6],
+        category) in sample order: the raw metrics (suffix "") and, with --eval.icp, the ICP-aligned ones ("_icp")."""
+        with open("{}/chamfer{}.txt".format(opt.output_path, suffix), "w") as f:
+            for r in allr:
+                f.write("{} {:.8f} {:.8f}\n".format(int(r[0]), r[1], r[2]))
+        C = opt.data.num_classes
+        names = getattr(self.test_data, "label2cat", {i: str(i) for i in range(C)})
+        with open(os.path.join(opt.output_path, "cd_cat{}.txt".format(suffix)), "w") as f:
+            f.write("CD     Acc    Comp   Count Cat\n")
+            for c in range(C):
+                sel = allr[allr[:, 9] == c]
+                n = sel.shape[0] + 0.001
+                a_, c_ = float(sel[:, 1].sum()) / n, float(sel[:, 2].sum()) / n
+                f.write("%.4f %.4f %.4f %5d %s\n" % ((a_ + c_) / 2, a_, c_, n, names[c]))
+        fs = allr[:, 3:9].mean(dim=0)
+        with open(os.path.join(opt.output_path, "f_score{}.txt".format(suffix)), "w") as f:
+            for i, th in enumerate(opt.eval.f_thresholds):
+                f.write("F-score @ %.2f: %.4f\n" % (th * 100, fs[i].item()))
 
     def evaluate_batch(self, opt, var, ep=None, it=None, single_gpu=False, visualize=False):
         var = util.move_to_device(var, opt.device)
@@ -645,7 +678,8 @@ class Runner:
     def dump_geometry(self, opt, var, folder):
         """{idx}_mesh.ply (the predicted mesh) and {idx}_pointclouds_comp.ply (prediction red, ground truth green) of an evaluated batch;
         with --hip.mesh_color also {idx}_mesh_color.ply (the device mesh with vertex normals and the sample's predicted colours); with
-        --eval.dual_mesh also {idx}_mesh_dual.ply (eval_3D.meshes_dual: the dual-contouring mesh of the same grid, positions and faces)."""
+        --eval.dual_mesh also {idx}_mesh_dual.ply (eval_3D.meshes_dual: the dual-contouring mesh of the same grid, positions and faces);
+        with --eval.icp also {idx}_pointclouds_comp_icp.ply (the ICP-aligned prediction of eval_3D.icp_metrics red, ground truth green)."""
         if eval_3D.HAVE_MESHING:
             meshes = var.mesh_pred                      # trimesh meshes of the PyMCubes branch
         else:
@@ -663,6 +697,8 @@ class Runner:
             util_vis.dump_meshes(opt, var.idx, "mesh_dual", dual, folder=folder)
         if "dpc" in var:
             util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_comp", var.dpc_pred, var.dpc.points, folder=folder)
+            if "dpc_pred_icp" in var:                   # --eval.icp: the ICP-aligned prediction red, the ground truth green
+                util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_comp_icp", var.dpc_pred_icp, var.dpc.points, folder=folder)
 
     @torch.no_grad()
     def dump_results(self, opt, var, ep, write_new=False, train=False):
@@ -675,6 +711,13 @@ class Runner:
                 with open("{}/components.txt".format(opt.output_path), "w" if write_new else "a") as f:
                     for row in zip(var.idx.tolist(), *(c.tolist() for c in _component_counts(var))):
                         f.write("{} {} {} {}\n".format(*row))
+            if "icp" in var:                            # --eval.icp: chamfer.txt's line of the aligned metrics; idx s angle_deg |t| objective first, last
+                with open("{}/chamfer_icp.txt".format(opt.output_path), "w" if write_new else "a") as f:
+                    for i, acc, comp in zip(var.idx, var.cd_acc_icp, var.cd_comp_icp):
+                        f.write("{} {:.8f} {:.8f}\n".format(i, acc, comp))
+                with open("{}/icp.txt".format(opt.output_path), "w" if write_new else "a") as f:
+                    for i, row in zip(var.idx.tolist(), eval_3D.icp_summary(var).tolist()):
+                        f.write("%d %.8f %.8f %.8f %.8f %.8f\n" % (i, *row))
 
     def save_checkpoint(self, opt, ep=0, it=0, best_val=np.inf, latest=False, best=False):
         assert _rank0(opt)

@@ -1596,3 +1596,139 @@ def chamfer_backward_ordered(xyz1, xyz2, graddist1, graddist2, idx1, idx2, want1
                                              _lib.ptr(graddist2), _lib.ptr(idx1), _lib.ptr(idx2), b, n, m, _lib.ptr(ws), _lib.stream())
     _lib.check(code, "sc_chamfer3d_backward_ordered")
     return g1, g2
+
+
+# ---- evaluation: similarity ICP of the prediction onto the ground truth (csrc/icp.hip; the search is chamfer_3D's) -----------------
+ICP_MAX_ITERS = 100
+ICP_MAX_IMAGES = 65535
+IcpResult = collections.namedtuple("IcpResult", ["transform", "s", "aligned", "dist1", "dist2", "idx1", "idx2", "objective"])
+
+
+def _icp_check(who, dev, **tensors):
+    """chamfer_3D._check for the ICP entry points (raw pointers go to the C ABI): TypeError for a wrong dtype, ValueError for a wrong
+    shape, another device or a non-contiguous tensor, RuntimeError for host tensors."""
+    if dev.type != "cuda":
+        raise RuntimeError(_lib.NO_CPU)
+    for name, (t, dtype, shape) in tensors.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("shapeclipper_amd: %s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
+        if t.dtype != dtype:
+            raise TypeError("shapeclipper_amd: %s: %s must be %s, got %s" % (who, name, dtype, t.dtype))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("shapeclipper_amd: %s: %s must have shape %s, got %s" % (who, name, tuple(shape), tuple(t.shape)))
+        if t.device != dev:
+            raise ValueError("shapeclipper_amd: %s: %s is on %s, src is on %s" % (who, name, t.device, dev))
+        if not t.is_contiguous():
+            raise ValueError("shapeclipper_amd: %s: %s must be contiguous" % (who, name))
+
+
+def _icp_dims(who, src, dst=None):
+    """(B, N[, M]) of src [B,N,3] (and dst [B,M,3]); ValueError for another rank, a mismatched B, an empty cloud or B > 65535."""
+    for name, t in (("src", src), ("dst", dst)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[2] != 3 or t.shape[1] < 1):
+            raise ValueError("shapeclipper_amd: %s: %s must be [B,N,3] with N >= 1, got %s" % (
+                who, name, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+    if src.shape[0] > ICP_MAX_IMAGES:
+        raise ValueError("shapeclipper_amd: %s takes at most %d images per call, got %d" % (who, ICP_MAX_IMAGES, src.shape[0]))
+    if dst is None:
+        return src.shape[0], src.shape[1]
+    if dst.shape[0] != src.shape[0]:
+        raise ValueError("shapeclipper_amd: %s: src has %d images, dst has %d" % (who, src.shape[0], dst.shape[0]))
+    return src.shape[0], src.shape[1], dst.shape[1]
+
+
+def _icp_workspace(lib, dev, B, N, M):
+    return _scratch("icp", dev, (lib.sc_icp_workspace_bytes(B, N, M) + 3) // 4) if B else None
+
+
+def icp_fit(src, dst, idx1, idx2, scale=True):
+    """src [B,N,3], dst [B,M,3] fp32, idx1 [B,N], idx2 [B,M] int32 (the nearest-neighbour indices chamfer_3D.forward writes for the
+    CURRENT source points against dst) -> (transform [B,4,4] float64, s [B] float64): the similarity (or rigid, scale=False) transform
+    that minimises the summed squared distance of the pairs (src[i], dst[idx1[i]]) / N and (src[idx2[j]], dst[j]) / M, by Umeyama's
+    closed form in float64 (sc_icp_fit; include/shapeclipper_hip.h states every sum's order).  transform = [s R, t; 0 0 0 1].  An image
+    whose sums are not finite or whose source pairs have rank <= 1 (one point, collinear points) gets the identity and s = 1."""
+    B, N, M = _icp_dims("icp_fit", src, dst)
+    i32 = torch.int32
+    _icp_check("icp_fit", src.device, src=(src, torch.float32, (B, N, 3)), dst=(dst, torch.float32, (B, M, 3)),
+               idx1=(idx1, i32, (B, N)), idx2=(idx2, i32, (B, M)))
+    lib = _lib.load()
+    T = torch.empty(B, 4, 4, device=src.device, dtype=torch.float64)
+    s = torch.empty(B, device=src.device, dtype=torch.float64)
+    with torch.cuda.device(src.device):
+        ws = _icp_workspace(lib, src.device, B, N, M)
+        code = lib.sc_icp_fit(_lib.ptr(src), _lib.ptr(dst), _lib.ptr(idx1), _lib.ptr(idx2), B, N, M, int(bool(scale)), None, None,
+                              _lib.ptr(ws), _lib.ptr(T), _lib.ptr(s), _lib.stream())
+    _lib.check(code, "sc_icp_fit")
+    return T, s
+
+
+def icp_apply(src, transform):
+    """src [B,N,3] fp32, transform [B,4,4] float64 -> [B,N,3] fp32: fp32(((m00 x + m01 y) + m02 z) + t0) per coordinate, formed in float64
+    without contraction and rounded once (sc_icp_apply); the last row of transform is not read."""
+    B, N = _icp_dims("icp_apply", src)
+    _icp_check("icp_apply", src.device, src=(src, torch.float32, (B, N, 3)), transform=(transform, torch.float64, (B, 4, 4)))
+    lib = _lib.load()
+    out = torch.empty_like(src)
+    with torch.cuda.device(src.device):
+        code = lib.sc_icp_apply(_lib.ptr(src), _lib.ptr(transform), B, N, _lib.ptr(out), _lib.stream())
+    _lib.check(code, "sc_icp_apply")
+    return out
+
+
+def icp_objective(dist1, dist2):
+    """dist1 [B,N], dist2 [B,M] fp32 (chamfer_3D.forward's squared distances) -> [B] float64 mean(dist1) + mean(dist2), summed in float64
+    in sc_icp_objective's fixed order: the quantity icp_align records per iteration."""
+    if not isinstance(dist1, torch.Tensor) or not isinstance(dist2, torch.Tensor) or dist1.dim() != 2 or dist2.dim() != 2 \
+            or dist1.shape[0] != dist2.shape[0] or dist1.shape[1] < 1 or dist2.shape[1] < 1 or dist1.shape[0] > ICP_MAX_IMAGES:
+        raise ValueError("shapeclipper_amd: icp_objective takes dist1 [B,N] and dist2 [B,M] with B <= %d" % ICP_MAX_IMAGES)
+    B, N, M = dist1.shape[0], dist1.shape[1], dist2.shape[1]
+    _icp_check("icp_objective", dist1.device, dist1=(dist1, torch.float32, (B, N)), dist2=(dist2, torch.float32, (B, M)))
+    lib = _lib.load()
+    out = torch.empty(B, device=dist1.device, dtype=torch.float64)
+    with torch.cuda.device(dist1.device):
+        ws = _icp_workspace(lib, dist1.device, B, N, M)
+        code = lib.sc_icp_objective(_lib.ptr(dist1), _lib.ptr(dist2), B, N, M, _lib.ptr(ws), _lib.ptr(out), 1, _lib.stream())
+    _lib.check(code, "sc_icp_objective")
+    return out
+
+
+def icp_align(src, dst, iters=30, scale=True):
+    """src [B,N,3], dst [B,M,3] fp32 -> IcpResult: `iters` rounds of (apply the transform to src, search both directions, fit), then one
+    last apply and search.  The count is fixed -- no convergence test, so no host synchronisation, and the result is reproducible bit
+    for bit.  The search is chamfer_3D.forward's (its path selection and chamfer_3D.SEARCH hold, ties as there), its workspace and outputs
+    allocated once.  Every fit pairs the ORIGINAL source points with dst, so the transform is absolute and nothing accumulates over the
+    rounds; a round whose fit is degenerate (icp_fit) keeps the transform it had.
+
+    transform [B,4,4] float64 = [s R, t; 0 0 0 1] and s [B] float64 after the last fit; aligned [B,N,3] = icp_apply(src, transform);
+    dist1 [B,N], dist2 [B,M] (squared, as Chamfer returns them), idx1, idx2 of the last search (aligned against dst); objective
+    [B, iters+1] float64, objective[:, j] = mean(dist1) + mean(dist2) under the transform after j fits (column 0: the input's own).
+    ValueError for iters outside 1..100; icp_fit's checks otherwise."""
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= ICP_MAX_ITERS:
+        raise ValueError("shapeclipper_amd: icp_align needs an integer iters in 1..%d, got %r" % (ICP_MAX_ITERS, iters))
+    B, N, M = _icp_dims("icp_align", src, dst)
+    _icp_check("icp_align", src.device, src=(src, torch.float32, (B, N, 3)), dst=(dst, torch.float32, (B, M, 3)))
+    import chamfer_3D
+    lib = _lib.load()
+    dev = src.device
+    f32, f64, i32 = torch.float32, torch.float64, torch.int32
+    T = torch.eye(4, device=dev, dtype=f64).repeat(B, 1, 1)
+    s = torch.ones(B, device=dev, dtype=f64)
+    cur = torch.empty_like(src)
+    d1, d2 = torch.empty(B, N, device=dev, dtype=f32), torch.empty(B, M, device=dev, dtype=f32)
+    i1, i2 = torch.empty(B, N, device=dev, dtype=i32), torch.empty(B, M, device=dev, dtype=i32)
+    objective = torch.empty(B, iters + 1, device=dev, dtype=f64)
+    if B == 0:
+        return IcpResult(T, s, cur, d1, d2, i1, i2, objective)
+    with torch.cuda.device(dev):
+        search_ws = chamfer_3D._workspace(lib, B, N, M, dev)
+        ws = _icp_workspace(lib, dev, B, N, M)
+        p = _lib.ptr
+        for j in range(iters + 1):
+            _lib.check(lib.sc_icp_apply(p(src), p(T), B, N, p(cur), _lib.stream()), "sc_icp_apply")
+            chamfer_3D._forward(lib, B, N, M, cur, dst, d1, d2, i1, i2, ws=search_ws)
+            col = ctypes.c_void_p(objective.data_ptr() + 8 * j)
+            _lib.check(lib.sc_icp_objective(p(d1), p(d2), B, N, M, p(ws), col, iters + 1, _lib.stream()), "sc_icp_objective")
+            if j < iters:
+                _lib.check(lib.sc_icp_fit(p(src), p(dst), p(i1), p(i2), B, N, M, int(bool(scale)), p(T), p(s), p(ws), p(T), p(s),
+                                          _lib.stream()), "sc_icp_fit")
+    return IcpResult(T, s, cur, d1, d2, i1, i2, objective)

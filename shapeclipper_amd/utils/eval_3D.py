@@ -9,6 +9,8 @@ Call surface of the reference's utils/eval_3D.py.
     They are used when importable; otherwise the mesh comes from the device marching-cubes kernels (csrc/isosurface.hip: the
     same vertex set, one vertex per sign-changing grid edge) and is sampled area-uniformly like trimesh does -- see DESIGN.md,
     SURVEY 8f-2.  meshes_device gives the same surface as an indexed mesh (shared vertices) for the PLY dumps of the evaluation.
+  * icp_metrics (`--eval.icp`): the same metrics after a similarity ICP of the prediction onto the ground truth (ops.icp_align,
+    csrc/icp.hip around the Chamfer search), reported beside the raw ones.
   * meshes_dual (`--eval.dual_mesh`): the dual-contouring mesh of the same grid from the SDF gradients at the crossings
     (csrc/dual_contour.hip), which keeps corners and creases that marching cubes chamfers at the grid pitch.
 """
@@ -292,6 +294,31 @@ def largest_component_enabled(opt):
     return bool(options.hip(opt, "largest_component"))
 
 
+@torch.no_grad()
+def icp_metrics(opt, var, iters, scale):
+    """`--eval.icp`: the metrics once more after ops.icp_align has registered the normalised prediction var.dpc_pred onto the normalised
+    ground truth var.dpc.points -- what is left when normalize_pc's centring, scaling and a small residual rotation no longer count.
+    Sets var.dpc_pred_icp (the aligned prediction), var.cd_acc_icp / var.cd_comp_icp [B] and var.f_score_icp [B,T], all from the square
+    roots of the distances of the loop's LAST search (no further search), and var.icp = dict(transform [B,4,4], s [B], objective
+    [B, iters+1]), float64.  The raw metrics are untouched.  A one-point prediction (an empty mesh) has no rotation to fit: its transform
+    stays the identity and the numbers equal the raw ones."""
+    res = ops.icp_align(var.dpc_pred.contiguous().float(), var.dpc.points.contiguous().float(), iters=iters, scale=scale)
+    dist_acc, dist_comp = res.dist1.sqrt(), res.dist2.sqrt()
+    var.dpc_pred_icp = res.aligned
+    var.f_score_icp = compute_fscore(dist_acc, dist_comp, opt.eval.f_thresholds)
+    var.cd_acc_icp = dist_acc.mean(dim=1)
+    var.cd_comp_icp = dist_comp.mean(dim=1)
+    var.icp = dict(transform=res.transform, s=res.s, objective=res.objective)
+
+
+def icp_summary(var):
+    """[B,5] float64 on the host, a row of icp.txt per sample: s, the rotation angle in degrees, |t|, the first and the last objective."""
+    T, s, obj = (var.icp[k].detach().cpu().double() for k in ("transform", "s", "objective"))
+    cos = ((T[:, 0, 0] + T[:, 1, 1] + T[:, 2, 2]) / s - 1) / 2
+    angle = torch.rad2deg(torch.acos(cos.clamp(-1, 1)))
+    return torch.stack([s, angle, T[:, :3, 3].norm(dim=1), obj[:, 0], obj[:, -1]], dim=1)
+
+
 _FLIP_PRED = [[1, 0, 0], [0, -1, 0], [0, 0, -1]]
 _FLIP_GT = [[-1, 0, 0], [0, 1, 0], [0, 0, 1]]
 
@@ -337,4 +364,7 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     assert dist_acc.shape[1] == opt.eval.num_points
     var.cd_acc = dist_acc.mean(dim=1)
     var.cd_comp = dist_comp.mean(dim=1)
+    icp = options.icp_settings(opt)
+    if icp is not None:                     # beside the raw metrics, never in their place
+        icp_metrics(opt, var, *icp)
     return dist_acc.mean(), dist_comp.mean()

@@ -97,6 +97,22 @@ def dual_mesh_reg(opt):
     return float(reg) if ev.get("dual_mesh", False) else None
 
 
+def icp_settings(opt):
+    """The evaluation's ICP-aligned metrics: None unless `--eval.icp` is set (absent means off), else (iters, scale) from
+    `--eval.icp_iters` (default 30, an integer in 1..100) and `--eval.icp_scale` (default true: fit a similarity; false: a rigid motion),
+    the arguments of ops.icp_align.  Evaluation settings beside eval.vox_res, not hip.* switches.  A bad value is a ValueError, whether
+    or not the switch is on."""
+    ev = opt.get("eval", None) or {}
+    on, iters, scale = ev.get("icp", False), ev.get("icp_iters", 30), ev.get("icp_scale", True)
+    if not isinstance(on, bool):
+        raise ValueError("eval.icp must be a bool, got %r" % (on,))
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= 100:
+        raise ValueError("eval.icp_iters must be an integer in 1..100, got %r" % (iters,))
+    if not isinstance(scale, bool):
+        raise ValueError("eval.icp_scale must be a bool, got %r" % (scale,))
+    return (iters, scale) if on else None
+
+
 def parse_arguments(args):
     """--key1.key2=value ; --flag (true) ; --flag! (false)"""
     opt_cmd = {}
@@ -187,6 +203,7 @@ def process_options(opt):
             if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
                 raise ValueError("hip.%s must be an integer in %d..%d, got %r" % (row.key, lo, hi, v))
     dual_mesh_reg(opt)
+    icp_settings(opt)
     torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
     for row in HIP_TABLE:
         if row.drives is not None:
