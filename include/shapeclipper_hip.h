@@ -683,6 +683,56 @@ int sc_icp_apply(const float* src, const double* transform, int n_images, int n,
 int sc_icp_objective(const float* dist1, const float* dist2, int n_images, int n, int m, double* workspace, double* objective,
                      long long objective_stride, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * k nearest neighbours inside a cloud, PCA normals from them, normal consistency of two clouds (csrc/point_normals.hip; what
+ * ops.knn_points / point_normals / normal_consistency run; the evaluation's --eval.normals).  The file is built without contraction:
+ * every operation below rounds once; tests/point_normals_ref.py restates all of it in numpy.
+ *
+ * sc_knn_points: points [n_images][n][3] fp32 -> idx [n_images][n][k] int32, dist [n_images][n][k] fp32.  For point i and every point j
+ *   of the same image (j = i included, as Open3D and PCL count it):
+ *       dx = p_j,0 - p_i,0, dy, dz likewise;   d = (dx dx + dy dy) + dz dz   in fp32 (five roundings; not Chamfer's fmaf form);
+ *       key = (bits(d) << 32) | j   as an unsigned 64-bit integer, bits(d) the 32 bits of the fp32 value.
+ *   Row i holds the k smallest keys in ascending order: idx = the low word, dist = the value whose bits are the high word.  d >= +0 or
+ *   NaN, so the unsigned order of the bits is the numeric order and a NaN sorts last; the keys of a row are distinct, so the order is
+ *   total: ties go to the lower index, duplicates need no rule, and the result is unique whatever order the search meets candidates in.
+ *   Search: a uniform grid over the cloud's bounding box (integer atomics only; arbitrary order inside a cell), the queries taken in
+ *   cell order, Chebyshev rings of cells around the query's cell.  After ring r every unseen point is at least lb away along one
+ *   axis; the walk stops when the list is full and  kth d < (lb - slack)^2 * 0.9999,  slack = 16 * 2^-23 * (max |coordinate| + largest
+ *   extent) for the rounding of the binning and of the faces, the factor for the rounding of d: no unseen point can beat or tie the
+ *   k-th key.  A query that has not stopped after 4 rings or 4,096 candidates, and every query of an image with a coordinate that is
+ *   not finite or >= 1e15 in magnitude, is answered by a scan of ALL points with the same key.  (SC_KNN_FORCE_SCAN=1 in the
+ *   environment, read once, sends every query to the scan: a timing aid.)
+ *   workspace: sc_knn_workspace_bytes(n_images, n, k) bytes, contents irrelevant on entry; -1 for sizes sc_knn_points refuses.
+ * sc_point_normals: points and idx [n_images][n][k] (any k indices per point; sc_knn_points' rows in rank order) -> normals
+ *   [n_images][n][3] fp32, variation [n_images][n] fp32.  Float64 throughout, q_r = points[idx[i][r]] widened (an index outside
+ *   0..n-1 counts as a NaN point, no read out of bounds):
+ *       m_a = (sum_r q_r,a) / k, r ascending from 0;    d_r = q_r - m;    C_ab = (sum_r d_r,a d_r,b) / k, r ascending (a <= b).
+ *   Eigenvectors by the cyclic two-sided Jacobi method, V = I, exactly 8 sweeps over the pairs (p, q) = (0,1), (0,2), (1,2), r the
+ *   third index.  A rotation is skipped when C_pq == 0; otherwise
+ *       theta = (C_qq - C_pp) / (2 C_pq);   t = sgn(theta) / (|theta| + sqrt(theta theta + 1))  (sgn(0) = 1),  or  t = 0.5 / theta
+ *       when |theta| > 1e150 (where theta theta overflows);   c = 1 / sqrt(t t + 1);   s = t c;   h = t C_pq;
+ *       C_pp = C_pp - h;  C_qq = C_qq + h;  C_pq = 0;  (C_rp, C_rq) = (c C_rp - s C_rq,  s C_rp + c C_rq);
+ *       (V_ip, V_iq) = (c V_ip - s V_iq,  s V_ip + c V_iq)  for i = 0, 1, 2.
+ *   The diagonal sorted ascending (equal values keep their index order) is l0 <= l1 <= l2.  The normal is V's column of l0, negated
+ *   when its component of largest magnitude (the first one on a tie) is negative, then rounded once to fp32: unoriented but
+ *   deterministic.  variation = fp32(l0 / ((l0 + l1) + l2)).  A point is degenerate -- normal (0,0,0), variation 0 -- when a component
+ *   of m or C or an eigenvalue is not finite, or when l1 <= 1e-12 l2 (rank <= 1: collinear or coincident neighbours, no plane).
+ * sc_normal_consistency: n1 [n_images][n][3], n2 [n_images][m][3] fp32, idx1 [n_images][n], idx2 [n_images][m] int32 (as
+ *   sc_chamfer3d_forward* writes them for the two clouds) -> acc, comp [n_images] float64:
+ *       acc[b] = S1(|n1[i] . n2[idx1[i]]|) / n,    comp[b] = S2(|n2[j] . n1[idx2[j]]|) / m,    u . v = (u_0 v_0 + u_1 v_1) + u_2 v_2
+ *   on values widened to float64; S1 and S2 are formed exactly in the order stated for sc_icp_objective above (chunks of SC_ICP_CHUNK,
+ *   thread, wave, workgroup, chunk stages; no float atomics).  An index outside its cloud contributes NaN (no read out of bounds), so
+ *   that image's value is NaN and the other images' are untouched.  workspace: 8 bytes per chunk of either half
+ *   (sc_icp_workspace_bytes(n_images, n, m) is more than enough), contents irrelevant on entry.
+ * Plain stores and integer atomics only: the same bits from run to run, on any stream, and for an image whatever else is in the batch.
+ * n_images <= 0 returns 0 and launches nothing; hipErrorInvalidValue for a NULL pointer, k outside 3..32, n < k (n, m < 1 for
+ * sc_normal_consistency) or n_images > 65535.                                                                                           */
+long long sc_knn_workspace_bytes(int n_images, int n, int k);
+int sc_knn_points(const float* points, int n_images, int n, int k, void* workspace, int* idx, float* dist, void* stream);
+int sc_point_normals(const float* points, const int* idx, int n_images, int n, int k, float* normals, float* variation, void* stream);
+int sc_normal_consistency(const float* n1, const float* n2, const int* idx1, const int* idx2, int n_images, int n, int m,
+                          double* workspace, double* acc, double* comp, void* stream);
+
 /* ---- camera algebra of a render -------------------------------------------------------------------
  * sc_camera_rays_*: utils/camera.py:157-196 (get_center_and_ray on the rendered pixels only) + the normalisation of
  * model/renderer.py:69-76.  pose [n_images][3][4] = [R|t] world->camera, intr [n_images][3][3], ray_idx

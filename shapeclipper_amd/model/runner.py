@@ -63,6 +63,18 @@ def _component_counts(var):
     return tuple(var.component_stats[k] for k in ("n_components", "inside_voxels", "kept_voxels"))
 
 
+NC_LINE = "%d %.8f %.8f %.8f\n"              # a line of normal_consistency.txt: idx nc_acc nc_comp nc
+
+
+def _normal_records(var):
+    """[B,5] float64 on the host, a record per sample of eval_3D.normal_metrics' results: idx, nc_acc, nc_comp, nc, category; [B,8]
+    with the three values after ICP behind them when --eval.icp ran as well."""
+    cols = [var.idx, var.nc_acc, var.nc_comp, var.nc, var.category_label]
+    if "nc_icp" in var:
+        cols += [var.nc_acc_icp, var.nc_comp_icp, var.nc_icp]
+    return torch.stack([c.detach().double().view(-1).cpu() for c in cols], dim=1)
+
+
 class Runner:
 
     def __init__(self, opt):
@@ -385,6 +397,7 @@ class Runner:
         C = opt.data.num_classes
         acc_cat, comp_cat, counts = [0.] * C, [0.] * C, [0.001] * C
         f_scores_icp, acc_cat_icp, comp_cat_icp = [], [0.] * C, [0.] * C     # --eval.icp: the same tallies of the ICP-aligned metrics
+        nc_recs = []                                    # --eval.normals: _normal_records of every batch
         loader = tqdm.tqdm(self.test_loader, desc="evaluating", leave=False)
         for it, batch in enumerate(loader):
             var = self.evaluate_batch(opt, edict(batch), ep, it, single_gpu=True)
@@ -397,6 +410,8 @@ class Runner:
                     acc_cat_icp[c] += var.cd_acc_icp[i].item(); comp_cat_icp[c] += var.cd_comp_icp[i].item()
             if "icp" in var:
                 f_scores_icp.append(var.f_score_icp)
+            if "nc" in var:
+                nc_recs.append(_normal_records(var))
             metric["dist_acc"] += dist_acc * len(var.idx)
             metric["dist_cov"] += dist_cov * len(var.idx)
             loader.set_postfix(CD="{:.3f}".format(float((dist_acc + dist_cov) / 2)))
@@ -426,6 +441,8 @@ class Runner:
                 with open(os.path.join(opt.output_path, "f_score_icp.txt"), "w") as f:
                     for i, th in enumerate(opt.eval.f_thresholds):
                         f.write("F-score @ %.2f: %.4f\n" % (th * 100, fs[i].item()))
+            if nc_recs:                                 # nc_cat.txt (and nc_cat_icp.txt); dump_results wrote the per-sample lines
+                self._write_normals(opt, torch.cat(nc_recs), per_sample=False)
         n = max(len(self.test_data), 1)
         for k in metric:
             metric[k] /= n
@@ -439,7 +456,8 @@ class Runner:
         rank r takes the test samples with index % world == r (eval.batch_size = 1), per-sample records are
         gathered once, rank 0 writes chamfer.txt / cd_cat.txt / f_score.txt in sample order (with --hip.largest_component also
         components.txt, from a second gather of the per-sample counts; with --eval.icp also chamfer_icp.txt / cd_cat_icp.txt /
-        f_score_icp.txt / icp.txt, from one more gather of the ICP-aligned records).  The value returned is the raw one.  Every rank
+        f_score_icp.txt / icp.txt, from one more gather of the ICP-aligned records; with --eval.normals also normal_consistency.txt /
+        nc_cat.txt and their _icp namesakes, from one more gather again).  The value returned is the raw one.  Every rank
         writes the per-sample files of its own samples (dump_visuals: PNGs, mesh and point-cloud PLYs)."""
         from ..parallel import gather_eval_records
         self.graph.eval()
@@ -447,7 +465,7 @@ class Runner:
         # the reference's single-node convention is rank == device index; the process group's rank is the same number there and stays
         # right when ranks and devices are numbered differently (several nodes; tests/test_gpu_two_ranks.py: two ranks on one GPU)
         rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else util.get_rank(opt)
-        recs, comps, icps = [], [], []
+        recs, comps, icps, ncs = [], [], [], []
         for it in range(rank, len(self.test_data), opt.world_size):
             sample = self.test_data[it]
             batch = {k: ({kk: vv[None] for kk, vv in v.items()} if isinstance(v, dict) else torch.as_tensor(v)[None]) for k, v in sample.items()}
@@ -461,6 +479,8 @@ class Runner:
             if "icp" in var:                            # --eval.icp: the record above of the aligned metrics, then icp.txt's five numbers
                 icps.append(torch.cat([t.double().view(-1).cpu() for t in (var.idx, var.cd_acc_icp, var.cd_comp_icp, var.f_score_icp,
                                                                            var.category_label, eval_3D.icp_summary(var))]))
+            if "nc" in var:                             # --eval.normals: (idx, nc_acc, nc_comp, nc, category[, the three after ICP])
+                ncs.append(_normal_records(var))
         dev = next(self.graph.parameters()).device
         records = torch.stack(recs) if recs else torch.zeros(0, 10, device=dev)
         allr = gather_eval_records(records.to(dev), opt.world_size).cpu()
@@ -472,7 +492,14 @@ class Runner:
         if options.icp_settings(opt) is not None:       # likewise: every rank joins
             alli = gather_eval_records(torch.stack(icps).to(dev) if icps else torch.zeros(0, 15, device=dev, dtype=torch.float64),
                                        opt.world_size).cpu()
+        alln = None
+        if options.normal_settings(opt) is not None:    # likewise
+            width = 5 if options.icp_settings(opt) is None else 8
+            alln = gather_eval_records(torch.cat(ncs).to(dev) if ncs else torch.zeros(0, width, device=dev, dtype=torch.float64),
+                                       opt.world_size).cpu()
         opt.H, opt.W = opt.image_size
+        if rank == 0 and alln is not None:
+            self._write_normals(opt, alln)
         if rank == 0 and alli is not None:
             self._write_gathered(opt, alli[:, :10].float(), "_icp")     # the metrics are fp32 values: tallied as the raw records are
             with open("{}/icp.txt".format(opt.output_path), "w") as f:
@@ -506,6 +533,26 @@ class Runner:
         with open(os.path.join(opt.output_path, "f_score{}.txt".format(suffix)), "w") as f:
             for i, th in enumerate(opt.eval.f_thresholds):
                 f.write("F-score @ %.2f: %.4f\n" % (th * 100, fs[i].item()))
+
+    def _write_normals(self, opt, alln, per_sample=True):
+        """The files of --eval.normals from records [N,5] = (idx, nc_acc, nc_comp, nc, category) in sample order, float64:
+        normal_consistency.txt (`idx nc_acc nc_comp nc` per sample; per_sample=False leaves it to dump_results) and nc_cat.txt, the
+        per-category means in cd_cat.txt's format.  Records [N,8] (with --eval.icp) carry the three values after ICP in columns 5..7,
+        which go to normal_consistency_icp.txt and nc_cat_icp.txt."""
+        C = opt.data.num_classes
+        names = getattr(self.test_data, "label2cat", {i: str(i) for i in range(C)})
+        for suffix, cols in (("", [1, 2, 3]), ("_icp", [5, 6, 7]))[:1 if alln.shape[1] < 8 else 2]:
+            if per_sample:
+                with open("{}/normal_consistency{}.txt".format(opt.output_path, suffix), "w") as f:
+                    for r in alln:
+                        f.write(NC_LINE % (int(r[0]), *(float(r[c]) for c in cols)))
+            with open(os.path.join(opt.output_path, "nc_cat{}.txt".format(suffix)), "w") as f:
+                f.write("NC     Acc    Comp   Count Cat\n")
+                for c in range(C):
+                    sel = alln[alln[:, 4] == c]
+                    n = sel.shape[0] + 0.001
+                    a_, c_ = float(sel[:, cols[0]].sum()) / n, float(sel[:, cols[1]].sum()) / n
+                    f.write("%.4f %.4f %.4f %5d %s\n" % ((a_ + c_) / 2, a_, c_, n, names[c]))
 
     def evaluate_batch(self, opt, var, ep=None, it=None, single_gpu=False, visualize=False):
         var = util.move_to_device(var, opt.device)
@@ -679,7 +726,9 @@ class Runner:
         """{idx}_mesh.ply (the predicted mesh) and {idx}_pointclouds_comp.ply (prediction red, ground truth green) of an evaluated batch;
         with --hip.mesh_color also {idx}_mesh_color.ply (the device mesh with vertex normals and the sample's predicted colours); with
         --eval.dual_mesh also {idx}_mesh_dual.ply (eval_3D.meshes_dual: the dual-contouring mesh of the same grid, positions and faces);
-        with --eval.icp also {idx}_pointclouds_comp_icp.ply (the ICP-aligned prediction of eval_3D.icp_metrics red, ground truth green)."""
+        with --eval.icp also {idx}_pointclouds_comp_icp.ply (the ICP-aligned prediction of eval_3D.icp_metrics red, ground truth green);
+        with --eval.normals also {idx}_pointclouds_normals.ply (pointclouds_comp's vertices as x y z nx ny nz red green blue: the SDF's
+        normals on the prediction, the estimated PCA normals on the ground truth)."""
         if eval_3D.HAVE_MESHING:
             meshes = var.mesh_pred                      # trimesh meshes of the PyMCubes branch
         else:
@@ -699,6 +748,9 @@ class Runner:
             util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_comp", var.dpc_pred, var.dpc.points, folder=folder)
             if "dpc_pred_icp" in var:                   # --eval.icp: the ICP-aligned prediction red, the ground truth green
                 util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_comp_icp", var.dpc_pred_icp, var.dpc.points, folder=folder)
+            if "normals_pred" in var:                   # --eval.normals: the clouds of pointclouds_comp with the normals that were compared
+                util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_normals", var.dpc_pred, var.dpc.points, folder=folder,
+                                                  pred_normals=var.normals_pred, gt_normals=var.dpc.normals)
 
     @torch.no_grad()
     def dump_results(self, opt, var, ep, write_new=False, train=False):
@@ -718,6 +770,12 @@ class Runner:
                 with open("{}/icp.txt".format(opt.output_path), "w" if write_new else "a") as f:
                     for i, row in zip(var.idx.tolist(), eval_3D.icp_summary(var).tolist()):
                         f.write("%d %.8f %.8f %.8f %.8f %.8f\n" % (i, *row))
+            if "nc" in var:                             # --eval.normals: idx nc_acc nc_comp nc (and the same after ICP)
+                rec = _normal_records(var)
+                for suffix, cols in (("", [1, 2, 3]), ("_icp", [5, 6, 7]))[:1 if rec.shape[1] < 8 else 2]:
+                    with open("{}/normal_consistency{}.txt".format(opt.output_path, suffix), "w" if write_new else "a") as f:
+                        for r in rec:
+                            f.write(NC_LINE % (int(r[0]), *(float(r[c]) for c in cols)))
 
     def save_checkpoint(self, opt, ep=0, it=0, best_val=np.inf, latest=False, best=False):
         assert _rank0(opt)

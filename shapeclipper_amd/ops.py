@@ -1732,3 +1732,76 @@ def icp_align(src, dst, iters=30, scale=True):
                 _lib.check(lib.sc_icp_fit(p(src), p(dst), p(i1), p(i2), B, N, M, int(bool(scale)), p(T), p(s), p(ws), p(T), p(s),
                                           _lib.stream()), "sc_icp_fit")
     return IcpResult(T, s, cur, d1, d2, i1, i2, objective)
+
+
+# ---- evaluation: k nearest neighbours, PCA normals and normal consistency (csrc/point_normals.hip) -----------------------------------
+KNN_MIN_K, KNN_MAX_K = 3, 32
+PointNormals = collections.namedtuple("PointNormals", ["normals", "variation", "idx", "dist"])
+
+
+def _knn_args(who, points, k):
+    """(B, N) of points [B,N,3] fp32 for a k in 3..32 with N >= k: _icp_dims' and _icp_check's refusals, ValueError for the k."""
+    if isinstance(k, bool) or not isinstance(k, int) or not KNN_MIN_K <= k <= KNN_MAX_K:
+        raise ValueError("shapeclipper_amd: %s needs an integer k in %d..%d, got %r" % (who, KNN_MIN_K, KNN_MAX_K, k))
+    B, N = _icp_dims(who, points)
+    _icp_check(who, points.device, points=(points, torch.float32, (B, N, 3)))
+    if N < k:
+        raise ValueError("shapeclipper_amd: %s: %d points per image are fewer than k = %d" % (who, N, k))
+    return B, N
+
+
+def knn_points(points, k):
+    """points [B,N,3] fp32 -> (idx [B,N,k] int32, dist [B,N,k] fp32): for every point the k nearest points of its own image, itself
+    included, by the key (bits of d, index) ascending with d = (dx dx + dy dy) + dz dz in fp32 -- an exact grid search (sc_knn_points;
+    include/shapeclipper_hip.h states the order and the search).  ValueError for k outside 3..32 or N < k."""
+    B, N = _knn_args("knn_points", points, k)
+    lib = _lib.load()
+    idx = torch.empty(B, N, k, device=points.device, dtype=torch.int32)
+    dist = torch.empty(B, N, k, device=points.device, dtype=torch.float32)
+    if B == 0:
+        return idx, dist
+    with torch.cuda.device(points.device):
+        ws = _scratch("knn", points.device, (lib.sc_knn_workspace_bytes(B, N, k) + 3) // 4)
+        code = lib.sc_knn_points(_lib.ptr(points), B, N, k, _lib.ptr(ws), _lib.ptr(idx), _lib.ptr(dist), _lib.stream())
+    _lib.check(code, "sc_knn_points")
+    return idx, dist
+
+
+def point_normals(points, k=16, idx=None):
+    """points [B,N,3] fp32 -> PointNormals(normals [B,N,3] fp32, variation [B,N] fp32, idx [B,N,k] int32, dist [B,N,k] fp32 or None): the
+    PCA normal of every point's k nearest neighbours (knn_points, or the idx [B,N,k] handed in, whose dist is then None) -- the
+    eigenvector of the smallest eigenvalue of their float64 covariance, unit, UNORIENTED (its largest component is made positive) -- and
+    the surface variation l0 / (l0 + l1 + l2).  Collinear, coincident or non-finite neighbourhoods get normal 0 and variation 0
+    (sc_point_normals)."""
+    B, N = _knn_args("point_normals", points, k)
+    dist = None
+    if idx is None:
+        idx, dist = knn_points(points, k)
+    else:
+        _icp_check("point_normals", points.device, idx=(idx, torch.int32, (B, N, k)))
+    lib = _lib.load()
+    normals = torch.empty(B, N, 3, device=points.device, dtype=torch.float32)
+    variation = torch.empty(B, N, device=points.device, dtype=torch.float32)
+    with torch.cuda.device(points.device):
+        code = lib.sc_point_normals(_lib.ptr(points), _lib.ptr(idx), B, N, k, _lib.ptr(normals), _lib.ptr(variation), _lib.stream())
+    _lib.check(code, "sc_point_normals")
+    return PointNormals(normals, variation, idx, dist)
+
+
+def normal_consistency(n1, n2, idx1, idx2):
+    """n1 [B,N,3], n2 [B,M,3] fp32 normals of two clouds, idx1 [B,N], idx2 [B,M] int32 (chamfer_3D.forward's nearest neighbours of the
+    clouds) -> (acc [B], comp [B]) float64: mean_i |n1[i] . n2[idx1[i]]| and mean_j |n2[j] . n1[idx2[j]]|, summed in float64 in
+    sc_icp_objective's fixed order (sc_normal_consistency).  An index outside its cloud makes that image's value NaN."""
+    B, N, M = _icp_dims("normal_consistency", n1, n2)
+    i32 = torch.int32
+    _icp_check("normal_consistency", n1.device, n1=(n1, torch.float32, (B, N, 3)), n2=(n2, torch.float32, (B, M, 3)),
+               idx1=(idx1, i32, (B, N)), idx2=(idx2, i32, (B, M)))
+    lib = _lib.load()
+    acc = torch.empty(B, device=n1.device, dtype=torch.float64)
+    comp = torch.empty(B, device=n1.device, dtype=torch.float64)
+    with torch.cuda.device(n1.device):
+        ws = _icp_workspace(lib, n1.device, B, N, M)
+        code = lib.sc_normal_consistency(_lib.ptr(n1), _lib.ptr(n2), _lib.ptr(idx1), _lib.ptr(idx2), B, N, M, _lib.ptr(ws), _lib.ptr(acc),
+                                         _lib.ptr(comp), _lib.stream())
+    _lib.check(code, "sc_normal_consistency")
+    return acc, comp

@@ -11,6 +11,9 @@ Call surface of the reference's utils/eval_3D.py.
     SURVEY 8f-2.  meshes_device gives the same surface as an indexed mesh (shared vertices) for the PLY dumps of the evaluation.
   * icp_metrics (`--eval.icp`): the same metrics after a similarity ICP of the prediction onto the ground truth (ops.icp_align,
     csrc/icp.hip around the Chamfer search), reported beside the raw ones.
+  * normal_metrics (`--eval.normals`): normal consistency, the mean |cosine| between each point's normal and its nearest neighbour's in
+    the other cloud, both ways: the SDF's own normals for the prediction, k-NN PCA normals (ops.point_normals,
+    csrc/point_normals.hip) for the ground truth, paired by the indices of the Chamfer search already made.
   * meshes_dual (`--eval.dual_mesh`): the dual-contouring mesh of the same grid from the SDF gradients at the crossings
     (csrc/dual_contour.hip), which keeps corners and creases that marching cubes chamfers at the grid pitch.
 """
@@ -301,7 +304,7 @@ def icp_metrics(opt, var, iters, scale):
     Sets var.dpc_pred_icp (the aligned prediction), var.cd_acc_icp / var.cd_comp_icp [B] and var.f_score_icp [B,T], all from the square
     roots of the distances of the loop's LAST search (no further search), and var.icp = dict(transform [B,4,4], s [B], objective
     [B, iters+1]), float64.  The raw metrics are untouched.  A one-point prediction (an empty mesh) has no rotation to fit: its transform
-    stays the identity and the numbers equal the raw ones."""
+    stays the identity and the numbers equal the raw ones.  Returns the IcpResult (normal_metrics pairs normals by its last search)."""
     res = ops.icp_align(var.dpc_pred.contiguous().float(), var.dpc.points.contiguous().float(), iters=iters, scale=scale)
     dist_acc, dist_comp = res.dist1.sqrt(), res.dist2.sqrt()
     var.dpc_pred_icp = res.aligned
@@ -309,6 +312,61 @@ def icp_metrics(opt, var, iters, scale):
     var.cd_acc_icp = dist_acc.mean(dim=1)
     var.cd_comp_icp = dist_comp.mean(dim=1)
     var.icp = dict(transform=res.transform, s=res.s, objective=res.objective)
+    return res
+
+
+@torch.no_grad()
+def predicted_normals(opt, sdf_network, proj_latent_sdf, points, S):
+    """points [B,N,3] sampled on the written surface of an S^3 level grid, in the object frame -> [B,N,3] fp32 unit normals of the SDF
+    there.  The sampled points carry the reference's v / S rescale (surface_points_device, convert_to_explicit_worker), which moves a
+    point p toward the grid's lower corner by (p - lo) / S (mesh_attributes); the network is asked where the grid was sampled,
+    lo + (p - lo) S / (S - 1).  One ops.sdf_forward with d sdf/dx for all images: P = 16 ceil(N / 16) rows per image, padding rows
+    repeat the image's first point and are dropped (_padded_vertex_queries' layout).  sdf_network.eager: stock operators."""
+    lo, hi = opt.eval.range
+    B, N = points.shape[0], points.shape[1]
+    q = lo + (points.float() - lo) * (S / (S - 1))
+    P = 16 * ((N + 15) // 16)
+    query = torch.cat([q, q[:, :1].expand(B, P - N, 3)], dim=1).reshape(-1, 3).contiguous()
+    if getattr(sdf_network, "eager", False):
+        from ..model import eager_path
+        _, _, grad = eager_path.sdf_conditional_output(sdf_network, B, query, proj_latent_sdf, compute_grad=True)
+    else:
+        w_pack, cbias = sdf_network.packed(proj_latent_sdf)
+        _, grad, _ = ops.sdf_forward(query, w_pack, cbias, P, symmetric=bool(sdf_network.force_symmetry), want_grad=True, want_feat=False)
+    normal = torch.nn.functional.normalize(grad.detach().float(), dim=1, eps=1e-12)
+    return normal.view(B, P, 3)[:, :N].contiguous()
+
+
+@torch.no_grad()
+def normal_metrics(opt, var, sdf_network, points_object, idx1, idx2, k, icp=None):
+    """`--eval.normals`: normal consistency beside the raw metrics.  points_object [B,N,3] are the prediction's samples in the object
+    frame, before eval_metrics moved them; idx1 [B,N] / idx2 [B,M] the nearest-neighbour indices of the raw Chamfer search between
+    var.dpc_pred and var.dpc.points (no further search).
+      prediction: predicted_normals at points_object, then the orthogonal maps the points went through -- var.pose[..., :3] and, for
+        Pix3D, the flip; normalize_pc is a translation and a uniform scale and leaves normals alone.  -> var.normals_pred [B,N,3].
+      ground truth: ops.point_normals(var.dpc.points, k) on the normalised cloud: PCA normals, ESTIMATED from the points (the processed
+        ground truth has none) and unoriented, hence the absolute cosine.  -> var.dpc.normals (the slot the loader leaves at zero) and
+        var.dpc.variation.
+    Sets var.nc_acc, var.nc_comp (ops.normal_consistency) and var.nc = (nc_acc + nc_comp) / 2, [B] float64.  With `icp` (the IcpResult
+    of icp_metrics): var.nc_acc_icp / nc_comp_icp / nc_icp from the last ICP search's indices, the predicted normals rotated by
+    transform[:, :3, :3] / s (var.normals_pred_icp)."""
+    dev = var.idx.device
+    B = points_object.shape[0]
+    rot = lambda Rm, P: (Rm @ P.permute(0, 2, 1)).permute(0, 2, 1).contiguous()
+    normals = predicted_normals(opt, sdf_network, var.proj_latent_sdf, points_object, var.level_vox.shape[1])
+    normals = rot(var.pose[..., :3].float(), normals)
+    if opt.data.dataset in ["pix3d"]:
+        normals = rot(torch.tensor(_FLIP_PRED).float().to(dev).unsqueeze(0).expand(B, 3, 3), normals)
+    gt = ops.point_normals(var.dpc.points.contiguous().float(), k)
+    var.normals_pred = normals
+    var.dpc.normals, var.dpc.variation = gt.normals, gt.variation
+    var.nc_acc, var.nc_comp = ops.normal_consistency(normals, gt.normals, idx1.contiguous(), idx2.contiguous())
+    var.nc = (var.nc_acc + var.nc_comp) / 2
+    if icp is not None:
+        R = icp.transform[:, :3, :3] / icp.s[:, None, None]
+        var.normals_pred_icp = rot(R, normals.double()).float()
+        var.nc_acc_icp, var.nc_comp_icp = ops.normal_consistency(var.normals_pred_icp, gt.normals, icp.idx1, icp.idx2)
+        var.nc_icp = (var.nc_acc_icp + var.nc_comp_icp) / 2
 
 
 def icp_summary(var):
@@ -343,6 +401,7 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
         lo, hi = opt.eval.range
         var.dpc_pred, var.mesh_pred = surface_points_device(level_vox, lo, hi, opt.eval.num_points,
                                                             seed=int(var.idx[0]) if len(var.idx) else 0)
+    points_object = var.dpc_pred                                        # the samples in the object frame (normal_metrics)
     if opt.data.dataset in ["openimage"]:
         var.f_score = torch.zeros(B, len(opt.eval.f_thresholds)).to(dev)
         var.cd_acc = torch.zeros(B).to(dev); var.cd_comp = torch.zeros(B).to(dev)
@@ -359,12 +418,16 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     var.dpc.points = normalize_pc(var.dpc.points)
     if vis_only:
         return
-    dist_acc, dist_comp, _, _ = chamfer_distance(opt, X1=var.dpc_pred, X2=var.dpc.points)
+    dist_acc, dist_comp, idx1, idx2 = chamfer_distance(opt, X1=var.dpc_pred, X2=var.dpc.points)
     var.f_score = compute_fscore(dist_acc, dist_comp, opt.eval.f_thresholds)
     assert dist_acc.shape[1] == opt.eval.num_points
     var.cd_acc = dist_acc.mean(dim=1)
     var.cd_comp = dist_comp.mean(dim=1)
     icp = options.icp_settings(opt)
+    aligned = None
     if icp is not None:                     # beside the raw metrics, never in their place
-        icp_metrics(opt, var, *icp)
+        aligned = icp_metrics(opt, var, *icp)
+    normals_k = options.normal_settings(opt)
+    if normals_k is not None:               # likewise
+        normal_metrics(opt, var, sdf_network, points_object, idx1, idx2, normals_k, icp=aligned)
     return dist_acc.mean(), dist_comp.mean()

@@ -113,6 +113,19 @@ def icp_settings(opt):
     return (iters, scale) if on else None
 
 
+def normal_settings(opt):
+    """The evaluation's normal consistency: None unless `--eval.normals` is set (absent means off), else `--eval.normals_k` (default 16,
+    an integer in 3..32), the neighbour count of ops.point_normals for the ground truth's PCA normals.  Evaluation settings beside
+    eval.vox_res, not hip.* switches.  A bad value is a ValueError, whether or not the switch is on."""
+    ev = opt.get("eval", None) or {}
+    on, k = ev.get("normals", False), ev.get("normals_k", 16)
+    if not isinstance(on, bool):
+        raise ValueError("eval.normals must be a bool, got %r" % (on,))
+    if isinstance(k, bool) or not isinstance(k, int) or not 3 <= k <= 32:
+        raise ValueError("eval.normals_k must be an integer in 3..32, got %r" % (k,))
+    return k if on else None
+
+
 def parse_arguments(args):
     """--key1.key2=value ; --flag (true) ; --flag! (false)"""
     opt_cmd = {}
@@ -204,6 +217,7 @@ def process_options(opt):
                 raise ValueError("hip.%s must be an integer in %d..%d, got %r" % (row.key, lo, hi, v))
     dual_mesh_reg(opt)
     icp_settings(opt)
+    normal_settings(opt)
     torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
     for row in HIP_TABLE:
         if row.drives is not None:

@@ -113,14 +113,20 @@ def write_ply_mesh(fname, vertices, faces, normals=None, colours=None):
         fh.write(_ply_header(len(vert), len(face), colours=colours is not None, normals=normals is not None) + vert.tobytes() + face.tobytes())
 
 
-def write_ply_pointcloud(fname, points, colours):
-    """points [N,3] float, colours [N,3] uint8 -> binary PLY with one `element vertex` of x y z red green blue."""
+def write_ply_pointcloud(fname, points, colours, normals=None):
+    """points [N,3] float, colours [N,3] uint8 -> binary PLY with one `element vertex` of x y z red green blue; with normals [N,3] float
+    the element is x y z nx ny nz red green blue (write_ply_mesh's order)."""
     p, c = _numpy(points).reshape(-1, 3), _numpy(colours).reshape(-1, 3)
-    vert = np.empty(len(p), PLY_COLOURED_VERTEX)
+    if normals is None:
+        vert = np.empty(len(p), PLY_COLOURED_VERTEX)
+    else:
+        vert = np.empty(len(p), np.dtype(PLY_VERTEX.descr + [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")] + PLY_COLOURED_VERTEX.descr[3:]))
+        n = _numpy(normals).reshape(-1, 3)
+        vert["nx"], vert["ny"], vert["nz"] = n[:, 0], n[:, 1], n[:, 2]
     vert["x"], vert["y"], vert["z"] = p[:, 0], p[:, 1], p[:, 2]
     vert["red"], vert["green"], vert["blue"] = c[:, 0], c[:, 1], c[:, 2]
     with open(fname, "wb") as fh:
-        fh.write(_ply_header(len(vert), colours=True) + vert.tobytes())
+        fh.write(_ply_header(len(vert), colours=True, normals=normals is not None) + vert.tobytes())
 
 
 def dump_meshes(opt, idx, name, meshes, folder="dump"):
@@ -142,12 +148,16 @@ def dump_meshes(opt, idx, name, meshes, folder="dump"):
         write_ply_mesh(fname, vertices, faces, *attributes)
 
 
-def dump_pointclouds_compare(opt, idx, name, preds, gts, folder="dump"):
-    """The prediction (red) and the ground truth (green) of every sample in one coloured point cloud."""
+def dump_pointclouds_compare(opt, idx, name, preds, gts, folder="dump", pred_normals=None, gt_normals=None):
+    """The prediction (red) and the ground truth (green) of every sample in one coloured point cloud; with both clouds' normals [B,N,3]
+    the vertices carry nx ny nz as well."""
     for i in range(len(idx)):
         pred, gt = _numpy(preds[i]).reshape(-1, 3), _numpy(gts[i]).reshape(-1, 3)
         colours = np.zeros((len(pred) + len(gt), 3), np.uint8)
         colours[:len(pred), 0] = 255
         colours[len(pred):, 1] = 255
         fname = "{}/{}/{}_{}.ply".format(opt.output_path, folder, int(idx[i]), name)
-        write_ply_pointcloud(fname, np.concatenate([pred, gt]), colours)
+        normals = None
+        if pred_normals is not None:
+            normals = np.concatenate([_numpy(pred_normals[i]).reshape(-1, 3), _numpy(gt_normals[i]).reshape(-1, 3)])
+        write_ply_pointcloud(fname, np.concatenate([pred, gt]), colours, normals)
