@@ -733,6 +733,73 @@ int sc_point_normals(const float* points, const int* idx, int n_images, int n, i
 int sc_normal_consistency(const float* n1, const float* n2, const int* idx1, const int* idx2, int n_images, int n, int m,
                           double* workspace, double* acc, double* comp, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Exact distance from points to a triangle mesh (csrc/point_mesh.hip; what ops.point_mesh_distance runs; the evaluation's
+ * --eval.mesh_dist).  The file is built without contraction: every operation below is fp32 and rounds once, every comparison is a true
+ * comparison (false when an operand is NaN); tests/point_mesh_ref.py restates all of it in numpy.
+ *
+ * points [n_images][n_points][3] fp32; verts [v_total][3] fp32 and faces [f_total][3] int32, the images' meshes packed one after the
+ * other; v_count, f_count [n_images] int32 on the device: image b owns the next v_count[b] vertices and f_count[b] faces (negative
+ * counts read as 0, nothing is read past v_total / f_total).  Face indices are LOCAL to the image's vertex slice, as
+ * sc_isosurface_mesh_* and sc_dual_contour_* write them; a face with an index outside [0, v_count[b]) is skipped (no read out of
+ * bounds).  -> dist2 [n_images][n_points] fp32 (squared distance), face [n_images][n_points] int32 (local index of the winning
+ * triangle), closest [n_images][n_points][3] fp32 (the closest point on it).
+ *
+ * Arithmetic of one pair, point p against triangle (a, b, c) -- the region walk of Ericson, Real-Time Collision Detection 5.1.5:
+ *       u . v = (u_0 v_0 + u_1 v_1) + u_2 v_2;      ab = b - a;  ac = c - a;  bc = c - b;  ap = p - a;  bp = p - b;  cp = p - c;
+ *       d1 = ab . ap;  d2 = ac . ap;  d3 = ab . bp;  d4 = ac . bp;  d5 = ab . cp;  d6 = ac . cp;
+ *       vc = d1 d4 - d3 d2;   vb = d5 d2 - d1 d6;   va = d3 d6 - d5 d4;   e1 = d4 - d3;   e2 = d5 - d6.
+ *   The first region whose test holds gives the closest point q:
+ *       vertex A:  d1 <= 0 and d2 <= 0:                                      q = a
+ *       vertex B:  d3 >= 0 and d4 <= d3:                                     q = b
+ *       edge AB:   vc <= 0 and d1 >= 0 and d3 <= 0 and d1 - d3 > 0:          v = d1 / (d1 - d3);          q = a + v ab
+ *       vertex C:  d6 >= 0 and d5 <= d6:                                     q = c
+ *       edge AC:   vb <= 0 and d2 >= 0 and d6 <= 0 and d2 - d6 > 0:          w = d2 / (d2 - d6);          q = a + w ac
+ *       edge BC:   va <= 0 and e1 >= 0 and e2 >= 0 and e1 + e2 > 0:          w = e1 / (e1 + e2);          q = b + w bc
+ *       interior:  den = (va + vb) + vc > 0 and va >= 0, vb >= 0, vc >= 0 and den > 1e-5f * ((ab . ab) * (ac . ac)):
+ *                                                                            v = vb / den;  w = vc / den;  q = (a + v ab) + w ac
+ *   (the "> 0" of the edge tests keeps 0 / 0 out: a == b leaves edge AB to the tests behind it; the signs asked of the interior keep
+ *   v and w in [0, 1], so every region returns a point within a few ulp of the triangle, which the search's stopping rule relies on;
+ *   den is |ab|^2 |ac|^2 sin^2 of the angle at a: below sin^2 = 1e-5 the weights are quotients of rounding noise and the triangle,
+ *   thinner than 0.0032 of its length, is taken as its edges by the rule below, an error of at most its width).
+ *   If no region claims the point -- a thin triangle, or rounding on one of zero area -- q is the first minimum, in the order AB, AC,
+ *   BC, over the clamped closest points of the three segments: for a segment from s along e,  l = e . e;  t = ((p - s) . e) / l;
+ *   t = 0 unless l > 0;  t = 0 unless t >= 0;  t = 1 if t > 1;  q = s + t e;  AB's candidate is taken first, AC's and then BC's replace
+ *   it when their distance is strictly smaller.  In every case  d = (p - q) . (p - q).  a == b == c acts as a point, a collinear triangle as a
+ *   segment; a finite query against finite vertices below 2^29 in magnitude (no product overflows) never yields NaN.
+ *   A triangle with a vertex that is not finite is tested like any other: no region claims the pair (every comparison with NaN is
+ *   false) and the segment rule decides, so it counts through an edge whose two ends are finite, if it has one.
+ * Winner: a candidate (d, f) replaces the best so far when  d < best || (d == best && f < best_f),  from best = +Inf, best_f = INT_MAX:
+ *   the lowest face index among the exact minima -- a query on a shared vertex or edge ties exactly -- whatever order the candidates are
+ *   met in, and a NaN distance never wins.  An image without a winner (f_count == 0, or only skipped faces) gets dist2 = +Inf,
+ *   face = -1, closest = 0;  a query with a coordinate that is not finite gets dist2 = NaN, face = -1, closest = NaN, and every other
+ *   row is untouched by it.
+ * sc_point_mesh_distance_brute tests all pairs (triangles staged through LDS, the query in registers).  sc_point_mesh_distance gives the
+ *   same bits from an exact grid search in the manner of sc_chamfer3d_forward_grid: a uniform grid over the bounding box of the image's
+ *   valid triangles, cell side max(2 x the mean of the triangles' largest AABB extents, cbrt(box volume / faces)) grown until the grid
+ *   has at most 2 faces + 64 cells; a triangle is referenced from every cell its AABB, padded by slack, overlaps (count pass, exclusive
+ *   scan, fill pass; integer atomics, arbitrary order inside a cell), or, when that is more than 16 cells, from the image's "large" list,
+ *   which every query of the image tests -- so the references fit 16 f_total slots whatever the mesh and nothing is read back to the
+ *   host.  A query (one thread each) walks Chebyshev rings of cells around its own cell, clamped into the grid.  After ring r no unseen
+ *   triangle has a point inside the (2r+1)^3 block, so all of it is at least lb away, lb the distance to the nearest block face that
+ *   is not a face of the grid; the walk stops when  best < (lb - slack)^2 * 0.9999,  slack = 16 * 2^-23 * (max |coordinate| + largest
+ *   extent), or when the block covers the grid.  A query that has not stopped after 6 rings or 4,096 candidates, or that lies more than
+ *   two cells outside the box, goes on a list, as does every query of an image whose grid is unusable (a referenced vertex that is not
+ *   finite or >= 1e15 in magnitude, a box of zero extent); the list is answered by the all-pairs loop, 16 slices of the faces merged
+ *   with 64-bit atomicMin on (bits of d) << 32 | face, the winner's closest point recomputed by the pair arithmetic.
+ * Plain vector stores and integer atomics only: the same bits from run to run, on any stream, for an image alone or in a batch.
+ * workspace: sc_point_mesh_workspace_bytes(n_images, n_points, v_total, f_total) bytes for either entry point, 16-byte aligned,
+ *   contents irrelevant on entry; 0 for n_images <= 0, -1 for sizes the entry points refuse.  n_images <= 0 returns 0 and launches
+ *   nothing; hipErrorInvalidValue for n_images > 65535, n_points < 1, n_images * n_points > 2^30, v_total < 0, f_total outside
+ *   [0, 2^26], a NULL pointer (verts / faces may be NULL when their total is 0) or a misaligned workspace.                          */
+long long sc_point_mesh_workspace_bytes(int n_images, int n_points, int v_total, int f_total);
+int sc_point_mesh_distance(const float* points, const float* verts, const int32_t* faces, const int32_t* v_count, const int32_t* f_count,
+                           int n_images, int n_points, int v_total, int f_total, void* workspace, float* dist2, int32_t* face,
+                           float* closest, void* stream);
+int sc_point_mesh_distance_brute(const float* points, const float* verts, const int32_t* faces, const int32_t* v_count,
+                                 const int32_t* f_count, int n_images, int n_points, int v_total, int f_total, void* workspace,
+                                 float* dist2, int32_t* face, float* closest, void* stream);
+
 /* ---- camera algebra of a render -------------------------------------------------------------------
  * sc_camera_rays_*: utils/camera.py:157-196 (get_center_and_ray on the rendered pixels only) + the normalisation of
  * model/renderer.py:69-76.  pose [n_images][3][4] = [R|t] world->camera, intr [n_images][3][3], ray_idx

@@ -1,0 +1,710 @@
+// point_mesh.hip -- EXACT distance from points to a triangle mesh (ops.point_mesh_distance; the evaluation's --eval.mesh_dist).
+// include/shapeclipper_hip.h states the arithmetic of one (point, triangle) pair one rounding at a time; tests/point_mesh_ref.py
+// restates it in numpy.  Built without contraction.
+//
+// For every query the result is the candidate (d, f) that wins  d < best || (d == best && f < best_f)  over ALL valid triangles of the
+// query's image: the lowest face index among the exact minima, whatever order the candidates are met in (a triangle may be met more than
+// once: the rule is idempotent).  Two ways to get there, bit for bit the same:
+//   * sc_point_mesh_distance_brute: all pairs.  A workgroup stages 256 triangles at a time in LDS (gathered through the face indices,
+//     out-of-range faces flagged), every thread keeps its query and its best candidate in registers and reads the staged triangles at
+//     wave-uniform addresses (LDS broadcasts).
+//   * sc_point_mesh_distance: the triangle counterpart of chamfer_grid.hip.  A uniform grid over the bounding box of the image's valid
+//     triangles; a triangle is referenced from every cell its AABB (padded by `slack`) overlaps: count pass, exclusive scan, fill pass
+//     (integer atomics; the order inside a cell is arbitrary).  The cell side is max(2 x mean AABB extent, cbrt(volume / F)), grown
+//     until the grid has at most 2 F + 64 cells, so a typical triangle overlaps at most 2 x 2 x 2 cells.  A triangle that overlaps more
+//     than PM_CELL_CAP cells (one huge triangle across the box) goes on the image's "large" list instead, which every query of the image
+//     tests first: the references never exceed PM_CELL_CAP x F whatever the mesh, so the workspace has a FIXED capacity and nothing is
+//     read back to the host.  A query (one THREAD per query in this first version; the wave-per-tile walk of cg_query_wave_kernel is the
+//     known next step) walks Chebyshev rings of cells around its own (clamped) cell.  After ring r every triangle not yet seen has no
+//     point inside the (2r+1)^3 block of cells: a triangle with a point x inside the block is referenced from cell(x), because the
+//     binning is monotone per axis.  So every point of it is at least `lb` away from the query, lb the distance to the nearest block
+//     face that is not a face of the grid.  Every region of the pair arithmetic returns a point within a few ulp of the triangle (vertex
+//     regions exactly, edge and interior regions with weights in [0, 1]; a triangle too thin for its interior weights to mean anything is
+//     taken as its three edges), so its computed d is at least (lb - slack)^2 up to the rounding
+//     of d: the walk stops when  best < (lb - slack)^2 * 0.9999  (slack = 16 ulp of the coordinate scale, as GridMeta.slack of
+//     chamfer_grid.hip) or when the block covers the grid.  No unseen triangle can beat or tie `best`.
+//   * queries that do not stop within PM_RMAX rings or PM_BUDGET candidates, that start more than PM_REMPTY cells outside the box, and
+//     every query of an image whose grid is invalid (a non-finite or huge vertex, a mesh of zero extent) go on a list and are answered by
+//     the brute kernel's inner loop, split over PM_SLICES slices of the faces and merged with 64-bit atomicMin keys
+//     (bits of d) << 32 | face  (d >= +0: the unsigned order is the numeric order, ties to the lower face); the closest point of the
+//     winner is recomputed by the same pair arithmetic.
+// Integer atomics only, plain stores, no cooperative launch: the same bits run to run, on any stream, whatever else is in the batch.
+// Bound: latency / L2 gathers (one thread per query fetches every candidate through dependent 16-byte gathers).
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <stdint.h>
+
+#include "shapeclipper_hip.h"
+
+#pragma clang fp contract(off)
+
+namespace sc_pm {
+
+constexpr int THREADS = 256;
+constexpr int PM_GMAX = 128;          // cells per axis
+constexpr int PM_CELL_CAP = 16;       // cells a triangle may be referenced from; more: the image's large list
+constexpr int PM_RMAX = 6;            // rings before a query is handed to the all-pairs scan
+constexpr int PM_BUDGET = 4096;       // candidates before a query is handed to the scan
+constexpr int PM_REMPTY = 2;          // cells outside the box / rings without a candidate before a query is handed to the scan
+constexpr int PM_SLICES = 16;         // slices of the faces the scan of the listed queries is split over
+constexpr int MAX_IMAGES = 65535;
+constexpr int MAX_FACES = 1 << 26;    // PM_CELL_CAP * f_total stays below 2^31
+constexpr long long MAX_QUERIES = 1ll << 30;
+constexpr float PM_FLAT = 1.0e-5f;   // den = |ab|^2 |ac|^2 sin^2: below this sin^2 the interior weights are rounding noise, the triangle counts as its edges
+constexpr float PM_HUGE = 1.0e15f;    // magnitudes the padding / slack arithmetic is not made for
+constexpr unsigned long long EMPTY = ~0ull;
+
+struct Meta {                         // one per image
+    float lo[3], h[3], inv_h[3];
+    int g[3];
+    float slack;
+    int valid;                        // the grid is usable: finite vertices of sensible magnitude, a box of positive extent
+    int cbase;                        // first cell of the image in the packed cell arrays
+};
+
+// ---- one (point, triangle) pair: include/shapeclipper_hip.h, "Arithmetic of one pair" ---------------------------------------------------
+__device__ __forceinline__ float pm_dot(float x0, float x1, float x2, float y0, float y1, float y2) { return (x0 * y0 + x1 * y1) + x2 * y2; }
+
+// clamped closest point of the segment a + t e, t in [0, 1]
+__device__ __forceinline__ void pm_segment(const float p[3], const float a[3], const float e[3], float q[3], float& d) {
+    const float l = pm_dot(e[0], e[1], e[2], e[0], e[1], e[2]);
+    float t = pm_dot(p[0] - a[0], p[1] - a[1], p[2] - a[2], e[0], e[1], e[2]) / l;
+    if (!(l > 0.f)) t = 0.f;
+    if (!(t >= 0.f)) t = 0.f;
+    if (t > 1.f) t = 1.f;
+    for (int i = 0; i < 3; ++i) q[i] = a[i] + t * e[i];
+    const float r0 = p[0] - q[0], r1 = p[1] - q[1], r2 = p[2] - q[2];
+    d = pm_dot(r0, r1, r2, r0, r1, r2);
+}
+
+__device__ __forceinline__ void pm_pair(const float p[3], const float a[3], const float b[3], const float c[3], float q[3], float& d) {
+    float ab[3], ac[3], bc[3], ap[3], bp[3], cp[3];
+    for (int i = 0; i < 3; ++i) {
+        ab[i] = b[i] - a[i]; ac[i] = c[i] - a[i]; bc[i] = c[i] - b[i];
+        ap[i] = p[i] - a[i]; bp[i] = p[i] - b[i]; cp[i] = p[i] - c[i];
+    }
+    const float d1 = pm_dot(ab[0], ab[1], ab[2], ap[0], ap[1], ap[2]), d2 = pm_dot(ac[0], ac[1], ac[2], ap[0], ap[1], ap[2]);
+    const float d3 = pm_dot(ab[0], ab[1], ab[2], bp[0], bp[1], bp[2]), d4 = pm_dot(ac[0], ac[1], ac[2], bp[0], bp[1], bp[2]);
+    const float d5 = pm_dot(ab[0], ab[1], ab[2], cp[0], cp[1], cp[2]), d6 = pm_dot(ac[0], ac[1], ac[2], cp[0], cp[1], cp[2]);
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    const float e1 = d4 - d3, e2 = d5 - d6;
+    const float nab = d1 - d3, nac = d2 - d6, nbc = e1 + e2;
+    bool claimed = true;
+    if (d1 <= 0.f && d2 <= 0.f) {                                               // vertex A
+        for (int i = 0; i < 3; ++i) q[i] = a[i];
+    } else if (d3 >= 0.f && d4 <= d3) {                                         // vertex B
+        for (int i = 0; i < 3; ++i) q[i] = b[i];
+    } else if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f && nab > 0.f) {              // edge AB
+        const float v = d1 / nab;
+        for (int i = 0; i < 3; ++i) q[i] = a[i] + v * ab[i];
+    } else if (d6 >= 0.f && d5 <= d6) {                                         // vertex C
+        for (int i = 0; i < 3; ++i) q[i] = c[i];
+    } else if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f && nac > 0.f) {              // edge AC
+        const float w = d2 / nac;
+        for (int i = 0; i < 3; ++i) q[i] = a[i] + w * ac[i];
+    } else if (va <= 0.f && e1 >= 0.f && e2 >= 0.f && nbc > 0.f) {              // edge BC
+        const float w = e1 / nbc;
+        for (int i = 0; i < 3; ++i) q[i] = b[i] + w * bc[i];
+    } else {
+        const float den = (va + vb) + vc;
+        const float flat = PM_FLAT * (pm_dot(ab[0], ab[1], ab[2], ab[0], ab[1], ab[2]) * pm_dot(ac[0], ac[1], ac[2], ac[0], ac[1], ac[2]));
+        if (den > 0.f && va >= 0.f && vb >= 0.f && vc >= 0.f && den > flat) {   // interior
+            const float v = vb / den, w = vc / den;
+            for (int i = 0; i < 3; ++i) q[i] = (a[i] + v * ab[i]) + w * ac[i];
+        } else {
+            claimed = false;
+        }
+    }
+    if (claimed) {
+        const float r0 = p[0] - q[0], r1 = p[1] - q[1], r2 = p[2] - q[2];
+        d = pm_dot(r0, r1, r2, r0, r1, r2);
+    } else {                                                                     // no region: first minimum over the segments AB, AC, BC
+        pm_segment(p, a, ab, q, d);
+        float q2[3], dd;
+        pm_segment(p, a, ac, q2, dd);
+        if (dd < d) { d = dd; for (int i = 0; i < 3; ++i) q[i] = q2[i]; }
+        pm_segment(p, b, bc, q2, dd);
+        if (dd < d) { d = dd; for (int i = 0; i < 3; ++i) q[i] = q2[i]; }
+    }
+}
+
+struct Best {
+    float d, q[3];
+    int f;
+};
+__device__ __forceinline__ void pm_init(Best& s) { s.d = __builtin_inff(); s.f = INT_MAX; s.q[0] = s.q[1] = s.q[2] = 0.f; }
+__device__ __forceinline__ void pm_test(Best& s, const float p[3], const float a[3], const float b[3], const float c[3], int f) {
+    float q[3], d;
+    pm_pair(p, a, b, c, q, d);
+    if (d < s.d || (d == s.d && f < s.f)) { s.d = d; s.f = f; s.q[0] = q[0]; s.q[1] = q[1]; s.q[2] = q[2]; }
+}
+__device__ __forceinline__ bool pm_finite(const float p[3]) {
+    return fabsf(p[0]) <= 3.4028234664e38f && fabsf(p[1]) <= 3.4028234664e38f && fabsf(p[2]) <= 3.4028234664e38f;
+}
+__device__ __forceinline__ void pm_write(const Best& s, bool finite_query, size_t at, float* __restrict__ dist2, int32_t* __restrict__ face,
+                                         float* __restrict__ closest) {
+    const float nan = __builtin_nanf("");
+    if (!finite_query) {
+        dist2[at] = nan; face[at] = -1;
+        closest[at * 3 + 0] = nan; closest[at * 3 + 1] = nan; closest[at * 3 + 2] = nan;
+    } else if (s.f == INT_MAX) {                        // no valid triangle (or none with a distance that compares)
+        dist2[at] = __builtin_inff(); face[at] = -1;
+        closest[at * 3 + 0] = 0.f; closest[at * 3 + 1] = 0.f; closest[at * 3 + 2] = 0.f;
+    } else {
+        dist2[at] = s.d; face[at] = s.f;
+        closest[at * 3 + 0] = s.q[0]; closest[at * 3 + 1] = s.q[1]; closest[at * 3 + 2] = s.q[2];
+    }
+}
+
+// ---- 0. the images' slices of the packed arrays: starts[0..B] of the vertices and of the faces, never past the packed lengths ----------
+__global__ void pm_offsets_kernel(int n_images, const int32_t* __restrict__ v_count, const int32_t* __restrict__ f_count, int v_total,
+                                  int f_total, int* __restrict__ v_start, int* __restrict__ f_start) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    long long v = 0, f = 0;
+    for (int b = 0; b < n_images; ++b) {
+        v_start[b] = (int)v; f_start[b] = (int)f;
+        const int vc = v_count[b], fc = f_count[b];
+        v += vc > 0 ? vc : 0; f += fc > 0 ? fc : 0;
+        v = v < v_total ? v : v_total; f = f < f_total ? f : f_total;
+    }
+    v_start[n_images] = (int)v; f_start[n_images] = (int)f;
+}
+
+// image of packed face k: the last b with f_start[b] <= k (k < f_start[n_images])
+__device__ __forceinline__ int pm_image_of(int k, const int* __restrict__ f_start, int n_images) {
+    int lo = 0, hi = n_images;                          // invariant: f_start[lo] <= k < f_start[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (f_start[mid] <= k) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// the vertices of packed face k of image b, or false when an index is outside [0, v_count[b])
+__device__ __forceinline__ bool pm_load(int k, int b, const float* __restrict__ verts, const int32_t* __restrict__ faces,
+                                        const int* __restrict__ v_start, float a[3], float bb[3], float c[3]) {
+    const int v0 = v_start[b], nv = v_start[b + 1] - v0;
+    const int i0 = faces[(size_t)k * 3 + 0], i1 = faces[(size_t)k * 3 + 1], i2 = faces[(size_t)k * 3 + 2];
+    if (i0 < 0 || i0 >= nv || i1 < 0 || i1 >= nv || i2 < 0 || i2 >= nv) return false;
+    for (int i = 0; i < 3; ++i) {
+        a[i] = verts[(size_t)(v0 + i0) * 3 + i]; bb[i] = verts[(size_t)(v0 + i1) * 3 + i]; c[i] = verts[(size_t)(v0 + i2) * 3 + i];
+    }
+    return true;
+}
+
+// order-preserving integer keys of floats (chamfer_grid.hip): the all-zero state of the cleared workspace means "nothing yet"
+__device__ __forceinline__ unsigned pm_key(float f) {
+    const unsigned u = __float_as_uint(f);
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float pm_unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
+
+// the lanes of a wave whose `ok` is set: all of one image -> the first such lane (it issues the wave's atomics after a reduction);
+// of several images -> -1 (every lane issues its own); none -> -2.  Every lane of the wave calls it.
+__device__ __forceinline__ int pm_wave_leader(bool ok, int b) {
+    const unsigned long long m = __ballot(ok);
+    if (!m) return -2;
+    const int first = __builtin_ctzll(m);
+    const int b0 = __shfl(b, first);
+    return __all(!ok || b == b0) ? first : -1;
+}
+
+// ---- 1. bounding box of the valid triangles; box[b] = {~key(min) x3, key(max) x3, bad flag, valid faces} --------------------------------
+__global__ __launch_bounds__(THREADS) void pm_bbox_kernel(int n_images, int f_total, const float* __restrict__ verts,
+                                                          const int32_t* __restrict__ faces, const int* __restrict__ v_start,
+                                                          const int* __restrict__ f_start, unsigned* __restrict__ box_all,
+                                                          float4* __restrict__ tris) {
+    const int k = blockIdx.x * THREADS + threadIdx.x, lane = threadIdx.x & 63;
+    const bool in = k < f_total && k < f_start[n_images];
+    const int b = in ? pm_image_of(k, f_start, n_images) : 0;
+    float a[3] = {0.f, 0.f, 0.f}, bb[3] = {0.f, 0.f, 0.f}, c[3] = {0.f, 0.f, 0.f};
+    const bool ok = in && pm_load(k, b, verts, faces, v_start, a, bb, c);
+    if (in) {       // the gathered triangle, for the walk: w of the first vertex says whether the face is valid
+        tris[(size_t)k * 3 + 0] = ok ? make_float4(a[0], a[1], a[2], 1.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+        tris[(size_t)k * 3 + 1] = ok ? make_float4(bb[0], bb[1], bb[2], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+        tris[(size_t)k * 3 + 2] = ok ? make_float4(c[0], c[1], c[2], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float mn[3], mx[3];
+    int bad = 0;
+    for (int i = 0; i < 3; ++i) {
+        bad |= ok && (!(fabsf(a[i]) < PM_HUGE) || !(fabsf(bb[i]) < PM_HUGE) || !(fabsf(c[i]) < PM_HUGE));
+        mn[i] = ok ? fminf(a[i], fminf(bb[i], c[i])) : __builtin_inff();
+        mx[i] = ok ? fmaxf(a[i], fmaxf(bb[i], c[i])) : -__builtin_inff();
+    }
+    const int leader = pm_wave_leader(ok, b);
+    unsigned count = ok ? 1u : 0u;
+    if (leader >= 0) {
+        for (int i = 0; i < 3; ++i)
+            for (int d = 32; d >= 1; d >>= 1) { mn[i] = fminf(mn[i], __shfl_xor(mn[i], d)); mx[i] = fmaxf(mx[i], __shfl_xor(mx[i], d)); }
+        bad = __any(bad);
+        count = (unsigned)__builtin_popcountll(__ballot(ok));
+    }
+    if (ok && (leader == -1 || lane == leader)) {
+        unsigned* box = box_all + (size_t)b * 8;
+        for (int i = 0; i < 3; ++i) { atomicMax(&box[i], ~pm_key(mn[i])); atomicMax(&box[3 + i], pm_key(mx[i])); }
+        if (bad) atomicOr(&box[6], 1u);
+        atomicAdd(&box[7], count);
+    }
+}
+
+// ---- 2. sum of the triangles' largest AABB extents, in units of (largest box extent) / 65536, as a 64-bit integer ------------------------
+__global__ __launch_bounds__(THREADS) void pm_extent_kernel(int n_images, int f_total, const int* __restrict__ f_start,
+                                                            const unsigned* __restrict__ box_all, const float4* __restrict__ tris,
+                                                            unsigned long long* __restrict__ ext_sum) {
+    const int k = blockIdx.x * THREADS + threadIdx.x, lane = threadIdx.x & 63;
+    const bool in = k < f_total && k < f_start[n_images];
+    const float4 a = in ? tris[(size_t)k * 3 + 0] : make_float4(0.f, 0.f, 0.f, 0.f);
+    bool ok = in && a.w != 0.f;
+    const int b = ok ? pm_image_of(k, f_start, n_images) : 0;
+    unsigned q = 0;
+    if (ok) {
+        const unsigned* box = box_all + (size_t)b * 8;
+        float emax = 0.f;
+        for (int i = 0; i < 3; ++i) emax = fmaxf(emax, pm_unkey(box[3 + i]) - pm_unkey(~box[i]));
+        ok = !box[6] && emax > 0.f;
+        if (ok) {
+            const float4 bb = tris[(size_t)k * 3 + 1], c = tris[(size_t)k * 3 + 2];
+            const float ex = fmaxf(a.x, fmaxf(bb.x, c.x)) - fminf(a.x, fminf(bb.x, c.x));
+            const float ey = fmaxf(a.y, fmaxf(bb.y, c.y)) - fminf(a.y, fminf(bb.y, c.y));
+            const float ez = fmaxf(a.z, fmaxf(bb.z, c.z)) - fminf(a.z, fminf(bb.z, c.z));
+            const float e = fminf(fmaxf(ex, fmaxf(ey, ez)) / emax * 65536.f, 65536.f);
+            q = (unsigned)(e >= 0.f ? e : 0.f);
+        }
+    }
+    const int leader = pm_wave_leader(ok, b);
+    if (leader >= 0)
+        for (int d = 32; d >= 1; d >>= 1) q += __shfl_xor(q, d);
+    if (ok && (leader == -1 || lane == leader)) atomicAdd(&ext_sum[b], (unsigned long long)q);
+}
+
+// ---- 3. grid geometry of every image, then the images' first cells -----------------------------------------------------------------------
+__global__ __launch_bounds__(THREADS) void pm_meta_kernel(int n_images, const unsigned* __restrict__ box_all,
+                                                          const unsigned long long* __restrict__ ext_sum, Meta* __restrict__ meta) {
+    for (int b = threadIdx.x; b < n_images; b += THREADS) {
+        const unsigned* box = box_all + (size_t)b * 8;
+        const int nf = (int)box[7];
+        Meta g;
+        float ext[3], scale = 0.f, emax = 0.f;
+        for (int a = 0; a < 3; ++a) {
+            const float lo = pm_unkey(~box[a]), hi = pm_unkey(box[3 + a]);
+            g.lo[a] = lo;
+            ext[a] = hi - lo;
+            emax = fmaxf(emax, ext[a]);
+            scale = fmaxf(scale, fmaxf(fabsf(lo), fabsf(hi)));
+        }
+        g.valid = (!box[6] && nf > 0 && emax > 0.f) ? 1 : 0;
+        float vol = 1.f;
+        for (int a = 0; a < 3; ++a) { ext[a] = fmaxf(ext[a], emax * 1.0e-3f); vol *= ext[a]; }     // a flat mesh still gets cells of a sensible size
+        const float mean_ext = emax * ((float)ext_sum[b] / (65536.f * (float)(nf > 0 ? nf : 1)));
+        float h = fmaxf(2.f * mean_ext, cbrtf(vol / (float)(nf > 0 ? nf : 1)));
+        const long long cap = 2ll * nf + 64;
+        g.g[0] = g.g[1] = g.g[2] = 1;
+        if (g.valid && h > 0.f) {
+            for (int it = 0; it < 24; ++it) {           // the per-axis ceil can overshoot the cell budget: grow h until it fits
+                long long cells = 1;
+                for (int a = 0; a < 3; ++a) {
+                    int n = (int)fminf(ceilf(ext[a] / h), (float)PM_GMAX);
+                    n = n < 1 ? 1 : (n > PM_GMAX ? PM_GMAX : n);
+                    g.g[a] = n;
+                    cells *= n;
+                }
+                if (cells <= cap) break;
+                h *= 1.26f;
+            }
+        }
+        if (!(h > 0.f) || (long long)g.g[0] * g.g[1] * g.g[2] > cap) g.valid = 0;
+        if (!g.valid) g.g[0] = g.g[1] = g.g[2] = 1;
+        for (int a = 0; a < 3; ++a) {
+            g.h[a] = ext[a] / (float)g.g[a];            // cells tile the extent exactly (the last cell also takes x == hi by clamping)
+            g.inv_h[a] = (float)g.g[a] / ext[a];
+        }
+        g.slack = 16.f * 1.1920929e-7f * (scale + emax);
+        g.cbase = 0;
+        meta[b] = g;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int base = 0;                                   // at most 2 F_b + 64 cells each: the sum fits the packed arrays (and an int)
+        for (int b = 0; b < n_images; ++b) { meta[b].cbase = base; base += meta[b].g[0] * meta[b].g[1] * meta[b].g[2]; }
+    }
+}
+
+__device__ __forceinline__ int pm_axis_cell(float v, float lo, float inv_h, int g) {
+    const int c = (int)fminf(fmaxf(floorf((v - lo) * inv_h), -1.f), (float)g);
+    return c < 0 ? 0 : (c >= g ? g - 1 : c);
+}
+
+// ---- 4. references: count pass (FILL = false; also builds the large lists) and fill pass (FILL = true) -----------------------------------
+template <bool FILL>
+__global__ __launch_bounds__(THREADS) void pm_bin_kernel(int n_images, int f_total, const int* __restrict__ f_start,
+                                                         const Meta* __restrict__ meta, const float4* __restrict__ tris,
+                                                         int* __restrict__ counts, int* __restrict__ cursor, int* __restrict__ refs,
+                                                         int* __restrict__ large, int* __restrict__ large_count) {
+    const int k = blockIdx.x * THREADS + threadIdx.x;
+    if (k >= f_total || k >= f_start[n_images]) return;
+    const float4 a = tris[(size_t)k * 3 + 0];
+    if (a.w == 0.f) return;
+    const int b = pm_image_of(k, f_start, n_images);
+    const Meta& g = meta[b];
+    if (!g.valid) return;
+    const float4 bb = tris[(size_t)k * 3 + 1], c = tris[(size_t)k * 3 + 2];
+    const float mn[3] = {fminf(a.x, fminf(bb.x, c.x)), fminf(a.y, fminf(bb.y, c.y)), fminf(a.z, fminf(bb.z, c.z))};
+    const float mx[3] = {fmaxf(a.x, fmaxf(bb.x, c.x)), fmaxf(a.y, fmaxf(bb.y, c.y)), fmaxf(a.z, fmaxf(bb.z, c.z))};
+    int c0[3], c1[3];
+    long long ncells = 1;
+    for (int i = 0; i < 3; ++i) {
+        c0[i] = pm_axis_cell(mn[i] - g.slack, g.lo[i], g.inv_h[i], g.g[i]);
+        c1[i] = pm_axis_cell(mx[i] + g.slack, g.lo[i], g.inv_h[i], g.g[i]);
+        ncells *= (c1[i] - c0[i] + 1);
+    }
+    const int local = k - f_start[b];
+    if (ncells > PM_CELL_CAP) {
+        if (!FILL) large[f_start[b] + atomicAdd(&large_count[b], 1)] = local;      // at most F_b entries: the image's own slice
+        return;
+    }
+    for (int z = c0[2]; z <= c1[2]; ++z)
+        for (int y = c0[1]; y <= c1[1]; ++y)
+            for (int x = c0[0]; x <= c1[0]; ++x) {
+                const int cell = g.cbase + (z * g.g[1] + y) * g.g[0] + x;
+                if (FILL) refs[counts[cell] + atomicAdd(&cursor[cell], 1)] = local;
+                else atomicAdd(&counts[cell], 1);
+            }
+}
+
+// ---- 5. exclusive scan of the packed histogram, in place, over [0, n): entry `cells` of the last image ends up holding the total ---------
+__global__ __launch_bounds__(1024) void pm_scan_local_kernel(int n, int* __restrict__ counts, int* __restrict__ block_tot) {
+    __shared__ int wtot[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = blockIdx.x * 1024 + tid;
+    const int v = i < n ? counts[i] : 0;
+    int incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(incl, d);
+        if (lane >= d) incl += up;
+    }
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) {
+        const int t = wtot[w];
+        if (w < wave) before += t;
+        total += t;
+    }
+    if (i < n) counts[i] = before + incl - v;
+    if (tid == 0) block_tot[blockIdx.x] = total;
+}
+
+// exclusive scan of the block totals, in place: one workgroup, 1,024 totals per round with a running carry
+__global__ __launch_bounds__(1024) void pm_scan_totals_kernel(int nblk, int* __restrict__ block_tot) {
+    __shared__ int wtot[16];
+    __shared__ int carry_s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) carry_s = 0;
+    __syncthreads();
+    for (int base = 0; base < nblk; base += 1024) {
+        const int i = base + tid;
+        const int v = i < nblk ? block_tot[i] : 0;
+        int incl = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(incl, d);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63) wtot[wave] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) {
+            const int t = wtot[w];
+            if (w < wave) before += t;
+            total += t;
+        }
+        const int carry = carry_s;
+        if (i < nblk) block_tot[i] = carry + before + incl - v;
+        __syncthreads();
+        if (tid == 0) carry_s = carry + total;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(1024) void pm_scan_add_kernel(int n, int* __restrict__ counts, const int* __restrict__ block_tot) {
+    const int i = blockIdx.x * 1024 + threadIdx.x;
+    const int off = block_tot[blockIdx.x];
+    if (i < n && off) counts[i] += off;
+}
+
+// ---- 6. the ring walk, one thread per query -----------------------------------------------------------------------------------------------
+__device__ __forceinline__ void pm_test_packed(Best& s, const float p[3], const float4* __restrict__ tris, int f0, int local) {
+    const float4 ta = tris[(size_t)(f0 + local) * 3 + 0], tb = tris[(size_t)(f0 + local) * 3 + 1], tc = tris[(size_t)(f0 + local) * 3 + 2];
+    const float a[3] = {ta.x, ta.y, ta.z}, b[3] = {tb.x, tb.y, tb.z}, c[3] = {tc.x, tc.y, tc.z};
+    pm_test(s, p, a, b, c, local);
+}
+
+__global__ __launch_bounds__(THREADS) void pm_query_kernel(int n, const float* __restrict__ pts, const Meta* __restrict__ meta,
+                                                           const int* __restrict__ f_start, const int* __restrict__ start,
+                                                           const int* __restrict__ refs, const float4* __restrict__ tris,
+                                                           const int* __restrict__ large, const int* __restrict__ large_count,
+                                                           float* __restrict__ dist2, int32_t* __restrict__ face, float* __restrict__ closest,
+                                                           int* __restrict__ todo, int* __restrict__ todo_count,
+                                                           unsigned long long* __restrict__ keys) {
+    const int b = blockIdx.y, j = blockIdx.x * THREADS + threadIdx.x, lane = threadIdx.x & 63;
+    const bool in = j < n;
+    const size_t at = (size_t)b * n + (in ? j : 0);
+    const float q[3] = {pts[at * 3 + 0], pts[at * 3 + 1], pts[at * 3 + 2]};
+    Best s;
+    pm_init(s);
+    const int f0 = f_start[b], nf = f_start[b + 1] - f0;
+    const bool direct = !pm_finite(q) || nf == 0;      // answered without a search
+    const Meta g = meta[b];
+    bool done = false;
+    if (in && !direct && g.valid && fabsf(q[0]) < PM_HUGE && fabsf(q[1]) < PM_HUGE && fabsf(q[2]) < PM_HUGE) {
+        int c[3];
+        bool outside = false;          // more than PM_REMPTY cells off the box: the walk could only confirm a candidate after many rings
+        for (int a = 0; a < 3; ++a) {
+            c[a] = pm_axis_cell(q[a], g.lo[a], g.inv_h[a], g.g[a]);
+            const float off = fmaxf(g.lo[a] - q[a], q[a] - (g.lo[a] + (float)g.g[a] * g.h[a]));
+            outside |= off > (float)PM_REMPTY * g.h[a];
+        }
+        if (!outside) {
+            const int nl = large_count[b];
+            for (int k = 0; k < nl; ++k) pm_test_packed(s, q, tris, f0, large[f0 + k]);
+        }
+        int seen = 0;
+        for (int r = 1; r <= PM_RMAX && !done && !outside && seen <= PM_BUDGET; ++r) {
+            const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.g[2] - 1), y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.g[1] - 1);
+            const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.g[0] - 1);
+            for (int z = z0; z <= z1; ++z)
+                for (int y = y0; y <= y1; ++y) {
+                    const int row = g.cbase + (z * g.g[1] + y) * g.g[0];
+                    // ring 1 takes the whole 3x3x3 block (ring 0 included); from ring 2 on only the shell
+                    const bool full = r == 1 || z == c[2] - r || z == c[2] + r || y == c[1] - r || y == c[1] + r;
+                    for (int side = 0; side < (full ? 1 : 2); ++side) {
+                        int xa, xb;
+                        if (full) { xa = x0; xb = x1; }
+                        else {
+                            xa = xb = side == 0 ? c[0] - r : c[0] + r;
+                            if (xa < 0 || xa >= g.g[0]) continue;
+                        }
+                        const int sb = start[row + xa], se = start[row + xb + 1];      // a run of cells along x is one run of references
+                        seen += se - sb;
+                        for (int k = sb; k < se; ++k) pm_test_packed(s, q, tris, f0, refs[k]);
+                    }
+                }
+            // every triangle not seen yet lies beyond a face of the block that is not a face of the grid
+            float lb = __builtin_inff();
+            for (int a = 0; a < 3; ++a) {
+                if (c[a] - r > 0) lb = fminf(lb, q[a] - (g.lo[a] + (float)(c[a] - r) * g.h[a]));
+                if (c[a] + r < g.g[a] - 1) lb = fminf(lb, (g.lo[a] + (float)(c[a] + r + 1) * g.h[a]) - q[a]);
+            }
+            const float safe = lb - g.slack;
+            done = lb == __builtin_inff() ? true : (safe > 0.f && s.d < safe * safe * 0.9999f);
+            if (r >= PM_REMPTY && s.f == INT_MAX) break;           // empty rings: the scan is the cheaper way
+        }
+    }
+    if (in && (direct || done)) pm_write(s, pm_finite(q), at, dist2, face, closest);
+    // the others go on the scan's list: one atomic per wave
+    const bool listed = in && !direct && !done;
+    const unsigned long long m = __ballot(listed);
+    if (m) {
+        const int leader = __builtin_ctzll(m);
+        int base = 0;
+        if (lane == leader) base = atomicAdd(&todo_count[b], __builtin_popcountll(m));
+        base = __shfl(base, leader);
+        if (listed) {
+            const int pos = base + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+            todo[(size_t)b * n + pos] = j;
+            keys[(size_t)b * n + pos] = EMPTY;          // the scan publishes (distance bits, face) with atomicMin
+        }
+    }
+}
+
+// ---- 7. all pairs.  LIST = false: every query of the image, results written directly.  LIST = true: the listed queries against slice
+// blockIdx.z of the faces, winners published as keys. -------------------------------------------------------------------------------------
+template <bool LIST>
+__global__ __launch_bounds__(THREADS) void pm_brute_kernel(int n, const float* __restrict__ pts, const float* __restrict__ verts,
+                                                           const int32_t* __restrict__ faces, const int* __restrict__ v_start,
+                                                           const int* __restrict__ f_start, const int* __restrict__ todo,
+                                                           const int* __restrict__ todo_count, unsigned long long* __restrict__ keys,
+                                                           float* __restrict__ dist2, int32_t* __restrict__ face,
+                                                           float* __restrict__ closest) {
+    __shared__ float tri[THREADS][9];
+    __shared__ int tri_ok[THREADS];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int cnt = LIST ? todo_count[b] : n;
+    if ((int)blockIdx.x * THREADS >= cnt) return;                   // uniform for the workgroup
+    const int e = blockIdx.x * THREADS + tid;
+    const bool live = e < cnt;
+    const int j = LIST ? todo[(size_t)b * n + (live ? e : cnt - 1)] : (live ? e : cnt - 1);
+    const size_t at = (size_t)b * n + j;
+    const float q[3] = {pts[at * 3 + 0], pts[at * 3 + 1], pts[at * 3 + 2]};
+    const int f0 = f_start[b], nf = f_start[b + 1] - f0;
+    int begin = 0, end = nf;
+    if (LIST) {
+        const int per = ((nf + PM_SLICES - 1) / PM_SLICES + THREADS - 1) / THREADS * THREADS;
+        begin = (int)blockIdx.z * per;
+        end = min(nf, begin + per);
+        if (begin >= end) return;                                   // uniform
+    }
+    Best s;
+    pm_init(s);
+    for (int k0 = begin; k0 < end; k0 += THREADS) {
+        const int chunk = min(THREADS, end - k0);
+        __syncthreads();
+        if (tid < chunk) {
+            float a[3], bb[3], c[3];
+            const bool ok = pm_load(f0 + k0 + tid, b, verts, faces, v_start, a, bb, c);
+            tri_ok[tid] = ok ? 1 : 0;
+            if (ok)
+                for (int i = 0; i < 3; ++i) { tri[tid][i] = a[i]; tri[tid][3 + i] = bb[i]; tri[tid][6 + i] = c[i]; }
+        }
+        __syncthreads();
+        for (int t = 0; t < chunk; ++t) {
+            if (!tri_ok[t]) continue;                               // uniform: every thread reads the same staged triangle
+            const float a[3] = {tri[t][0], tri[t][1], tri[t][2]}, bb[3] = {tri[t][3], tri[t][4], tri[t][5]};
+            const float c[3] = {tri[t][6], tri[t][7], tri[t][8]};
+            pm_test(s, q, a, bb, c, k0 + t);
+        }
+    }
+    if (!live) return;
+    if (LIST) {
+        if (s.f != INT_MAX)
+            atomicMin(&keys[(size_t)b * n + e], ((unsigned long long)__float_as_uint(s.d) << 32) | (unsigned int)s.f);
+    } else {
+        pm_write(s, pm_finite(q), at, dist2, face, closest);
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void pm_unpack_kernel(int n, const float* __restrict__ pts, const float* __restrict__ verts,
+                                                            const int32_t* __restrict__ faces, const int* __restrict__ v_start,
+                                                            const int* __restrict__ f_start, const int* __restrict__ todo,
+                                                            const int* __restrict__ todo_count, const unsigned long long* __restrict__ keys,
+                                                            float* __restrict__ dist2, int32_t* __restrict__ face,
+                                                            float* __restrict__ closest) {
+    const int b = blockIdx.y, cnt = todo_count[b];
+    const int e = blockIdx.x * THREADS + threadIdx.x;
+    if (e >= cnt) return;
+    const unsigned long long key = keys[(size_t)b * n + e];
+    const int j = todo[(size_t)b * n + e];
+    const size_t at = (size_t)b * n + j;
+    const float q[3] = {pts[at * 3 + 0], pts[at * 3 + 1], pts[at * 3 + 2]};
+    Best s;
+    pm_init(s);
+    if (key != EMPTY) {                                             // the winner's closest point: the same pair, the same bits
+        const int f = (int)(unsigned int)(key & 0xFFFFFFFFull);
+        float a[3], bb[3], c[3];
+        if (pm_load(f_start[b] + f, b, verts, faces, v_start, a, bb, c)) pm_test(s, q, a, bb, c, f);
+    }
+    pm_write(s, true, at, dist2, face, closest);                    // non-finite queries never reach the list
+}
+
+// workspace, in 4-byte words
+struct Carve {
+    size_t box, ext_sum, large_count, todo_count, counts, cursor, cleared;      // cleared by one memset: first and adjacent
+    size_t v_start, f_start, meta, block_tot, large, todo, keys, tris, refs, total;
+    size_t n_cells, nblk;
+};
+inline Carve carve(int b, int n, int f_total) {
+    Carve c;
+    size_t o = 0;
+    auto take = [&](size_t words) { const size_t at = o; o += (words + 3) & ~(size_t)3; return at; };
+    c.n_cells = 2 * (size_t)f_total + 64 * (size_t)b + 1;           // sum of the images' cell budgets, and the entry behind the last cell
+    c.nblk = (c.n_cells + 1023) / 1024;
+    c.box = take((size_t)b * 8);
+    c.ext_sum = take((size_t)b * 2);
+    c.large_count = take((size_t)b);
+    c.todo_count = take((size_t)b);
+    c.counts = take(c.n_cells);
+    c.cursor = take(c.n_cells);
+    c.cleared = o;
+    c.v_start = take((size_t)b + 1);
+    c.f_start = take((size_t)b + 1);
+    c.meta = take((size_t)b * (sizeof(Meta) / 4));
+    c.block_tot = take(c.nblk);
+    c.large = take((size_t)f_total);
+    c.todo = take((size_t)b * n);
+    c.keys = take((size_t)b * n * 2);                               // 64-bit: offsets are multiples of 4 words
+    c.tris = take((size_t)f_total * 12);
+    c.refs = take((size_t)f_total * PM_CELL_CAP);
+    c.total = o;
+    return c;
+}
+
+inline bool refused(int b, int n, int v_total, int f_total) {
+    return b > MAX_IMAGES || n < 1 || v_total < 0 || f_total < 0 || f_total > MAX_FACES || (long long)b * n > MAX_QUERIES;
+}
+
+}  // namespace sc_pm
+
+extern "C" {
+
+// See include/shapeclipper_hip.h for the contract.
+long long sc_point_mesh_workspace_bytes(int n_images, int n_points, int v_total, int f_total) {
+    if (n_images <= 0) return 0;
+    if (sc_pm::refused(n_images, n_points, v_total, f_total)) return -1;
+    return (long long)(sc_pm::carve(n_images, n_points, f_total).total * sizeof(int));
+}
+
+int sc_point_mesh_distance_brute(const float* points, const float* verts, const int32_t* faces, const int32_t* v_count,
+                                 const int32_t* f_count, int n_images, int n_points, int v_total, int f_total, void* workspace,
+                                 float* dist2, int32_t* face, float* closest, void* stream_) {
+    using namespace sc_pm;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_images <= 0) return 0;
+    if (refused(n_images, n_points, v_total, f_total) || !points || !v_count || !f_count || !workspace || !dist2 || !face || !closest ||
+        (v_total > 0 && !verts) || (f_total > 0 && !faces) || ((uintptr_t)workspace & 15))
+        return (int)hipErrorInvalidValue;
+    const Carve c = carve(n_images, n_points, f_total);
+    int* ws = (int*)workspace;
+    hipLaunchKernelGGL(pm_offsets_kernel, dim3(1), dim3(64), 0, stream, n_images, v_count, f_count, v_total, f_total, ws + c.v_start,
+                       ws + c.f_start);
+    hipLaunchKernelGGL(pm_brute_kernel<false>, dim3((n_points + THREADS - 1) / THREADS, n_images), dim3(THREADS), 0, stream, n_points, points,
+                       verts, faces, ws + c.v_start, ws + c.f_start, (const int*)nullptr, (const int*)nullptr,
+                       (unsigned long long*)nullptr, dist2, face, closest);
+    return (int)hipGetLastError();
+}
+
+int sc_point_mesh_distance(const float* points, const float* verts, const int32_t* faces, const int32_t* v_count, const int32_t* f_count,
+                           int n_images, int n_points, int v_total, int f_total, void* workspace, float* dist2, int32_t* face,
+                           float* closest, void* stream_) {
+    using namespace sc_pm;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_images <= 0) return 0;
+    if (f_total <= 0 || refused(n_images, n_points, v_total, f_total) || !points || !verts || !faces || !v_count || !f_count || !workspace ||
+        !dist2 || !face || !closest || ((uintptr_t)workspace & 15))           // no face at all: the twin writes the empty result
+        return sc_point_mesh_distance_brute(points, verts, faces, v_count, f_count, n_images, n_points, v_total, f_total, workspace, dist2,
+                                            face, closest, stream_);
+    const Carve c = carve(n_images, n_points, f_total);
+    int* ws = (int*)workspace;
+    int *v_start = ws + c.v_start, *f_start = ws + c.f_start;
+    unsigned* box = (unsigned*)(ws + c.box);
+    unsigned long long* ext_sum = (unsigned long long*)(ws + c.ext_sum);
+    unsigned long long* keys = (unsigned long long*)(ws + c.keys);
+    Meta* meta = (Meta*)(ws + c.meta);
+    float4* tris = (float4*)(ws + c.tris);
+    const int face_blocks = (f_total + THREADS - 1) / THREADS, query_blocks = (n_points + THREADS - 1) / THREADS;
+    const int n_cells = (int)c.n_cells, nblk = (int)c.nblk;
+    (void)hipMemsetAsync(ws, 0, c.cleared * sizeof(int), stream);
+    hipLaunchKernelGGL(pm_offsets_kernel, dim3(1), dim3(64), 0, stream, n_images, v_count, f_count, v_total, f_total, v_start, f_start);
+    hipLaunchKernelGGL(pm_bbox_kernel, dim3(face_blocks), dim3(THREADS), 0, stream, n_images, f_total, verts, faces, v_start, f_start, box, tris);
+    hipLaunchKernelGGL(pm_extent_kernel, dim3(face_blocks), dim3(THREADS), 0, stream, n_images, f_total, f_start, box, tris, ext_sum);
+    hipLaunchKernelGGL(pm_meta_kernel, dim3(1), dim3(THREADS), 0, stream, n_images, box, ext_sum, meta);
+    hipLaunchKernelGGL(pm_bin_kernel<false>, dim3(face_blocks), dim3(THREADS), 0, stream, n_images, f_total, f_start, meta, tris,
+                       ws + c.counts, ws + c.cursor, ws + c.refs, ws + c.large, ws + c.large_count);
+    hipLaunchKernelGGL(pm_scan_local_kernel, dim3(nblk), dim3(1024), 0, stream, n_cells, ws + c.counts, ws + c.block_tot);
+    hipLaunchKernelGGL(pm_scan_totals_kernel, dim3(1), dim3(1024), 0, stream, nblk, ws + c.block_tot);
+    hipLaunchKernelGGL(pm_scan_add_kernel, dim3(nblk), dim3(1024), 0, stream, n_cells, ws + c.counts, ws + c.block_tot);
+    hipLaunchKernelGGL(pm_bin_kernel<true>, dim3(face_blocks), dim3(THREADS), 0, stream, n_images, f_total, f_start, meta, tris,
+                       ws + c.counts, ws + c.cursor, ws + c.refs, ws + c.large, ws + c.large_count);
+    hipLaunchKernelGGL(pm_query_kernel, dim3(query_blocks, n_images), dim3(THREADS), 0, stream, n_points, points, meta, f_start,
+                       ws + c.counts, ws + c.refs, tris, ws + c.large, ws + c.large_count, dist2, face, closest, ws + c.todo,
+                       ws + c.todo_count, keys);
+    hipLaunchKernelGGL(pm_brute_kernel<true>, dim3(query_blocks, n_images, PM_SLICES), dim3(THREADS), 0, stream, n_points, points, verts,
+                       faces, v_start, f_start, ws + c.todo, ws + c.todo_count, keys, dist2, face, closest);
+    hipLaunchKernelGGL(pm_unpack_kernel, dim3(query_blocks, n_images), dim3(THREADS), 0, stream, n_points, points, verts, faces, v_start,
+                       f_start, ws + c.todo, ws + c.todo_count, keys, dist2, face, closest);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

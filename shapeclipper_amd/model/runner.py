@@ -75,6 +75,19 @@ def _normal_records(var):
     return torch.stack([c.detach().double().view(-1).cpu() for c in cols], dim=1)
 
 
+MESH_LINE = "%d %.8f %.8f\n"                  # a line of completeness_mesh.txt: idx cd_comp cd_comp_mesh
+
+
+def _mesh_records(var):
+    """[B, 5 + T] float64 on the host, a record per sample of eval_3D.mesh_metrics' results: idx, cd_acc, cd_comp, cd_comp_mesh,
+    f_score_mesh [T], category; [B, 6 + 2 T] with cd_comp_dual and f_score_dual [T] behind them when --eval.dual_mesh is on as well."""
+    cols = [var.idx, var.cd_acc, var.cd_comp, var.cd_comp_mesh, var.f_score_mesh, var.category_label]
+    if "cd_comp_dual" in var:
+        cols += [var.cd_comp_dual, var.f_score_dual]
+    B = len(var.idx)
+    return torch.cat([c.detach().double().view(B, -1).cpu() for c in cols], dim=1)
+
+
 class Runner:
 
     def __init__(self, opt):
@@ -398,6 +411,7 @@ class Runner:
         acc_cat, comp_cat, counts = [0.] * C, [0.] * C, [0.001] * C
         f_scores_icp, acc_cat_icp, comp_cat_icp = [], [0.] * C, [0.] * C     # --eval.icp: the same tallies of the ICP-aligned metrics
         nc_recs = []                                    # --eval.normals: _normal_records of every batch
+        mesh_recs = []                                  # --eval.mesh_dist: _mesh_records of every batch
         loader = tqdm.tqdm(self.test_loader, desc="evaluating", leave=False)
         for it, batch in enumerate(loader):
             var = self.evaluate_batch(opt, edict(batch), ep, it, single_gpu=True)
@@ -412,6 +426,8 @@ class Runner:
                 f_scores_icp.append(var.f_score_icp)
             if "nc" in var:
                 nc_recs.append(_normal_records(var))
+            if "cd_comp_mesh" in var:
+                mesh_recs.append(_mesh_records(var))
             metric["dist_acc"] += dist_acc * len(var.idx)
             metric["dist_cov"] += dist_cov * len(var.idx)
             loader.set_postfix(CD="{:.3f}".format(float((dist_acc + dist_cov) / 2)))
@@ -443,6 +459,8 @@ class Runner:
                         f.write("F-score @ %.2f: %.4f\n" % (th * 100, fs[i].item()))
             if nc_recs:                                 # nc_cat.txt (and nc_cat_icp.txt); dump_results wrote the per-sample lines
                 self._write_normals(opt, torch.cat(nc_recs), per_sample=False)
+            if mesh_recs:                               # cd_cat_mesh.txt / f_score_mesh.txt (and the _dual namesakes); likewise
+                self._write_mesh(opt, torch.cat(mesh_recs), per_sample=False)
         n = max(len(self.test_data), 1)
         for k in metric:
             metric[k] /= n
@@ -457,7 +475,9 @@ class Runner:
         gathered once, rank 0 writes chamfer.txt / cd_cat.txt / f_score.txt in sample order (with --hip.largest_component also
         components.txt, from a second gather of the per-sample counts; with --eval.icp also chamfer_icp.txt / cd_cat_icp.txt /
         f_score_icp.txt / icp.txt, from one more gather of the ICP-aligned records; with --eval.normals also normal_consistency.txt /
-        nc_cat.txt and their _icp namesakes, from one more gather again).  The value returned is the raw one.  Every rank
+        nc_cat.txt and their _icp namesakes, from one more gather again; with --eval.mesh_dist also completeness_mesh.txt /
+        cd_cat_mesh.txt / f_score_mesh.txt and, with --eval.dual_mesh, their _dual namesakes, from one more gather).  The value
+        returned is the raw one.  Every rank
         writes the per-sample files of its own samples (dump_visuals: PNGs, mesh and point-cloud PLYs)."""
         from ..parallel import gather_eval_records
         self.graph.eval()
@@ -465,7 +485,7 @@ class Runner:
         # the reference's single-node convention is rank == device index; the process group's rank is the same number there and stays
         # right when ranks and devices are numbered differently (several nodes; tests/test_gpu_two_ranks.py: two ranks on one GPU)
         rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else util.get_rank(opt)
-        recs, comps, icps, ncs = [], [], [], []
+        recs, comps, icps, ncs, meshes = [], [], [], [], []
         for it in range(rank, len(self.test_data), opt.world_size):
             sample = self.test_data[it]
             batch = {k: ({kk: vv[None] for kk, vv in v.items()} if isinstance(v, dict) else torch.as_tensor(v)[None]) for k, v in sample.items()}
@@ -481,6 +501,8 @@ class Runner:
                                                                            var.category_label, eval_3D.icp_summary(var))]))
             if "nc" in var:                             # --eval.normals: (idx, nc_acc, nc_comp, nc, category[, the three after ICP])
                 ncs.append(_normal_records(var))
+            if "cd_comp_mesh" in var:                   # --eval.mesh_dist: _mesh_records' columns
+                meshes.append(_mesh_records(var))
         dev = next(self.graph.parameters()).device
         records = torch.stack(recs) if recs else torch.zeros(0, 10, device=dev)
         allr = gather_eval_records(records.to(dev), opt.world_size).cpu()
@@ -497,7 +519,15 @@ class Runner:
             width = 5 if options.icp_settings(opt) is None else 8
             alln = gather_eval_records(torch.cat(ncs).to(dev) if ncs else torch.zeros(0, width, device=dev, dtype=torch.float64),
                                        opt.world_size).cpu()
+        allm = None
+        if options.mesh_dist_settings(opt) is not None:     # likewise
+            T = len(opt.eval.f_thresholds)
+            width = 5 + T if options.dual_mesh_reg(opt) is None else 6 + 2 * T
+            allm = gather_eval_records(torch.cat(meshes).to(dev) if meshes else torch.zeros(0, width, device=dev, dtype=torch.float64),
+                                       opt.world_size).cpu()
         opt.H, opt.W = opt.image_size
+        if rank == 0 and allm is not None:
+            self._write_mesh(opt, allm)
         if rank == 0 and alln is not None:
             self._write_normals(opt, alln)
         if rank == 0 and alli is not None:
@@ -553,6 +583,30 @@ class Runner:
                     n = sel.shape[0] + 0.001
                     a_, c_ = float(sel[:, cols[0]].sum()) / n, float(sel[:, cols[1]].sum()) / n
                     f.write("%.4f %.4f %.4f %5d %s\n" % ((a_ + c_) / 2, a_, c_, n, names[c]))
+
+    def _write_mesh(self, opt, allm, per_sample=True):
+        """The files of --eval.mesh_dist from _mesh_records' rows in sample order, float64: completeness_mesh.txt (`idx cd_comp
+        cd_comp_mesh` per sample; per_sample=False leaves it to dump_results), cd_cat_mesh.txt (cd_cat.txt's format with Comp replaced by
+        the mesh value) and f_score_mesh.txt (f_score.txt's format: precision from the samples, recall from the mesh).  Rows that carry
+        the dual-contouring mesh's columns also give completeness_mesh_dual.txt, cd_cat_mesh_dual.txt and f_score_mesh_dual.txt."""
+        C, T = opt.data.num_classes, len(opt.eval.f_thresholds)
+        names = getattr(self.test_data, "label2cat", {i: str(i) for i in range(C)})
+        for suffix, comp, fs0 in (("", 3, 4), ("_dual", 5 + T, 6 + T))[:1 if allm.shape[1] < 6 + 2 * T else 2]:
+            if per_sample:
+                with open("{}/completeness_mesh{}.txt".format(opt.output_path, suffix), "w") as f:
+                    for r in allm:
+                        f.write(MESH_LINE % (int(r[0]), float(r[2]), float(r[comp])))
+            with open(os.path.join(opt.output_path, "cd_cat_mesh{}.txt".format(suffix)), "w") as f:
+                f.write("CD     Acc    Comp   Count Cat\n")
+                for c in range(C):
+                    sel = allm[allm[:, 4 + T] == c]
+                    n = sel.shape[0] + 0.001
+                    a_, c_ = float(sel[:, 1].sum()) / n, float(sel[:, comp].sum()) / n
+                    f.write("%.4f %.4f %.4f %5d %s\n" % ((a_ + c_) / 2, a_, c_, n, names[c]))
+            fs = allm[:, fs0:fs0 + T].mean(dim=0) if allm.shape[0] else torch.zeros(T, dtype=torch.float64)
+            with open(os.path.join(opt.output_path, "f_score_mesh{}.txt".format(suffix)), "w") as f:
+                for i, th in enumerate(opt.eval.f_thresholds):
+                    f.write("F-score @ %.2f: %.4f\n" % (th * 100, fs[i].item()))
 
     def evaluate_batch(self, opt, var, ep=None, it=None, single_gpu=False, visualize=False):
         var = util.move_to_device(var, opt.device)
@@ -728,7 +782,7 @@ class Runner:
         --eval.dual_mesh also {idx}_mesh_dual.ply (eval_3D.meshes_dual: the dual-contouring mesh of the same grid, positions and faces);
         with --eval.icp also {idx}_pointclouds_comp_icp.ply (the ICP-aligned prediction of eval_3D.icp_metrics red, ground truth green);
         with --eval.normals also {idx}_pointclouds_normals.ply (pointclouds_comp's vertices as x y z nx ny nz red green blue: the SDF's
-        normals on the prediction, the estimated PCA normals on the ground truth)."""
+        normals on the prediction, the estimated PCA normals on the ground truth).  --eval.mesh_dist adds no per-sample file."""
         if eval_3D.HAVE_MESHING:
             meshes = var.mesh_pred                      # trimesh meshes of the PyMCubes branch
         else:
@@ -742,7 +796,8 @@ class Runner:
         reg = options.dual_mesh_reg(opt)
         if reg is not None:
             net = self.graph.module
-            dual = eval_3D.meshes_dual(opt, net.sdf_network, var.proj_latent_sdf, var.level_vox, reg)
+            # (--eval.mesh_dist measured against this mesh already and left it in var)
+            dual = var.mesh_dual if "mesh_dual" in var else eval_3D.meshes_dual(opt, net.sdf_network, var.proj_latent_sdf, var.level_vox, reg)
             util_vis.dump_meshes(opt, var.idx, "mesh_dual", dual, folder=folder)
         if "dpc" in var:
             util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_comp", var.dpc_pred, var.dpc.points, folder=folder)
@@ -770,6 +825,12 @@ class Runner:
                 with open("{}/icp.txt".format(opt.output_path), "w" if write_new else "a") as f:
                     for i, row in zip(var.idx.tolist(), eval_3D.icp_summary(var).tolist()):
                         f.write("%d %.8f %.8f %.8f %.8f %.8f\n" % (i, *row))
+            if "cd_comp_mesh" in var:                   # --eval.mesh_dist: idx cd_comp cd_comp_mesh (and the same for the dual mesh)
+                rec, T = _mesh_records(var), len(opt.eval.f_thresholds)
+                for suffix, comp in (("", 3), ("_dual", 5 + T))[:1 if rec.shape[1] < 6 + 2 * T else 2]:
+                    with open("{}/completeness_mesh{}.txt".format(opt.output_path, suffix), "w" if write_new else "a") as f:
+                        for r in rec:
+                            f.write(MESH_LINE % (int(r[0]), float(r[2]), float(r[comp])))
             if "nc" in var:                             # --eval.normals: idx nc_acc nc_comp nc (and the same after ICP)
                 rec = _normal_records(var)
                 for suffix, cols in (("", [1, 2, 3]), ("_icp", [5, 6, 7]))[:1 if rec.shape[1] < 8 else 2]:

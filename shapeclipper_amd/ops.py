@@ -1805,3 +1805,84 @@ def normal_consistency(n1, n2, idx1, idx2):
                                          _lib.ptr(comp), _lib.stream())
     _lib.check(code, "sc_normal_consistency")
     return acc, comp
+
+
+# ---- evaluation: exact distance from points to a triangle mesh (csrc/point_mesh.hip) --------------------------------------------------
+POINT_MESH_MAX_IMAGES = 65535
+POINT_MESH_MAX_FACES = 1 << 26
+PointMesh = collections.namedtuple("PointMesh", ["dist2", "face", "closest"])
+
+
+def _point_mesh_args(points, verts, faces, v_count, f_count, search):
+    """(B, N, Vtot, Ftot) of point_mesh_distance's arguments; every refusal is a ValueError (the index check is the caller's)."""
+    who = "shapeclipper_amd: point_mesh_distance"
+    if search not in ("grid", "brute"):
+        raise ValueError("%s: search must be 'grid' or 'brute', got %r" % (who, search))
+    f32, i32 = torch.float32, torch.int32
+    for name, t, dtype in (("points", points, f32), ("verts", verts, f32), ("faces", faces, i32), ("v_count", v_count, i32),
+                           ("f_count", f_count, i32)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
+        if not t.is_cuda:
+            raise ValueError("%s: %s is a CPU tensor; the HIP kernels need device tensors (no CPU fallback)" % (who, name))
+        if t.device != points.device:
+            raise ValueError("%s: %s is on %s, points is on %s" % (who, name, t.device, points.device))
+        if t.dtype != dtype:
+            raise ValueError("%s: %s must be %s, got %s" % (who, name, dtype, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (who, name))
+    if points.dim() != 3 or points.shape[2] != 3 or points.shape[1] < 1:
+        raise ValueError("%s: points must be [B,N,3] with N >= 1, got %s" % (who, tuple(points.shape)))
+    B, N = points.shape[0], points.shape[1]
+    for name, t in (("verts", verts), ("faces", faces)):
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("%s: %s must be [n,3], got %s" % (who, name, tuple(t.shape)))
+    for name, t in (("v_count", v_count), ("f_count", f_count)):
+        if tuple(t.shape) != (B,):
+            raise ValueError("%s: %s must have shape (%d,), got %s" % (who, name, B, tuple(t.shape)))
+    if B > POINT_MESH_MAX_IMAGES or B * N > 1 << 30 or faces.shape[0] > POINT_MESH_MAX_FACES:
+        raise ValueError("%s takes at most %d images, 2^30 queries and 2^26 faces per call, got %d, %d and %d"
+                         % (who, POINT_MESH_MAX_IMAGES, B, B * N, faces.shape[0]))
+    return B, N, verts.shape[0], faces.shape[0]
+
+
+def point_mesh_distance(points, verts, faces, v_count, f_count, search="grid"):
+    """points [B,N,3] fp32 against B triangle meshes packed one after the other -- verts [Vtot,3] fp32, faces [Ftot,3] int32 with indices
+    LOCAL to the image's vertex slice, v_count / f_count [B] int32 on the device, the form isosurface_mesh and dual_contour_mesh return
+    -> PointMesh(dist2 [B,N] fp32, face [B,N] int32, closest [B,N,3] fp32): for every point the squared distance to the nearest
+    triangle of its image, that triangle's local index (the LOWEST among exact ties) and the closest point on it, in the fp32 arithmetic
+    include/shapeclipper_hip.h states for sc_point_mesh_distance (PyTorch3D's point_mesh_face_distance keeps the distance only).
+    search="grid": the exact uniform-grid search; search="brute": all pairs, the same bits.  An image without faces gets +Inf, -1, 0; a
+    point that is not finite NaN, -1, NaN.
+
+    Host synchronisation: ONE device reduction and host read per call, which validates the inputs -- the counts must be non-negative and
+    sum to the packed lengths, every face index must lie inside its image's vertex range (ValueError otherwise).  The search itself
+    reads nothing back: its workspace has a fixed capacity (the `_scratch` cache, tag "point_mesh"; faces that overlap more than 16
+    cells go on a per-image list instead of the grid).  Runs on the current stream."""
+    B, N, Vtot, Ftot = _point_mesh_args(points, verts, faces, v_count, f_count, search)
+    dev = points.device
+    dist2 = torch.empty(B, N, device=dev, dtype=torch.float32)
+    face = torch.empty(B, N, device=dev, dtype=torch.int32)
+    closest = torch.empty(B, N, 3, device=dev, dtype=torch.float32)
+    if B == 0:
+        return PointMesh(dist2, face, closest)
+    # the one reduction: (counts non-negative, sum of v_count, sum of f_count, faces inside their image's vertex range) -> 4 numbers
+    vc, fc = v_count.long(), f_count.long()
+    inside = torch.ones((), dtype=torch.bool, device=dev)
+    if Ftot:        # the image of every packed face, from the running sum of f_count (no host read; meaningful only if the sums hold)
+        owner = torch.searchsorted(torch.cumsum(fc.clamp_min(0), 0), torch.arange(Ftot, device=dev), right=True).clamp_max(B - 1)
+        inside = ((faces >= 0) & (faces < vc[owner][:, None])).all()
+    ok_counts, v_sum, f_sum, ok_faces = torch.stack([((vc >= 0) & (fc >= 0)).all().long(), vc.sum(), fc.sum(), inside.long()]).tolist()
+    if not ok_counts or v_sum != Vtot or f_sum != Ftot:
+        raise ValueError("shapeclipper_amd: point_mesh_distance: v_count / f_count must be non-negative and sum to the packed lengths "
+                         "(%d vertices, %d faces), got sums %d and %d" % (Vtot, Ftot, v_sum, f_sum))
+    if not ok_faces:
+        raise ValueError("shapeclipper_amd: point_mesh_distance: a face index lies outside its image's vertex range [0, v_count[b])")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = _scratch("point_mesh", dev, (lib.sc_point_mesh_workspace_bytes(B, N, Vtot, Ftot) + 3) // 4)
+        fn = lib.sc_point_mesh_distance if search == "grid" else lib.sc_point_mesh_distance_brute
+        code = fn(_lib.ptr(points), _lib.ptr(verts) if Vtot else None, _lib.ptr(faces) if Ftot else None, _lib.ptr(v_count),
+                  _lib.ptr(f_count), B, N, Vtot, Ftot, _lib.ptr(ws), _lib.ptr(dist2), _lib.ptr(face), _lib.ptr(closest), _lib.stream())
+    _lib.check(code, "sc_point_mesh_distance" if search == "grid" else "sc_point_mesh_distance_brute")
+    return PointMesh(dist2, face, closest)

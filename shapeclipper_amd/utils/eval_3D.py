@@ -14,6 +14,9 @@ Call surface of the reference's utils/eval_3D.py.
   * normal_metrics (`--eval.normals`): normal consistency, the mean |cosine| between each point's normal and its nearest neighbour's in
     the other cloud, both ways: the SDF's own normals for the prediction, k-NN PCA normals (ops.point_normals,
     csrc/point_normals.hip) for the ground truth, paired by the indices of the Chamfer search already made.
+  * mesh_metrics (`--eval.mesh_dist`): completeness as the exact distance from every ground-truth point to the predicted MESH
+    (ops.point_mesh_distance, csrc/point_mesh.hip) instead of to its nearest sample, for the marching-cubes mesh and, with
+    `--eval.dual_mesh`, for the dual-contouring one, reported beside the sample-based metrics.
   * meshes_dual (`--eval.dual_mesh`): the dual-contouring mesh of the same grid from the SDF gradients at the crossings
     (csrc/dual_contour.hip), which keeps corners and creases that marching cubes chamfers at the grid pitch.
 """
@@ -70,6 +73,19 @@ def normalize_pc(pc):
     ext = centred.amax(dim=1) - centred.amin(dim=1)                     # [B, 3]
     scale = ext[:, :2].amax(dim=-1)[:, None, None]
     return centred / (scale + 1.e-7)
+
+
+@torch.no_grad()
+def normalize_pc_params(pc):
+    """(centre [B,1,3], scale [B,1,1]) of normalize_pc, by exactly its expressions: (pc - centre) / (scale + 1e-7) has the bits of
+    normalize_pc(pc), and the same map applied to other points (the vertices of the mesh the cloud was sampled from: mesh_metrics) puts
+    them in the cloud's normalised frame."""
+    assert len(pc.shape) == 3
+    centre = pc.mean(dim=1, keepdim=True)
+    centred = pc - centre
+    ext = centred.amax(dim=1) - centred.amin(dim=1)                     # [B, 3]
+    scale = ext[:, :2].amax(dim=-1)[:, None, None]
+    return centre, scale
 
 
 def _edge_crossing_points(level, lo, hi, num_points, rng):
@@ -369,6 +385,67 @@ def normal_metrics(opt, var, sdf_network, points_object, idx1, idx2, k, icp=None
         var.nc_icp = (var.nc_acc_icp + var.nc_comp_icp) / 2
 
 
+def _pack_meshes(meshes, anchors):
+    """[(verts [V,3], faces [F,3] int32)] per image -> (verts [Vtot,3], faces [Ftot,3], v_count [B], f_count [B]) in the packed form of
+    ops.point_mesh_distance.  An image with an empty mesh is given ONE degenerate triangle, three times anchors[b] (anchors [B,3]: a
+    point per image)."""
+    dev = anchors.device
+    verts, faces, nv, nf = [], [], [], []
+    for b, (v, f) in enumerate(meshes):
+        if f.shape[0] == 0 or v.shape[0] == 0:
+            v, f = anchors[b:b + 1].float().expand(3, 3), torch.tensor([[0, 1, 2]], dtype=torch.int32, device=dev)
+        verts.append(v.float()); faces.append(f.to(torch.int32)); nv.append(v.shape[0]); nf.append(f.shape[0])
+    i32 = dict(dtype=torch.int32, device=dev)
+    return torch.cat(verts).contiguous(), torch.cat(faces).contiguous(), torch.tensor(nv, **i32), torch.tensor(nf, **i32)
+
+
+@torch.no_grad()
+def mesh_metrics(opt, var, sdf_network, frame):
+    """`--eval.mesh_dist`: completeness against the predicted SURFACE instead of against samples of it.  The sample-based completeness
+    is the distance from a ground-truth point to the nearest of eval.num_points samples, which has a floor of about the sample spacing
+    (0.005 at 100,000 samples, the finest F-score threshold) and a seed-dependent jitter of that size; the exact distance to the mesh
+    (ops.point_mesh_distance) has neither, and works for any mesh.
+
+    The mesh is meshes_device(var.level_vox, lo, hi) -- also when PyMCubes is importable: the vertex set is the same -- with the v / S
+    rescale the samples carry.  Its vertices go through the maps the samples went through: var.pose[..., :3], the Pix3D flip, then
+    `frame` = (centre, scale) of normalize_pc_params of the SAMPLES, which eval_metrics captured before it normalised var.dpc_pred; a
+    sample lies on the mesh, so after the same maps it still does.  An image with an empty mesh gets one degenerate triangle at
+    var.dpc_pred[b, 0], so its numbers equal the sample-based ones (the convention of --eval.icp for an empty mesh).
+    Sets var.dist_comp_mesh [B,M] (the square root of the kernel's squared distance), var.cd_comp_mesh [B], var.face_mesh [B,M] int32
+    and var.f_score_mesh [B,T] = compute_fscore(precision from the sample-based var.dist_acc, recall from the mesh distances).  With
+    `--eval.dual_mesh`: the same for the mesh of meshes_dual -> var.dist_comp_dual, var.cd_comp_dual, var.f_score_dual, var.face_dual;
+    that mesh stays in var.mesh_dual (object frame) for the dump.  The accuracy direction stays sample-based (the ground truth is a
+    bare point cloud), nothing is ICP-aligned, nothing enters a loss."""
+    lo, hi = opt.eval.range
+    dev = var.idx.device
+    centre, scale = frame
+    gt = var.dpc.points.contiguous().float()
+    rot = lambda Rm, P: (Rm @ P.t()).t()
+
+    def to_frame(meshes):
+        out = []
+        for b, (v, f) in enumerate(meshes):
+            v = rot(var.pose[b, :, :3].float(), v.float())
+            if opt.data.dataset in ["pix3d"]:
+                v = rot(torch.tensor(_FLIP_PRED).float().to(dev), v)
+            out.append((((v - centre[b]) / (scale[b] + 1.e-7)).contiguous(), f))
+        return out
+
+    def measure(meshes, suffix):
+        res = ops.point_mesh_distance(gt, *_pack_meshes(to_frame(meshes), var.dpc_pred[:, 0]), search="grid")
+        dist = res.dist2.sqrt()
+        var["dist_comp_" + suffix] = dist
+        var["cd_comp_" + suffix] = dist.mean(dim=1)
+        var["face_" + suffix] = res.face
+        var["f_score_" + suffix] = compute_fscore(var.dist_acc, dist, opt.eval.f_thresholds)
+
+    measure(meshes_device(var.level_vox, lo, hi), "mesh")
+    reg = options.dual_mesh_reg(opt)
+    if reg is not None:
+        var.mesh_dual = meshes_dual(opt, sdf_network, var.proj_latent_sdf, var.level_vox, reg)
+        measure(var.mesh_dual, "dual")
+
+
 def icp_summary(var):
     """[B,5] float64 on the host, a row of icp.txt per sample: s, the rotation angle in degrees, |t|, the first and the last objective."""
     T, s, obj = (var.icp[k].detach().cpu().double() for k in ("transform", "s", "objective"))
@@ -414,6 +491,8 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
         fg = torch.tensor(_FLIP_GT).float().to(dev).unsqueeze(0).expand(B, 3, 3)
         var.dpc_pred = rot(fp, var.dpc_pred)
         var.dpc.points = rot(fg, var.dpc.points)
+    mesh_dist = None if vis_only else options.mesh_dist_settings(opt)
+    frame = normalize_pc_params(var.dpc_pred) if mesh_dist is not None else None      # the samples' centre and scale (mesh_metrics)
     var.dpc_pred = normalize_pc(var.dpc_pred)
     var.dpc.points = normalize_pc(var.dpc.points)
     if vis_only:
@@ -430,4 +509,7 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     normals_k = options.normal_settings(opt)
     if normals_k is not None:               # likewise
         normal_metrics(opt, var, sdf_network, points_object, idx1, idx2, normals_k, icp=aligned)
+    if mesh_dist is not None:               # likewise
+        var.dist_acc, var.dist_comp = dist_acc, dist_comp
+        mesh_metrics(opt, var, sdf_network, frame)
     return dist_acc.mean(), dist_comp.mean()

@@ -126,6 +126,18 @@ def normal_settings(opt):
     return k if on else None
 
 
+def mesh_dist_settings(opt):
+    """The evaluation's mesh-based completeness: None unless `--eval.mesh_dist` is set (absent means off), else True -- the distance
+    from every ground-truth point to the predicted MESH (eval_3D.mesh_metrics, ops.point_mesh_distance) beside the sample-based
+    metrics.  An evaluation setting beside eval.vox_res, not a hip.* switch.  A value that is not a bool is a ValueError, whether or
+    not the switch is on."""
+    ev = opt.get("eval", None) or {}
+    on = ev.get("mesh_dist", False)
+    if not isinstance(on, bool):
+        raise ValueError("eval.mesh_dist must be a bool, got %r" % (on,))
+    return True if on else None
+
+
 def parse_arguments(args):
     """--key1.key2=value ; --flag (true) ; --flag! (false)"""
     opt_cmd = {}
@@ -218,6 +230,7 @@ def process_options(opt):
     dual_mesh_reg(opt)
     icp_settings(opt)
     normal_settings(opt)
+    mesh_dist_settings(opt)
     torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
     for row in HIP_TABLE:
         if row.drives is not None:
