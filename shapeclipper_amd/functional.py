@@ -250,6 +250,14 @@ def _bn_state(bn):
             bn.num_batches_tracked if (track and training) else None, training, float(bn.momentum), float(bn.eps))
 
 
+def _bn_check_batch(bn, x, groups):
+    """nn.BatchNorm2d's own refusal of one value per channel (and statistics group) in training, before any launch: the kernels would
+    normalise with variance 0 and blend a biased 0 into running_var where torch raises."""
+    if x.shape[0] // groups == 1 and x.shape[2] * x.shape[3] == 1 and (bn.training or not bn.track_running_stats):
+        raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(
+            torch.Size((x.shape[0] // groups,) + tuple(x.shape[1:]))))
+
+
 def bn_act(bn, x, residual=None, relu=True, groups=1):
     """nn.BatchNorm2d `bn` applied to x, then `+ residual`, then ReLU.  Device tensors take the fused HIP path (raises
     if the library is missing); host tensors use the stock torch operators (pretrain plumbing on CPU, config[0]).
@@ -260,6 +268,7 @@ def bn_act(bn, x, residual=None, relu=True, groups=1):
         if residual is not None:
             out = out + residual
         return torch.relu_(out) if relu else out
+    _bn_check_batch(bn, x, groups)
     return BnActFunction.apply(x, residual, bn.weight, bn.bias, *_bn_state(bn), relu, groups)
 
 
@@ -282,6 +291,7 @@ def bn_relu_maxpool(bn, x, groups=1):
     if not _bn_fusable(bn, x):
         out = bn(x) if groups == 1 else torch.cat([bn(c) for c in x.chunk(groups)], 0)
         return torch.nn.functional.max_pool2d(torch.relu_(out), 3, 2, 1)
+    _bn_check_batch(bn, x, groups)
     return BnReluPoolFunction.apply(x, bn.weight, bn.bias, *_bn_state(bn), groups)
 
 

@@ -1,6 +1,7 @@
 """Fused BatchNorm (+ residual add, ReLU, stem max-pool) kernels of csrc/bn_act.hip against the stock torch operators
 they replace inside the ResNet encoders (torchvision BasicBlock / stem semantics).
-Tolerance: fp32, 2e-5 of the tensor's scale for outputs and input gradients (different summation order only)."""
+Tolerance: fp32, 2e-5 of the tensor's scale for outputs and input gradients (different summation order only).
+The bars against float64 (every launch form, ill-conditioned channels, chains of running-statistics updates): tests/test_gpu_bn_float64.py."""
 import copy
 
 import pytest
