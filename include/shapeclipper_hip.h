@@ -800,6 +800,51 @@ int sc_point_mesh_distance_brute(const float* points, const float* verts, const 
                                  const int32_t* f_count, int n_images, int n_points, int v_total, int f_total, void* workspace,
                                  float* dist2, int32_t* face, float* closest, void* stream);
 
+/* ---- evaluation: Earth Mover's Distance of two equal-sized clouds by an auction matching (csrc/emd3d.hip) -----------------------
+ * sc_emd3d_match finds, per image, a bijection phi of the persons xyz1 [n_images][n][3] onto the objects xyz2 [n_images][n][3] (fp32,
+ * 2 <= n <= SC_EMD3D_MAX_POINTS) that minimises  sum_i |xyz1_i - xyz2_phi(i)|  (Euclidean, not squared) to within n eps, by Bertsekas'
+ * forward auction in its Jacobi form with epsilon scaling, and reports the mean cost of its pairs.  tests/emd_ref.py restates the
+ * rule below in numpy and the outputs match it bit for bit.
+ *
+ * Cost of person i = (ax, ay, az) and object j = (bx, by, bz), fp32, one rounding per operation (built without contraction):
+ *       dx = ax - bx;  dy = ay - by;  dz = az - bz;  d2 = (dx dx + dy dy) + dz dz;  c_ij = sqrt(d2), correctly rounded.
+ *   It is recomputed by this expression wherever it is needed.
+ * Phases: eps_list [n_eps] fp32 on the HOST (copied into the launch; 1 <= n_eps <= SC_EMD3D_MAX_PHASES, every entry finite and > 0)
+ *   holds the epsilon of every phase.  ops.emd_match computes it in fp32:  e = eps_start;  while e > eps: emit e, e = fl(e / 4);  then
+ *   emit eps  (0.25 and 1e-4 give 7 phases).  Prices p_j are zero before the first phase and kept from phase to phase; at the start of a
+ *   phase every person is unassigned and every object unowned.
+ * Round: a pure function of the state at its start.  Every person i that is unassigned at the start of the round bids, against the
+ *   prices at the start of the round:
+ *       w_j = fl(fl(-c_ij) - p_j) for every object j;   j* = the lowest j among the maxima of w, w1 = w_j*;   w2 = max of w_j over j != j*;
+ *       b = fl(p_j* + fl(fl(w1 - w2) + e)).
+ *   Object j goes to the highest b bid for it, among equal b to the lowest person index -- the maximum of the 64-bit integer key
+ *   (bits(b) << 32) | (0xFFFFFFFF - i), b > 0 so bit order is value order: the winner becomes its owner, the previous owner becomes
+ *   unassigned, p_j = b.  A bidder that wins nothing stays unassigned.
+ * A phase ends when nobody is unassigned; the auction has converged when the last phase has ended.  rounds counts the rounds of all
+ *   phases.  Before every round, if rounds >= max_rounds (>= 1) the auction stops where it is with converged = 0 (an auction that ends
+ *   in exactly max_rounds rounds has converged), so the kernel ends under every input; the bijection is then completed: the persons
+ *   still unassigned, in ascending index, take the objects still unowned, in ascending index.
+ * -> assignment [n_images][n] int32 (phi), cost [n_images][n] fp32 (c_i,phi(i)), price [n_images][n] fp32 (p_j of every object),
+ *   rounds, converged [n_images] int32, emd [n_images] float64 = (cost[0] + cost[1] + ... in ascending i, added in float64 by one
+ *   lane) / n.  For a converged auction every person's pair is within eps of its best at the final prices (epsilon-complementary
+ *   slackness, up to the fp32 roundings of a bid), hence  optimum <= emd <= optimum + eps.
+ * An image with a coordinate that is not finite is detected before the first round: assignment = identity, cost = price = 0,
+ *   rounds = 0, converged = 0, emd = NaN; the other images of the batch are untouched by it.  Finite coordinates so large that a cost
+ *   overflows (above about 1e19) give an unspecified bijection; indices stay in bounds and max_rounds still ends the auction.
+ * Launch: ONE workgroup of 1024 threads per image, the whole auction inside it with workgroup barriers only --
+ *   no wait on another workgroup, no host read, no float atomics.  A wave takes one bidder at a time, its lanes striding over the
+ *   objects; the bids of a round meet in one 64-bit integer LDS max per bidder.  Dynamic LDS 48 n bytes: key 8, object position 12,
+ *   price 4, owner 4, object of a person 4, list of the unassigned 4, person position 12 -- 96 KiB at n = 2048 of the CU's 160 KiB,
+ *   above the 64 KiB default, so the launch raises the kernel's dynamic-LDS limit first.
+ * The rounds are Jacobi and the winner rule does not depend on the order bids arrive in: the same bits from run to run, on any stream,
+ *   for an image alone or in a batch.  No workspace.  n_images <= 0 returns 0 and launches nothing; hipErrorInvalidValue for
+ *   n_images > 65535, n outside [2, SC_EMD3D_MAX_POINTS], n_eps outside [1, SC_EMD3D_MAX_PHASES], an epsilon that is not finite and
+ *   positive, max_rounds < 1 or a NULL pointer.                                                                                      */
+#define SC_EMD3D_MAX_POINTS 2048
+#define SC_EMD3D_MAX_PHASES 80
+int sc_emd3d_match(const float* xyz1, const float* xyz2, int n_images, int n, const float* eps_list, int n_eps, int max_rounds,
+                   int32_t* assignment, float* cost, float* price, int32_t* rounds, int32_t* converged, double* emd, void* stream);
+
 /* ---- camera algebra of a render -------------------------------------------------------------------
  * sc_camera_rays_*: utils/camera.py:157-196 (get_center_and_ray on the rendered pixels only) + the normalisation of
  * model/renderer.py:69-76.  pose [n_images][3][4] = [R|t] world->camera, intr [n_images][3][3], ray_idx

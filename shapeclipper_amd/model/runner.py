@@ -88,6 +88,19 @@ def _mesh_records(var):
     return torch.cat([c.detach().double().view(B, -1).cpu() for c in cols], dim=1)
 
 
+EMD_LINE = "%d %d %.8f %d %d\n"              # a line of emd.txt: idx n emd rounds converged
+
+
+def _emd_records(var):
+    """[B,6] float64 on the host, a record per sample of eval_3D.emd_metrics' results: idx, n, emd, rounds, converged, category; [B,9]
+    with emd, rounds and converged of the ICP-aligned prediction behind them when --eval.icp ran as well."""
+    B = len(var.idx)
+    cols = [var.idx, torch.full((B,), var.emd_n), var.emd, var.emd_rounds, var.emd_converged, var.category_label]
+    if "emd_icp" in var:
+        cols += [var.emd_icp, var.emd_rounds_icp, var.emd_converged_icp]
+    return torch.stack([c.detach().double().view(-1).cpu() for c in cols], dim=1)
+
+
 class Runner:
 
     def __init__(self, opt):
@@ -412,6 +425,7 @@ class Runner:
         f_scores_icp, acc_cat_icp, comp_cat_icp = [], [0.] * C, [0.] * C     # --eval.icp: the same tallies of the ICP-aligned metrics
         nc_recs = []                                    # --eval.normals: _normal_records of every batch
         mesh_recs = []                                  # --eval.mesh_dist: _mesh_records of every batch
+        emd_recs = []                                   # --eval.emd: _emd_records of every batch
         loader = tqdm.tqdm(self.test_loader, desc="evaluating", leave=False)
         for it, batch in enumerate(loader):
             var = self.evaluate_batch(opt, edict(batch), ep, it, single_gpu=True)
@@ -428,6 +442,8 @@ class Runner:
                 nc_recs.append(_normal_records(var))
             if "cd_comp_mesh" in var:
                 mesh_recs.append(_mesh_records(var))
+            if "emd" in var:
+                emd_recs.append(_emd_records(var))
             metric["dist_acc"] += dist_acc * len(var.idx)
             metric["dist_cov"] += dist_cov * len(var.idx)
             loader.set_postfix(CD="{:.3f}".format(float((dist_acc + dist_cov) / 2)))
@@ -461,6 +477,8 @@ class Runner:
                 self._write_normals(opt, torch.cat(nc_recs), per_sample=False)
             if mesh_recs:                               # cd_cat_mesh.txt / f_score_mesh.txt (and the _dual namesakes); likewise
                 self._write_mesh(opt, torch.cat(mesh_recs), per_sample=False)
+            if emd_recs:                                # emd_cat.txt (and emd_cat_icp.txt); likewise
+                self._write_emd(opt, torch.cat(emd_recs), per_sample=False)
         n = max(len(self.test_data), 1)
         for k in metric:
             metric[k] /= n
@@ -476,7 +494,8 @@ class Runner:
         components.txt, from a second gather of the per-sample counts; with --eval.icp also chamfer_icp.txt / cd_cat_icp.txt /
         f_score_icp.txt / icp.txt, from one more gather of the ICP-aligned records; with --eval.normals also normal_consistency.txt /
         nc_cat.txt and their _icp namesakes, from one more gather again; with --eval.mesh_dist also completeness_mesh.txt /
-        cd_cat_mesh.txt / f_score_mesh.txt and, with --eval.dual_mesh, their _dual namesakes, from one more gather).  The value
+        cd_cat_mesh.txt / f_score_mesh.txt and, with --eval.dual_mesh, their _dual namesakes, from one more gather; with --eval.emd
+        also emd.txt / emd_cat.txt and, with --eval.icp, their _icp namesakes, from one more gather).  The value
         returned is the raw one.  Every rank
         writes the per-sample files of its own samples (dump_visuals: PNGs, mesh and point-cloud PLYs)."""
         from ..parallel import gather_eval_records
@@ -485,7 +504,7 @@ class Runner:
         # the reference's single-node convention is rank == device index; the process group's rank is the same number there and stays
         # right when ranks and devices are numbered differently (several nodes; tests/test_gpu_two_ranks.py: two ranks on one GPU)
         rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else util.get_rank(opt)
-        recs, comps, icps, ncs, meshes = [], [], [], [], []
+        recs, comps, icps, ncs, meshes, emds = [], [], [], [], [], []
         for it in range(rank, len(self.test_data), opt.world_size):
             sample = self.test_data[it]
             batch = {k: ({kk: vv[None] for kk, vv in v.items()} if isinstance(v, dict) else torch.as_tensor(v)[None]) for k, v in sample.items()}
@@ -503,6 +522,8 @@ class Runner:
                 ncs.append(_normal_records(var))
             if "cd_comp_mesh" in var:                   # --eval.mesh_dist: _mesh_records' columns
                 meshes.append(_mesh_records(var))
+            if "emd" in var:                            # --eval.emd: _emd_records' columns
+                emds.append(_emd_records(var))
         dev = next(self.graph.parameters()).device
         records = torch.stack(recs) if recs else torch.zeros(0, 10, device=dev)
         allr = gather_eval_records(records.to(dev), opt.world_size).cpu()
@@ -525,7 +546,14 @@ class Runner:
             width = 5 + T if options.dual_mesh_reg(opt) is None else 6 + 2 * T
             allm = gather_eval_records(torch.cat(meshes).to(dev) if meshes else torch.zeros(0, width, device=dev, dtype=torch.float64),
                                        opt.world_size).cpu()
+        alle = None
+        if options.emd_settings(opt) is not None:       # likewise
+            width = 6 if options.icp_settings(opt) is None else 9
+            alle = gather_eval_records(torch.cat(emds).to(dev) if emds else torch.zeros(0, width, device=dev, dtype=torch.float64),
+                                       opt.world_size).cpu()
         opt.H, opt.W = opt.image_size
+        if rank == 0 and alle is not None:
+            self._write_emd(opt, alle)
         if rank == 0 and allm is not None:
             self._write_mesh(opt, allm)
         if rank == 0 and alln is not None:
@@ -607,6 +635,25 @@ class Runner:
             with open(os.path.join(opt.output_path, "f_score_mesh{}.txt".format(suffix)), "w") as f:
                 for i, th in enumerate(opt.eval.f_thresholds):
                     f.write("F-score @ %.2f: %.4f\n" % (th * 100, fs[i].item()))
+
+    def _write_emd(self, opt, alle, per_sample=True):
+        """The files of --eval.emd from _emd_records' rows in sample order, float64: emd.txt (`idx n emd rounds converged` per sample;
+        per_sample=False leaves it to dump_results) and emd_cat.txt, the per-category mean in cd_cat.txt's format with the one column.
+        Rows [N,9] (with --eval.icp) carry the values of the ICP-aligned prediction in columns 6..8, which go to emd_icp.txt and
+        emd_cat_icp.txt."""
+        C = opt.data.num_classes
+        names = getattr(self.test_data, "label2cat", {i: str(i) for i in range(C)})
+        for suffix, cols in (("", [2, 3, 4]), ("_icp", [6, 7, 8]))[:1 if alle.shape[1] < 9 else 2]:
+            if per_sample:
+                with open("{}/emd{}.txt".format(opt.output_path, suffix), "w") as f:
+                    for r in alle:
+                        f.write(EMD_LINE % (int(r[0]), int(r[1]), float(r[cols[0]]), int(r[cols[1]]), int(r[cols[2]])))
+            with open(os.path.join(opt.output_path, "emd_cat{}.txt".format(suffix)), "w") as f:
+                f.write("EMD    Count Cat\n")
+                for c in range(C):
+                    sel = alle[alle[:, 5] == c]
+                    n = sel.shape[0] + 0.001
+                    f.write("%.4f %5d %s\n" % (float(sel[:, cols[0]].sum()) / n, n, names[c]))
 
     def evaluate_batch(self, opt, var, ep=None, it=None, single_gpu=False, visualize=False):
         var = util.move_to_device(var, opt.device)
@@ -782,7 +829,9 @@ class Runner:
         --eval.dual_mesh also {idx}_mesh_dual.ply (eval_3D.meshes_dual: the dual-contouring mesh of the same grid, positions and faces);
         with --eval.icp also {idx}_pointclouds_comp_icp.ply (the ICP-aligned prediction of eval_3D.icp_metrics red, ground truth green);
         with --eval.normals also {idx}_pointclouds_normals.ply (pointclouds_comp's vertices as x y z nx ny nz red green blue: the SDF's
-        normals on the prediction, the estimated PCA normals on the ground truth).  --eval.mesh_dist adds no per-sample file."""
+        normals on the prediction, the estimated PCA normals on the ground truth); with --eval.emd also {idx}_pointclouds_emd.ply (the
+        two n-point sub-samples eval_3D.emd_metrics matched, prediction red, ground truth green).  --eval.mesh_dist adds no per-sample
+        file."""
         if eval_3D.HAVE_MESHING:
             meshes = var.mesh_pred                      # trimesh meshes of the PyMCubes branch
         else:
@@ -806,6 +855,9 @@ class Runner:
             if "normals_pred" in var:                   # --eval.normals: the clouds of pointclouds_comp with the normals that were compared
                 util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_normals", var.dpc_pred, var.dpc.points, folder=folder,
                                                   pred_normals=var.normals_pred, gt_normals=var.dpc.normals)
+            if "emd" in var:                            # --eval.emd: what was matched
+                sub_pred, sub_gt, _ = eval_3D.emd_subsample(var.dpc_pred, var.dpc.points, var.emd_n)
+                util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_emd", sub_pred, sub_gt, folder=folder)
 
     @torch.no_grad()
     def dump_results(self, opt, var, ep, write_new=False, train=False):
@@ -837,6 +889,12 @@ class Runner:
                     with open("{}/normal_consistency{}.txt".format(opt.output_path, suffix), "w" if write_new else "a") as f:
                         for r in rec:
                             f.write(NC_LINE % (int(r[0]), *(float(r[c]) for c in cols)))
+            if "emd" in var:                            # --eval.emd: idx n emd rounds converged (and the same after ICP)
+                rec = _emd_records(var)
+                for suffix, cols in (("", [2, 3, 4]), ("_icp", [6, 7, 8]))[:1 if rec.shape[1] < 9 else 2]:
+                    with open("{}/emd{}.txt".format(opt.output_path, suffix), "w" if write_new else "a") as f:
+                        for r in rec:
+                            f.write(EMD_LINE % (int(r[0]), int(r[1]), float(r[cols[0]]), int(r[cols[1]]), int(r[cols[2]])))
 
     def save_checkpoint(self, opt, ep=0, it=0, best_val=np.inf, latest=False, best=False):
         assert _rank0(opt)

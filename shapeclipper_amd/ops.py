@@ -1886,3 +1886,91 @@ def point_mesh_distance(points, verts, faces, v_count, f_count, search="grid"):
                   _lib.ptr(f_count), B, N, Vtot, Ftot, _lib.ptr(ws), _lib.ptr(dist2), _lib.ptr(face), _lib.ptr(closest), _lib.stream())
     _lib.check(code, "sc_point_mesh_distance" if search == "grid" else "sc_point_mesh_distance_brute")
     return PointMesh(dist2, face, closest)
+
+
+# ---- evaluation: Earth Mover's Distance by an auction matching (csrc/emd3d.hip) --------------------------------------------------------
+EMD_MAX_POINTS = 2048           # SC_EMD3D_MAX_POINTS
+EMD_MAX_PHASES = 80             # SC_EMD3D_MAX_PHASES
+EMD_MAX_IMAGES = 65535
+EmdResult = collections.namedtuple("EmdResult", ["assignment", "cost", "price", "emd", "rounds", "converged"])
+
+
+def emd_eps_list(eps=1e-4, eps_start=0.25):
+    """The epsilon of every phase of the auction as fp32 values (Python floats that hold them exactly): e = eps_start; while e > eps:
+    emit e, e = fl(e / 4); then emit eps -- include/shapeclipper_hip.h, sc_emd3d_match.  0.25 and 1e-4 give 7 phases."""
+    f32 = lambda x: ctypes.c_float(x).value         # one rounding to fp32
+    eps, e, out = f32(eps), f32(eps_start), []
+    while e > eps:
+        out.append(e)
+        e = f32(e / 4.0)                            # the float64 quotient of an fp32 value by 4 is exact; rounded once
+    out.append(eps)
+    return out
+
+
+def _emd_args(xyz1, xyz2, eps, eps_start, max_rounds):
+    """(B, n, eps list) of emd_match's arguments.  TypeError for something that is not an fp32 tensor, ValueError for shapes, sizes and
+    settings -- all before the device is looked at -- then RuntimeError for host tensors (as the ICP entry points) and ValueError for
+    another device or a non-contiguous tensor."""
+    who = "shapeclipper_amd: emd_match"
+    for name, t in (("xyz1", xyz1), ("xyz2", xyz2)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
+        if t.dtype != torch.float32:
+            raise TypeError("%s: %s must be torch.float32, got %s" % (who, name, t.dtype))
+    if xyz1.dim() != 3 or xyz1.shape[2] != 3 or tuple(xyz2.shape) != tuple(xyz1.shape):
+        raise ValueError("%s: xyz1 and xyz2 must have one shape [B,n,3], got %s and %s" % (who, tuple(xyz1.shape), tuple(xyz2.shape)))
+    B, n = xyz1.shape[0], xyz1.shape[1]
+    if not 2 <= n <= EMD_MAX_POINTS:
+        raise ValueError("%s: n must be in 2..%d, got %d" % (who, EMD_MAX_POINTS, n))
+    if B > EMD_MAX_IMAGES:
+        raise ValueError("%s takes at most %d images per call, got %d" % (who, EMD_MAX_IMAGES, B))
+    for name, v in (("eps", eps), ("eps_start", eps_start)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError("%s: %s must be a real number, got %r" % (who, name, v))
+    if not 0.0 < eps <= eps_start or not ctypes.c_float(eps_start).value < float("inf") or not ctypes.c_float(eps).value > 0.0:
+        raise ValueError("%s: need 0 < eps <= eps_start (both fp32 numbers: eps_start finite, eps not below the smallest), got eps = %r, eps_start = %r"
+                         % (who, eps, eps_start))
+    if isinstance(max_rounds, bool) or not isinstance(max_rounds, int):
+        raise TypeError("%s: max_rounds must be an integer, got %r" % (who, max_rounds))
+    if not 1 <= max_rounds < 1 << 31:
+        raise ValueError("%s: max_rounds must be in 1..2^31 - 1, got %r" % (who, max_rounds))
+    phases = emd_eps_list(eps, eps_start)
+    if len(phases) > EMD_MAX_PHASES:
+        raise ValueError("%s: eps = %r, eps_start = %r need %d phases, at most %d" % (who, eps, eps_start, len(phases), EMD_MAX_PHASES))
+    if not xyz1.is_cuda or not xyz2.is_cuda:
+        raise RuntimeError(_lib.NO_CPU)
+    if xyz2.device != xyz1.device:
+        raise ValueError("%s: xyz2 is on %s, xyz1 is on %s" % (who, xyz2.device, xyz1.device))
+    if not xyz1.is_contiguous() or not xyz2.is_contiguous():
+        raise ValueError("%s: xyz1 and xyz2 must be contiguous" % who)
+    return B, n, phases
+
+
+def emd_match(xyz1, xyz2, eps=1e-4, eps_start=0.25, max_rounds=1 << 18):
+    """xyz1, xyz2 [B,n,3] fp32, 2 <= n <= 2048 -> EmdResult(assignment [B,n] int32, cost [B,n] fp32, price [B,n] fp32, emd [B] float64,
+    rounds [B] int32, converged [B] int32): per image the one-to-one matching of the points of xyz1 (persons) to those of xyz2 (objects)
+    that minimises the summed Euclidean distance of the pairs to within n eps, by a forward auction with epsilon scaling from eps_start
+    down to eps (include/shapeclipper_hip.h, sc_emd3d_match, states the rule; csrc/emd3d.hip runs one workgroup per image).
+    assignment[b, i] is the object of person i, cost its distance, price the objects' final prices, emd the float64 mean of cost --
+    the Earth Mover's Distance of the two clouds, at most eps above the optimum when converged is 1.  After max_rounds rounds the
+    auction stops, completes the matching in index order and reports converged 0.  An image with a non-finite coordinate gets the
+    identity, zeros, converged 0 and emd NaN.  No gradient.  The same bits from run to run, alone or in a batch.
+
+    Host synchronisation: none.  Runs on the current stream."""
+    B, n, phases = _emd_args(xyz1, xyz2, eps, eps_start, max_rounds)
+    dev = xyz1.device
+    assignment = torch.empty(B, n, device=dev, dtype=torch.int32)
+    cost = torch.empty(B, n, device=dev, dtype=torch.float32)
+    price = torch.empty(B, n, device=dev, dtype=torch.float32)
+    emd = torch.empty(B, device=dev, dtype=torch.float64)
+    rounds = torch.empty(B, device=dev, dtype=torch.int32)
+    converged = torch.empty(B, device=dev, dtype=torch.int32)
+    if B == 0:
+        return EmdResult(assignment, cost, price, emd, rounds, converged)
+    lib = _lib.load()
+    eps_host = (ctypes.c_float * len(phases))(*phases)              # read by the entry point before it returns
+    with torch.cuda.device(dev):
+        code = lib.sc_emd3d_match(_lib.ptr(xyz1), _lib.ptr(xyz2), B, n, eps_host, len(phases), max_rounds, _lib.ptr(assignment),
+                                  _lib.ptr(cost), _lib.ptr(price), _lib.ptr(rounds), _lib.ptr(converged), _lib.ptr(emd), _lib.stream())
+    _lib.check(code, "sc_emd3d_match")
+    return EmdResult(assignment, cost, price, emd, rounds, converged)

@@ -138,6 +138,29 @@ def mesh_dist_settings(opt):
     return True if on else None
 
 
+def emd_settings(opt):
+    """The evaluation's Earth Mover's Distance: None unless `--eval.emd` is set (absent means off), else (points, eps) from
+    `--eval.emd_points` (default 1024, the count of the Pix3D benchmark; an integer in 2..2048, the sizes ops.emd_match takes) and
+    `--eval.emd_eps` (default 1e-4, a float in (0, 0.25]: the last epsilon of the auction, which starts at 0.25), the arguments of
+    eval_3D.emd_metrics.  Evaluation settings beside eval.vox_res, not hip.* switches.  A bad value is a ValueError, whether or not the
+    switch is on.  (`--eval.emd_eps=1e-4` arrives as the string "1e-4" -- YAML 1.1 reads a float only with a dot, "1.0e-4" -- so a
+    string that float() reads is taken as that number.)"""
+    ev = opt.get("eval", None) or {}
+    on, points, eps = ev.get("emd", False), ev.get("emd_points", 1024), ev.get("emd_eps", 1e-4)
+    if isinstance(eps, str):
+        try:
+            eps = float(eps)
+        except ValueError:
+            pass
+    if not isinstance(on, bool):
+        raise ValueError("eval.emd must be a bool, got %r" % (on,))
+    if isinstance(points, bool) or not isinstance(points, int) or not 2 <= points <= 2048:
+        raise ValueError("eval.emd_points must be an integer in 2..2048, got %r" % (points,))
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 < eps <= 0.25:
+        raise ValueError("eval.emd_eps must be a float in (0, 0.25], got %r" % (eps,))
+    return (points, float(eps)) if on else None
+
+
 def parse_arguments(args):
     """--key1.key2=value ; --flag (true) ; --flag! (false)"""
     opt_cmd = {}
@@ -231,6 +254,7 @@ def process_options(opt):
     icp_settings(opt)
     normal_settings(opt)
     mesh_dist_settings(opt)
+    emd_settings(opt)
     torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
     for row in HIP_TABLE:
         if row.drives is not None:
