@@ -1178,7 +1178,63 @@ int sc_ray_bracket_step(const float* cam_loc, const float* ray_dirs, const float
                         float* t_lo, float* t_hi, float* f_lo, float* f_hi, const int32_t* hit, float* t, float* points, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Launch policy (csrc/device.hip) -- the one process-level setting of the library.  The persistent one-workgroup-per-CU grids
+ * Per-triangle texture atlas (csrc/texture_bake.hip): the kernels between the indexed marching-cubes mesh and a textured OBJ
+ * (eval_3D.mesh_texture, `--eval.texture`).  All arithmetic is fp32, every operation rounded once (no contraction), division correctly
+ * rounded.  tests/texture_ref.py restates every line below in numpy.
+ *
+ * Layout, a pure function of the face index.  T = texels (4..32) is the side of a square cell; every cell holds two triangular charts.
+ *   atlas:   A x A texels, A a power of two in 64..8192, n = A / T (integer division) cells per row and per column; one A serves every
+ *            image of a call.  x runs to the right, y downward (image row 0 is y = 0).  Columns and rows >= n T belong to no cell.
+ *   face f:  cell c = f >> 1, half h = f & 1;  the cell's origin is (X0, Y0) = (T (c % n), T (c / n)).
+ *   texel (i, j) of a cell (i = x - X0, j = y - Y0, both in [0, T)) belongs to the lower half (h = 0) iff i + j <= T - 1, else to the upper.
+ *   corners (cell-local texel indices, at texel centres):   lower p0 = (0, 0),     p1 = (T-3, 0), p2 = (0, T-3);
+ *                                                           upper p0 = (T-1, T-1), p1 = (2, T-1), p2 = (T-1, 2)   (the lower chart
+ *            rotated by 180 degrees: orientation is kept).
+ *   barycentrics of texel (i, j):   lower  b1 = (float)i / (float)(T-3),        b2 = (float)j / (float)(T-3);
+ *                                   upper  b1 = (float)(T-1-i) / (float)(T-3),  b2 = (float)(T-1-j) / (float)(T-3);
+ *                                   b0 = (1 - b1) - b2.    Nothing is clamped: texels outside the triangle (the gutter) take the affine
+ *            extrapolation in the triangle's plane, by at most (T-1)/(T-3) edge lengths from p0.  A bilinear footprint of a point inside
+ *            the lower chart touches texels with i + j <= T-2 only, one inside the upper chart texels with i + j >= T only.
+ *   OBJ texture coordinate of corner k of face f:  vt = ((X0 + pk.x + 0.5) / A, 1 - (Y0 + pk.y + 0.5) / A); both are exact in fp32, and
+ *            so are u A - 0.5 and (1 - v) A - 0.5 there, so the look-up of a corner is that one texel.
+ *
+ * sc_texture_queries: one thread per texel (image b, row y < rows, column x < A); verts [n_verts][3] fp32 in grid-index units and faces
+ * [n_faces][3] int32 (vertex numbers local to their image) as sc_marching_cubes_mesh_* write them; v_start, f_start, f_count [n_images]
+ * int64 on the device: image b's faces are faces[f_start[b] .. f_start[b] + f_count[b]), its vertex k is verts[v_start[b] + k].
+ *   used texel (x < n T, face f = 2 c + h < f_count[b]):  with v0, v1, v2 the face's vertices, per coordinate
+ *            v = (b0 v0 + b1 v1) + b2 v2;    query = (float)lo + v * scale,    scale = (float)((hi - lo) / (double)(n_axis - 1))
+ *            (lo, hi doubles: the positions the level grid was sampled at, eval_3D.mesh_attributes' expression);  face_of_texel = f.
+ *   unused texel:  face_of_texel = -1;  query = that of texel (0, 0) of the image (corner p0 of its face 0: b0 = 1), or ((float)lo) x 3
+ *            for an image without faces, so the networks see finite input.
+ *   query [n_images][image_stride][3]: image b's texel (x, y) at row y A + x of its block; image_stride >= rows A, the rows behind
+ *   rows A are not written (the caller's further queries of that image).  face_of_texel [n_images][rows A] int32.  A vertex number
+ *   outside [0, n_verts) is read as vertex 0 or n_verts - 1 (no access outside verts); the caller keeps f_start + f_count <= n_faces.
+ *
+ * sc_texture_pack: rgb, normal [n_images][rows A][3] fp32 (the colours and unit normals at the queries) -> atlas, normal_atlas
+ * [n_images][A][A][3] uint8, every byte written.  Used texel:  colour byte = trunc(clamp(c, 0, 1) * 255), normal byte =
+ * trunc(clamp((n + 1) * 0.5, 0, 1) * 255); a NaN gives 0.  Texels with face_of_texel < 0 and rows >= `rows`: 127 on every channel.
+ * One thread per four texels, 12-byte stores: both atlases 4-byte aligned.
+ *
+ * sc_texture_sample: the bilinear look-up a viewer performs.  atlas [n_images][A][A][C], fp32 (is_u8 = 0) or uint8 (is_u8 = 1, converted
+ * to float without scaling); uv [n_points][2] in the OBJ convention; image_of_point [n_points] int32 (clamped to [0, n_images)).
+ *   x = u * A - 0.5;  y = (1 - v) * A - 0.5;  x0 = floor(x), fx = x - x0;  y0 = floor(y), fy = y - y0;
+ *   columns clamp(x0, 0, A-1) and clamp(x0 + 1, 0, A-1), rows likewise:  t00 = (x0, y0), t10 = (x0 + 1, y0), t01 = (x0, y0 + 1), t11;
+ *   out = ((1 - fx) * t00 + fx * t10) * (1 - fy) + ((1 - fx) * t01 + fx * t11) * fy        -> out [n_points][C] fp32.
+ *
+ * Plain vector stores, no atomics, no random draws: the same bits from run to run, whatever the batch or the stream.  One launch each.
+ * A count <= 0 returns 0 and launches nothing; hipErrorInvalidValue for texels outside 4..32, an atlas that is not a power of two in
+ * 64..8192, rows outside [0, A], n_axis < 2, image_stride < rows A, channels outside 1..16, more than 65535 images, a NULL pointer or a
+ * misaligned atlas.                                                                                                              */
+int sc_texture_queries(const float* verts, const int32_t* faces, const long long* v_start, const long long* f_start,
+                       const long long* f_count, int n_images, long long n_verts, long long n_faces, int atlas, int texels, double lo,
+                       double hi, int n_axis, int rows, long long image_stride, float* query, int32_t* face_of_texel, void* stream);
+int sc_texture_pack(const float* rgb, const float* normal, const int32_t* face_of_texel, int n_images, int atlas, int rows,
+                    unsigned char* atlas_rgb, unsigned char* atlas_normal, void* stream);
+int sc_texture_sample(const void* atlas_data, int is_u8, const float* uv, const int32_t* image_of_point, long long n_points,
+                      int n_images, int atlas, int channels, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Launch policy (csrc/device.hip) -- the one process-level setting of the library. The persistent one-workgroup-per-CU grids
  * (stream-K 3x3 convolutions and their weight gradients, stem / 1x1 / stride-2 gradients) are sized for
  * sc_grid_cus() = device CUs - reserved.  Reserve CUs when another stream must make progress beside them: RCCL's
  * all-reduce kernels in a multi-GPU step (the reference leaves this to DDP / NCCL: model/runner.py:121).  Call before sizing

@@ -101,6 +101,22 @@ def _emd_records(var):
     return torch.stack([c.detach().double().view(-1).cpu() for c in cols], dim=1)
 
 
+TEXTURE_LINE = "%d %d %d %d %.6f %.6f\n"     # a line of texture.txt: idx faces atlas rows err_mean err_max
+
+
+def _texture_records(var):
+    """[B,6] float64 on the host, a record per sample of eval_3D.mesh_texture's stats (var.texture, left by dump_geometry with
+    --eval.texture): idx, faces, atlas, rows, err_mean, err_max."""
+    return torch.tensor([[float(i)] + [float(m.stats[k]) for k in ("faces", "atlas", "rows", "err_mean", "err_max")]
+                         for i, m in zip(var.idx.tolist(), var.texture)], dtype=torch.float64).view(-1, 6)
+
+
+def _write_texture(opt, rec, mode="w"):
+    with open("{}/texture.txt".format(opt.output_path), mode) as f:
+        for r in rec:
+            f.write(TEXTURE_LINE % (int(r[0]), int(r[1]), int(r[2]), int(r[3]), float(r[4]), float(r[5])))
+
+
 class Runner:
 
     def __init__(self, opt):
@@ -491,7 +507,8 @@ class Runner:
         """Evaluation over all ranks (BASELINE config[4]; the reference evaluates on one GPU, evaluate.py:16-18):
         rank r takes the test samples with index % world == r (eval.batch_size = 1), per-sample records are
         gathered once, rank 0 writes chamfer.txt / cd_cat.txt / f_score.txt in sample order (with --hip.largest_component also
-        components.txt, from a second gather of the per-sample counts; with --eval.icp also chamfer_icp.txt / cd_cat_icp.txt /
+        components.txt, from a second gather of the per-sample counts; with --eval.texture also texture.txt, from one more gather of
+        the bake's per-sample records; with --eval.icp also chamfer_icp.txt / cd_cat_icp.txt /
         f_score_icp.txt / icp.txt, from one more gather of the ICP-aligned records; with --eval.normals also normal_consistency.txt /
         nc_cat.txt and their _icp namesakes, from one more gather again; with --eval.mesh_dist also completeness_mesh.txt /
         cd_cat_mesh.txt / f_score_mesh.txt and, with --eval.dual_mesh, their _dual namesakes, from one more gather; with --eval.emd
@@ -504,7 +521,7 @@ class Runner:
         # the reference's single-node convention is rank == device index; the process group's rank is the same number there and stays
         # right when ranks and devices are numbered differently (several nodes; tests/test_gpu_two_ranks.py: two ranks on one GPU)
         rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else util.get_rank(opt)
-        recs, comps, icps, ncs, meshes, emds = [], [], [], [], [], []
+        recs, comps, icps, ncs, meshes, emds, texs = [], [], [], [], [], [], []
         for it in range(rank, len(self.test_data), opt.world_size):
             sample = self.test_data[it]
             batch = {k: ({kk: vv[None] for kk, vv in v.items()} if isinstance(v, dict) else torch.as_tensor(v)[None]) for k, v in sample.items()}
@@ -524,6 +541,8 @@ class Runner:
                 meshes.append(_mesh_records(var))
             if "emd" in var:                            # --eval.emd: _emd_records' columns
                 emds.append(_emd_records(var))
+            if "texture" in var:                        # --eval.texture: _texture_records' columns (dump_geometry baked the atlas)
+                texs.append(_texture_records(var))
         dev = next(self.graph.parameters()).device
         records = torch.stack(recs) if recs else torch.zeros(0, 10, device=dev)
         allr = gather_eval_records(records.to(dev), opt.world_size).cpu()
@@ -551,7 +570,13 @@ class Runner:
             width = 6 if options.icp_settings(opt) is None else 9
             alle = gather_eval_records(torch.cat(emds).to(dev) if emds else torch.zeros(0, width, device=dev, dtype=torch.float64),
                                        opt.world_size).cpu()
+        allt = None
+        if options.texture_texels(opt) is not None and util_vis is not None:      # likewise
+            allt = gather_eval_records(torch.cat(texs).to(dev) if texs else torch.zeros(0, 6, device=dev, dtype=torch.float64),
+                                       opt.world_size).cpu()
         opt.H, opt.W = opt.image_size
+        if rank == 0 and allt is not None:
+            _write_texture(opt, allt)
         if rank == 0 and alle is not None:
             self._write_emd(opt, alle)
         if rank == 0 and allm is not None:
@@ -830,8 +855,10 @@ class Runner:
         with --eval.icp also {idx}_pointclouds_comp_icp.ply (the ICP-aligned prediction of eval_3D.icp_metrics red, ground truth green);
         with --eval.normals also {idx}_pointclouds_normals.ply (pointclouds_comp's vertices as x y z nx ny nz red green blue: the SDF's
         normals on the prediction, the estimated PCA normals on the ground truth); with --eval.emd also {idx}_pointclouds_emd.ply (the
-        two n-point sub-samples eval_3D.emd_metrics matched, prediction red, ground truth green).  --eval.mesh_dist adds no per-sample
-        file."""
+        two n-point sub-samples eval_3D.emd_metrics matched, prediction red, ground truth green); with --eval.texture also
+        {idx}_mesh_tex.obj / .mtl / .png and {idx}_mesh_tex_normal.png (eval_3D.mesh_texture: the device mesh with a per-triangle
+        texture atlas of the predicted colours, and the atlas of its normals; var.texture keeps the result for texture.txt).
+        --eval.mesh_dist adds no per-sample file."""
         if eval_3D.HAVE_MESHING:
             meshes = var.mesh_pred                      # trimesh meshes of the PyMCubes branch
         else:
@@ -848,6 +875,10 @@ class Runner:
             # (--eval.mesh_dist measured against this mesh already and left it in var)
             dual = var.mesh_dual if "mesh_dual" in var else eval_3D.meshes_dual(opt, net.sdf_network, var.proj_latent_sdf, var.level_vox, reg)
             util_vis.dump_meshes(opt, var.idx, "mesh_dual", dual, folder=folder)
+        if options.texture_texels(opt) is not None:
+            net = self.graph.module
+            var.texture = eval_3D.mesh_texture(opt, net.sdf_network, net.rgb_network, var.proj_latent_sdf, var.proj_latent_rgb, var.level_vox)
+            util_vis.dump_textured_meshes(opt, var.idx, "mesh_tex", var.texture, folder=folder)
         if "dpc" in var:
             util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_comp", var.dpc_pred, var.dpc.points, folder=folder)
             if "dpc_pred_icp" in var:                   # --eval.icp: the ICP-aligned prediction red, the ground truth green
@@ -870,6 +901,8 @@ class Runner:
                 with open("{}/components.txt".format(opt.output_path), "w" if write_new else "a") as f:
                     for row in zip(var.idx.tolist(), *(c.tolist() for c in _component_counts(var))):
                         f.write("{} {} {} {}\n".format(*row))
+            if "texture" in var:                        # --eval.texture: idx faces atlas rows err_mean err_max
+                _write_texture(opt, _texture_records(var), "w" if write_new else "a")
             if "icp" in var:                            # --eval.icp: chamfer.txt's line of the aligned metrics; idx s angle_deg |t| objective first, last
                 with open("{}/chamfer_icp.txt".format(opt.output_path), "w" if write_new else "a") as f:
                     for i, acc, comp in zip(var.idx, var.cd_acc_icp, var.cd_comp_icp):

@@ -1974,3 +1974,149 @@ def emd_match(xyz1, xyz2, eps=1e-4, eps_start=0.25, max_rounds=1 << 18):
                                   _lib.ptr(cost), _lib.ptr(price), _lib.ptr(rounds), _lib.ptr(converged), _lib.ptr(emd), _lib.stream())
     _lib.check(code, "sc_emd3d_match")
     return EmdResult(assignment, cost, price, emd, rounds, converged)
+
+
+# ---- evaluation: per-triangle texture atlas (csrc/texture_bake.hip) --------------------------------------------------------------------
+TEXTURE_TEXELS = (4, 32)            # the cell side T sc_texture_* take
+TEXTURE_ATLAS = (64, 8192)          # the atlas side A: a power of two in this range
+TEXTURE_MAX_IMAGES = 65535
+TextureLayout = collections.namedtuple("TextureLayout", ["atlas", "cells", "rows"])
+
+
+def texture_layout(f_max: int, texels: int) -> TextureLayout:
+    """The atlas of a batch whose largest mesh has f_max faces, at `texels` = T texels per cell side: (A, n, rows) with A the smallest
+    power of two in 64..8192 whose n = A // T cells per side hold ceil(f_max / 2) cells (two faces share a cell), and rows =
+    T ceil(ceil(f_max / 2) / n), the atlas rows that hold a face.  ValueError when 8192 does not suffice (names eval.texture_texels)."""
+    if isinstance(texels, bool) or not isinstance(texels, int) or not TEXTURE_TEXELS[0] <= texels <= TEXTURE_TEXELS[1]:
+        raise ValueError("shapeclipper_amd: texture_layout: texels must be an integer in %d..%d, got %r" % (*TEXTURE_TEXELS, texels))
+    if f_max < 0:
+        raise ValueError("shapeclipper_amd: texture_layout: f_max must be >= 0, got %r" % (f_max,))
+    cells = (int(f_max) + 1) // 2
+    A = TEXTURE_ATLAS[0]
+    while (A // texels) ** 2 < cells:
+        A *= 2
+        if A > TEXTURE_ATLAS[1]:
+            raise ValueError("shapeclipper_amd: a mesh of %d faces does not fit an %d x %d atlas at eval.texture_texels = %d; lower "
+                             "eval.texture_texels or eval.vox_res" % (f_max, TEXTURE_ATLAS[1], TEXTURE_ATLAS[1], texels))
+    n = A // texels
+    return TextureLayout(A, n, texels * ((cells + n - 1) // n))
+
+
+def _texture_atlas_arg(who, A):
+    if isinstance(A, bool) or not isinstance(A, int) or not TEXTURE_ATLAS[0] <= A <= TEXTURE_ATLAS[1] or A & (A - 1):
+        raise ValueError("shapeclipper_amd: %s: the atlas side must be a power of two in %d..%d, got %r" % (who, *TEXTURE_ATLAS, A))
+
+
+def _texture_tensor(who, name, t, dtypes, dev=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError("shapeclipper_amd: %s: %s must be a device tensor (no CPU fallback)" % (who, name))
+    if t.dtype not in dtypes:
+        raise ValueError("shapeclipper_amd: %s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype))
+    if dev is not None and t.device != dev:
+        raise ValueError("shapeclipper_amd: %s: %s is on %s, expected %s" % (who, name, t.device, dev))
+    return t.contiguous()
+
+
+def texture_queries(verts, faces, v_start, f_start, f_count, A, T, lo, hi, S, rows, extra=0):
+    """The network query point of every atlas texel: verts [V,3] fp32 (grid-index units) and faces [F,3] int32 (vertex numbers local to
+    their image) as isosurface_mesh returns them, v_start / f_start / f_count sequences of B host integers (image b's faces are
+    faces[f_start[b]:f_start[b] + f_count[b]], its vertex k is verts[v_start[b] + k]) -> (query [B (rows A + extra), 3] fp32,
+    face_of_texel [B, rows A] int32).  Image b's texel (x, y) is row y A + x of its block of rows A + extra query rows, the padded
+    one-launch layout of sdf_forward / rgb_points_forward with n_per_image = rows A + extra; the `extra` rows behind the texels are
+    left unwritten for the caller (eval_3D.mesh_texture puts the face centroids there).  A used texel is queried at
+    lo + v (hi - lo) / (S - 1), v the affine map of its face at the texel's barycentrics; an unused one (face_of_texel -1) repeats the
+    image's first texel.  include/shapeclipper_hip.h states layout and arithmetic (sc_texture_queries); texture_layout gives A and
+    rows.  One launch on the current stream, no host synchronisation."""
+    who = "texture_queries"
+    verts = _texture_tensor(who, "verts", verts, (torch.float32,))
+    faces = _texture_tensor(who, "faces", faces, (torch.int32,), verts.device)
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("shapeclipper_amd: texture_queries takes verts [V,3] and faces [F,3], got %s and %s" % (tuple(verts.shape), tuple(faces.shape)))
+    _texture_atlas_arg(who, A)
+    v_start, f_start, f_count = ([int(v) for v in s] for s in (v_start, f_start, f_count))
+    B, V, F = len(f_count), verts.shape[0], faces.shape[0]
+    if len(v_start) != B or len(f_start) != B or B > TEXTURE_MAX_IMAGES:
+        raise ValueError("shapeclipper_amd: texture_queries takes v_start, f_start and f_count of one length <= %d" % TEXTURE_MAX_IMAGES)
+    if isinstance(T, bool) or not isinstance(T, int) or not TEXTURE_TEXELS[0] <= T <= TEXTURE_TEXELS[1]:
+        raise ValueError("shapeclipper_amd: texture_queries: T must be an integer in %d..%d, got %r" % (*TEXTURE_TEXELS, T))
+    n = A // T
+    for b in range(B):
+        if f_count[b] < 0 or f_start[b] < 0 or f_start[b] + f_count[b] > F or not 0 <= v_start[b] <= V:
+            raise ValueError("shapeclipper_amd: texture_queries: image %d's faces [%d, %d) / first vertex %d lie outside the %d faces / %d "
+                             "vertices given" % (b, f_start[b], f_start[b] + f_count[b], v_start[b], F, V))
+        if f_count[b] > 2 * n * (rows // T):
+            raise ValueError("shapeclipper_amd: texture_queries: image %d has %d faces; %d rows of an atlas of %d hold %d at T = %d"
+                             % (b, f_count[b], rows, A, 2 * n * (rows // T), T))
+    if not 0 <= rows <= A or rows % T or extra < 0 or S < 2:
+        raise ValueError("shapeclipper_amd: texture_queries needs 0 <= rows <= A, rows a multiple of T, extra >= 0 and S >= 2")
+    dev = verts.device
+    stride = rows * A + extra
+    query = torch.empty(B * stride, 3, device=dev, dtype=torch.float32)
+    face_of_texel = torch.empty(B, rows * A, device=dev, dtype=torch.int32)
+    if B == 0 or rows == 0:
+        return query, face_of_texel
+    starts = torch.tensor([v_start, f_start, f_count], dtype=torch.int64).to(dev)
+    with torch.cuda.device(dev):
+        code = _lib.load().sc_texture_queries(_lib.ptr(verts) if V else None, _lib.ptr(faces) if F else None, _lib.ptr(starts[0]),
+                                              _lib.ptr(starts[1]), _lib.ptr(starts[2]), B, V, F, A, T, float(lo), float(hi), int(S), rows,
+                                              stride, _lib.ptr(query), _lib.ptr(face_of_texel), _lib.stream())
+    _lib.check(code, "sc_texture_queries")
+    return query, face_of_texel
+
+
+def texture_pack(rgb, normal, face_of_texel, A, rows):
+    """rgb, normal [B rows A, 3] fp32 (the colours and unit normals at texture_queries' points, image after image) and face_of_texel
+    [B, rows A] int32 -> (atlas, normal_atlas) uint8 [B, A, A, 3]: a used texel holds trunc(clamp(c, 0, 1) * 255) -- the recipe of the
+    PNG dumps and of mesh_attributes -- and trunc(clamp((n + 1) / 2, 0, 1) * 255) of the object-space normal; texels without a face
+    and the rows >= `rows` hold 127.  One launch (sc_texture_pack), no host synchronisation."""
+    who = "texture_pack"
+    _texture_atlas_arg(who, A)
+    face_of_texel = _texture_tensor(who, "face_of_texel", face_of_texel, (torch.int32,))
+    dev = face_of_texel.device
+    rgb = _texture_tensor(who, "rgb", rgb, (torch.float32,), dev)
+    normal = _texture_tensor(who, "normal", normal, (torch.float32,), dev)
+    if not 0 <= rows <= A or face_of_texel.dim() != 2 or face_of_texel.shape[1] != rows * A:
+        raise ValueError("shapeclipper_amd: texture_pack takes face_of_texel [B, rows A] with 0 <= rows <= A, got %s at rows = %r, A = %d"
+                         % (tuple(face_of_texel.shape), rows, A))
+    B = face_of_texel.shape[0]
+    if B > TEXTURE_MAX_IMAGES or tuple(rgb.shape) != (B * rows * A, 3) or tuple(normal.shape) != (B * rows * A, 3):
+        raise ValueError("shapeclipper_amd: texture_pack takes rgb and normal [B rows A, 3] = [%d, 3] for at most %d images, got %s and %s"
+                         % (B * rows * A, TEXTURE_MAX_IMAGES, tuple(rgb.shape), tuple(normal.shape)))
+    atlas = torch.empty(B, A, A, 3, device=dev, dtype=torch.uint8)
+    atlas_n = torch.empty(B, A, A, 3, device=dev, dtype=torch.uint8)
+    if B == 0:
+        return atlas, atlas_n
+    live = rows > 0
+    with torch.cuda.device(dev):
+        code = _lib.load().sc_texture_pack(_lib.ptr(rgb) if live else None, _lib.ptr(normal) if live else None,
+                                           _lib.ptr(face_of_texel) if live else None, B, A, rows, _lib.ptr(atlas), _lib.ptr(atlas_n),
+                                           _lib.stream())
+    _lib.check(code, "sc_texture_pack")
+    return atlas, atlas_n
+
+
+def texture_sample(atlas, uv, image_of_point):
+    """The bilinear look-up a viewer performs: atlas [B, A, A, C] fp32 or uint8 (read as float, not scaled), uv [N, 2] fp32 in the OBJ
+    convention (u to the right, v upward, texel centres at (k + 0.5) / A), image_of_point [N] int32 -> [N, C] fp32.  Indices clamp to the
+    atlas edge; include/shapeclipper_hip.h states the expression (sc_texture_sample).  One launch, no host synchronisation."""
+    who = "texture_sample"
+    atlas = _texture_tensor(who, "atlas", atlas, (torch.float32, torch.uint8))
+    dev = atlas.device
+    uv = _texture_tensor(who, "uv", uv, (torch.float32,), dev)
+    image_of_point = _texture_tensor(who, "image_of_point", image_of_point, (torch.int32,), dev)
+    if atlas.dim() != 4 or atlas.shape[1] != atlas.shape[2] or not 1 <= atlas.shape[3] <= 16 or atlas.shape[0] < 1:
+        raise ValueError("shapeclipper_amd: texture_sample takes an atlas [B, A, A, C] with B >= 1 and 1 <= C <= 16, got %s" % (tuple(atlas.shape),))
+    B, A, C = atlas.shape[0], atlas.shape[1], atlas.shape[3]
+    _texture_atlas_arg(who, A)
+    N = uv.shape[0]
+    if B > TEXTURE_MAX_IMAGES or tuple(uv.shape) != (N, 2) or tuple(image_of_point.shape) != (N,):
+        raise ValueError("shapeclipper_amd: texture_sample takes uv [N, 2] and image_of_point [N], got %s and %s"
+                         % (tuple(uv.shape), tuple(image_of_point.shape)))
+    out = torch.empty(N, C, device=dev, dtype=torch.float32)
+    if N == 0:
+        return out
+    with torch.cuda.device(dev):
+        code = _lib.load().sc_texture_sample(_lib.ptr(atlas), 1 if atlas.dtype == torch.uint8 else 0, _lib.ptr(uv), _lib.ptr(image_of_point),
+                                             N, B, A, C, _lib.ptr(out), _lib.stream())
+    _lib.check(code, "sc_texture_sample")
+    return out

@@ -25,6 +25,7 @@ Call surface of the reference's utils/eval_3D.py.
 """
 from __future__ import annotations
 
+import collections
 import threading
 
 import numpy as np
@@ -184,6 +185,28 @@ def _padded_vertex_queries(verts, v_count, v_start, lo, hi, S):
     return P, (lo + verts[rows] * ((hi - lo) / (S - 1))).contiguous()
 
 
+def _colours_and_normals(sdf_network, rgb_network, proj_latent_sdf, proj_latent_rgb):
+    """-> run(query, B, P): query [B P, 3] in the padded one-launch layout (P a multiple of 16 rows per image) -> (rgb [B P, 3] sigmoid
+    colours, normal [B P, 3] unit SDF gradients), by one ops.sdf_forward with d sdf/dx and the feature and one ops.rgb_points_forward on
+    weight images packed once here; architectures outside the compiled family (sdf_network.eager / rgb_network.eager) run the same
+    steps on stock operators (model/eager_path.py)."""
+    if sdf_network.eager or rgb_network.eager:
+        from ..model import eager_path
+
+        def run(query, B, P):
+            _, feat, grad = eager_path.sdf_conditional_output(sdf_network, B, query, proj_latent_sdf, compute_grad=True)
+            rgb = eager_path.rgb_mlp(rgb_network, query.view(B, P, 3), proj_latent_rgb, feat.detach().view(B, P, -1)).reshape(-1, 3)
+            return rgb, torch.nn.functional.normalize(grad.detach(), dim=1, eps=1e-12)
+        return run
+    w_pack, cbias = sdf_network.packed(proj_latent_sdf)
+    v_pack, dbias = rgb_network.packed(proj_latent_rgb)
+
+    def run(query, B, P):
+        _, grad, feat = ops.sdf_forward(query, w_pack, cbias, P, symmetric=bool(sdf_network.force_symmetry), want_grad=True, want_feat=True)
+        return ops.rgb_points_forward(query, grad, feat, v_pack, dbias, P, symmetric=bool(rgb_network.force_symmetry))
+    return run
+
+
 @torch.no_grad()
 def mesh_attributes(opt, sdf_network, rgb_network, proj_latent_sdf, proj_latent_rgb, level_vox):
     """level_vox [B,S,S,S] (compute_level_grid) -> per image (vertices [V,3] fp32, faces [F,3] int32, normals [V,3] fp32 unit,
@@ -212,19 +235,102 @@ def mesh_attributes(opt, sdf_network, rgb_network, proj_latent_sdf, proj_latent_
         empty = (torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.int32, device=dev),
                  torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.uint8, device=dev))
         return [empty] * B
-    if sdf_network.eager or rgb_network.eager:
-        from ..model import eager_path
-        _, feat, grad = eager_path.sdf_conditional_output(sdf_network, B, query, proj_latent_sdf, compute_grad=True)
-        rgb = eager_path.rgb_mlp(rgb_network, query.view(B, P, 3), proj_latent_rgb, feat.detach().view(B, P, -1)).reshape(-1, 3)
-        normal = torch.nn.functional.normalize(grad.detach(), dim=1, eps=1e-12)
-    else:
-        w_pack, cbias = sdf_network.packed(proj_latent_sdf)
-        _, grad, feat = ops.sdf_forward(query, w_pack, cbias, P, symmetric=bool(sdf_network.force_symmetry), want_grad=True, want_feat=True)
-        v_pack, dbias = rgb_network.packed(proj_latent_rgb)
-        rgb, normal = ops.rgb_points_forward(query, grad, feat, v_pack, dbias, P, symmetric=bool(rgb_network.force_symmetry))
+    rgb, normal = _colours_and_normals(sdf_network, rgb_network, proj_latent_sdf, proj_latent_rgb)(query, B, P)
     colours = (rgb.clamp(0, 1) * 255).to(torch.uint8)
     return [(written[v_start[b]:v_end[b]], faces[f_start[b]:f_end[b]], normal[b * P:b * P + V[b]], colours[b * P:b * P + V[b]])
             for b in range(B)]
+
+
+TEXTURE_SLAB = 1 << 20     # texels per launch of mesh_texture's network chain: the feature tile costs 256 B a texel
+TexturedMesh = collections.namedtuple("TexturedMesh", ["vertices", "faces", "uv", "atlas", "normal_atlas", "stats"])
+
+
+def texture_face_uv(n_faces, A, T, device=None):
+    """OBJ texture coordinates [n_faces, 3, 2] fp32 of the chart corners of faces 0..n_faces-1 in an A x A atlas of T-texel cells
+    (include/shapeclipper_hip.h states the layout): vt = ((X0 + pk.x + 0.5) / A, 1 - (Y0 + pk.y + 0.5) / A), exact in fp32."""
+    n = A // T
+    f = torch.arange(n_faces, device=device)
+    c, h = f >> 1, f & 1
+    corner = torch.tensor([[[0, 0], [T - 3, 0], [0, T - 3]], [[T - 1, T - 1], [2, T - 1], [T - 1, 2]]], device=device)[h]     # [F,3,2]
+    origin = torch.stack([T * (c % n), T * (c // n)], dim=1)[:, None]
+    p = (origin + corner).double() + 0.5
+    return torch.stack([p[..., 0] / A, 1 - p[..., 1] / A], dim=-1).float()
+
+
+@torch.no_grad()
+def mesh_texture(opt, sdf_network, rgb_network, proj_latent_sdf, proj_latent_rgb, level_vox, slab=None):
+    """level_vox [B,S,S,S] (compute_level_grid) -> per image TexturedMesh(vertices [V,3] fp32, faces [F,3] int32, uv [F,3,2] fp32,
+    atlas uint8 [A,A,3], normal_atlas uint8 [A,A,3], stats), on the device: the mesh of meshes_device, written the same way (so an OBJ
+    of it overlays {idx}_mesh.ply), with one triangular chart of eval.texture_texels = T texels per face in an A x A atlas
+    (ops.texture_layout: one A for the batch, set by its largest mesh) that holds the predicted colour, and a second atlas that holds
+    the unit SDF normal as (n + 1) / 2.  include/shapeclipper_hip.h states the layout; unused texels are (127, 127, 127).
+
+    ops.texture_queries turns the texels of the atlas rows that hold a face into query points at the positions the level grid was
+    sampled at (mesh_attributes' positions, not the written v / S rescale); one sdf_forward with gradient and feature and one
+    rgb_points_forward per slab evaluate them (_colours_and_normals; the eager path for other architectures); ops.texture_pack
+    quantises.  The chain runs in slabs of at most `slab` (default TEXTURE_SLAB = 2^20) texels per launch over the whole batch, a whole
+    number of 16-point tiles per image each: every texel is evaluated on its own, so the slab size changes no bit.
+
+    stats = dict(faces, atlas, rows, err_mean, err_max): the self-check.  Every face's centroid (b = 1/3 each) is evaluated by the
+    network directly -- its queries ride behind the texels as one more padded block per image -- and compared with the bilinear look-up
+    (ops.texture_sample) of the colour atlas at the centroid's texture coordinate, in 0..255 units, largest channel difference per
+    face, mean and max over the faces: how well T texels resolve the colour field at hand.  An image without faces gets an all-127
+    atlas of side 64, rows 0 and errors 0."""
+    lo, hi = opt.eval.range
+    T = options.texture_texels(opt, always=True)
+    B, S = level_vox.shape[0], level_vox.shape[1]
+    dev = level_vox.device
+    verts, faces, v_count, f_count = ops.isosurface_mesh(level_vox)
+    written = verts / S * (hi - lo) + lo                                # meshes_device's expression: the same bytes as {idx}_mesh.ply
+    v_end, f_end = torch.cumsum(v_count, 0).tolist(), torch.cumsum(f_count, 0).tolist()
+    v_start, f_start = [0] + v_end[:-1], [0] + f_end[:-1]
+    F = f_count.tolist()
+    A, _, rows = ops.texture_layout(max(F, default=0), T)
+    grey = torch.full((64, 64, 3), 127, dtype=torch.uint8, device=dev)
+    blank = lambda b: TexturedMesh(written[v_start[b]:v_end[b]], faces[f_start[b]:f_end[b]], torch.zeros(0, 3, 2, device=dev), grey, grey,
+                                   dict(faces=0, atlas=64, rows=0, err_mean=0.0, err_max=0.0))
+    if rows == 0:
+        return [blank(b) for b in range(B)]
+    n_tex = rows * A
+    Pc = 16 * ((max(F) + 15) // 16)                                     # the centroid block
+    P = n_tex + Pc
+    query, face_of_texel = ops.texture_queries(verts, faces, v_start, f_start, F, A, T, lo, hi, S, rows, extra=Pc)
+    q = query.view(B, P, 3)
+    scale = (hi - lo) / (S - 1)
+    for b in range(B):
+        tri = verts[v_start[b]:v_end[b]][faces[f_start[b]:f_end[b]].long()]            # [F_b,3,3] grid-index units
+        q[b, n_tex:] = q[b, 0]                                                         # padding repeats the image's first texel
+        q[b, n_tex:n_tex + F[b]] = lo + (tri.sum(dim=1) / 3) * scale
+    # the chain, slab by slab: rows [s, e) of every image's block are one padded launch of e - s points per image
+    slab = TEXTURE_SLAB if slab is None else int(slab)
+    step = max(16, (slab // B) // 16 * 16)
+    chain = _colours_and_normals(sdf_network, rgb_network, proj_latent_sdf, proj_latent_rgb)
+    if step >= P:
+        rgb, normal = chain(query, B, P)
+        rgb, normal = rgb.view(B, P, 3), normal.view(B, P, 3)
+    else:
+        rgb, normal = torch.empty(B, P, 3, device=dev), torch.empty(B, P, 3, device=dev)
+        for s in range(0, P, step):
+            e = min(s + step, P)
+            c, m = chain(q[:, s:e].reshape(-1, 3).contiguous(), B, e - s)
+            rgb[:, s:e], normal[:, s:e] = c.view(B, e - s, 3), m.view(B, e - s, 3)
+    atlas, atlas_n = ops.texture_pack(rgb[:, :n_tex].reshape(-1, 3).contiguous(), normal[:, :n_tex].reshape(-1, 3).contiguous(),
+                                      face_of_texel, A, rows)
+    # self-check at the face centroids: the viewer's look-up against the network's colour there
+    uv = [texture_face_uv(F[b], A, T, dev) for b in range(B)]
+    image = torch.cat([torch.full((F[b],), b, dtype=torch.int32, device=dev) for b in range(B)])
+    looked = ops.texture_sample(atlas, torch.cat([u.mean(dim=1) for u in uv]).contiguous(), image)
+    direct = torch.cat([rgb[b, n_tex:n_tex + F[b]] for b in range(B)]).clamp(0, 1) * 255
+    err = (looked - direct).abs().amax(dim=1).double()
+    out = []
+    for b in range(B):
+        if F[b] == 0:
+            out.append(blank(b))
+            continue
+        e = err[f_start[b]:f_end[b]]
+        out.append(TexturedMesh(written[v_start[b]:v_end[b]], faces[f_start[b]:f_end[b]], uv[b], atlas[b], atlas_n[b],
+                                dict(faces=F[b], atlas=A, rows=rows, err_mean=float(e.mean()), err_max=float(e.max()))))
+    return out
 
 
 @torch.no_grad()

@@ -97,6 +97,20 @@ def dual_mesh_reg(opt):
     return float(reg) if ev.get("dual_mesh", False) else None
 
 
+def texture_texels(opt, always=False):
+    """The evaluation's textured OBJ dump: None unless `--eval.texture` is set (absent means off), else `--eval.texture_texels` (default
+    8, an integer in 4..32), the side T in texels of the square atlas cell that two faces share (eval_3D.mesh_texture;
+    include/shapeclipper_hip.h states the layout).  Evaluation settings beside eval.vox_res, not hip.* switches.  A bad value is a
+    ValueError, whether or not the switch is on.  always=True returns T whatever the switch says (a direct call of mesh_texture)."""
+    ev = opt.get("eval", None) or {}
+    on, texels = ev.get("texture", False), ev.get("texture_texels", 8)
+    if not isinstance(on, bool):
+        raise ValueError("eval.texture must be a bool, got %r" % (on,))
+    if isinstance(texels, bool) or not isinstance(texels, int) or not 4 <= texels <= 32:
+        raise ValueError("eval.texture_texels must be an integer in 4..32, got %r" % (texels,))
+    return texels if on or always else None
+
+
 def icp_settings(opt):
     """The evaluation's ICP-aligned metrics: None unless `--eval.icp` is set (absent means off), else (iters, scale) from
     `--eval.icp_iters` (default 30, an integer in 1..100) and `--eval.icp_scale` (default true: fit a similarity; false: a rigid motion),
@@ -251,6 +265,7 @@ def process_options(opt):
             if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
                 raise ValueError("hip.%s must be an integer in %d..%d, got %r" % (row.key, lo, hi, v))
     dual_mesh_reg(opt)
+    texture_texels(opt)
     icp_settings(opt)
     normal_settings(opt)
     mesh_dist_settings(opt)

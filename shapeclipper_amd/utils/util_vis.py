@@ -1,6 +1,7 @@
-"""Evaluation and training-time dumps: PNG images with optional pose axes and rotating GIFs (via PIL when available) and PLY geometry
-(numpy only) -- the reference's utils/util_vis.py dump_images, draw_pose, dump_gifs, dump_meshes and dump_pointclouds_compare.  The GIF
-frames arrive as bytes (ops.vis_frames computes the reference's float -> uint8 recipe on the device).  Its TensorBoard grids are not
+"""Evaluation and training-time dumps: PNG images with optional pose axes and rotating GIFs (via PIL when available), PLY geometry
+(numpy only) and textured Wavefront OBJ meshes -- the reference's utils/util_vis.py dump_images, draw_pose, dump_gifs, dump_meshes and
+dump_pointclouds_compare; the OBJ / MTL writers have no counterpart there.  The GIF frames arrive as bytes (ops.vis_frames computes the
+reference's float -> uint8 recipe on the device).  Its TensorBoard grids are not
 reproduced."""
 import os
 
@@ -161,3 +162,47 @@ def dump_pointclouds_compare(opt, idx, name, preds, gts, folder="dump", pred_nor
         if pred_normals is not None:
             normals = np.concatenate([_numpy(pred_normals[i]).reshape(-1, 3), _numpy(gt_normals[i]).reshape(-1, 3)])
         write_ply_pointcloud(fname, np.concatenate([pred, gt]), colours, normals)
+
+
+# ---- textured Wavefront OBJ: {name}.obj + {name}.mtl + {name}.png (`--eval.texture`, eval_3D.mesh_texture) ---------------------------
+def write_obj_textured(fname, vertices, faces, uv, mtl_name):
+    """vertices [V,3] float, faces [F,3] int, uv [F,3,2] float (a texture coordinate per face corner: every face has its own chart) ->
+    ASCII OBJ: `mtllib` with the bare file name of mtl_name, the V `v` lines, 3 F `vt` lines in face order, `usemtl tex` and the F faces
+    as `f a/ta b/tb c/tc`, all indices 1-based.  Nine significant digits: an fp32 value reads back to the same bits."""
+    v, f = _numpy(vertices).reshape(-1, 3), _numpy(faces).reshape(-1, 3)
+    t = _numpy(uv).reshape(-1, 2)
+    assert len(t) == 3 * len(f), "one texture coordinate per face corner"
+    lines = ["mtllib %s" % os.path.basename(mtl_name)]
+    lines += ["v %.9g %.9g %.9g" % (float(p[0]), float(p[1]), float(p[2])) for p in v]
+    lines += ["vt %.9g %.9g" % (float(p[0]), float(p[1])) for p in t]
+    lines.append("usemtl tex")
+    lines += ["f %d/%d %d/%d %d/%d" % (a[0] + 1, 3 * k + 1, a[1] + 1, 3 * k + 2, a[2] + 1, 3 * k + 3) for k, a in enumerate(f.tolist())]
+    with open(fname, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+def write_mtl(fname, png_name):
+    """The material `tex` of write_obj_textured: white ambient and diffuse, the diffuse map `map_Kd` naming png_name's bare file name (it
+    lies beside the .mtl)."""
+    with open(fname, "w") as fh:
+        fh.write("newmtl tex\nKa 1 1 1\nKd 1 1 1\nmap_Kd %s\n" % os.path.basename(png_name))
+
+
+_WARNED_NO_PIL = []
+
+
+def dump_textured_meshes(opt, idx, name, meshes, folder="dump"):
+    """meshes: per sample an eval_3D.TexturedMesh -> {idx}_{name}.obj, {idx}_{name}.mtl, {idx}_{name}.png (the colour atlas, the MTL's
+    map_Kd) and {idx}_{name}_normal.png (the object-space normal atlas).  An empty mesh writes an OBJ without faces and its grey atlases.
+    Without PIL there is no texture to point at: nothing is written, with one warning per process."""
+    if Image is None:
+        if not _WARNED_NO_PIL:
+            _WARNED_NO_PIL.append(True)
+            print("warning: PIL is not importable -- the textured OBJ dump ({idx}_%s.*) is skipped" % name)
+        return
+    for i, mesh in zip(idx, meshes):
+        base = "{}/{}/{}_{}".format(opt.output_path, folder, int(i), name)
+        write_obj_textured(base + ".obj", mesh.vertices, mesh.faces, mesh.uv, base + ".mtl")
+        write_mtl(base + ".mtl", base + ".png")
+        Image.fromarray(_numpy(mesh.atlas)).save(base + ".png")
+        Image.fromarray(_numpy(mesh.normal_atlas)).save(base + "_normal.png")
