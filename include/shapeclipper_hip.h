@@ -320,7 +320,20 @@ int sc_loss_fused_forward(const float* rgb, const float* rgb_t, const float* mas
  * w_f32: fp32 vectors in this order: class_embedding [D], position_embedding [T][D], ln_pre gamma, beta;
  *   per layer ln_1 gamma, beta, qkv bias [3D], out_proj bias, ln_2 gamma, beta, fc1 bias [mlp], fc2 bias;
  *   then ln_post gamma, beta.
- * workspace: >= sc_clip_vit_workspace_bytes(...) bytes of device memory.                               */
+ * workspace: >= sc_clip_vit_workspace_bytes(...) bytes of device memory.  It begins with the patch matrix [B*(T-1)][Kp] (16 bit), the
+ *   patch embeddings [B*(T-1)][D] fp32 and the residual stream x [B*T][D] fp32 (after the call: the last layer's output; layers == 0:
+ *   ln_pre's), each rounded up to 256 bytes.
+ * Token-count branches of the attention stage (one workgroup per image and head; Tp = T rounded up to 32):
+ *   T <= 32 or T > 64   attention_kernel: V^T [64][Tp + 4] in LDS, two passes over the keys in chunks of 32, a masked last chunk
+ *                       when T % 32 != 0; query blocks of 32 go round-robin over eight waves;
+ *   32 < T <= 64        attention_small_kernel: both key chunks in registers, one pass;
+ *   272 Tp + 512 <= 160 KiB (T <= 576)   K is staged in LDS beside V^T; above (T = 577: ViT-L/14 at 336 x 336) both passes read K
+ *                       from global memory;
+ *   K in LDS, more than 8 query blocks and (number of query blocks) % 8 == 1 (T = 257..288, 513..544)   the last query block is
+ *                       split over the KEYS: the eight waves' partial (max, sum, O) are merged in wave order through LDS;
+ *   128 (Tp + 4) > 160 KiB (T > 1248)   refused (hipErrorInvalidValue).
+ * LayerNorm: D % 256 == 0 and D <= 1024 with stride % 4 == 0 keeps the row in registers; any other D re-reads the row.  Both take
+ * the mean first and then the centred squares (fp32).                                                   */
 long long sc_clip_vit_workspace_bytes(int B, int C, int H, int W, int patch, int D, int mlp);
 int sc_clip_vit_forward(const float* image, int B, int C, int H, int W, int patch, int D, int mlp, int layers,
                         int heads, int proj_dim, const uint16_t* w_bf16, const float* w_f32, float ln_eps,
@@ -338,6 +351,16 @@ int sc_clip_vit_forward_f16(const float* image, int B, int C, int H, int W, int 
                             float* out, void* workspace, long long workspace_bytes, void* stream);
 int sc_gemm_f16(int epi, const uint16_t* A, const uint16_t* Wt, const float* bias, void* out, int M, int N, int K, void* stream);
 int sc_f32_to_f16(const float* x, uint16_t* y, long long n, void* stream);
+/* Two stages of the tower on their own (for tests: the tower launches them through the same code).
+ * sc_clip_attention: qkv [B*T][3D] 16-bit values (q | k | v; fp16 != 0: IEEE fp16 bit patterns, else bf16), head dim 64 ->
+ *   out [B*T][D] = softmax(0.125 q k^T) v per image and head, same 16-bit type.  hipErrorInvalidValue where the tower refuses:
+ *   D % 64 != 0, D / heads != 64, a V^T tile over 160 KiB (branches: above).
+ * sc_clip_layernorm: rows of D floats, `stride` floats apart (ln_post: stride = T*D reads the class token of every image) ->
+ *   out [rows][D] = (x - mean) / sqrt(var + eps) * gamma + beta as fp32 (out16 == 0; out may be x when stride == D, as ln_pre does),
+ *   bf16 (1) or fp16 (2).                                                                              */
+int sc_clip_attention(const uint16_t* qkv, uint16_t* out, int B, int T, int D, int heads, int fp16, void* stream);
+int sc_clip_layernorm(const float* x, int stride, const float* gamma, const float* beta, void* out,
+                      int rows, int D, float eps, int out16 /*0: fp32, 1: bf16, 2: fp16*/, void* stream);
 /* Small-batch form of the ViT-B layers (csrc/clip_cluster.hpp; same call site, CLIP_anno.py:166-167, at the batch the annotator
  * uses): all transformer layers in ONE launch, an image per cluster of 8 CUs of one XCD, four bounded cluster barriers per layer, no
  * chip-wide synchronisation.  It reads the layer matrices from a RE-PACKED image (same values, the order its waves consume them in: every

@@ -20,6 +20,8 @@
 //   layernorm       fp32 row -> bf16 (GEMM input) or fp32, one wave per token
 //   embed           [cls; patch tokens] + positional embedding -> fp32 residual stream
 //   attention       MFMA: one workgroup per (image, head), K/Q operands straight from global, V^T in LDS, any token count
+// The attention and LayerNorm launches are made by launch_attention / launch_layernorm, which sc_clip_attention / sc_clip_layernorm
+// export: tests/test_gpu_clip_stages.py compares each stage with float64 on every branch of the launch rule (attention_plan).
 // Bound: the four GEMMs per layer -> bf16 MFMA (dense peak 2.5 PFLOP/s).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -626,7 +628,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_persist_kernel(const bf16_t*
 }
 
 // ---------------------------------------------------------------------------------------------------
-// LayerNorm over D (multiple of 64, <= 1024 here) per row; x rows are `stride` floats apart.
+// LayerNorm over D per row (one wave per row); x rows are `stride` floats apart, out rows D.  Two paths, both with the two-pass variance.
 template <bool OUT_BF16, bool H16>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int stride, const float* __restrict__ g,
                                                         const float* __restrict__ b, void* __restrict__ out, int rows, int D,
@@ -671,12 +673,15 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
             }
         return;
     }
+    // any other D: the same two-pass variance, the row re-read from cache (the one-pass ss / D - mean^2 cancels on a row whose mean is
+    // large against its spread: mean 1e3, sigma 1 left an absolute error of ~0.06 on a variance of 1)
     float s = 0.f, ss = 0.f;
-    for (int d = lane; d < D; d += 64) { const float v = xr[d]; s += v; ss += v * v; }
-    for (int o = 32; o >= 1; o >>= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }
+    for (int d = lane; d < D; d += 64) s += xr[d];
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
     const float mean = s / D;
-    const float var = fmaxf(ss / D - mean * mean, 0.f);
-    const float inv = rsqrtf(var + eps);
+    for (int d = lane; d < D; d += 64) { const float v = xr[d] - mean; ss += v * v; }
+    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
+    const float inv = rsqrtf(ss / D + eps);
     for (int d = lane; d < D; d += 64) {
         const float v = (xr[d] - mean) * inv * g[d] + b[d];
         if (OUT_BF16) reinterpret_cast<bf16_t*>(out)[(size_t)row * D + d] = cvt16<H16>(v);
@@ -935,6 +940,9 @@ __global__ __launch_bounds__(64 * ATT_NW) void attention_kernel(const bf16_t* __
 // -- one per 32-query block; the four-wave kernel above left two of them idle here -- request Q and ALL K fragments in one round
 // trip, keep both score tiles in registers, take the softmax statistics from them and feed P straight into P V: one pass, 8 + 8 MFMAs per
 // wave.  (The general kernel recomputes S in its second pass and re-reads K from global memory: 45 us per layer at batch 256.)
+// As in attention_kernel, P goes into the MFMA as p = exp(s - max) in (0, 1] and O is divided by the fp32 sum at the end: rounding
+// p / sum to 16 bits instead put the SAME relative rounding error on every key of a flat row (uniform attention over 50 keys came out
+// scaled by fl16(1/50) * 50: 2e-4 in fp16, 1e-3 in bf16, on top of the output's own rounding).
 template <bool H16>
 __global__ __launch_bounds__(128) void attention_small_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, int T, int D,
                                                               int heads, float scale) {
@@ -1005,7 +1013,7 @@ __global__ __launch_bounds__(128) void attention_small_kernel(const bf16_t* __re
         for (int j = 0; j < 2; ++j) {
             bf16_t tmp[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) tmp[e] = cvt16<H16>(v[c][8 * j + e] * inv);
+            for (int e = 0; e < 8; ++e) tmp[e] = cvt16<H16>(v[c][8 * j + e]);
             const bf16x8 pf = __builtin_bit_cast(bf16x8, tmp);
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
@@ -1021,8 +1029,8 @@ __global__ __launch_bounds__(128) void attention_small_kernel(const bf16_t* __re
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
-                const uint32_t lo = (uint32_t)cvt16<H16>(O[t][4 * r4]) | ((uint32_t)cvt16<H16>(O[t][4 * r4 + 1]) << 16);
-                const uint32_t hi = (uint32_t)cvt16<H16>(O[t][4 * r4 + 2]) | ((uint32_t)cvt16<H16>(O[t][4 * r4 + 3]) << 16);
+                const uint32_t lo = (uint32_t)cvt16<H16>(O[t][4 * r4] * inv) | ((uint32_t)cvt16<H16>(O[t][4 * r4 + 1] * inv) << 16);
+                const uint32_t hi = (uint32_t)cvt16<H16>(O[t][4 * r4 + 2] * inv) | ((uint32_t)cvt16<H16>(O[t][4 * r4 + 3] * inv) << 16);
                 *reinterpret_cast<uint2*>(orow + 32 * t + 8 * r4) = make_uint2(lo, hi);
             }
     }
@@ -1202,6 +1210,48 @@ static int launch_gemm(int epi, const bf16_t* A, const bf16_t* Wt, const float* 
     return (int)hipGetLastError();
 }
 
+// The attention launch decision for T tokens per image (head dim 64), in one place for the tower and for sc_clip_attention:
+//   Tp = T rounded up to 32; V^T [64][Tp + 4] must fit the 160 KiB of LDS (else the geometry is refused);
+//   K [Tp][72] is staged beside it when both fit (k_lds: T <= 576), else attention_kernel reads K from global memory in both passes;
+//   32 < T <= 64 takes attention_small_kernel (static LDS), every other T attention_kernel with `lds` bytes of dynamic LDS.
+struct AttentionPlan { int small, k_lds, lds; };
+static bool attention_plan(int T, AttentionPlan& p) {
+    if (T <= 0) return false;
+    const int Tp32 = (T + 31) & ~31, att_v = 64 * (Tp32 + 4) * (int)sizeof(bf16_t), att_k = Tp32 * ATT_KLD * (int)sizeof(bf16_t);
+    if (att_v > 160 * 1024) return false;
+    p.k_lds = att_v + att_k <= 160 * 1024 ? 1 : 0;          // T = 257 (ViT-L/14 at 224 x 224): 77 KB, two workgroups per CU
+    p.lds = att_v + (p.k_lds ? att_k : 0);
+    p.small = T <= 64 && T > 32;
+    return true;
+}
+
+// out[B*T][D] = softmax(0.125 q k^T) v per (image, head); qkv [B*T][3D] = q | k | v
+template <bool H16>
+static int launch_attention(const bf16_t* qkv, bf16_t* out, int B, int T, int D, int heads, hipStream_t st) {
+    AttentionPlan p;
+    if (B <= 0 || heads <= 0 || D % 64 || D / heads != 64 || !attention_plan(T, p)) return (int)hipErrorInvalidValue;
+    if (p.small) {
+        hipLaunchKernelGGL(attention_small_kernel<H16>, dim3(B * heads), dim3(128), 0, st, qkv, out, T, D, heads, 0.125f);
+    } else {
+        if (p.lds > 48 * 1024)
+            hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<H16>), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
+        hipLaunchKernelGGL(attention_kernel<H16>, dim3(B * heads), dim3(64 * ATT_NW), p.lds, st, qkv, out, T, D, heads, 0.125f, p.k_lds);
+    }
+    return (int)hipGetLastError();
+}
+
+// LayerNorm of `rows` rows of D floats, `stride` floats apart; out rows are D apart: fp32 (out16 == 0; may be x itself when
+// stride == D), bf16 (1) or fp16 (2).  One wave per row.
+static int launch_layernorm(const float* x, int stride, const float* g, const float* b, void* out, int rows, int D, float eps, int out16,
+                            hipStream_t st) {
+    if (rows <= 0 || D <= 0 || stride < D || out16 < 0 || out16 > 2) return (int)hipErrorInvalidValue;
+    const dim3 grid((rows + 3) / 4), block(256);
+    if (out16 == 0) hipLaunchKernelGGL((layernorm_kernel<false, false>), grid, block, 0, st, x, stride, g, b, out, rows, D, eps);
+    else if (out16 == 1) hipLaunchKernelGGL((layernorm_kernel<true, false>), grid, block, 0, st, x, stride, g, b, out, rows, D, eps);
+    else hipLaunchKernelGGL((layernorm_kernel<true, true>), grid, block, 0, st, x, stride, g, b, out, rows, D, eps);
+    return (int)hipGetLastError();
+}
+
 // batch range of the cluster form (sc_clip_cluster_set_batch_range; environment SC_CLIP_CLUSTER_MIN_B / _MAX_B at load time)
 static std::atomic<int> g_cluster_min_b{[] { const char* e = getenv("SC_CLIP_CLUSTER_MIN_B"); return e ? atoi(e) : 26; }()};
 static std::atomic<int> g_cluster_max_b{[] { const char* e = getenv("SC_CLIP_CLUSTER_MAX_B"); return e ? atoi(e) : 32; }()};
@@ -1240,16 +1290,13 @@ static int clip_vit_forward(const float* image, int B, int C, int H, int W, int 
 
     if ((long long)B * np * (Kp / 8) >= (1LL << 31)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(patchify_kernel<H16>, dim3(4096), dim3(256), 0, st, image, a_patch, B, C, H, W, patch, Kp);
-    const int Tp32 = (T + 31) & ~31, att_v = 64 * (Tp32 + 4) * (int)sizeof(bf16_t), att_k = Tp32 * ATT_KLD * (int)sizeof(bf16_t);
-    if (att_v > 160 * 1024) return (int)hipErrorInvalidValue;
-    const int k_lds = att_v + att_k <= 160 * 1024 ? 1 : 0;          // T = 257 (ViT-L/14 at 224 x 224): 77 KB, two workgroups per CU
-    const int att_lds = att_v + (k_lds ? att_k : 0);
-    if (att_lds > 48 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<H16>), hipFuncAttributeMaxDynamicSharedMemorySize, att_lds);
+    AttentionPlan att_plan;
+    if (!attention_plan(T, att_plan)) return (int)hipErrorInvalidValue;          // a V tile over the LDS: refused before the layers
+    const int ln16 = H16 ? 2 : 1;
     int rc = launch_gemm<H16>(EPI_F32, a_patch, w_patch, nullptr, patch_out, B * np, D, Kp, st);
     if (rc) return rc;
     hipLaunchKernelGGL(embed_kernel, dim3(1024), dim3(256), 0, st, patch_out, cls, pos, x, B, T, D);
-    hipLaunchKernelGGL((layernorm_kernel<false, H16>), dim3((M + 3) / 4), dim3(256), 0, st, x, D, lnpre_g, lnpre_b, (void*)x, M, D, ln_eps);
+    if ((rc = launch_layernorm(x, D, lnpre_g, lnpre_b, (void*)x, M, D, ln_eps, 0, st))) return rc;
     // One batch range of the ViT-B geometry runs all its layers in one launch, an image per cluster of 8 CUs (clip_cluster.hpp).  Measured
     // (profiles/r05_clip_cluster_ab.txt): below ~26 images the launch-per-operation form is faster (its GEMMs are small), above 32 the
     // cluster form needs a second round of the chip.
@@ -1279,12 +1326,11 @@ static int clip_vit_forward(const float* image, int B, int C, int H, int W, int 
         const float* ln2_b = wf; wf += D;
         const float* b_fc1 = wf; wf += mlp;
         const float* b_fc2 = wf; wf += D;
-        hipLaunchKernelGGL((layernorm_kernel<true, H16>), dim3((M + 3) / 4), dim3(256), 0, st, x, D, ln1_g, ln1_b, (void*)xn, M, D, ln_eps);
+        if ((rc = launch_layernorm(x, D, ln1_g, ln1_b, (void*)xn, M, D, ln_eps, ln16, st))) return rc;
         if ((rc = launch_gemm<H16>(EPI_BF16, xn, w_qkv, b_qkv, qkv, M, 3 * D, D, st))) return rc;
-        if (T <= 64 && T > 32) hipLaunchKernelGGL(attention_small_kernel<H16>, dim3(B * heads), dim3(128), 0, st, qkv, att, T, D, heads, 0.125f);
-        else hipLaunchKernelGGL(attention_kernel<H16>, dim3(B * heads), dim3(64 * ATT_NW), att_lds, st, qkv, att, T, D, heads, 0.125f, k_lds);
+        if ((rc = launch_attention<H16>(qkv, att, B, T, D, heads, st))) return rc;
         if ((rc = launch_gemm<H16>(EPI_RESID, att, w_o, b_o, x, M, D, D, st))) return rc;
-        hipLaunchKernelGGL((layernorm_kernel<true, H16>), dim3((M + 3) / 4), dim3(256), 0, st, x, D, ln2_g, ln2_b, (void*)xn, M, D, ln_eps);
+        if ((rc = launch_layernorm(x, D, ln2_g, ln2_b, (void*)xn, M, D, ln_eps, ln16, st))) return rc;
         if ((rc = launch_gemm<H16>(EPI_GELU_BF16, xn, w_fc1, b_fc1, hbuf, M, mlp, D, st))) return rc;
         if ((rc = launch_gemm<H16>(EPI_RESID, hbuf, w_fc2, b_fc2, x, M, D, mlp, st))) return rc;
     }
@@ -1292,7 +1338,7 @@ static int clip_vit_forward(const float* image, int B, int C, int H, int W, int 
     const float* lnpost_g = wf; wf += D;
     const float* lnpost_b = wf; wf += D;
     // ln_post on the class token of every image (row stride T*D), then the projection (no bias)
-    hipLaunchKernelGGL((layernorm_kernel<true, H16>), dim3((B + 3) / 4), dim3(256), 0, st, x, T * D, lnpost_g, lnpost_b, (void*)pooled, B, D, ln_eps);
+    if ((rc = launch_layernorm(x, T * D, lnpost_g, lnpost_b, (void*)pooled, B, D, ln_eps, ln16, st))) return rc;
     return launch_gemm<H16>(EPI_F32, pooled, w_proj, nullptr, out, B, proj_dim, D, st);
 }
 
@@ -1324,6 +1370,17 @@ int sc_gemm_bf16(int epi, const uint16_t* A, const uint16_t* Wt, const float* bi
 // The same GEMM with IEEE fp16 operands (A, Wt and the 16-bit outputs of epilogues 2 / 3 are fp16 bit patterns)
 int sc_gemm_f16(int epi, const uint16_t* A, const uint16_t* Wt, const float* bias, void* out, int M, int N, int K, void* stream_) {
     return sc::launch_gemm<true>(epi, A, Wt, bias, out, M, N, K, (hipStream_t)stream_);
+}
+
+// One attention stage of the tower on its own (exported for tests): exactly the launch the tower makes per layer.
+int sc_clip_attention(const uint16_t* qkv, uint16_t* out, int B, int T, int D, int heads, int fp16, void* stream_) {
+    if (fp16) return sc::launch_attention<true>(qkv, out, B, T, D, heads, (hipStream_t)stream_);
+    return sc::launch_attention<false>(qkv, out, B, T, D, heads, (hipStream_t)stream_);
+}
+// One LayerNorm of the tower on its own (exported for tests): exactly the launch the tower makes for ln_pre / ln_1 / ln_2 / ln_post.
+int sc_clip_layernorm(const float* x, int stride, const float* gamma, const float* beta, void* out, int rows, int D, float eps, int out16,
+                      void* stream_) {
+    return sc::launch_layernorm(x, stride, gamma, beta, out, rows, D, eps, out16, (hipStream_t)stream_);
 }
 
 #if SC_CL_PROF

@@ -51,6 +51,9 @@ def _check(got, ref, dtype, what):
     (128, 2, 2, 256, 14, 112, 64, 2),            # 65 tokens (> one key chunk... and 2 query blocks + 1), patch K = 588 (padded)
     (192, 2, 3, 384, 8, 112, 96, 2),             # 197 tokens: 7 key chunks, query blocks wrap over the 4 waves
     (1024, 2, 16, 4096, 14, 224, 768, 2),        # ViT-L/14 geometry (257 tokens), 2 layers
+    (128, 2, 2, 256, 13, 221, 64, 2),            # 290 tokens: ten query blocks, no key split (a wave walks two query blocks); K = 507 (padded)
+    (128, 2, 2, 256, 16, 368, 64, 2),            # 530 tokens: key split with 18 left-over queries, three key chunks for wave 0
+    (128, 2, 2, 256, 14, 336, 64, 2),            # 577 tokens (ViT-L/14@336px): K no longer fits LDS, read from global memory in both passes
 ])
 def test_clip_tower_vs_transformers(width, layers, heads, mlp, patch, image, proj, B, dtype):
     from shapeclipper_amd.model.clip_vit import ClipVisionTower
@@ -262,6 +265,35 @@ def test_clip_cluster_form_vs_transformers_and_launch_form(B, dtype, cluster_ran
     assert not torch.equal(got_c, got_l), "both calls ran the same form: the batch range did not take effect"
     cos = torch.nn.functional.cosine_similarity(got_c, got_l, dim=-1).min().item()
     print("cluster form vs launch form, %s, B=%d: min cosine %.8f, max |diff| %.2e" % (dtype, B, cos, (got_c - got_l).abs().max().item()))
+    assert cos > (0.999999 if dtype == "fp16" else 0.9999)
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+@pytest.mark.parametrize("image", [160, 192])            # 26 tokens (one key chunk, masked) and 37 (two chunks): ViT-B/32 runs 50
+def test_clip_cluster_form_vs_launch_form_at_other_token_counts(image, dtype, cluster_range):
+    """The cluster form at token counts other than ViT-B/32's 50, B = 2 with the batch range opened: both forms against the fp32
+    architecture oracle at the tower's bars and against each other at the bars of the test above."""
+    from shapeclipper_amd.model.clip_vit import ClipVisionTower, VIT_B32
+    c = dict(VIT_B32, image_size=image)
+    hf = _hf(c["width"], c["layers"], c["heads"], c["mlp"], c["patch"], image, c["proj"], seed=image)
+    x = torch.randn(2, 3, image, image)
+    with torch.no_grad():
+        ref = hf(pixel_values=x).image_embeds
+    tower = ClipVisionTower(**c, dtype=dtype)
+    tower.load_state_dict(hf.state_dict())
+    tower = tower.cuda()
+    cluster_range(1, 64)
+    got_c = tower.encode_image(x.cuda()).cpu()
+    again = tower.encode_image(x.cuda()).cpu()
+    cluster_range(1, 0)                                   # never
+    got_l = tower.encode_image(x.cuda()).cpu()
+    T = (image // 32) ** 2 + 1
+    _check(got_c, ref, dtype, "ViT-B width, %d tokens, cluster form" % T)
+    _check(got_l, ref, dtype, "ViT-B width, %d tokens, launch form" % T)
+    assert torch.equal(got_c, again)
+    assert not torch.equal(got_c, got_l), "both calls ran the same form: the batch range did not take effect"
+    cos = torch.nn.functional.cosine_similarity(got_c, got_l, dim=-1).min().item()
+    print("cluster form vs launch form, %s, %d tokens: min cosine %.8f, max |diff| %.2e" % (dtype, T, cos, (got_c - got_l).abs().max().item()))
     assert cos > (0.999999 if dtype == "fp16" else 0.9999)
 
 
