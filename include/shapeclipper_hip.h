@@ -1257,6 +1257,62 @@ int sc_texture_sample(const void* atlas_data, int is_u8, const float* uv, const 
                       int n_images, int atlas, int channels, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Triangle rasteriser (csrc/mesh_raster.hip): the indexed marching-cubes mesh seen from n_views cameras per image -- nearest face,
+ * camera depth and perspective-correct barycentrics at every pixel centre (eval_3D.mesh_render, `--eval.mesh_render`).  Float
+ * arithmetic is fp32, every operation rounded once (no contraction), division correctly rounded; coverage is exact integer arithmetic.
+ * tests/mesh_raster_ref.py restates every line below in numpy.
+ *
+ * Inputs: verts [n_verts][3] fp32 in world units; faces [n_faces][3] int32, vertex numbers local to their image; v_start, f_start,
+ * f_count [n_images] int64 on the device as for sc_texture_queries: image b's faces are faces[f_start[b] .. f_start[b] + f_count[b]),
+ * its vertices are verts[v_start[b] .. v_end), v_end = v_start[b + 1] (n_verts for the last image), v_start non-decreasing.  A vertex
+ * number is clamped into the image's range [0, v_end - v_start[b]) (and no access leaves verts); the caller keeps f_start + f_count <=
+ * n_faces and the images' face ranges disjoint.  pose [n_images][n_views][3][4] world-to-camera, rows (r00 r01 r02 t0), ...: the
+ * convention of camera.world2cam; intr [n_images][3][3], of which k00, k02, k11, k12 are read -- the skew k01 and k22 are not.
+ *
+ * Per vertex (x, y, z) and view, once:
+ *   xc = ((r00 x + r01 y) + r02 z) + t0,  yc and zc likewise with rows 1 and 2;
+ *   sx = (k00 * xc) / zc + k02,  sy = (k11 * yc) / zc + k12     (x to the right, y downward; pixel (i, j), column i and row j, has
+ *        its centre at (i + 0.5, j + 0.5): camera.pixel_centers);
+ *   X = (long long)rintf(sx * 256.0f),  Y = (long long)rintf(sy * 256.0f): the 1/256-pixel lattice, ties to even; a pixel centre is
+ *        (256 i + 128, 256 j + 128).
+ *   The vertex is `near` when zc < near (a NaN is not), else `out of range` when zc, sx * 256 or sy * 256 is not finite or |X| or
+ *   |Y| >= 2^28.
+ * Per face and view: dropped whole -- there is no clipping -- and counted in stats[1] when one of its vertices is near, else in
+ * stats[2] when one is out of range.  With a, b, c its vertices on the lattice
+ *   area = (bx - ax)(cy - ay) - (by - ay)(cx - ax)   in int64 (every edge function here is below 2^60);
+ *   area == 0: dropped, stats[3];  area < 0: b and c swap, with their depths and barycentric slots, and area = -area (two-sided
+ *   rendering); every other face is drawn, stats[0], whether or not it covers a pixel.
+ *   For each edge p -> q of the oriented triangle (a -> b, b -> c, c -> a), d = q - p and a pixel centre P:
+ *        E = dx (Py - py) - dy (Px - px)   in int64;  the edge holds P iff E > 0, or E == 0 and (dy < 0, or dy == 0 and dx > 0)
+ *   (the top-left rule: a centre on an edge shared by two faces, or on a vertex shared by a fan, belongs to exactly one of them);
+ *   the face covers P iff all three edges hold it.  Only centres inside the bounding box of the three lattice points and inside the
+ *   image are looked at.
+ *   With E_k the edge function opposite oriented vertex k (E_0 of b -> c, E_1 of c -> a, E_2 of a -> b; E_0 + E_1 + E_2 = area):
+ *        b_k = (float)E_k / (float)area;  q_k = b_k / z_k;  s = (q_0 + q_1) + q_2  (oriented order);  depth = 1.0f / s;
+ *        bary_k = q_k / s, stored in the slot of the face's own vertex (slots 1 and 2 swap back when b and c were swapped).
+ * Visibility: the pixel goes to the smallest (bits(depth) << 32) | face, a 64-bit integer atomicMin (depth > 0, so bit order is value
+ * order): the nearest face, on an exact tie the lowest face index.  A resolve pass, one thread per pixel, computes depth and bary
+ * of the winning face again and writes the outputs; there are no float atomics and the outputs are the same bits from run to run.
+ *
+ * Two coverage paths that agree bit for bit (one device function evaluates a pixel for both): a face whose clamped box holds at
+ * most large_pixels pixel centres is walked by its own thread; a larger one goes onto its (image, view)'s list through an integer
+ * atomic cursor and is walked by one wave, lanes striding over the box.  large_pixels <= 0: every face by a wave.
+ *
+ * Outputs, [n_images][n_views][height][width] row-major: face int32 (local face number, -1 where no face covers the centre), depth
+ * fp32 (camera z, 0 on a miss), bary [..][3] fp32 (0 on a miss); stats [n_images][n_views][4] int32 = faces drawn, culled by near,
+ * culled by range or not finite, of zero area.  Every element is written.  scratch: sc_mesh_raster_scratch_bytes(...) bytes,
+ * 16-byte aligned (keys, projected vertices [n_views][n_verts] of 16 B, lists, cursors); the query returns -1 for sizes the call
+ * refuses.  Three memsets and four launches on the caller's stream, plain vector stores, no host synchronisation.
+ * n_images, n_verts or n_faces <= 0 returns 0 and launches nothing (the outputs are not written); hipErrorInvalidValue for height or
+ * width outside 1..4096, n_views outside 1..65535, near <= 0 (or NaN), more than 65535 images, more than 2^31 vertices or faces, more
+ * than 2^40 output pixels, a NULL pointer or a misaligned scratch.                                                              */
+long long sc_mesh_raster_scratch_bytes(int n_images, int n_views, long long n_verts, long long n_faces, int height, int width);
+int sc_mesh_raster(const float* verts, const int32_t* faces, const long long* v_start, const long long* f_start,
+                   const long long* f_count, const float* pose, const float* intr, int n_images, long long n_verts, long long n_faces,
+                   int n_views, int height, int width, float near, long long large_pixels, int32_t* face, float* depth, float* bary,
+                   int32_t* stats, void* scratch, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Launch policy (csrc/device.hip) -- the one process-level setting of the library. The persistent one-workgroup-per-CU grids
  * (stream-K 3x3 convolutions and their weight gradients, stem / 1x1 / stride-2 gradients) are sized for
  * sc_grid_cus() = device CUs - reserved.  Reserve CUs when another stream must make progress beside them: RCCL's

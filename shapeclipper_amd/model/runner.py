@@ -117,6 +117,24 @@ def _write_texture(opt, rec, mode="w"):
             f.write(TEXTURE_LINE % (int(r[0]), int(r[1]), int(r[2]), int(r[3]), float(r[4]), float(r[5])))
 
 
+MESH_RENDER_LINE = "%d %d %d %.6f %.6f\n"   # a line of mesh_render.txt: idx faces pixels iou_input iou_volume
+
+
+def _mesh_render_records(var):
+    """[B,5] float64 on the host, a record per sample of eval_3D.mesh_render_sample (var.mesh_render, left by dump_geometry with
+    --eval.mesh_render): idx, faces, pixels, iou_input, iou_volume (nan where the map to compare with is missing)."""
+    m = var.mesh_render
+    cols = [var.idx.double().view(-1).cpu(), torch.tensor(m.faces, dtype=torch.float64), torch.tensor(m.pixels, dtype=torch.float64),
+            m.iou_input.double().view(-1).cpu(), m.iou_volume.double().view(-1).cpu()]
+    return torch.stack(cols, dim=1)
+
+
+def _write_mesh_render(opt, rec, mode="w"):
+    with open("{}/mesh_render.txt".format(opt.output_path), mode) as f:
+        for r in rec:
+            f.write(MESH_RENDER_LINE % (int(r[0]), int(r[1]), int(r[2]), float(r[3]), float(r[4])))
+
+
 class Runner:
 
     def __init__(self, opt):
@@ -508,7 +526,7 @@ class Runner:
         rank r takes the test samples with index % world == r (eval.batch_size = 1), per-sample records are
         gathered once, rank 0 writes chamfer.txt / cd_cat.txt / f_score.txt in sample order (with --hip.largest_component also
         components.txt, from a second gather of the per-sample counts; with --eval.texture also texture.txt, from one more gather of
-        the bake's per-sample records; with --eval.icp also chamfer_icp.txt / cd_cat_icp.txt /
+        the bake's per-sample records; with --eval.mesh_render also mesh_render.txt, likewise; with --eval.icp also chamfer_icp.txt / cd_cat_icp.txt /
         f_score_icp.txt / icp.txt, from one more gather of the ICP-aligned records; with --eval.normals also normal_consistency.txt /
         nc_cat.txt and their _icp namesakes, from one more gather again; with --eval.mesh_dist also completeness_mesh.txt /
         cd_cat_mesh.txt / f_score_mesh.txt and, with --eval.dual_mesh, their _dual namesakes, from one more gather; with --eval.emd
@@ -521,7 +539,7 @@ class Runner:
         # the reference's single-node convention is rank == device index; the process group's rank is the same number there and stays
         # right when ranks and devices are numbered differently (several nodes; tests/test_gpu_two_ranks.py: two ranks on one GPU)
         rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else util.get_rank(opt)
-        recs, comps, icps, ncs, meshes, emds, texs = [], [], [], [], [], [], []
+        recs, comps, icps, ncs, meshes, emds, texs, mrs = [], [], [], [], [], [], [], []
         for it in range(rank, len(self.test_data), opt.world_size):
             sample = self.test_data[it]
             batch = {k: ({kk: vv[None] for kk, vv in v.items()} if isinstance(v, dict) else torch.as_tensor(v)[None]) for k, v in sample.items()}
@@ -541,8 +559,10 @@ class Runner:
                 meshes.append(_mesh_records(var))
             if "emd" in var:                            # --eval.emd: _emd_records' columns
                 emds.append(_emd_records(var))
-            if "texture" in var:                        # --eval.texture: _texture_records' columns (dump_geometry baked the atlas)
+            if "texture" in var and options.texture_texels(opt) is not None:    # --eval.texture: _texture_records' columns (dump_geometry baked the atlas)
                 texs.append(_texture_records(var))
+            if "mesh_render" in var:                    # --eval.mesh_render: _mesh_render_records' columns (dump_geometry rendered)
+                mrs.append(_mesh_render_records(var))
         dev = next(self.graph.parameters()).device
         records = torch.stack(recs) if recs else torch.zeros(0, 10, device=dev)
         allr = gather_eval_records(records.to(dev), opt.world_size).cpu()
@@ -574,7 +594,13 @@ class Runner:
         if options.texture_texels(opt) is not None and util_vis is not None:      # likewise
             allt = gather_eval_records(torch.cat(texs).to(dev) if texs else torch.zeros(0, 6, device=dev, dtype=torch.float64),
                                        opt.world_size).cpu()
+        allmr = None
+        if options.mesh_render(opt) and util_vis is not None:                     # likewise
+            allmr = gather_eval_records(torch.cat(mrs).to(dev) if mrs else torch.zeros(0, 5, device=dev, dtype=torch.float64),
+                                        opt.world_size).cpu()
         opt.H, opt.W = opt.image_size
+        if rank == 0 and allmr is not None:
+            _write_mesh_render(opt, allmr)
         if rank == 0 and allt is not None:
             _write_texture(opt, allt)
         if rank == 0 and alle is not None:
@@ -797,6 +823,8 @@ class Runner:
         self.dump_geometry(opt, var, folder)
         for name, frames in self.turntable_frames(opt, var).items():
             util_vis.dump_gifs(opt, var.idx, name, frames, folder=folder)
+        if options.mesh_render(opt) and "vis_pose" in var:
+            self.dump_mesh_turntable(opt, var, folder)
         if _surface_render(opt):
             self.dump_surface(opt, var, folder, rotate=True)
 
@@ -848,6 +876,18 @@ class Runner:
                 frames = ops.vis_frames(x.reshape(x.shape[0], B, H, W, 3), kind).transpose(0, 1)
                 util_vis.dump_gifs(opt, var.idx, name, frames, folder=folder)
 
+    def dump_mesh_turntable(self, opt, var, folder):
+        """{idx}_image_mesh_rotate.gif and {idx}_normal_mesh_rotate.gif of `--eval.mesh_render` in the vis_{ep}/ dump: the textured mesh from
+        every pose of var.vis_pose at the size of the per-sample pictures, all views through ONE ops.mesh_raster call
+        (eval_3D.mesh_render), frames by ops.vis_frames."""
+        from .. import ops
+        B = len(var.idx)
+        H, W = (int(s) for s in var.mesh_render.render.depth.shape[-2:])
+        pose = var.vis_pose[None].expand(B, -1, -1, -1)
+        views = eval_3D.mesh_render(opt, var.level_vox, var.texture, pose, var.intr, H, W)
+        for name, x in (("image_mesh_rotate", views.rgb), ("normal_mesh_rotate", views.normal)):
+            util_vis.dump_gifs(opt, var.idx, name, ops.vis_frames(x.contiguous(), "rgb"), folder=folder)
+
     def dump_geometry(self, opt, var, folder):
         """{idx}_mesh.ply (the predicted mesh) and {idx}_pointclouds_comp.ply (prediction red, ground truth green) of an evaluated batch;
         with --hip.mesh_color also {idx}_mesh_color.ply (the device mesh with vertex normals and the sample's predicted colours); with
@@ -857,7 +897,11 @@ class Runner:
         normals on the prediction, the estimated PCA normals on the ground truth); with --eval.emd also {idx}_pointclouds_emd.ply (the
         two n-point sub-samples eval_3D.emd_metrics matched, prediction red, ground truth green); with --eval.texture also
         {idx}_mesh_tex.obj / .mtl / .png and {idx}_mesh_tex_normal.png (eval_3D.mesh_texture: the device mesh with a per-triangle
-        texture atlas of the predicted colours, and the atlas of its normals; var.texture keeps the result for texture.txt).
+        texture atlas of the predicted colours, and the atlas of its normals; var.texture keeps the result for texture.txt); with
+        --eval.mesh_render also {idx}_image_mesh.png, {idx}_mask_mesh.png, {idx}_normal_mesh.png, {idx}_depth_mesh.png (the grey mapping
+        of Renderer.surface_depth_grey) and {idx}_depth_mesh.npy: that textured mesh rasterised from the sample's own camera at the size
+        of var.mask_input_map (eval_3D.mesh_render_sample; var.mesh_render keeps the result for mesh_render.txt; the texture is baked
+        for it when --eval.texture is off, and no OBJ is written then).
         --eval.mesh_dist adds no per-sample file."""
         if eval_3D.HAVE_MESHING:
             meshes = var.mesh_pred                      # trimesh meshes of the PyMCubes branch
@@ -879,6 +923,19 @@ class Runner:
             net = self.graph.module
             var.texture = eval_3D.mesh_texture(opt, net.sdf_network, net.rgb_network, var.proj_latent_sdf, var.proj_latent_rgb, var.level_vox)
             util_vis.dump_textured_meshes(opt, var.idx, "mesh_tex", var.texture, folder=folder)
+        if options.mesh_render(opt):
+            net = self.graph.module
+            if "texture" not in var:
+                var.texture = eval_3D.mesh_texture(opt, net.sdf_network, net.rgb_network, var.proj_latent_sdf, var.proj_latent_rgb, var.level_vox)
+            var.mesh_render = eval_3D.mesh_render_sample(opt, var, var.texture)
+            out = var.mesh_render.render
+            as_map = lambda x: x[:, 0].permute(0, 3, 1, 2) if x.dim() == 5 else x[:, 0, None]
+            dump = lambda name, images: util_vis.dump_images(opt, var.idx, name, images, folder=folder)
+            dump("image_mesh", as_map(out.rgb))
+            dump("mask_mesh", as_map(out.mask))
+            dump("normal_mesh", as_map(out.normal))
+            dump("depth_mesh", as_map(eval_3D.mesh_depth_grey(opt, out, var.intr, var.scale_dist)))
+            util_vis.dump_arrays(opt, var.idx, "depth_mesh", out.depth[:, 0], folder=folder)
         if "dpc" in var:
             util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_comp", var.dpc_pred, var.dpc.points, folder=folder)
             if "dpc_pred_icp" in var:                   # --eval.icp: the ICP-aligned prediction red, the ground truth green
@@ -901,8 +958,11 @@ class Runner:
                 with open("{}/components.txt".format(opt.output_path), "w" if write_new else "a") as f:
                     for row in zip(var.idx.tolist(), *(c.tolist() for c in _component_counts(var))):
                         f.write("{} {} {} {}\n".format(*row))
-            if "texture" in var:                        # --eval.texture: idx faces atlas rows err_mean err_max
+            # --eval.texture: idx faces atlas rows err_mean err_max (--eval.mesh_render alone bakes var.texture too and writes no texture.txt)
+            if "texture" in var and options.texture_texels(opt) is not None:
                 _write_texture(opt, _texture_records(var), "w" if write_new else "a")
+            if "mesh_render" in var:                    # --eval.mesh_render: idx faces pixels iou_input iou_volume
+                _write_mesh_render(opt, _mesh_render_records(var), "w" if write_new else "a")
             if "icp" in var:                            # --eval.icp: chamfer.txt's line of the aligned metrics; idx s angle_deg |t| objective first, last
                 with open("{}/chamfer_icp.txt".format(opt.output_path), "w" if write_new else "a") as f:
                     for i, acc, comp in zip(var.idx, var.cd_acc_icp, var.cd_comp_icp):

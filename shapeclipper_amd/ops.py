@@ -2120,3 +2120,76 @@ def texture_sample(atlas, uv, image_of_point):
                                              N, B, A, C, _lib.ptr(out), _lib.stream())
     _lib.check(code, "sc_texture_sample")
     return out
+
+
+# ---- evaluation: triangle rasteriser (csrc/mesh_raster.hip) -----------------------------------------------------------------------------
+RASTER_MAX_SIDE = 4096
+RASTER_MAX_VIEWS = 65535
+RASTER_LARGE_PIXELS = 64            # a face whose box holds more pixel centres is walked by a wave, not by its own thread
+MeshRaster = collections.namedtuple("MeshRaster", ["face", "depth", "bary", "stats"])
+
+
+def mesh_raster(verts, faces, v_start, f_start, f_count, pose, intr, H, W, near, large_pixels=RASTER_LARGE_PIXELS):
+    """The packed meshes of B images, each seen from n_views cameras: verts [V,3] fp32 in world units, faces [F,3] int32 (vertex numbers
+    local to their image), v_start / f_start / f_count sequences of B host integers as texture_queries takes them (image b's vertices
+    are verts[v_start[b]:v_start[b + 1]], the last image's run to V), pose [B, n_views, 3, 4] world-to-camera (camera.world2cam's
+    convention), intr [B, 3, 3] -> MeshRaster(face [B, n_views, H, W] int32 -- the image's face nearest to the camera at the pixel's
+    centre, -1 where none covers it --, depth [B, n_views, H, W] fp32 camera z (0 on a miss), bary [B, n_views, H, W, 3] fp32
+    perspective-correct barycentrics (0 on a miss), stats [B, n_views, 4] int32: faces drawn, culled by `near`, culled by range or not
+    finite, of zero area).  A face with a vertex nearer than `near` is dropped whole (no clipping); rendering is two-sided.
+    include/shapeclipper_hip.h states the arithmetic (sc_mesh_raster): integer coverage with the top-left rule on a 1/256-pixel
+    lattice, visibility by a 64-bit integer atomicMin, the same bits from run to run.  large_pixels chooses between the two coverage
+    paths, which agree bit for bit.  Scratch from the `_scratch` cache (tag "mesh_raster"); three memsets and four launches on the
+    current stream, no host synchronisation."""
+    who = "mesh_raster"
+    verts = _texture_tensor(who, "verts", verts, (torch.float32,))
+    dev = verts.device
+    faces = _texture_tensor(who, "faces", faces, (torch.int32,), dev)
+    pose = _texture_tensor(who, "pose", pose, (torch.float32,), dev)
+    intr = _texture_tensor(who, "intr", intr, (torch.float32,), dev)
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("shapeclipper_amd: mesh_raster takes verts [V,3] and faces [F,3], got %s and %s" % (tuple(verts.shape), tuple(faces.shape)))
+    v_start, f_start, f_count = ([int(v) for v in s] for s in (v_start, f_start, f_count))
+    B, V, F = len(f_count), verts.shape[0], faces.shape[0]
+    if len(v_start) != B or len(f_start) != B or B > TEXTURE_MAX_IMAGES:
+        raise ValueError("shapeclipper_amd: mesh_raster takes v_start, f_start and f_count of one length <= %d" % TEXTURE_MAX_IMAGES)
+    if pose.dim() != 4 or pose.shape[0] != B or tuple(pose.shape[2:]) != (3, 4) or not 1 <= pose.shape[1] <= RASTER_MAX_VIEWS:
+        raise ValueError("shapeclipper_amd: mesh_raster takes pose [B, n_views, 3, 4] with B = %d and 1 <= n_views <= %d, got %s"
+                         % (B, RASTER_MAX_VIEWS, tuple(pose.shape)))
+    if tuple(intr.shape) != (B, 3, 3):
+        raise ValueError("shapeclipper_amd: mesh_raster takes intr [B, 3, 3] with B = %d, got %s" % (B, tuple(intr.shape)))
+    for name, v in (("H", H), ("W", W)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= RASTER_MAX_SIDE:
+            raise ValueError("shapeclipper_amd: mesh_raster: %s must be an integer in 1..%d, got %r" % (name, RASTER_MAX_SIDE, v))
+    if isinstance(near, bool) or not isinstance(near, (int, float)) or not near > 0:
+        raise ValueError("shapeclipper_amd: mesh_raster: near must be a positive number, got %r" % (near,))
+    if isinstance(large_pixels, bool) or not isinstance(large_pixels, int) or large_pixels < 0:
+        raise ValueError("shapeclipper_amd: mesh_raster: large_pixels must be an integer >= 0, got %r" % (large_pixels,))
+    n_views = pose.shape[1]
+    for b in range(B):
+        v_end = v_start[b + 1] if b + 1 < B else V
+        if not 0 <= v_start[b] <= v_end <= V:
+            raise ValueError("shapeclipper_amd: mesh_raster: v_start must be non-decreasing within 0..%d, got %r" % (V, v_start))
+        if f_count[b] < 0 or f_start[b] < (f_start[b - 1] + f_count[b - 1] if b else 0) or f_start[b] + f_count[b] > F:
+            raise ValueError("shapeclipper_amd: mesh_raster: image %d's faces [%d, %d) overlap the image before or lie outside the %d "
+                             "faces given" % (b, f_start[b], f_start[b] + f_count[b], F))
+        if f_count[b] > 0 and v_end == v_start[b]:
+            raise ValueError("shapeclipper_amd: mesh_raster: image %d has %d faces and no vertex" % (b, f_count[b]))
+    lib = _lib.load()
+    n_bytes = lib.sc_mesh_raster_scratch_bytes(B, n_views, V, F, H, W)
+    if n_bytes < 0:
+        raise ValueError("shapeclipper_amd: mesh_raster: %d images x %d views of %d x %d pixels are more than one call takes" % (B, n_views, H, W))
+    if B == 0 or V == 0 or F == 0:          # nothing to draw: every pixel a miss
+        return MeshRaster(torch.full((B, n_views, H, W), -1, device=dev, dtype=torch.int32), torch.zeros(B, n_views, H, W, device=dev),
+                          torch.zeros(B, n_views, H, W, 3, device=dev), torch.zeros(B, n_views, 4, device=dev, dtype=torch.int32))
+    out = MeshRaster(torch.empty(B, n_views, H, W, device=dev, dtype=torch.int32), torch.empty(B, n_views, H, W, device=dev),
+                     torch.empty(B, n_views, H, W, 3, device=dev), torch.empty(B, n_views, 4, device=dev, dtype=torch.int32))
+    ws = _scratch("mesh_raster", dev, (n_bytes + 3) // 4)
+    starts = torch.tensor([v_start, f_start, f_count], dtype=torch.int64).to(dev)
+    with torch.cuda.device(dev):
+        code = lib.sc_mesh_raster(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(starts[0]), _lib.ptr(starts[1]), _lib.ptr(starts[2]),
+                                  _lib.ptr(pose), _lib.ptr(intr), B, V, F, n_views, H, W, float(near), int(large_pixels),
+                                  _lib.ptr(out.face), _lib.ptr(out.depth), _lib.ptr(out.bary), _lib.ptr(out.stats), _lib.ptr(ws),
+                                  _lib.stream())
+    _lib.check(code, "sc_mesh_raster")
+    return out

@@ -333,6 +333,115 @@ def mesh_texture(opt, sdf_network, rgb_network, proj_latent_sdf, proj_latent_rgb
     return out
 
 
+MESH_RENDER_NEAR = 0.05    # world units: a face with a vertex nearer to the camera plane is dropped (the cameras stand camera.dist ~ 5 away)
+MeshRender = collections.namedtuple("MeshRender", ["rgb", "mask", "normal", "depth", "face", "bary", "stats"])
+
+
+class MeshRenderSample:
+    """What mesh_render_sample leaves in var.mesh_render (a plain object: an EasyDict would turn a tuple into a list)."""
+
+    def __init__(self, render, faces, pixels, iou_input, iou_volume):
+        self.render, self.faces, self.pixels, self.iou_input, self.iou_volume = render, faces, pixels, iou_input, iou_volume
+
+
+@torch.no_grad()
+def mesh_render(opt, level_vox, textured, pose, intr, H, W, large_pixels=None):
+    """The textured mesh as an unlit viewer draws it: level_vox [B,S,S,S] (compute_level_grid), textured the batch's TexturedMesh list
+    (mesh_texture of the same grid), pose [B,3,4] or [B,V,3,4] world-to-camera, intr [B,3,3] for opt.H x opt.W pixels -> MeshRender(rgb
+    [B,V,H,W,3] in [0, 1], mask [B,V,H,W] (1 where a face covers the pixel centre), normal [B,V,H,W,3] in the (n + 1) / 2 encoding of
+    the normal PNGs, depth [B,V,H,W] camera z (0 on a miss), face int32, bary, stats as ops.mesh_raster returns them), on the device.
+
+    The mesh is that of ops.isosurface_mesh(level_vox) -- the same call, bits and face order as the atlas of mesh_texture -- drawn at the
+    positions the level grid was sampled at, lo + v (hi - lo) / (S - 1): mesh_attributes' positions, where the surface is and where the
+    texture was baked.  The written v / S rescale of {idx}_mesh.ply and the OBJ is NOT used: it shifts the shape by up to (hi - lo) / S,
+    several pixels at 224 x 224.  One ops.mesh_raster call for all views (include/shapeclipper_hip.h states its arithmetic); then per
+    pixel uv = (bary0 vt0 + bary1 vt1) + bary2 vt2 with vt the face's chart corners (texture_face_uv) and ops.texture_sample of the
+    colour atlas and of the normal atlas, both / 255.  A miss is data.bgcolor in rgb and mid-grey (0.5) in normal.  For H x W other
+    than opt.H x opt.W the intrinsics are diag(W / opt.W, H / opt.H, 1) @ intr.  camera.model: orthographic is not implemented."""
+    if opt.camera.model != "perspective":
+        raise NotImplementedError("camera.model: %s -- eval_3D.mesh_render rasterises perspective cameras only" % (opt.camera.model,))
+    lo, hi = opt.eval.range
+    B, S = level_vox.shape[0], level_vox.shape[1]
+    dev = level_vox.device
+    verts, faces, v_count, f_count = ops.isosurface_mesh(level_vox)
+    world = (lo + verts * ((hi - lo) / (S - 1))).contiguous()              # mesh_attributes' expression
+    v_end, f_end = torch.cumsum(v_count, 0).tolist(), torch.cumsum(f_count, 0).tolist()
+    v_start, f_start = [0] + v_end[:-1], [0] + f_end[:-1]
+    F = f_count.tolist()
+    pose = pose.float()
+    pose = (pose[:, None] if pose.dim() == 3 else pose).contiguous()
+    intr = intr.float()
+    if (int(H), int(W)) != (int(opt.H), int(opt.W)):
+        intr = intr * torch.tensor([W / opt.W, H / opt.H, 1.0], device=intr.device).view(1, 3, 1)
+    kw = {} if large_pixels is None else dict(large_pixels=large_pixels)
+    r = ops.mesh_raster(world, faces, v_start, f_start, F, pose, intr.contiguous(), int(H), int(W), MESH_RENDER_NEAR, **kw)
+    V = pose.shape[1]
+    mask = r.face >= 0
+    bg, grey = float(opt.data.bgcolor), 0.5
+    if sum(F) == 0:
+        rgb, normal = torch.full((B, V, H, W, 3), bg, device=dev), torch.full((B, V, H, W, 3), grey, device=dev)
+        return MeshRender(rgb, mask.float(), normal, r.depth, r.face, r.bary, r.stats)
+    assert all(m.faces.shape[0] == F[b] for b, m in enumerate(textured)), "the texture was baked for another mesh"
+    A = max(m.atlas.shape[0] for b, m in enumerate(textured) if F[b])
+    blank = torch.full((A, A, 3), 127, dtype=torch.uint8, device=dev)
+    atlas = torch.stack([m.atlas if F[b] else blank for b, m in enumerate(textured)]).contiguous()
+    atlas_n = torch.stack([m.normal_atlas if F[b] else blank for b, m in enumerate(textured)]).contiguous()
+    vt = torch.cat([m.uv for m in textured])                               # [sum F, 3, 2], image after image
+    first = torch.tensor(f_start, device=dev).view(B, 1, 1, 1)
+    corner = vt[(r.face.clamp(min=0).long() + first).clamp(max=vt.shape[0] - 1).view(-1)]      # [N,3,2]; a miss reads some face, unused
+    t = r.bary.view(-1, 3, 1) * corner
+    uv = ((t[:, 0] + t[:, 1]) + t[:, 2]).contiguous()
+    image = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(V * H * W)
+    covered = mask.view(B, V, H, W, 1)
+    rgb = torch.where(covered, (ops.texture_sample(atlas, uv, image) / 255).view(B, V, H, W, 3), torch.full((), bg, device=dev))
+    normal = torch.where(covered, (ops.texture_sample(atlas_n, uv, image) / 255).view(B, V, H, W, 3), torch.full((), grey, device=dev))
+    return MeshRender(rgb, mask.float(), normal, r.depth, r.face, r.bary, r.stats)
+
+
+def mask_iou(a, b):
+    """Boolean masks [B, ...] -> [B] float64 intersection over union, from integer sums on the device; an empty union gives 1."""
+    a, b = a.reshape(a.shape[0], -1), b.reshape(b.shape[0], -1)
+    inter, union = (a & b).sum(dim=1), (a | b).sum(dim=1)
+    return torch.where(union == 0, torch.ones_like(union, dtype=torch.float64), inter.double() / union.clamp(min=1).double())
+
+
+def mesh_depth_grey(opt, render, intr, scale_dist):
+    """Renderer.surface_depth_grey's mapping for a MeshRender of opt.H x opt.W intrinsics `intr` [B,3,3]: [B,V,H,W] in [0, 1], (depth -
+    near f) / (1.4 f) clamped, near = camera.dist scale_dist - 0.7 and f the camera z per unit length of the pixel's ray -- black at the
+    near sample plane of the volume render, white at the far one and on a miss."""
+    B, V, H, W = render.depth.shape
+    k = intr.float() * torch.tensor([W / opt.W, H / opt.H, 1.0], device=intr.device).view(1, 3, 1)
+    x = (torch.arange(W, device=intr.device).float() + 0.5).view(1, 1, W)
+    y = (torch.arange(H, device=intr.device).float() + 0.5).view(1, H, 1)
+    dx, dy = (x - k[:, 0, 2].view(B, 1, 1)) / k[:, 0, 0].view(B, 1, 1), (y - k[:, 1, 2].view(B, 1, 1)) / k[:, 1, 1].view(B, 1, 1)
+    fac = (1.0 / torch.sqrt(dx * dx + dy * dy + 1.0)).view(B, 1, H, W)
+    near = (float(opt.camera.dist) * scale_dist.float() - 0.7).view(B, 1, 1, 1)
+    grey = ((render.depth - near * fac) / (1.4 * fac)).clamp(0, 1)
+    return torch.where(render.mask > 0, grey, torch.ones_like(grey))
+
+
+@torch.no_grad()
+def mesh_render_sample(opt, var, textured):
+    """`--eval.mesh_render` for an evaluated batch: the textured mesh from the samples' own cameras (var.pose, var.intr) ->
+    MeshRenderSample(render: the MeshRender at the size of var.mask_input_map (opt.H x opt.W without that map), faces [B] and pixels [B] (covered
+    pixel centres of that render) as host lists, iou_input [B] float64: the mesh mask against var.mask_input_map >= 0.5 at that map's
+    size, iou_volume [B] float64: a second rasterisation at opt.H x opt.W against var.mask_hard_map >= 0.5 -- integer sums on the
+    device, an empty union gives 1, a missing map nan)."""
+    B = len(var.idx)
+    nan = torch.full((B,), float("nan"), dtype=torch.float64, device=var.level_vox.device)
+    has_input = "mask_input_map" in var and var.mask_input_map is not None
+    H, W = (int(s) for s in var.mask_input_map.shape[-2:]) if has_input else (int(opt.H), int(opt.W))
+    render = mesh_render(opt, var.level_vox, textured, var.pose, var.intr, H, W)
+    mask = render.mask[:, 0] > 0
+    iou_input = mask_iou(mask, var.mask_input_map.reshape(B, H, W) >= 0.5) if has_input else nan
+    iou_volume = nan
+    if "mask_hard_map" in var and var.mask_hard_map is not None:
+        at_render = render if (H, W) == (int(opt.H), int(opt.W)) else mesh_render(opt, var.level_vox, textured, var.pose, var.intr,
+                                                                                    int(opt.H), int(opt.W))
+        iou_volume = mask_iou(at_render.mask[:, 0] > 0, var.mask_hard_map.reshape(B, int(opt.H), int(opt.W)) >= 0.5)
+    return MeshRenderSample(render, [int(m.faces.shape[0]) for m in textured], mask.reshape(B, -1).sum(dim=1).tolist(), iou_input, iou_volume)
+
+
 @torch.no_grad()
 def meshes_dual(opt, sdf_network, proj_latent_sdf, level_vox, reg):
     """level_vox [B,S,S,S] (compute_level_grid) -> per image (vertices [Vd,3] fp32, faces [Fd,3] int32) on the device: the dual-contouring

@@ -111,6 +111,16 @@ def texture_texels(opt, always=False):
     return texels if on or always else None
 
 
+def mesh_render(opt):
+    """The evaluation's picture of the textured mesh and its mask IoU (eval_3D.mesh_render, mesh_render.txt): `--eval.mesh_render`, absent
+    means off.  An evaluation setting beside eval.texture, not a hip.* switch; it bakes the texture (eval.texture_texels) when
+    `--eval.texture` has not.  A value that is not a bool is a ValueError, whether or not the switch is on."""
+    on = (opt.get("eval", None) or {}).get("mesh_render", False)
+    if not isinstance(on, bool):
+        raise ValueError("eval.mesh_render must be a bool, got %r" % (on,))
+    return on
+
+
 def icp_settings(opt):
     """The evaluation's ICP-aligned metrics: None unless `--eval.icp` is set (absent means off), else (iters, scale) from
     `--eval.icp_iters` (default 30, an integer in 1..100) and `--eval.icp_scale` (default true: fit a similarity; false: a rigid motion),
@@ -266,6 +276,7 @@ def process_options(opt):
                 raise ValueError("hip.%s must be an integer in %d..%d, got %r" % (row.key, lo, hi, v))
     dual_mesh_reg(opt)
     texture_texels(opt)
+    mesh_render(opt)
     icp_settings(opt)
     normal_settings(opt)
     mesh_dist_settings(opt)
