@@ -868,6 +868,60 @@ int sc_point_mesh_distance_brute(const float* points, const float* verts, const 
 int sc_emd3d_match(const float* xyz1, const float* xyz2, int n_images, int n, const float* eps_list, int n_eps, int max_rounds,
                    int32_t* assignment, float* cost, float* price, int32_t* rounds, int32_t* converged, double* emd, void* stream);
 
+/* ---- evaluation: volumetric IoU of two point clouds from voxel solids (csrc/voxel_solid.hip) -------------------------------------
+ * A cloud becomes a solid of an R^3 grid (SC_VOXEL_MIN_RES <= R <= SC_VOXEL_MAX_RES): its points are splatted to a voxel shell, the
+ * shell is closed by c dilations (0 <= c <= SC_VOXEL_MAX_CLOSE), the space the exterior cannot reach is filled, and the result is
+ * eroded c times.  Two clouds share one frame and the IoU is that of their solids.  tests/voxel_iou_ref.py restates every step in
+ * numpy and all outputs match it bit for bit.  fp32 below is un-fused, one rounding per operation (built without contraction).
+ *
+ * sc_voxel_frame: the frame of a pair of clouds a [n_images][n_a][3], b [n_images][n_b][3] (fp32; n_a, n_b >= 1), m = c + 1:
+ *       lo = min over both clouds, hi = max over both clouds, per axis;   side = max(max(hi_x - lo_x, hi_y - lo_y), hi_z - lo_z);
+ *       pitch = side / float(R - 2 m),  pitch = 1.0f when side == 0;   centre = (lo + hi) * 0.5f;
+ *       origin = centre - (R * 0.5f) * pitch     per axis.
+ *   The object fills the cube up to m empty layers on every side: a dilation never reaches the border and the exterior is connected
+ *   around the object.  If any coordinate of either cloud is not finite, origin and pitch are the quiet NaN 0x7fc00000; finite
+ *   coordinates whose differences or sums overflow give the Inf or NaN of the expressions above.
+ *   -> origin [n_images][3], pitch [n_images] fp32.  One workgroup of 1024 threads per image; minima and maxima do not depend on order.
+ *
+ * sc_voxel_solid: points [n_images][n][3] fp32 (n >= 1), origin [n_images][3], pitch [n_images] (any frame, usually sc_voxel_frame's).
+ *   Storage: one 64-bit word per (x, y) row, bit z: a volume is R^2 words, bit z of word x R + y is voxel (x, y, z).
+ *   Shell: for every point p with three finite coordinates, per axis
+ *       q = (p - origin) / pitch  (a true division);   i = int(min(max(floorf(q), float(m)), float(R - 1 - m)))
+ *     (the clamp is made in fp32, so a q beyond the integers is defined: it is  clamp(int(floorf(q)), m, R - 1 - m)  wherever that
+ *     is), and voxel (i_x, i_y, i_z) is set.  A point with a coordinate that is not finite sets nothing; with an origin or a pitch
+ *     that is not finite, or pitch <= 0, no point sets anything.
+ *   Solid:  D = the shell dilated c times by the 3x3x3 cube.   Exterior E = the least set that holds the border voxels (x, y or z
+ *     equal to 0 or R - 1) not in D and, with a voxel, its 6-neighbours not in D.   F = not E.   Solid = F eroded c times by the cube,
+ *     the outside of the grid counting as empty --  binary_erosion(binary_fill_holes(binary_dilation(shell, cube, c)), cube, c)  of
+ *     scipy.ndimage.  E is a unique fixed point: no schedule of the flood changes a bit of it.
+ *   The flood runs Jacobi sweeps until one changes nothing: with `free` = the voxels of a row not in D,
+ *       v = (E[x][y] | E[x-1][y] | E[x+1][y] | E[x][y-1] | E[x][y+1]) & free     (rows outside the grid are empty),
+ *       E'[x][y] = v smeared along z inside `free` until it stops growing,
+ *     from  E[x][y] = free  on the border rows (x or y equal to 0 or R - 1) and  free & (bit 0 | bit R - 1)  elsewhere.  sweeps
+ *     counts every sweep, the last, which changes nothing, included.
+ *   -> bits [n_images][R][R] int64 (the solid), shell_voxels, solid_voxels, sweeps [n_images] int32.
+ *   Launch: ONE workgroup of 1024 threads per image, the whole job in LDS with workgroup barriers only: no wait on another
+ *   workgroup, no spin on global memory, no host read; the sweep loop ends because E only grows in a finite grid.  Points are
+ *   splatted by a 64-bit integer LDS OR; dilation and erosion are separable (shifts inside a word along z, neighbouring words along
+ *   y and x); every reduction is an integer sum.  Dynamic LDS 24 R^2 bytes (three volumes: 96 KiB at R = 64 of the CU's 160 KiB,
+ *   above the 64 KiB default, so the launch raises the kernel's dynamic-LDS limit first).
+ *
+ * sc_voxel_iou: bits_a, bits_b [n_images][words] int64 -> inter [n_images] = popcount of the AND, uni [n_images] = popcount of the
+ *   OR, int32 (words <= 2^24, so they cannot overflow).  One workgroup of 256 threads per image.  The IoU is inter / uni in float64,
+ *   1 for an empty union (ops.mask_iou's convention) -- left to the caller.
+ *
+ * No float atomics anywhere: the same bits from run to run, on any stream, for an image alone or in a batch.  No workspace.
+ * n_images <= 0 returns 0 and launches nothing; hipErrorInvalidValue for n_images > 65535, a count < 1, res or close out of range,
+ * words outside [1, 2^24] or a NULL pointer.                                                                                          */
+#define SC_VOXEL_MIN_RES 8
+#define SC_VOXEL_MAX_RES 64
+#define SC_VOXEL_MAX_CLOSE 2
+int sc_voxel_frame(const float* a, const float* b, int n_images, int n_a, int n_b, int res, int close, float* origin, float* pitch,
+                   void* stream);
+int sc_voxel_solid(const float* points, const float* origin, const float* pitch, int n_images, int n, int res, int close, int64_t* bits,
+                   int32_t* shell_voxels, int32_t* solid_voxels, int32_t* sweeps, void* stream);
+int sc_voxel_iou(const int64_t* bits_a, const int64_t* bits_b, int n_images, int words, int32_t* inter, int32_t* uni, void* stream);
+
 /* ---- camera algebra of a render -------------------------------------------------------------------
  * sc_camera_rays_*: utils/camera.py:157-196 (get_center_and_ray on the rendered pixels only) + the normalisation of
  * model/renderer.py:69-76.  pose [n_images][3][4] = [R|t] world->camera, intr [n_images][3][3], ray_idx

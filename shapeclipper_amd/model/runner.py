@@ -101,6 +101,26 @@ def _emd_records(var):
     return torch.stack([c.detach().double().view(-1).cpu() for c in cols], dim=1)
 
 
+IOU_LINE = "%d %d %.8f %d %d %d %d %d %d\n"  # a line of iou.txt: idx res iou inter union vox_pred vox_gt shell_pred shell_gt
+IOU_KEYS = ("iou", "iou_inter", "iou_union", "iou_vox_pred", "iou_vox_gt", "iou_shell_pred", "iou_shell_gt")
+IOU_COLS = (("", [2, 3, 4, 5, 6, 7, 8]), ("_icp", [10, 11, 12, 13, 14, 15, 16]))      # the columns of a line behind idx and res
+
+
+def _iou_records(var):
+    """[B,10] float64 on the host, a record per sample of eval_3D.iou_metrics' results: idx, res, the seven values of IOU_KEYS, category;
+    [B,17] with the seven values of the ICP-aligned prediction behind them when --eval.icp ran as well."""
+    B = len(var.idx)
+    cols = [var.idx, torch.full((B,), var.iou_res)] + [var[k] for k in IOU_KEYS] + [var.category_label]
+    if "iou_icp" in var:
+        cols += [var[k + "_icp"] for k in IOU_KEYS]
+    return torch.stack([c.detach().double().view(-1).cpu() for c in cols], dim=1)
+
+
+def iou_line(r, cols):
+    """The line of iou.txt (or iou_icp.txt) of one row of _iou_records."""
+    return IOU_LINE % (int(r[0]), int(r[1]), float(r[cols[0]]), *(int(r[c]) for c in cols[1:]))
+
+
 TEXTURE_LINE = "%d %d %d %d %.6f %.6f\n"     # a line of texture.txt: idx faces atlas rows err_mean err_max
 
 
@@ -460,6 +480,7 @@ class Runner:
         nc_recs = []                                    # --eval.normals: _normal_records of every batch
         mesh_recs = []                                  # --eval.mesh_dist: _mesh_records of every batch
         emd_recs = []                                   # --eval.emd: _emd_records of every batch
+        iou_recs = []                                   # --eval.iou: _iou_records of every batch
         loader = tqdm.tqdm(self.test_loader, desc="evaluating", leave=False)
         for it, batch in enumerate(loader):
             var = self.evaluate_batch(opt, edict(batch), ep, it, single_gpu=True)
@@ -478,6 +499,8 @@ class Runner:
                 mesh_recs.append(_mesh_records(var))
             if "emd" in var:
                 emd_recs.append(_emd_records(var))
+            if "iou" in var:
+                iou_recs.append(_iou_records(var))
             metric["dist_acc"] += dist_acc * len(var.idx)
             metric["dist_cov"] += dist_cov * len(var.idx)
             loader.set_postfix(CD="{:.3f}".format(float((dist_acc + dist_cov) / 2)))
@@ -513,6 +536,8 @@ class Runner:
                 self._write_mesh(opt, torch.cat(mesh_recs), per_sample=False)
             if emd_recs:                                # emd_cat.txt (and emd_cat_icp.txt); likewise
                 self._write_emd(opt, torch.cat(emd_recs), per_sample=False)
+            if iou_recs:                                # iou_cat.txt (and iou_cat_icp.txt); likewise
+                self._write_iou(opt, torch.cat(iou_recs), per_sample=False)
         n = max(len(self.test_data), 1)
         for k in metric:
             metric[k] /= n
@@ -530,7 +555,8 @@ class Runner:
         f_score_icp.txt / icp.txt, from one more gather of the ICP-aligned records; with --eval.normals also normal_consistency.txt /
         nc_cat.txt and their _icp namesakes, from one more gather again; with --eval.mesh_dist also completeness_mesh.txt /
         cd_cat_mesh.txt / f_score_mesh.txt and, with --eval.dual_mesh, their _dual namesakes, from one more gather; with --eval.emd
-        also emd.txt / emd_cat.txt and, with --eval.icp, their _icp namesakes, from one more gather).  The value
+        also emd.txt / emd_cat.txt and, with --eval.icp, their _icp namesakes, from one more gather; with --eval.iou also iou.txt /
+        iou_cat.txt and, with --eval.icp, their _icp namesakes, from one more gather).  The value
         returned is the raw one.  Every rank
         writes the per-sample files of its own samples (dump_visuals: PNGs, mesh and point-cloud PLYs)."""
         from ..parallel import gather_eval_records
@@ -539,7 +565,7 @@ class Runner:
         # the reference's single-node convention is rank == device index; the process group's rank is the same number there and stays
         # right when ranks and devices are numbered differently (several nodes; tests/test_gpu_two_ranks.py: two ranks on one GPU)
         rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else util.get_rank(opt)
-        recs, comps, icps, ncs, meshes, emds, texs, mrs = [], [], [], [], [], [], [], []
+        recs, comps, icps, ncs, meshes, emds, texs, mrs, ious = [], [], [], [], [], [], [], [], []
         for it in range(rank, len(self.test_data), opt.world_size):
             sample = self.test_data[it]
             batch = {k: ({kk: vv[None] for kk, vv in v.items()} if isinstance(v, dict) else torch.as_tensor(v)[None]) for k, v in sample.items()}
@@ -559,6 +585,8 @@ class Runner:
                 meshes.append(_mesh_records(var))
             if "emd" in var:                            # --eval.emd: _emd_records' columns
                 emds.append(_emd_records(var))
+            if "iou" in var:                            # --eval.iou: _iou_records' columns
+                ious.append(_iou_records(var))
             if "texture" in var and options.texture_texels(opt) is not None:    # --eval.texture: _texture_records' columns (dump_geometry baked the atlas)
                 texs.append(_texture_records(var))
             if "mesh_render" in var:                    # --eval.mesh_render: _mesh_render_records' columns (dump_geometry rendered)
@@ -590,6 +618,11 @@ class Runner:
             width = 6 if options.icp_settings(opt) is None else 9
             alle = gather_eval_records(torch.cat(emds).to(dev) if emds else torch.zeros(0, width, device=dev, dtype=torch.float64),
                                        opt.world_size).cpu()
+        allv = None
+        if options.iou_settings(opt) is not None:       # likewise
+            width = 10 if options.icp_settings(opt) is None else 17
+            allv = gather_eval_records(torch.cat(ious).to(dev) if ious else torch.zeros(0, width, device=dev, dtype=torch.float64),
+                                       opt.world_size).cpu()
         allt = None
         if options.texture_texels(opt) is not None and util_vis is not None:      # likewise
             allt = gather_eval_records(torch.cat(texs).to(dev) if texs else torch.zeros(0, 6, device=dev, dtype=torch.float64),
@@ -603,6 +636,8 @@ class Runner:
             _write_mesh_render(opt, allmr)
         if rank == 0 and allt is not None:
             _write_texture(opt, allt)
+        if rank == 0 and allv is not None:
+            self._write_iou(opt, allv)
         if rank == 0 and alle is not None:
             self._write_emd(opt, alle)
         if rank == 0 and allm is not None:
@@ -703,6 +738,25 @@ class Runner:
                 f.write("EMD    Count Cat\n")
                 for c in range(C):
                     sel = alle[alle[:, 5] == c]
+                    n = sel.shape[0] + 0.001
+                    f.write("%.4f %5d %s\n" % (float(sel[:, cols[0]].sum()) / n, n, names[c]))
+
+    def _write_iou(self, opt, allv, per_sample=True):
+        """The files of --eval.iou from _iou_records' rows in sample order, float64: iou.txt (`idx res iou inter union vox_pred vox_gt
+        shell_pred shell_gt` per sample; per_sample=False leaves it to dump_results) and iou_cat.txt, the per-category mean in
+        cd_cat.txt's format with the one column.  Rows [N,17] (with --eval.icp) carry the values of the ICP-aligned prediction in
+        columns 10..16, which go to iou_icp.txt and iou_cat_icp.txt."""
+        C = opt.data.num_classes
+        names = getattr(self.test_data, "label2cat", {i: str(i) for i in range(C)})
+        for suffix, cols in IOU_COLS[:1 if allv.shape[1] < 17 else 2]:
+            if per_sample:
+                with open("{}/iou{}.txt".format(opt.output_path, suffix), "w") as f:
+                    for r in allv:
+                        f.write(iou_line(r, cols))
+            with open(os.path.join(opt.output_path, "iou_cat{}.txt".format(suffix)), "w") as f:
+                f.write("IoU    Count Cat\n")
+                for c in range(C):
+                    sel = allv[allv[:, 9] == c]
                     n = sel.shape[0] + 0.001
                     f.write("%.4f %5d %s\n" % (float(sel[:, cols[0]].sum()) / n, n, names[c]))
 
@@ -895,7 +949,8 @@ class Runner:
         with --eval.icp also {idx}_pointclouds_comp_icp.ply (the ICP-aligned prediction of eval_3D.icp_metrics red, ground truth green);
         with --eval.normals also {idx}_pointclouds_normals.ply (pointclouds_comp's vertices as x y z nx ny nz red green blue: the SDF's
         normals on the prediction, the estimated PCA normals on the ground truth); with --eval.emd also {idx}_pointclouds_emd.ply (the
-        two n-point sub-samples eval_3D.emd_metrics matched, prediction red, ground truth green); with --eval.texture also
+        two n-point sub-samples eval_3D.emd_metrics matched, prediction red, ground truth green); with --eval.iou also
+        {idx}_voxels_comp.ply (the voxel centres of the two solids eval_3D.iou_metrics compared, likewise); with --eval.texture also
         {idx}_mesh_tex.obj / .mtl / .png and {idx}_mesh_tex_normal.png (eval_3D.mesh_texture: the device mesh with a per-triangle
         texture atlas of the predicted colours, and the atlas of its normals; var.texture keeps the result for texture.txt); with
         --eval.mesh_render also {idx}_image_mesh.png, {idx}_mask_mesh.png, {idx}_normal_mesh.png, {idx}_depth_mesh.png (the grey mapping
@@ -946,6 +1001,10 @@ class Runner:
             if "emd" in var:                            # --eval.emd: what was matched
                 sub_pred, sub_gt, _ = eval_3D.emd_subsample(var.dpc_pred, var.dpc.points, var.emd_n)
                 util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_emd", sub_pred, sub_gt, folder=folder)
+            if "iou" in var:                            # --eval.iou: the voxel centres of the two solids that were compared
+                centres = [[eval_3D.voxel_centres(bits[i], var.iou_origin[i], var.iou_pitch[i]) for i in range(len(var.idx))]
+                           for bits in (var.iou_bits_pred, var.iou_bits_gt)]
+                util_vis.dump_pointclouds_compare(opt, var.idx, "voxels_comp", centres[0], centres[1], folder=folder)
 
     @torch.no_grad()
     def dump_results(self, opt, var, ep, write_new=False, train=False):
@@ -982,6 +1041,12 @@ class Runner:
                     with open("{}/normal_consistency{}.txt".format(opt.output_path, suffix), "w" if write_new else "a") as f:
                         for r in rec:
                             f.write(NC_LINE % (int(r[0]), *(float(r[c]) for c in cols)))
+            if "iou" in var:                            # --eval.iou: idx res iou inter union and the voxel counts (and the same after ICP)
+                rec = _iou_records(var)
+                for suffix, cols in IOU_COLS[:1 if rec.shape[1] < 17 else 2]:
+                    with open("{}/iou{}.txt".format(opt.output_path, suffix), "w" if write_new else "a") as f:
+                        for r in rec:
+                            f.write(iou_line(r, cols))
             if "emd" in var:                            # --eval.emd: idx n emd rounds converged (and the same after ICP)
                 rec = _emd_records(var)
                 for suffix, cols in (("", [2, 3, 4]), ("_icp", [6, 7, 8]))[:1 if rec.shape[1] < 9 else 2]:

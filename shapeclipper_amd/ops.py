@@ -2193,3 +2193,137 @@ def mesh_raster(verts, faces, v_start, f_start, f_count, pose, intr, H, W, near,
                                   _lib.stream())
     _lib.check(code, "sc_mesh_raster")
     return out
+
+
+# ---- evaluation: volumetric IoU of two point clouds from voxel solids (csrc/voxel_solid.hip) ------------------------------------------
+VOXEL_MIN_RES = 8               # SC_VOXEL_MIN_RES
+VOXEL_MAX_RES = 64              # SC_VOXEL_MAX_RES
+VOXEL_MAX_CLOSE = 2             # SC_VOXEL_MAX_CLOSE
+VOXEL_MAX_IMAGES = 65535
+VOXEL_MAX_WORDS = 1 << 24
+VoxelSolid = collections.namedtuple("VoxelSolid", ["bits", "shell_voxels", "solid_voxels", "sweeps"])
+
+
+def _voxel_grid(who, res, close):
+    """ValueError unless res is an integer in 8..64 and close an integer in 0..2."""
+    if isinstance(res, bool) or not isinstance(res, int) or not VOXEL_MIN_RES <= res <= VOXEL_MAX_RES:
+        raise ValueError("%s: res must be an integer in %d..%d, got %r" % (who, VOXEL_MIN_RES, VOXEL_MAX_RES, res))
+    if isinstance(close, bool) or not isinstance(close, int) or not 0 <= close <= VOXEL_MAX_CLOSE:
+        raise ValueError("%s: close must be an integer in 0..%d, got %r" % (who, VOXEL_MAX_CLOSE, close))
+
+
+def _voxel_args(who, tensors, dtype, check):
+    """The checks of the voxel entry points, in _emd_args' order: TypeError for something that is not a tensor of `dtype`, then
+    check() (ValueError for shapes, sizes and settings) -- all before the device is looked at -- then RuntimeError for host tensors
+    and ValueError for another device or a non-contiguous tensor.  tensors: ((name, tensor), ...)."""
+    for name, t in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
+        if t.dtype != dtype:
+            raise TypeError("%s: %s must be %s, got %s" % (who, name, dtype, t.dtype))
+    check()
+    if not all(t.is_cuda for _, t in tensors):
+        raise RuntimeError(_lib.NO_CPU)
+    first = tensors[0]
+    for name, t in tensors[1:]:
+        if t.device != first[1].device:
+            raise ValueError("%s: %s is on %s, %s is on %s" % (who, name, t.device, first[0], first[1].device))
+    for name, t in tensors:
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (who, name))
+
+
+def voxel_frame(a, b, res=32, close=1):
+    """a [B,N,3], b [B,M,3] fp32 (N, M >= 1), res in 8..64, close in 0..2 -> (origin [B,3], pitch [B]) fp32: the frame the two clouds
+    share as res^3 voxels -- the cube around their common bounding box, close + 1 empty layers on every side (include/
+    shapeclipper_hip.h, sc_voxel_frame, states the expression).  Coincident clouds get pitch 1; a coordinate that is not finite makes
+    the image's origin and pitch NaN.
+
+    Host synchronisation: none.  Runs on the current stream."""
+    who = "shapeclipper_amd: voxel_frame"
+
+    def check():
+        if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3 or a.shape[0] != b.shape[0]:
+            raise ValueError("%s: a and b must be [B,N,3] and [B,M,3], got %s and %s" % (who, tuple(a.shape), tuple(b.shape)))
+        if a.shape[1] < 1 or b.shape[1] < 1:
+            raise ValueError("%s: a cloud needs at least one point, got %d and %d" % (who, a.shape[1], b.shape[1]))
+        if a.shape[0] > VOXEL_MAX_IMAGES:
+            raise ValueError("%s takes at most %d images per call, got %d" % (who, VOXEL_MAX_IMAGES, a.shape[0]))
+        _voxel_grid(who, res, close)
+    _voxel_args(who, (("a", a), ("b", b)), torch.float32, check)
+    B = a.shape[0]
+    origin = torch.empty(B, 3, device=a.device, dtype=torch.float32)
+    pitch = torch.empty(B, device=a.device, dtype=torch.float32)
+    if B == 0:
+        return origin, pitch
+    lib = _lib.load()
+    with torch.cuda.device(a.device):
+        code = lib.sc_voxel_frame(_lib.ptr(a), _lib.ptr(b), B, a.shape[1], b.shape[1], res, close, _lib.ptr(origin), _lib.ptr(pitch),
+                                  _lib.stream())
+    _lib.check(code, "sc_voxel_frame")
+    return origin, pitch
+
+
+def voxel_solid(points, origin, pitch, res=32, close=1):
+    """points [B,N,3], origin [B,3], pitch [B] fp32 -> VoxelSolid(bits [B,res,res] int64, shell_voxels [B], solid_voxels [B], sweeps [B]
+    int32): the solid of a point cloud in the frame (origin, pitch) of res^3 voxels.  Bit z of bits[b, x, y] is voxel (x, y, z).  The
+    points are splatted to a voxel shell (shell_voxels of them), the shell is dilated `close` times by the 3x3x3 cube, the space the
+    exterior cannot reach through 6-neighbours is filled, and the result is eroded `close` times: scipy.ndimage's
+    binary_erosion(binary_fill_holes(binary_dilation(shell))).  sweeps counts the Jacobi sweeps of the exterior flood.  A point with
+    a coordinate that is not finite sets nothing; a frame that is not finite gives the empty solid.  One workgroup per image, the
+    whole job in LDS (csrc/voxel_solid.hip); the same bits from run to run, alone or in a batch.  No gradient.
+
+    Host synchronisation: none.  Runs on the current stream."""
+    who = "shapeclipper_amd: voxel_solid"
+
+    def check():
+        if points.dim() != 3 or points.shape[2] != 3:
+            raise ValueError("%s: points must be [B,N,3], got %s" % (who, tuple(points.shape)))
+        B = points.shape[0]
+        if tuple(origin.shape) != (B, 3) or tuple(pitch.shape) != (B,):
+            raise ValueError("%s: origin and pitch must be [%d,3] and [%d], got %s and %s" % (who, B, B, tuple(origin.shape), tuple(pitch.shape)))
+        if points.shape[1] < 1:
+            raise ValueError("%s: a cloud needs at least one point" % who)
+        if B > VOXEL_MAX_IMAGES:
+            raise ValueError("%s takes at most %d images per call, got %d" % (who, VOXEL_MAX_IMAGES, B))
+        _voxel_grid(who, res, close)
+    _voxel_args(who, (("points", points), ("origin", origin), ("pitch", pitch)), torch.float32, check)
+    B, dev = points.shape[0], points.device
+    bits = torch.empty(B, res, res, device=dev, dtype=torch.int64)
+    shell, solid, sweeps = (torch.empty(B, device=dev, dtype=torch.int32) for _ in range(3))
+    if B == 0:
+        return VoxelSolid(bits, shell, solid, sweeps)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        code = lib.sc_voxel_solid(_lib.ptr(points), _lib.ptr(origin), _lib.ptr(pitch), B, points.shape[1], res, close, _lib.ptr(bits),
+                                  _lib.ptr(shell), _lib.ptr(solid), _lib.ptr(sweeps), _lib.stream())
+    _lib.check(code, "sc_voxel_solid")
+    return VoxelSolid(bits, shell, solid, sweeps)
+
+
+def voxel_iou(bits_a, bits_b):
+    """bits_a, bits_b [B,...] int64 of one shape (bit volumes, voxel_solid's bits) -> (inter [B], union [B]) int32: the voxels in both
+    and the voxels in either.  The IoU is inter / union, 1 for an empty union (mask_iou's convention); the division is the caller's.
+
+    Host synchronisation: none.  Runs on the current stream."""
+    who = "shapeclipper_amd: voxel_iou"
+
+    def check():
+        if bits_a.dim() < 2 or tuple(bits_a.shape) != tuple(bits_b.shape):
+            raise ValueError("%s: bits_a and bits_b must have one shape [B,...], got %s and %s" % (who, tuple(bits_a.shape), tuple(bits_b.shape)))
+        words = bits_a[0].numel() if bits_a.shape[0] else 1
+        if not 1 <= words <= VOXEL_MAX_WORDS:
+            raise ValueError("%s: 1..%d words per image, got %d" % (who, VOXEL_MAX_WORDS, words))
+        if bits_a.shape[0] > VOXEL_MAX_IMAGES:
+            raise ValueError("%s takes at most %d images per call, got %d" % (who, VOXEL_MAX_IMAGES, bits_a.shape[0]))
+    _voxel_args(who, (("bits_a", bits_a), ("bits_b", bits_b)), torch.int64, check)
+    B, dev = bits_a.shape[0], bits_a.device
+    inter = torch.empty(B, device=dev, dtype=torch.int32)
+    union = torch.empty(B, device=dev, dtype=torch.int32)
+    if B == 0:
+        return inter, union
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        code = lib.sc_voxel_iou(_lib.ptr(bits_a), _lib.ptr(bits_b), B, bits_a[0].numel(), _lib.ptr(inter), _lib.ptr(union), _lib.stream())
+    _lib.check(code, "sc_voxel_iou")
+    return inter, union

@@ -20,6 +20,9 @@ Call surface of the reference's utils/eval_3D.py.
   * emd_metrics (`--eval.emd`): the Earth Mover's Distance of `--eval.emd_points` points of the prediction and of the ground truth, the
     mean pair distance of the best one-to-one matching (ops.emd_match, csrc/emd3d.hip: a forward auction, one workgroup per image),
     reported beside Chamfer: the third number of the Pix3D benchmark table.
+  * iou_metrics (`--eval.iou`): the volumetric IoU of the two clouds, each turned into a solid of `--eval.iou_res`^3 voxels the same way
+    -- shell, closing, fill of what the exterior cannot reach (ops.voxel_solid, csrc/voxel_solid.hip: one workgroup per cloud, the whole
+    flood in LDS) -- reported beside Chamfer: the first number of that table, in the clouds' own frame.
   * meshes_dual (`--eval.dual_mesh`): the dual-contouring mesh of the same grid from the SDF gradients at the crossings
     (csrc/dual_contour.hip), which keeps corners and creases that marching cubes chamfers at the grid pitch.
 """
@@ -695,6 +698,45 @@ def emd_metrics(opt, var, points, eps, icp=None):
     var.emd_n = n
 
 
+@torch.no_grad()
+def iou_metrics(opt, var, res, close, icp=None):
+    """`--eval.iou`: the volumetric IoU of the normalised prediction var.dpc_pred and the normalised ground truth var.dpc.points.  The
+    ground truth is a bare point cloud, so BOTH solids are built the same way, in the one frame ops.voxel_frame gives the pair:
+    splat to a shell of res^3 voxels, dilate `close` times so that pinholes close, fill what the exterior cannot reach, erode `close`
+    times (ops.voxel_solid, csrc/voxel_solid.hip) -- a symmetric measure, like Chamfer, that charges for enclosed volume.  Sets
+    var.iou [B] float64 (inter / union; 1 for an empty union, ops.mask_iou's convention; NaN where the frame is not finite),
+    var.iou_inter / var.iou_union, var.iou_vox_pred / var.iou_vox_gt (the solids' voxels), var.iou_shell_pred / var.iou_shell_gt (the
+    shells': a solid no larger than its shell did not fill) [B] int32, var.iou_bits_pred / var.iou_bits_gt [B,res,res] int64,
+    var.iou_origin [B,3], var.iou_pitch [B] and var.iou_res (the int).  With `--eval.icp` (icp = icp_metrics' result): the same with
+    the suffix _icp for var.dpc_pred_icp, in the frame of that cloud and the ground truth.  The raw metrics are untouched, nothing
+    enters a loss."""
+    gt = var.dpc.points.contiguous().float()
+    for suffix, pred in (("", var.dpc_pred),) + ((("_icp", var.dpc_pred_icp),) if icp is not None else ()):
+        pred = pred.contiguous().float()
+        origin, pitch = ops.voxel_frame(pred, gt, res, close)
+        solid_pred = ops.voxel_solid(pred, origin, pitch, res, close)
+        solid_gt = ops.voxel_solid(gt, origin, pitch, res, close)
+        inter, union = ops.voxel_iou(solid_pred.bits, solid_gt.bits)
+        iou = torch.where(union > 0, inter.double() / union.clamp(min=1).double(), torch.ones_like(inter, dtype=torch.float64))
+        finite = torch.isfinite(origin).all(dim=1) & torch.isfinite(pitch)
+        var["iou" + suffix] = torch.where(finite, iou, torch.full_like(iou, float("nan")))
+        var["iou_inter" + suffix], var["iou_union" + suffix] = inter, union
+        var["iou_vox_pred" + suffix], var["iou_vox_gt" + suffix] = solid_pred.solid_voxels, solid_gt.solid_voxels
+        var["iou_shell_pred" + suffix], var["iou_shell_gt" + suffix] = solid_pred.shell_voxels, solid_gt.shell_voxels
+        var["iou_bits_pred" + suffix], var["iou_bits_gt" + suffix] = solid_pred.bits, solid_gt.bits
+        var["iou_origin" + suffix], var["iou_pitch" + suffix] = origin, pitch
+    var.iou_res = res
+
+
+def voxel_centres(bits, origin, pitch):
+    """bits [R,R] int64 (bit z of bits[x, y] is voxel (x, y, z)), origin [3], pitch scalar -> [n,3] fp32 on the host: the centres
+    origin + (index + 0.5) pitch of the voxels that are set, in (x, y, z) order (the dump's {idx}_voxels_comp.ply)."""
+    R = bits.shape[0]
+    z = torch.arange(R, device=bits.device, dtype=torch.int64)
+    index = ((bits.unsqueeze(-1) >> z) & 1).nonzero().float()
+    return ((index + 0.5) * pitch.float() + origin.float()).cpu()
+
+
 def icp_summary(var):
     """[B,5] float64 on the host, a row of icp.txt per sample: s, the rotation angle in degrees, |t|, the first and the last objective."""
     T, s, obj = (var.icp[k].detach().cpu().double() for k in ("transform", "s", "objective"))
@@ -764,4 +806,7 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     emd = options.emd_settings(opt)
     if emd is not None:                     # likewise
         emd_metrics(opt, var, *emd, icp=aligned)
+    iou = options.iou_settings(opt)
+    if iou is not None:                     # likewise
+        iou_metrics(opt, var, *iou, icp=aligned)
     return dist_acc.mean(), dist_comp.mean()

@@ -185,6 +185,22 @@ def emd_settings(opt):
     return (points, float(eps)) if on else None
 
 
+def iou_settings(opt):
+    """The evaluation's volumetric IoU: None unless `--eval.iou` is set (absent means off), else (res, close) from `--eval.iou_res`
+    (default 32, Pix3D's resolution; an integer in 8..64, the grids ops.voxel_solid takes) and `--eval.iou_close` (default 1, an
+    integer in 0..2: the dilations that close the voxel shell before it is filled), the arguments of eval_3D.iou_metrics.  Evaluation
+    settings beside eval.vox_res, not hip.* switches.  A bad value is a ValueError, whether or not the switch is on."""
+    ev = opt.get("eval", None) or {}
+    on, res, close = ev.get("iou", False), ev.get("iou_res", 32), ev.get("iou_close", 1)
+    if not isinstance(on, bool):
+        raise ValueError("eval.iou must be a bool, got %r" % (on,))
+    if isinstance(res, bool) or not isinstance(res, int) or not 8 <= res <= 64:
+        raise ValueError("eval.iou_res must be an integer in 8..64, got %r" % (res,))
+    if isinstance(close, bool) or not isinstance(close, int) or not 0 <= close <= 2:
+        raise ValueError("eval.iou_close must be an integer in 0..2, got %r" % (close,))
+    return (res, close) if on else None
+
+
 def parse_arguments(args):
     """--key1.key2=value ; --flag (true) ; --flag! (false)"""
     opt_cmd = {}
@@ -281,6 +297,7 @@ def process_options(opt):
     normal_settings(opt)
     mesh_dist_settings(opt)
     emd_settings(opt)
+    iou_settings(opt)
     torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
     for row in HIP_TABLE:
         if row.drives is not None:
