@@ -922,6 +922,62 @@ int sc_voxel_solid(const float* points, const float* origin, const float* pitch,
                    int32_t* shell_voxels, int32_t* solid_voxels, int32_t* sweeps, void* stream);
 int sc_voxel_iou(const int64_t* bits_a, const int64_t* bits_b, int n_images, int words, int32_t* inter, int32_t* uni, void* stream);
 
+/* ---- evaluation: topology, area and volume of indexed triangle meshes (csrc/mesh_topology.hip) ----------------------------------------
+ * A batch of meshes packed one after the other, the form of the sc_marching_cubes_mesh_* and sc_dual_contour_* entry points:
+ * verts [n_verts][3] fp32, faces [n_faces][3] int32 with vertex numbers LOCAL to their image, v_off / f_off [n_images + 1] int64 the
+ * running sums of the per-image counts (v_off[0] = f_off[0] = 0, v_off[n_images] = n_verts, f_off[n_images] = n_faces, ascending).
+ * Image b sees only verts[v_off[b] : v_off[b+1]] and faces[f_off[b] : f_off[b+1]]; everything below is per image, and face numbers
+ * are local to the image as well.  tests/mesh_topology_ref.py restates every rule in numpy.
+ *
+ * Faces.  A face with an index outside [0, v_off[b+1] - v_off[b]) sets *bad_index to 1, is never dereferenced and takes part in
+ *   nothing (the caller raises; the other outputs of the call are then unspecified).  A face with two equal indices is DEGENERATE:
+ *   it is counted in degenerate_faces and takes part in nothing else.
+ * Edges.  An undirected edge is {a, b} of consecutive indices (i0,i1), (i1,i2), (i2,i0) of a non-degenerate face; the face traverses
+ *   it FORWARD when it lists min(a,b) before max(a,b) in that cyclic order.  Per edge: count = the faces on it (two faces with the same
+ *   three indices are two faces), fwd = how many of them traverse it forward, minface = the lowest face number on it.
+ * Components.  Classes of the non-degenerate faces under "share an undirected edge" (every face of an edge is united with the edge's
+ *   minface).  face_component [n_faces] int32 = the lowest local face number of the face's class; -1 for a face that takes no part.
+ * Corners.  A corner is a (face, vertex) pair of a non-degenerate face.  For every edge {a, b} and every face f on it, corner (f, a) is
+ *   united with (minface, a) and (f, b) with (minface, b).  The FANS of a vertex are the corner classes at it; a vertex with more
+ *   than one fan is non-manifold (a pinch point, or two boundary chains that meet in a point).
+ * counts [SC_MESH_TOPOLOGY_FIELDS][n_images] int64, row by row:
+ *    0 vertices               referenced by a non-degenerate face        1 unreferenced_vertices  the others
+ *    2 faces                  non-degenerate                             3 degenerate_faces
+ *    4 edges                  distinct undirected edges                  5 boundary_edges         count == 1
+ *    6 nonmanifold_edges      count >= 3                                 7 inconsistent_edges     count == 2 and fwd != 1
+ *    8 components                                                        9 largest_component_faces
+ *   10 nonmanifold_vertices   more than one fan                         11 euler = vertices - edges + faces
+ *   12 genus = components - euler / 2 when rows 13, 14, 15 are all 1 and faces > 0 (euler is even then), else -1
+ *   13 watertight = boundary_edges == 0 && nonmanifold_edges == 0       14 oriented = inconsistent_edges == 0
+ *   15 manifold = nonmanifold_edges == 0 && nonmanifold_vertices == 0
+ *   An image without faces gets zeros (unreferenced_vertices = its vertices), genus -1 and the three flags 1.
+ * area, volume [n_images] float64.  Per non-degenerate face with vertices p0, p1, p2 widened exactly to float64, every operation
+ *   rounded once (the file is built without contraction; sqrt and the division are the correctly rounded ones):
+ *       e1 = p1 - p0, e2 = p2 - p0;   n = (e1_y e2_z - e1_z e2_y,  e1_z e2_x - e1_x e2_z,  e1_x e2_y - e1_y e2_x);
+ *       area term   = sqrt((n_x n_x + n_y n_y) + n_z n_z) * 0.5;
+ *       c = (p1_y p2_z - p1_z p2_y,  p1_z p2_x - p1_x p2_z,  p1_x p2_y - p1_y p2_x);
+ *       volume term = ((p0_x c_x + p0_y c_y) + p0_z c_z) / 6.0      (signed; meaningful for a watertight, oriented mesh).
+ *   A face that takes no part has the terms +0.0.  Order of the sums: an image's faces are cut into chunks of SC_MESH_TOPOLOGY_CHUNK =
+ *   256 consecutive faces from its first face; a chunk's partial is 0.0 plus its terms in ascending face number, one addition at a
+ *   time; the image's sum is 0.0 plus the chunk partials in ascending chunk number.  Partials are plain stores read by a later
+ *   launch: no float atomics, and the order does not depend on the launch shape, the batch or the stream.
+ * Edge table.  Open addressing in scratch, table_slots slots: a power of two, > 3 n_faces (so every linear probe meets an empty or
+ *   matching slot) and <= 2^30.  The key (global lo << 32) | global hi over image-offset vertex numbers is claimed by a 64-bit
+ *   compare-and-swap on the empty key; count and fwd by integer adds, minface by an integer min.  The two union-finds hook by an
+ *   integer min onto a smaller label, so every find loop walks strictly decreasing labels and ends whatever other threads do.  Only
+ *   integer atomics decide integer outputs: no output depends on arrival order or on table_slots.
+ * Seven launches on `stream` (three when n_faces == 0), no wait on another workgroup, no host synchronisation.  scratch:
+ * sc_mesh_topology_scratch_bytes(n_images, n_verts, n_faces, table_slots) bytes of device memory, 16-byte aligned, contents irrelevant
+ * on entry (the query gives 0 for sizes the entry point refuses).  n_images <= 0 returns 0 and launches nothing;
+ * hipErrorInvalidValue for n_images > 65535, n_faces > 2^26, a negative count, a table_slots that is not such a power of two, a NULL
+ * pointer or a misaligned scratch (verts may be NULL when n_verts == 0, faces and face_component when n_faces == 0).                     */
+#define SC_MESH_TOPOLOGY_CHUNK 256
+#define SC_MESH_TOPOLOGY_FIELDS 16
+long long sc_mesh_topology_scratch_bytes(int n_images, int n_verts, int n_faces, int table_slots);
+int sc_mesh_topology(const float* verts, const int32_t* faces, const int64_t* v_off, const int64_t* f_off, int n_images, int n_verts,
+                     int n_faces, int table_slots, void* scratch, int64_t* counts, double* area, double* volume, int32_t* face_component,
+                     int32_t* bad_index, void* stream);
+
 /* ---- camera algebra of a render -------------------------------------------------------------------
  * sc_camera_rays_*: utils/camera.py:157-196 (get_center_and_ray on the rendered pixels only) + the normalisation of
  * model/renderer.py:69-76.  pose [n_images][3][4] = [R|t] world->camera, intr [n_images][3][3], ray_idx

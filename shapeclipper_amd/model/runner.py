@@ -121,6 +121,44 @@ def iou_line(r, cols):
     return IOU_LINE % (int(r[0]), int(r[1]), float(r[cols[0]]), *(int(r[c]) for c in cols[1:]))
 
 
+# a line of mesh_stats.txt: idx vertices faces edges boundary nonmanifold_edges nonmanifold_vertices inconsistent degenerate unreferenced
+# components largest_faces euler genus watertight oriented manifold area volume
+MESH_STATS_LINE = "%d" + " %d" * 16 + " %.8f %.8f\n"
+MESH_STATS_KEYS = ("vertices", "faces", "edges", "boundary_edges", "nonmanifold_edges", "nonmanifold_vertices", "inconsistent_edges",
+                   "degenerate_faces", "unreferenced_vertices", "components", "largest_component_faces", "euler", "genus", "watertight",
+                   "oriented", "manifold", "area", "volume")
+MESH_STATS_COLS = (("", 1), ("_dual", 20))      # the first of a mesh's 18 columns in a row of _mesh_stats_records
+
+
+def _mesh_stats_records(var, key="mesh_stats"):
+    """[B,20] float64 on the host, a record per sample of eval_3D.mesh_stats' result var[key]: idx, the 18 values of MESH_STATS_KEYS (the
+    counts are exact in float64), category."""
+    stats = var[key]
+    stats = stats._asdict() if hasattr(stats, "_asdict") else stats
+    cols = [var.idx] + [stats[k] for k in MESH_STATS_KEYS] + [var.category_label]
+    return torch.stack([c.detach().double().view(-1).cpu() for c in cols], dim=1)
+
+
+def _mesh_stats_rows(var):
+    """_mesh_stats_records of the marching-cubes mesh; [B,38] with the 18 values of the dual-contouring mesh behind them when
+    --eval.dual_mesh gave var.mesh_stats_dual."""
+    rec = _mesh_stats_records(var)
+    return rec if "mesh_stats_dual" not in var else torch.cat([rec, _mesh_stats_records(var, "mesh_stats_dual")[:, 1:19]], dim=1)
+
+
+def mesh_stats_line(r, first=1):
+    """The line of mesh_stats.txt (or mesh_stats_dual.txt) of one row of _mesh_stats_records."""
+    return MESH_STATS_LINE % (int(r[0]), *(int(r[c]) for c in range(first, first + 16)), float(r[first + 16]), float(r[first + 17]))
+
+
+def _write_mesh_stats_lines(path, rows, mode="w"):
+    """mesh_stats.txt at `path` (and mesh_stats_dual.txt beside it for rows that carry the dual mesh's columns) from _mesh_stats_rows."""
+    for suffix, first in MESH_STATS_COLS[:1 if rows.shape[1] < 38 else 2]:
+        with open(os.path.join(path, "mesh_stats{}.txt".format(suffix)), mode) as f:
+            for r in rows:
+                f.write(mesh_stats_line(r, first))
+
+
 TEXTURE_LINE = "%d %d %d %d %.6f %.6f\n"     # a line of texture.txt: idx faces atlas rows err_mean err_max
 
 
@@ -481,6 +519,7 @@ class Runner:
         mesh_recs = []                                  # --eval.mesh_dist: _mesh_records of every batch
         emd_recs = []                                   # --eval.emd: _emd_records of every batch
         iou_recs = []                                   # --eval.iou: _iou_records of every batch
+        stats_recs = []                                 # --eval.mesh_stats: _mesh_stats_rows of every batch
         loader = tqdm.tqdm(self.test_loader, desc="evaluating", leave=False)
         for it, batch in enumerate(loader):
             var = self.evaluate_batch(opt, edict(batch), ep, it, single_gpu=True)
@@ -501,6 +540,8 @@ class Runner:
                 emd_recs.append(_emd_records(var))
             if "iou" in var:
                 iou_recs.append(_iou_records(var))
+            if "mesh_stats" in var:
+                stats_recs.append(_mesh_stats_rows(var))
             metric["dist_acc"] += dist_acc * len(var.idx)
             metric["dist_cov"] += dist_cov * len(var.idx)
             loader.set_postfix(CD="{:.3f}".format(float((dist_acc + dist_cov) / 2)))
@@ -538,6 +579,8 @@ class Runner:
                 self._write_emd(opt, torch.cat(emd_recs), per_sample=False)
             if iou_recs:                                # iou_cat.txt (and iou_cat_icp.txt); likewise
                 self._write_iou(opt, torch.cat(iou_recs), per_sample=False)
+            if stats_recs:                              # mesh_stats_cat.txt (and mesh_stats_cat_dual.txt); likewise
+                self._write_mesh_stats(opt, torch.cat(stats_recs), per_sample=False)
         n = max(len(self.test_data), 1)
         for k in metric:
             metric[k] /= n
@@ -556,7 +599,8 @@ class Runner:
         nc_cat.txt and their _icp namesakes, from one more gather again; with --eval.mesh_dist also completeness_mesh.txt /
         cd_cat_mesh.txt / f_score_mesh.txt and, with --eval.dual_mesh, their _dual namesakes, from one more gather; with --eval.emd
         also emd.txt / emd_cat.txt and, with --eval.icp, their _icp namesakes, from one more gather; with --eval.iou also iou.txt /
-        iou_cat.txt and, with --eval.icp, their _icp namesakes, from one more gather).  The value
+        iou_cat.txt and, with --eval.icp, their _icp namesakes, from one more gather; with --eval.mesh_stats also mesh_stats.txt /
+        mesh_stats_cat.txt and, with --eval.dual_mesh, their _dual namesakes, from one more gather).  The value
         returned is the raw one.  Every rank
         writes the per-sample files of its own samples (dump_visuals: PNGs, mesh and point-cloud PLYs)."""
         from ..parallel import gather_eval_records
@@ -565,7 +609,7 @@ class Runner:
         # the reference's single-node convention is rank == device index; the process group's rank is the same number there and stays
         # right when ranks and devices are numbered differently (several nodes; tests/test_gpu_two_ranks.py: two ranks on one GPU)
         rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else util.get_rank(opt)
-        recs, comps, icps, ncs, meshes, emds, texs, mrs, ious = [], [], [], [], [], [], [], [], []
+        recs, comps, icps, ncs, meshes, emds, texs, mrs, ious, stats = [], [], [], [], [], [], [], [], [], []
         for it in range(rank, len(self.test_data), opt.world_size):
             sample = self.test_data[it]
             batch = {k: ({kk: vv[None] for kk, vv in v.items()} if isinstance(v, dict) else torch.as_tensor(v)[None]) for k, v in sample.items()}
@@ -587,6 +631,8 @@ class Runner:
                 emds.append(_emd_records(var))
             if "iou" in var:                            # --eval.iou: _iou_records' columns
                 ious.append(_iou_records(var))
+            if "mesh_stats" in var:                     # --eval.mesh_stats: _mesh_stats_rows' columns
+                stats.append(_mesh_stats_rows(var))
             if "texture" in var and options.texture_texels(opt) is not None:    # --eval.texture: _texture_records' columns (dump_geometry baked the atlas)
                 texs.append(_texture_records(var))
             if "mesh_render" in var:                    # --eval.mesh_render: _mesh_render_records' columns (dump_geometry rendered)
@@ -623,6 +669,11 @@ class Runner:
             width = 10 if options.icp_settings(opt) is None else 17
             allv = gather_eval_records(torch.cat(ious).to(dev) if ious else torch.zeros(0, width, device=dev, dtype=torch.float64),
                                        opt.world_size).cpu()
+        alls = None
+        if options.mesh_stats_settings(opt):            # likewise
+            width = 20 if options.dual_mesh_reg(opt) is None else 38
+            alls = gather_eval_records(torch.cat(stats).to(dev) if stats else torch.zeros(0, width, device=dev, dtype=torch.float64),
+                                       opt.world_size).cpu()
         allt = None
         if options.texture_texels(opt) is not None and util_vis is not None:      # likewise
             allt = gather_eval_records(torch.cat(texs).to(dev) if texs else torch.zeros(0, 6, device=dev, dtype=torch.float64),
@@ -636,6 +687,8 @@ class Runner:
             _write_mesh_render(opt, allmr)
         if rank == 0 and allt is not None:
             _write_texture(opt, allt)
+        if rank == 0 and alls is not None:
+            self._write_mesh_stats(opt, alls)
         if rank == 0 and allv is not None:
             self._write_iou(opt, allv)
         if rank == 0 and alle is not None:
@@ -760,6 +813,28 @@ class Runner:
                     n = sel.shape[0] + 0.001
                     f.write("%.4f %5d %s\n" % (float(sel[:, cols[0]].sum()) / n, n, names[c]))
 
+    def _write_mesh_stats(self, opt, alls, per_sample=True):
+        """The files of --eval.mesh_stats from _mesh_stats_rows' rows in sample order, float64: mesh_stats.txt (MESH_STATS_LINE per sample;
+        per_sample=False leaves it to dump_results) and mesh_stats_cat.txt, per category in cd_cat.txt's style: the share of samples whose
+        mesh is watertight and manifold, the mean number of components, and the mean genus over the samples whose genus is >= 0 (0 when
+        there is none).  Rows [N,38] (with --eval.dual_mesh) carry the dual-contouring mesh in columns 20..37, which go to
+        mesh_stats_dual.txt and mesh_stats_cat_dual.txt."""
+        C = opt.data.num_classes
+        names = getattr(self.test_data, "label2cat", {i: str(i) for i in range(C)})
+        if per_sample:
+            _write_mesh_stats_lines(opt.output_path, alls)
+        for suffix, first in MESH_STATS_COLS[:1 if alls.shape[1] < 38 else 2]:
+            comps, genus, water, manifold = (first + MESH_STATS_KEYS.index(k) for k in ("components", "genus", "watertight", "manifold"))
+            with open(os.path.join(opt.output_path, "mesh_stats_cat{}.txt".format(suffix)), "w") as f:
+                f.write("Closed Comps   Genus  Count Cat\n")
+                for c in range(C):
+                    sel = alls[alls[:, 19] == c]
+                    n = sel.shape[0] + 0.001
+                    closed = float(((sel[:, water] != 0) & (sel[:, manifold] != 0)).sum()) / n
+                    g = sel[sel[:, genus] >= 0][:, genus]
+                    f.write("%.4f %.4f %.4f %5d %s\n" % (closed, float(sel[:, comps].sum()) / n, float(g.sum()) / (g.shape[0] + 0.001), n,
+                                                         names[c]))
+
     def evaluate_batch(self, opt, var, ep=None, it=None, single_gpu=False, visualize=False):
         var = util.move_to_device(var, opt.device)
         return self.graph.module(opt, var, training=False, visualize=visualize, get_loss=False)
@@ -786,12 +861,14 @@ class Runner:
         its TensorBoard grids -- the visualize=True render, the n_views turn-table (batched on the HIP chain), the mesh and the dumps."""
         renderer = self.graph.module.renderer
         batched = not renderer.eager and opt.camera.model == "perspective"
-        for sample in self.viz_data:
+        for n, sample in enumerate(self.viz_data):
             var = self.evaluate_batch(opt, edict(deepcopy(sample)), ep, 0, single_gpu=True, visualize=True)
             var = self.graph.module.get_rotate_pose(opt, var, n_views=n_views)
             self.vis_rotate(opt, var, n_views=n_views, batched=batched)
             eval_3D.eval_metrics(opt, var, self.graph.module.sdf_network, vis_only=True)
             self.dump_train_vis(opt, var, ep)
+            if "mesh_stats" in var:                     # --eval.mesh_stats: vis_{ep}/mesh_stats.txt of the visualised samples
+                _write_mesh_stats_lines("{}/vis_{}".format(opt.output_path, ep), _mesh_stats_records(var), "w" if n == 0 else "a")
 
     @torch.no_grad()
     def vis_rotate(self, opt, var, n_views=50, vis_NN=False, batched=False, chunk_views=None):
@@ -1047,6 +1124,8 @@ class Runner:
                     with open("{}/iou{}.txt".format(opt.output_path, suffix), "w" if write_new else "a") as f:
                         for r in rec:
                             f.write(iou_line(r, cols))
+            if "mesh_stats" in var:                     # --eval.mesh_stats: MESH_STATS_LINE (and the same for the dual mesh)
+                _write_mesh_stats_lines(opt.output_path, _mesh_stats_rows(var), "w" if write_new else "a")
             if "emd" in var:                            # --eval.emd: idx n emd rounds converged (and the same after ICP)
                 rec = _emd_records(var)
                 for suffix, cols in (("", [2, 3, 4]), ("_icp", [6, 7, 8]))[:1 if rec.shape[1] < 9 else 2]:

@@ -2327,3 +2327,94 @@ def voxel_iou(bits_a, bits_b):
         code = lib.sc_voxel_iou(_lib.ptr(bits_a), _lib.ptr(bits_b), B, bits_a[0].numel(), _lib.ptr(inter), _lib.ptr(union), _lib.stream())
     _lib.check(code, "sc_voxel_iou")
     return inter, union
+
+
+# ---- evaluation: topology, area and volume of indexed triangle meshes (csrc/mesh_topology.hip) -----------------------------------------
+MESH_TOPOLOGY_MAX_IMAGES = 65535
+MESH_TOPOLOGY_MAX_FACES = 1 << 26
+MESH_TOPOLOGY_MAX_SLOTS = 1 << 30
+MESH_TOPOLOGY_COUNTS = ("vertices", "unreferenced_vertices", "faces", "degenerate_faces", "edges", "boundary_edges", "nonmanifold_edges",
+                        "inconsistent_edges", "components", "largest_component_faces", "nonmanifold_vertices", "euler", "genus")
+MESH_TOPOLOGY_FLAGS = ("watertight", "oriented", "manifold")        # rows 13..15 of sc_mesh_topology's counts (SC_MESH_TOPOLOGY_FIELDS = 16)
+MeshTopology = collections.namedtuple("MeshTopology", MESH_TOPOLOGY_COUNTS + MESH_TOPOLOGY_FLAGS + ("area", "volume", "face_component"))
+
+
+def mesh_topology_slots(n_faces: int) -> int:
+    """The default size of mesh_topology's edge table: the smallest power of two >= 6 n_faces + 2, twice the half-edges and more."""
+    return 1 << (6 * n_faces + 1).bit_length()
+
+
+def mesh_topology(verts, faces, v_count, f_count, table_slots=None):
+    """B triangle meshes packed one after the other, exactly what isosurface_mesh and dual_contour_mesh return -- verts [V,3] fp32 and
+    faces [F,3] int32 on the device, indices LOCAL to the image's vertex slice, v_count / f_count [B] int64 or int32 (on the host, as
+    those two return them, or on the device) -> MeshTopology of [B] int64 device tensors vertices (referenced ones), unreferenced_vertices,
+    faces (non-degenerate), degenerate_faces, edges, boundary_edges (one face), nonmanifold_edges (three or more), inconsistent_edges
+    (two faces that traverse the edge the same way), components (what trimesh.split returns), largest_component_faces,
+    nonmanifold_vertices (more than one fan of corners), euler = V - E + F and genus (components - euler / 2 for a watertight, oriented,
+    manifold mesh with faces; -1 otherwise); [B] bool watertight, oriented, manifold; [B] float64 area and signed volume (fixed-order
+    sums); and face_component [F] int32, the lowest local face number of the face's component (-1 for a degenerate face).
+    include/shapeclipper_hip.h states every rule (sc_mesh_topology); tests/mesh_topology_ref.py restates them in numpy.  An image
+    without faces gets zeros, genus -1 and the flags as defined (all true).
+
+    The edges are matched in an open-addressing table of `table_slots` slots in the scratch cache ("mesh topology"): a power of two
+    greater than 3 F, by default mesh_topology_slots(F) >= 6 F (for tests: no output depends on it).  Integer atomics only decide the
+    integer outputs and no float is accumulated by an atomic: the same bits from run to run, for any batch and stream.
+
+    ValueError for wrong dtypes, shapes or devices, counts that are negative or do not sum to the packed lengths, a bad table_slots --
+    all before any launch -- and for a face index outside its image's vertex range: that is checked on the device (such a face is
+    never dereferenced) and raised after the launches.
+
+    Host synchronisation: one read of a 4-byte flag after the launches (the index check).  Runs on the current stream."""
+    who = "shapeclipper_amd: mesh_topology"
+    for name, t, dtypes in (("verts", verts, (torch.float32,)), ("faces", faces, (torch.int32,)),
+                            ("v_count", v_count, (torch.int64, torch.int32)), ("f_count", f_count, (torch.int64, torch.int32))):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
+        if t.dtype not in dtypes:
+            raise ValueError("%s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype))
+    for name, t in (("verts", verts), ("faces", faces)):
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("%s: %s must be [n,3], got %s" % (who, name, tuple(t.shape)))
+        if not t.is_cuda:
+            raise ValueError("%s: %s is a CPU tensor; the HIP kernels need device tensors (no CPU fallback)" % (who, name))
+    if faces.device != verts.device:
+        raise ValueError("%s: faces is on %s, verts is on %s" % (who, faces.device, verts.device))
+    if v_count.dim() != 1 or v_count.shape != f_count.shape:
+        raise ValueError("%s: v_count and f_count must be [B], got %s and %s" % (who, tuple(v_count.shape), tuple(f_count.shape)))
+    for name, t in (("v_count", v_count), ("f_count", f_count)):
+        if t.is_cuda and t.device != verts.device:
+            raise ValueError("%s: %s is on %s, verts is on %s" % (who, name, t.device, verts.device))
+    B, V, F, dev = v_count.shape[0], verts.shape[0], faces.shape[0], verts.device
+    if B > MESH_TOPOLOGY_MAX_IMAGES or F > MESH_TOPOLOGY_MAX_FACES or V > 2 ** 31 - 1:
+        raise ValueError("%s takes at most %d images, 2^26 faces and 2^31 - 1 vertices per call, got %d, %d and %d"
+                         % (who, MESH_TOPOLOGY_MAX_IMAGES, B, F, V))
+    if table_slots is None:
+        table_slots = mesh_topology_slots(F)
+    if (isinstance(table_slots, bool) or not isinstance(table_slots, int) or table_slots < 1 or table_slots & (table_slots - 1)
+            or table_slots <= 3 * F or table_slots > MESH_TOPOLOGY_MAX_SLOTS):
+        raise ValueError("%s: table_slots must be a power of two greater than 3 F = %d (and at most 2^30), got %r" % (who, 3 * F, table_slots))
+    counts_host = torch.stack([v_count.long(), f_count.long()]).cpu()               # free for host counts, the form the meshers return
+    if B and int(counts_host.min()) < 0 or int(counts_host[0].sum()) != V or int(counts_host[1].sum()) != F:
+        raise ValueError("%s: v_count / f_count must be non-negative and sum to the packed lengths (%d vertices, %d faces), got sums %d and %d"
+                         % (who, V, F, int(counts_host[0].sum()), int(counts_host[1].sum())))
+    counts = torch.empty(len(MESH_TOPOLOGY_COUNTS) + len(MESH_TOPOLOGY_FLAGS), B, device=dev, dtype=torch.int64)
+    measures = torch.empty(2, B, device=dev, dtype=torch.float64)
+    face_component = torch.empty(F, device=dev, dtype=torch.int32)
+    if B > 0:
+        offsets = torch.zeros(2, B + 1, dtype=torch.int64)
+        offsets[:, 1:] = counts_host.cumsum(1)
+        offsets = offsets.to(dev)
+        bad = torch.empty(1, device=dev, dtype=torch.int32)
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            ws = _scratch("mesh topology", dev, (lib.sc_mesh_topology_scratch_bytes(B, V, F, table_slots) + 3) // 4)
+            code = lib.sc_mesh_topology(_lib.ptr(verts.contiguous()) if V else None, _lib.ptr(faces.contiguous()) if F else None,
+                                        _lib.ptr(offsets[0]), _lib.ptr(offsets[1]), B, V, F, table_slots, _lib.ptr(ws), _lib.ptr(counts),
+                                        _lib.ptr(measures[0]), _lib.ptr(measures[1]), _lib.ptr(face_component) if F else None,
+                                        _lib.ptr(bad), _lib.stream())
+        _lib.check(code, "sc_mesh_topology")
+        if int(bad.item()):
+            raise ValueError("%s: a face index lies outside its image's vertex range [0, v_count[b])" % who)
+    n = len(MESH_TOPOLOGY_COUNTS)
+    return MeshTopology(*counts[:n].unbind(0), *(counts[n + k] != 0 for k in range(len(MESH_TOPOLOGY_FLAGS))), measures[0], measures[1],
+                        face_component)

@@ -23,6 +23,8 @@ Call surface of the reference's utils/eval_3D.py.
   * iou_metrics (`--eval.iou`): the volumetric IoU of the two clouds, each turned into a solid of `--eval.iou_res`^3 voxels the same way
     -- shell, closing, fill of what the exterior cannot reach (ops.voxel_solid, csrc/voxel_solid.hip: one workgroup per cloud, the whole
     flood in LDS) -- reported beside Chamfer: the first number of that table, in the clouds' own frame.
+  * mesh_stats (`--eval.mesh_stats`): watertightness, manifoldness, orientation, components, genus, area and volume of the meshes that
+    are written, from an edge table and two union-finds on the device (ops.mesh_topology, csrc/mesh_topology.hip).
   * meshes_dual (`--eval.dual_mesh`): the dual-contouring mesh of the same grid from the SDF gradients at the crossings
     (csrc/dual_contour.hip), which keeps corners and creases that marching cubes chamfers at the grid pitch.
 """
@@ -446,7 +448,7 @@ def mesh_render_sample(opt, var, textured):
 
 
 @torch.no_grad()
-def meshes_dual(opt, sdf_network, proj_latent_sdf, level_vox, reg):
+def meshes_dual(opt, sdf_network, proj_latent_sdf, level_vox, reg, keep=None):
     """level_vox [B,S,S,S] (compute_level_grid) -> per image (vertices [Vd,3] fp32, faces [Fd,3] int32) on the device: the dual-contouring
     mesh of ops.dual_contour_mesh (`--eval.dual_mesh`, {idx}_mesh_dual.ply), which puts one vertex INSIDE every surface cell, where the
     tangent planes of the cell's crossings meet, so corners and creases narrower than the grid pitch survive; `reg` holds the vertex near
@@ -455,7 +457,8 @@ def meshes_dual(opt, sdf_network, proj_latent_sdf, level_vox, reg):
     The normals are the unit SDF gradients at the crossing vertices of ops.isosurface_mesh, queried at mesh_attributes' positions in its
     padded one-launch layout (one ops.sdf_forward with d sdf/dx; sdf_network.eager: stock operators, model/eager_path.py).  The written
     vertices take meshes_device's v / S (hi - lo) + lo, so the mesh overlays {idx}_mesh.ply.  The crossing vertices are extracted twice,
-    here for the queries and again inside dual_contour_mesh, whose public form takes the grid and the normals."""
+    here for the queries and again inside dual_contour_mesh, whose public form takes the grid and the normals.  keep (the batch's var):
+    keep.mesh_dual_packed = [verts, faces, v_count, f_count] as ops.dual_contour_mesh returned them, when there is a mesh."""
     lo, hi = opt.eval.range
     B, S = level_vox.shape[0], level_vox.shape[1]
     dev = level_vox.device
@@ -474,6 +477,8 @@ def meshes_dual(opt, sdf_network, proj_latent_sdf, level_vox, reg):
     normal = torch.nn.functional.normalize(grad.detach(), dim=1, eps=1e-12)
     normals = torch.cat([normal[b * P:b * P + n] for b, n in enumerate(v_count.tolist())])
     dverts, dfaces, dv_count, df_count = ops.dual_contour_mesh(level_vox, normals, 0.0, reg)
+    if keep is not None:                    # the packed mesh in grid-index units, for mesh_stats
+        keep.mesh_dual_packed = [dverts, dfaces, dv_count, df_count]
     dverts = dverts / S * (hi - lo) + lo
     dv_end, df_end = torch.cumsum(dv_count, 0).tolist(), torch.cumsum(df_count, 0).tolist()
     dv_start, df_start = [0] + dv_end[:-1], [0] + df_end[:-1]
@@ -663,7 +668,7 @@ def mesh_metrics(opt, var, sdf_network, frame):
     measure(meshes_device(var.level_vox, lo, hi), "mesh")
     reg = options.dual_mesh_reg(opt)
     if reg is not None:
-        var.mesh_dual = meshes_dual(opt, sdf_network, var.proj_latent_sdf, var.level_vox, reg)
+        var.mesh_dual = meshes_dual(opt, sdf_network, var.proj_latent_sdf, var.level_vox, reg, keep=var)
         measure(var.mesh_dual, "dual")
 
 
@@ -737,6 +742,45 @@ def voxel_centres(bits, origin, pitch):
     return ((index + 0.5) * pitch.float() + origin.float()).cpu()
 
 
+@torch.no_grad()
+def mesh_stats(opt, var, sdf_network=None):
+    """`--eval.mesh_stats`: is the mesh that is written a valid surface?  ops.mesh_topology (csrc/mesh_topology.hip) on the mesh of
+    ops.isosurface_mesh(var.level_vox) -- the faces of {idx}_mesh.ply, _mesh_color.ply and _mesh_tex.obj -- with the vertices at the
+    positions the level grid was sampled at, lo + v (hi - lo) / (S - 1), so that area and volume are in object units.  Sets
+    var.mesh_stats: ops.MeshTopology as a dict (var keeps dicts with attribute access; a tuple would become a plain list) -- per image
+    vertices, faces, edges, boundary / non-manifold / inconsistent edges, non-manifold vertices, degenerate faces, unreferenced
+    vertices, components, largest_component_faces, euler, genus, the flags watertight, oriented, manifold, area, volume -- and
+    face_component [F].  The packed mesh stays in var.mesh_packed = [verts (grid-index units), faces, v_count, f_count] and is taken
+    from there when it is already present.  With `--eval.dual_mesh`: the same for the dual-contouring mesh in var.mesh_stats_dual,
+    from var.mesh_dual_packed when --eval.mesh_dist left it there, else built here with sdf_network (var.mesh_dual then serves the
+    dump); without a network and without that mesh the dual statistics are left out.  Nothing is repaired, nothing enters a loss."""
+    lo, hi = opt.eval.range
+    S = var.level_vox.shape[1]
+    B = var.level_vox.shape[0]
+
+    def measure(packed):
+        verts, faces, v_count, f_count = packed
+        stats = ops.mesh_topology((lo + verts * ((hi - lo) / (S - 1))).contiguous(), faces, v_count, f_count)
+        return stats._asdict()
+
+    if "mesh_packed" not in var:
+        var.mesh_packed = list(ops.isosurface_mesh(var.level_vox))
+    var.mesh_stats = measure(var.mesh_packed)
+    reg = options.dual_mesh_reg(opt)
+    if reg is None:
+        return
+    if "mesh_dual_packed" not in var and sdf_network is not None:
+        dual = meshes_dual(opt, sdf_network, var.proj_latent_sdf, var.level_vox, reg, keep=var)
+        if "mesh_dual" not in var:
+            var.mesh_dual = dual
+        if "mesh_dual_packed" not in var:       # no crossing vertex in the whole batch
+            dev = var.level_vox.device
+            var.mesh_dual_packed = [torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.int32, device=dev),
+                                    torch.zeros(B, dtype=torch.int64), torch.zeros(B, dtype=torch.int64)]
+    if "mesh_dual_packed" in var:
+        var.mesh_stats_dual = measure(var.mesh_dual_packed)
+
+
 def icp_summary(var):
     """[B,5] float64 on the host, a row of icp.txt per sample: s, the rotation angle in degrees, |t|, the first and the last objective."""
     T, s, obj = (var.icp[k].detach().cpu().double() for k in ("transform", "s", "objective"))
@@ -787,6 +831,8 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     var.dpc_pred = normalize_pc(var.dpc_pred)
     var.dpc.points = normalize_pc(var.dpc.points)
     if vis_only:
+        if options.mesh_stats_settings(opt):    # vis_{ep}/mesh_stats.txt of --hip.train_vis
+            mesh_stats(opt, var, sdf_network)
         return
     dist_acc, dist_comp, idx1, idx2 = chamfer_distance(opt, X1=var.dpc_pred, X2=var.dpc.points)
     var.f_score = compute_fscore(dist_acc, dist_comp, opt.eval.f_thresholds)
@@ -809,4 +855,6 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     iou = options.iou_settings(opt)
     if iou is not None:                     # likewise
         iou_metrics(opt, var, *iou, icp=aligned)
+    if options.mesh_stats_settings(opt):    # likewise
+        mesh_stats(opt, var, sdf_network)
     return dist_acc.mean(), dist_comp.mean()

@@ -201,6 +201,16 @@ def iou_settings(opt):
     return (res, close) if on else None
 
 
+def mesh_stats_settings(opt):
+    """The evaluation's mesh statistics: True when `--eval.mesh_stats` is set (absent means off) -- eval_3D.mesh_stats then reports
+    watertightness, manifoldness, orientation, components, genus, area and volume of the meshes that are written (ops.mesh_topology).
+    An evaluation setting beside eval.vox_res, not a hip.* switch.  A value that is not a bool is a ValueError."""
+    on = (opt.get("eval", None) or {}).get("mesh_stats", False)
+    if not isinstance(on, bool):
+        raise ValueError("eval.mesh_stats must be a bool, got %r" % (on,))
+    return on
+
+
 def parse_arguments(args):
     """--key1.key2=value ; --flag (true) ; --flag! (false)"""
     opt_cmd = {}
@@ -298,6 +308,7 @@ def process_options(opt):
     mesh_dist_settings(opt)
     emd_settings(opt)
     iou_settings(opt)
+    mesh_stats_settings(opt)
     torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
     for row in HIP_TABLE:
         if row.drives is not None:
