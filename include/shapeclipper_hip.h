@@ -338,9 +338,32 @@ long long sc_clip_vit_workspace_bytes(int B, int C, int H, int W, int patch, int
 int sc_clip_vit_forward(const float* image, int B, int C, int H, int W, int patch, int D, int mlp, int layers,
                         int heads, int proj_dim, const uint16_t* w_bf16, const float* w_f32, float ln_eps,
                         float* out, void* workspace, long long workspace_bytes, void* stream);
-/* out[M][N] = A[M][K] (bf16) * Wt[N][K]^T (bf16) + bias; epi 0: fp32 store, 1: fp32 +=, 2: quick_gelu -> bf16,
- * 3: bf16.  K % 64 == 0.                                                                               */
+/* out[M][N] = A[M][K] (bf16) * Wt[N][K]^T (bf16) + bias (bias may be NULL); epi 0: fp32 store, 1: fp32 +=, 2: quick_gelu -> bf16,
+ * 3: bf16.  M, N, K > 0, K % 64 == 0 and 0 <= epi <= 3, anything else is refused (hipErrorInvalidValue, nothing launched).
+ * Kernel branches (one decision, gemm_plan in csrc/clip_vit.hip, which sc_gemm_plan reports; first match wins):
+ *   t128 = ceil(N/128) ceil(M/128), t256 = (N/256) ceil(M/256), t192 = (N/192) ceil(M/256); `fits`: (M + 256) N 4, (M + 256) K 2 and
+ *   N K 2 bytes each below 4 GiB (32-bit offsets of the buffer resource and the LDS-DMA)
+ *   gemm8p      N % 256 == 0, M >= 2048, t256 >= 200 (SC_GEMM_G8_MIN), fits: gemm8p_kernel, 256 x 256 tiles walked by one workgroup per
+ *               CU (grid = CUs rounded down to 8).  Its last M % 256 rows go to a `thin` tail when they are at most 64, N % 32 == 0,
+ *               K % 256 == 0 and the ragged row tile would open another round of that grid;
+ *   gemm8p_192  epi 0 / 1, N % 192 == 0, M >= 2048, 180 <= t192 <= 256, fits, SC_GEMM_G8_MIN < 2^40: the 256 x 192 form;
+ *   gemm256     N % 256 == 0, M >= 2048, t256 >= 128 (SC_GEMM_T256_MIN) and t256 >= 85 % (SC_GEMM_FILL_PCT) of its rounds of 256:
+ *               gemm256_kernel, one workgroup per tile.  With the default thresholds every such shape is a gemm8p shape: it is
+ *               reached only with SC_GEMM_G8_MIN raised or where `fits` fails;
+ *   t64         t128 < 384 (SC_GEMM_T128_MIN): gemm_bf16_kernel with 64 x 64 tiles, one workgroup per tile;
+ *   persist     N % 8 == 0: gemm_bf16_persist_kernel, 512 resident workgroups walk the 128 x 128 tiles.  With rem = M % 128:
+ *               rem != 0, N % 32 == 0, K % 256 == 0 and the ragged row tile would open another round of 512 (SC_GEMM_PEEL=0: never)
+ *               -> the last rem rows are a `thin` tail; else rem == 0, t128 > 512 and a last round less than 25 % (SC_GEMM_TAIL_PCT)
+ *               full -> the row tiles of that round are a `t64` tail;
+ *   t128        everything else (N % 8 != 0): gemm_bf16_kernel with 128 x 128 tiles, one workgroup per tile.
+ *   thin = gemm_thin_kernel: one workgroup per 32 x 32 block, sixteen waves split K, added in wave order.
+ * The SC_GEMM_* overrides are read from the environment once per process.                                */
 int sc_gemm_bf16(int epi, const uint16_t* A, const uint16_t* Wt, const float* bias, void* out, int M, int N, int K, void* stream);
+/* The plan sc_gemm_bf16 / sc_gemm_f16 and the tower follow for (epi, M, N, K): host only, launches nothing.  cus: compute units the
+ * gemm8p tail rule counts with; cus <= 0 asks the current device (only where the shape reaches that rule).  plan[5] (host memory) =
+ * { main kernel (0 t64, 1 t128, 2 persist, 3 gemm8p, 4 gemm8p_192, 5 gemm256), rows of the main kernel, tail kernel (0 none, 1 thin,
+ * 2 t64), rows of the tail, tiles of the main kernel }.  Refuses what the GEMM refuses.                     */
+int sc_gemm_plan(int epi, int M, int N, int K, int cus, int* plan);
 int sc_f32_to_bf16(const float* x, uint16_t* y, long long n, void* stream);
 /* The same three entry points with IEEE fp16 operands instead of bf16 (16-bit images / activations are fp16 bit patterns, fp32
  * accumulation, LayerNorm / softmax statistics / residual stream in fp32): the arithmetic the reference's dependency uses on a GPU --

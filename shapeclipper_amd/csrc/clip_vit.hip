@@ -22,6 +22,8 @@
 //   attention       MFMA: one workgroup per (image, head), K/Q operands straight from global, V^T in LDS, any token count
 // The attention and LayerNorm launches are made by launch_attention / launch_layernorm, which sc_clip_attention / sc_clip_layernorm
 // export: tests/test_gpu_clip_stages.py compares each stage with float64 on every branch of the launch rule (attention_plan).
+// The GEMM launches are made by launch_gemm from the plan of gemm_plan, which sc_gemm_plan exports: tests/test_gpu_clip_gemm.py asserts the
+// branch of every case from it and compares each kernel with float64 (tests/test_clip_gemm_plan_host.py: the rule itself, no GPU).
 // Bound: the four GEMMs per layer -> bf16 MFMA (dense peak 2.5 PFLOP/s).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -1095,10 +1097,25 @@ __global__ __launch_bounds__(64 * THIN_NW) void gemm_thin_kernel(const bf16_t* _
     }
 }
 
-template <bool H16>
-static int launch_gemm(int epi, const bf16_t* A, const bf16_t* Wt, const float* bias, void* out, int M, int N, int K,
-                       hipStream_t st) {
-    if (K % 64) return (int)hipErrorInvalidValue;
+// The GEMM launch decision, in one place for the tower, sc_gemm_bf16 / sc_gemm_f16 and sc_gemm_plan (include/shapeclipper_hip.h states
+// the rule branch by branch): the main kernel gets the first main_rows rows, the tail kernel the tail_rows after them.
+enum { GEMM_T64 = 0, GEMM_T128, GEMM_PERSIST, GEMM_G8P, GEMM_G8P_192, GEMM_256 };
+enum { GEMM_TAIL_NONE = 0, GEMM_TAIL_THIN, GEMM_TAIL_T64 };
+struct GemmPlan { int main, main_rows, tail, tail_rows, tiles, cus; };     // tiles: of the main kernel; cus: what the gemm8p forms launch with
+// cus <= 0: the current device's count, asked only where a gemm8p form is taken.  Returns 0 or a hipError_t.
+static int gemm_plan(int epi, int M, int N, int K, int cus, GemmPlan& p) {
+    if (M <= 0 || N <= 0 || K <= 0 || (K % 64) || epi < 0 || epi > 3) return (int)hipErrorInvalidValue;
+    auto device_cus = [&cus]() -> int {
+        if (cus > 0) return 0;
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
+        static std::atomic<int> cu_cache[64];
+        if (dev >= 0 && dev < 64 && cu_cache[dev].load()) { cus = cu_cache[dev].load(); return 0; }
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return (int)hipGetLastError();
+        if (dev >= 0 && dev < 64) cu_cache[dev].store(cus);
+        return 0;
+    };
+    p = GemmPlan{GEMM_T64, M, GEMM_TAIL_NONE, 0, 0, 0};
     // 128-wide tiles when they give every CU work (>= 1.5 workgroups per CU), 64-wide ones otherwise
     const long long t128 = (long long)((N + 127) / 128) * ((M + 127) / 128);
     static const long long t128_min = [] { const char* e = getenv("SC_GEMM_T128_MIN"); return e ? atoll(e) : 384LL; }();   // tuning override
@@ -1132,34 +1149,18 @@ static int launch_gemm(int epi, const bf16_t* A, const bf16_t* Wt, const float* 
     static const long long g8_min = [] { const char* e = getenv("SC_GEMM_G8_MIN"); return e ? atoll(e) : 200LL; }();              // tuning override
     if ((N % 256) == 0 && M >= 2048 && t256 >= g8_min && (unsigned long long)(M + 256) * N * 4ull < (1ull << 32) &&
         (unsigned long long)(M + 256) * K * 2ull < (1ull << 32) && (unsigned long long)N * K * 2ull < (1ull << 32)) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-        static int cu_cache[64] = {0};
-        if (dev >= 0 && dev < 64 && cu_cache[dev]) cus = cu_cache[dev];
-        else {
-            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return (int)hipGetLastError();
-            if (dev >= 0 && dev < 64) cu_cache[dev] = cus;
-        }
+        if (const int rc = device_cus()) return rc;
+        p.main = GEMM_G8P; p.tiles = (int)t256; p.cus = cus;
         // A ragged last row tile that opens another ROUND of the one-workgroup-per-CU grid goes to gemm_thin_kernel instead (ViT-L/14 at batch
         // 32: 8,224 rows = 32 row tiles + 32 rows; fc1 = 33 x 16 = 528 tiles = three rounds of 256, 32 x 16 = 512 = exactly two)
         const int rem8 = M % 256, ntn8 = N / 256;
         const long long t_main = (long long)(M / 256) * ntn8, gridw = (cus / 8) * 8;
         if (rem8 != 0 && rem8 <= 64 && t_main > 0 && gridw > 0 && (N % 32) == 0 && (K % 256) == 0 &&
             (t256 + gridw - 1) / gridw > (t_main + gridw - 1) / gridw) {
-            const int rc8 = g8::launch_gemm8p<H16>(epi, A, Wt, bias, out, M - rem8, N, K, cus, st);
-            if (rc8) return rc8;
-            const size_t esz = (epi == EPI_F32 || epi == EPI_RESID) ? 4 : 2;
-            const bf16_t* A2 = A + (size_t)(M - rem8) * K;
-            void* out2 = (char*)out + (size_t)(M - rem8) * N * esz;
-            switch (epi) {
-                case EPI_F32: hipLaunchKernelGGL((gemm_thin_kernel<EPI_F32, H16>), dim3(N / 32, (rem8 + 31) / 32), dim3(64 * THIN_NW), 0, st, A2, Wt, bias, out2, rem8, N, K); break;
-                case EPI_RESID: hipLaunchKernelGGL((gemm_thin_kernel<EPI_RESID, H16>), dim3(N / 32, (rem8 + 31) / 32), dim3(64 * THIN_NW), 0, st, A2, Wt, bias, out2, rem8, N, K); break;
-                case EPI_GELU_BF16: hipLaunchKernelGGL((gemm_thin_kernel<EPI_GELU_BF16, H16>), dim3(N / 32, (rem8 + 31) / 32), dim3(64 * THIN_NW), 0, st, A2, Wt, bias, out2, rem8, N, K); break;
-                default: hipLaunchKernelGGL((gemm_thin_kernel<EPI_BF16, H16>), dim3(N / 32, (rem8 + 31) / 32), dim3(64 * THIN_NW), 0, st, A2, Wt, bias, out2, rem8, N, K); break;
-            }
-            return (int)hipGetLastError();
+            p.main_rows = M - rem8; p.tiles = (int)t_main;
+            p.tail = GEMM_TAIL_THIN; p.tail_rows = rem8;
         }
-        return g8::launch_gemm8p<H16>(epi, A, Wt, bias, out, M, N, K, cus, st);
+        return 0;
     }
     // ... and its 256 x 192 form for the fp32-output GEMMs with N = 768 (proj / fc2 of ViT-B/32 at 12,800 tokens: 150 tiles of 256 x 256 on 256
     // CUs, 200 of 256 x 192: 32.4 vs 34.4 us and 78.6 vs 90.9 us against the kernels below)
@@ -1167,38 +1168,71 @@ static int launch_gemm(int epi, const bf16_t* A, const bf16_t* Wt, const float* 
     if ((epi == EPI_F32 || epi == EPI_RESID) && (N % 192) == 0 && M >= 2048 && t192 >= 180 && t192 <= 256 && g8_min < (1LL << 40) &&
         (unsigned long long)(M + 256) * N * 4ull < (1ull << 32) && (unsigned long long)(M + 256) * K * 2ull < (1ull << 32) &&
         (unsigned long long)N * K * 2ull < (1ull << 32)) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return (int)hipGetLastError();
-        return g8::launch_gemm8p<H16, 1>(epi, A, Wt, bias, out, M, N, K, cus, st);
+        if (const int rc = device_cus()) return rc;
+        p.main = GEMM_G8P_192; p.tiles = (int)t192; p.cus = cus;
+        return 0;
     }
+    if (big) {                          // one workgroup per 256 x 256 tile
+        p.main = GEMM_256; p.tiles = (int)t256;
+    } else if (small) {
+        p.main = GEMM_T64; p.tiles = ((N + 63) / 64) * ((M + 63) / 64);
+    } else if ((N % 8) == 0) {          // persistent: 2 resident workgroups per CU walk the tile list
+        p.main = GEMM_PERSIST;
+        p.main_rows = peel ? M - rem : tail64 ? M0t : M;
+        p.tiles = (int)(peel ? t_full : tail64 ? main_mt * ntn128 : t128);
+        p.tail = peel ? GEMM_TAIL_THIN : tail64 ? GEMM_TAIL_T64 : GEMM_TAIL_NONE;
+        p.tail_rows = M - p.main_rows;
+    } else {
+        p.main = GEMM_T128; p.tiles = (int)t128;
+    }
+    return 0;
+}
+
+template <bool H16>
+static int launch_gemm(int epi, const bf16_t* A, const bf16_t* Wt, const float* bias, void* out, int M, int N, int K,
+                       hipStream_t st) {
+    GemmPlan p;
+    if (const int rc = gemm_plan(epi, M, N, K, 0, p)) return rc;
+    const int M0 = p.main_rows, M1 = p.tail_rows;
+    const bf16_t* A1 = A + (size_t)M0 * K;                       // the tail's rows
+    void* out1 = (char*)out + (size_t)M0 * N * ((epi == EPI_F32 || epi == EPI_RESID) ? 4 : 2);
 #define SC_LAUNCH(E)                                                                                                          \
-    if (big) {                                                                                                         \
-        (void)hipFuncSetAttribute((const void*)gemm256_kernel<E, H16>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);        \
-        hipLaunchKernelGGL((gemm256_kernel<E, H16>), dim3(N / 256, (M + 255) / 256), dim3(512), 131072, st, A, Wt, bias, out, M, N, K); \
-    } else if (small) {                                                                                                       \
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<E, 64, H16>, hipFuncAttributeMaxDynamicSharedMemorySize,           \
-                                   SC_GEMM64_STAGES * 2 * 64 * 8 * 16);                                                       \
-        hipLaunchKernelGGL((gemm_bf16_kernel<E, 64, H16>), dim3((N + 63) / 64, (M + 63) / 64), dim3(256),                          \
-                           SC_GEMM64_STAGES * 2 * 64 * 8 * 16, st, A, Wt, bias, out, M, N, K);                                \
-    } else if ((N % 8) == 0) {          /* persistent: 2 resident workgroups per CU walk the tile list */                     \
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_persist_kernel<E, H16>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); \
-        hipLaunchKernelGGL((gemm_bf16_persist_kernel<E, H16>), dim3(512), dim3(256), 65536, st, A, Wt, bias, out,                  \
-                           peel ? M - rem : tail64 ? M0t : M, N, K, (N + 127) / 128, (int)(peel ? t_full : tail64 ? main_mt * ntn128 : t128)); \
-        if (tail64) {                                                                                                         \
+    switch (p.main) {                                                                                                         \
+        case GEMM_G8P:                                                                                                        \
+            if (const int rc = g8::launch_gemm8p<H16>(epi, A, Wt, bias, out, M0, N, K, p.cus, st)) return rc;                 \
+            break;                                                                                                            \
+        case GEMM_G8P_192:                                                                                                    \
+            if (const int rc = g8::launch_gemm8p<H16, 1>(epi, A, Wt, bias, out, M0, N, K, p.cus, st)) return rc;              \
+            break;                                                                                                            \
+        case GEMM_256:                                                                                                        \
+            (void)hipFuncSetAttribute((const void*)gemm256_kernel<E, H16>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);    \
+            hipLaunchKernelGGL((gemm256_kernel<E, H16>), dim3(N / 256, (M0 + 255) / 256), dim3(512), 131072, st, A, Wt, bias, out, M0, N, K); \
+            break;                                                                                                            \
+        case GEMM_T64:                                                                                                        \
             (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<E, 64, H16>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
                                        SC_GEMM64_STAGES * 2 * 64 * 8 * 16);                                                   \
-            hipLaunchKernelGGL((gemm_bf16_kernel<E, 64, H16>), dim3((N + 63) / 64, (M - M0t + 63) / 64), dim3(256),                \
-                               SC_GEMM64_STAGES * 2 * 64 * 8 * 16, st, A + (size_t)M0t * K, Wt, bias,                         \
-                               (char*)out + (size_t)M0t * N * ((E) == EPI_F32 || (E) == EPI_RESID ? 4 : 2), M - M0t, N, K);    \
-        }                                                                                                                     \
-        if (peel)                                                                                                             \
-            hipLaunchKernelGGL((gemm_thin_kernel<E, H16>), dim3(N / 32, (rem + 31) / 32), dim3(64 * THIN_NW), 0, st, A + (size_t)(M - rem) * K, Wt, bias, \
-                               (char*)out + (size_t)(M - rem) * N * ((E) == EPI_F32 || (E) == EPI_RESID ? 4 : 2), rem, N, K);  \
-    } else {                                                                                                                  \
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<E, 128, H16>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);  \
-        hipLaunchKernelGGL((gemm_bf16_kernel<E, 128, H16>), dim3((N + 127) / 128, (M + 127) / 128), dim3(256), 65536, st,          \
-                           A, Wt, bias, out, M, N, K);                                                                        \
+            hipLaunchKernelGGL((gemm_bf16_kernel<E, 64, H16>), dim3((N + 63) / 64, (M0 + 63) / 64), dim3(256),                     \
+                               SC_GEMM64_STAGES * 2 * 64 * 8 * 16, st, A, Wt, bias, out, M0, N, K);                           \
+            break;                                                                                                            \
+        case GEMM_PERSIST:                                                                                                    \
+            (void)hipFuncSetAttribute((const void*)gemm_bf16_persist_kernel<E, H16>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); \
+            hipLaunchKernelGGL((gemm_bf16_persist_kernel<E, H16>), dim3(512), dim3(256), 65536, st, A, Wt, bias, out,              \
+                               M0, N, K, (N + 127) / 128, p.tiles);                                                           \
+            break;                                                                                                            \
+        case GEMM_T128:                                                                                                       \
+            (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<E, 128, H16>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); \
+            hipLaunchKernelGGL((gemm_bf16_kernel<E, 128, H16>), dim3((N + 127) / 128, (M0 + 127) / 128), dim3(256), 65536, st,     \
+                               A, Wt, bias, out, M0, N, K);                                                                   \
+            break;                                                                                                            \
+        default: return (int)hipErrorInvalidValue;                                                                            \
+    }                                                                                                                         \
+    if (p.tail == GEMM_TAIL_T64) {                                                                                            \
+        (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<E, 64, H16>, hipFuncAttributeMaxDynamicSharedMemorySize,           \
+                                   SC_GEMM64_STAGES * 2 * 64 * 8 * 16);                                                       \
+        hipLaunchKernelGGL((gemm_bf16_kernel<E, 64, H16>), dim3((N + 63) / 64, (M1 + 63) / 64), dim3(256),                         \
+                           SC_GEMM64_STAGES * 2 * 64 * 8 * 16, st, A1, Wt, bias, out1, M1, N, K);                             \
+    } else if (p.tail == GEMM_TAIL_THIN) {                                                                                    \
+        hipLaunchKernelGGL((gemm_thin_kernel<E, H16>), dim3(N / 32, (M1 + 31) / 32), dim3(64 * THIN_NW), 0, st, A1, Wt, bias, out1, M1, N, K); \
     }
     switch (epi) {
         case EPI_F32: SC_LAUNCH(EPI_F32) break;
@@ -1209,6 +1243,8 @@ static int launch_gemm(int epi, const bf16_t* A, const bf16_t* Wt, const float* 
 #undef SC_LAUNCH
     return (int)hipGetLastError();
 }
+
+
 
 // The attention launch decision for T tokens per image (head dim 64), in one place for the tower and for sc_clip_attention:
 //   Tp = T rounded up to 32; V^T [64][Tp + 4] must fit the 160 KiB of LDS (else the geometry is refused);
@@ -1370,6 +1406,14 @@ int sc_gemm_bf16(int epi, const uint16_t* A, const uint16_t* Wt, const float* bi
 // The same GEMM with IEEE fp16 operands (A, Wt and the 16-bit outputs of epilogues 2 / 3 are fp16 bit patterns)
 int sc_gemm_f16(int epi, const uint16_t* A, const uint16_t* Wt, const float* bias, void* out, int M, int N, int K, void* stream_) {
     return sc::launch_gemm<true>(epi, A, Wt, bias, out, M, N, K, (hipStream_t)stream_);
+}
+// The plan both follow (host only; exported for tests): plan[5] = main kernel, its rows, tail kernel, its rows, the main kernel's tiles
+int sc_gemm_plan(int epi, int M, int N, int K, int cus, int* plan) {
+    sc::GemmPlan p;
+    if (plan == nullptr) return (int)hipErrorInvalidValue;
+    if (const int rc = sc::gemm_plan(epi, M, N, K, cus, p)) return rc;
+    plan[0] = p.main; plan[1] = p.main_rows; plan[2] = p.tail; plan[3] = p.tail_rows; plan[4] = p.tiles;
+    return 0;
 }
 
 // One attention stage of the tower on its own (exported for tests): exactly the launch the tower makes per layer.

@@ -123,14 +123,25 @@ def test_clip_knn_indices_match_fp32_oracle():
     assert exact.float().mean() > 0.97
 
 
+def _gemm_plan(epi, M, N, K):
+    """"main kernel[+tail kernel]" of the plan sc_gemm_plan reports for this device: the kernel a GEMM test runs is asserted, not assumed"""
+    import ctypes
+    from shapeclipper_amd import _lib
+    out = (ctypes.c_int * 5)()
+    assert _lib.load().sc_gemm_plan(epi, M, N, K, 0, out) == 0
+    main = ("t64", "t128", "persist", "gemm8p", "gemm8p_192", "gemm256")[out[0]]
+    return main + ("", "+thin", "+t64")[out[2]]
+
+
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
-@pytest.mark.parametrize("M,N,K", [(200, 192, 128), (1600, 768, 768), (12800, 2304, 768)])       # 64-wide tiles / persistent 128-wide tiles
+@pytest.mark.parametrize("M,N,K", [(200, 192, 128), (1600, 768, 768), (12800, 2304, 768)])       # 12 / 300 tiles of 64 x 64; 450 tiles of 256 x 256 (csrc/gemm8p.hpp)
 def test_gemm_16bit_transpose_detecting(M, N, K, dtype):
     """C = A W^T with asymmetric operands (catches swapped row/col in the MFMA C/D mapping); the 16-bit operands are exact inputs,
     so the only error is the fp32 accumulation order."""
     import ctypes
     from shapeclipper_amd import _lib
     lib = _lib.load()
+    assert _gemm_plan(0, M, N, K) == {200: "t64", 1600: "t64", 12800: "gemm8p"}[M]
     dev = torch.device("cuda:0")
     torch.manual_seed(1)
     td = torch.bfloat16 if dtype == "bf16" else torch.float16
@@ -147,6 +158,19 @@ def test_gemm_16bit_transpose_detecting(M, N, K, dtype):
     assert (out - ref).abs().max().item() < 1e-5 * ref.abs().max().item()
 
 
+GEMM_PLANS = {          # per epilogue 0..3, on 256 CUs
+    (12800, 768, 3072): ("gemm8p_192", "gemm8p_192", "persist+t64", "persist+t64"),
+    (8224, 1024, 1024): ("persist+thin",) * 4,
+    (2049, 256, 64): ("t64",) * 4,
+    (12800, 3072, 768): ("gemm8p",) * 4,
+    (8224, 3072, 1024): ("gemm8p",) * 4,
+    (8288, 1024, 4096): ("persist+thin",) * 4,
+    (8224, 4096, 1024): ("gemm8p+thin",) * 4,
+    (2049, 6144, 64): ("gemm8p",) * 4,
+    (4100, 3328, 192): ("gemm8p",) * 4,
+}
+
+
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 @pytest.mark.parametrize("M,N,K", [(12800, 768, 3072), (8224, 1024, 1024), (2049, 256, 64), (12800, 3072, 768),
                                    (8224, 3072, 1024), (8288, 1024, 4096), (8224, 4096, 1024),
@@ -154,11 +178,12 @@ def test_gemm_16bit_transpose_detecting(M, N, K, dtype):
 def test_gemm_256_tiles_all_epilogues(M, N, K, dtype):
     """Round 4: shapes with >= 200 tiles of 256 x 256 (12800 x 3072, 8224 x 3072 / 4096, the last two) run on csrc/gemm8p.hpp -- hand-counted
     vmcnt, residual tile as accumulator init, paired 16-byte 16-bit stores through a buffer resource that ends at row M (tools/micro/gemm_lab
-    `stress` is its race screen: profiles/r04_gemm_stress.txt).
-    The 256 x 256 tile kernel (M >= 2048, N % 256 == 0) and the persistent 128 x 128 kernel with its ragged last rows peeled off into
-    gemm_thin_kernel (8224 = 64 x 128 + 32 rows: ViT-L/14 at batch 32; 8288: 96 rows): every epilogue (fp32, residual accumulate,
-    QuickGELU -> 16 bit, 16 bit) against float64; the residual epilogue must read its rows before it writes them, nothing is written
-    past row M."""
+    `stress` is its race screen: profiles/r04_gemm_stress.txt); 8224 x 4096 with its 32 ragged rows peeled off into gemm_thin_kernel.
+    12800 x 768: the 256 x 192 form of gemm8p for the fp32 epilogues, the persistent 128 x 128 kernel with a 64-wide tail for the 16-bit
+    ones.  8224 / 8288 x 1024: the persistent 128 x 128 kernel with its ragged last rows peeled off into gemm_thin_kernel (8224 = 64 x 128
+    + 32 rows: ViT-L/14 at batch 32; 8288: 96 rows).  2049 x 256: 64 x 64 tiles.  (gemm256_kernel runs for none of them: GEMM_PLANS, asserted
+    below.)  Every epilogue (fp32, residual accumulate, QuickGELU -> 16 bit, 16 bit) against float64; the residual epilogue must read its
+    rows before it writes them, nothing is written past row M."""
     import ctypes
     from shapeclipper_amd import _lib
     lib = _lib.load()
@@ -173,6 +198,7 @@ def test_gemm_256_tiles_all_epilogues(M, N, K, dtype):
     scale = ref.abs().max().item()
     resid = torch.randn(M, N, device=dev)
     for epi in (0, 1, 2, 3):
+        assert _gemm_plan(epi, M, N, K) == GEMM_PLANS[M, N, K][epi]
         if epi == 1:
             out = resid.clone()
             want = ref + resid.double()
