@@ -27,6 +27,7 @@
 // Bound: latency / L2 (12-byte rows gathered by index); about 40 bytes of traffic per source.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "block_scan.hpp"
 #include "shapeclipper_hip.h"
 
 #pragma clang fp contract(off)      // t = (2 g) * (a - b) and the sums below: every operation rounded on its own, whatever the build's flags
@@ -88,27 +89,14 @@ __global__ __launch_bounds__(1024) void cb_scan_local_kernel(CbArgs A, int* __re
     __shared__ int wtot[16];
     const CbDir& D = A.d[blockIdx.z >> 1];
     if (!D.out) return;
-    const int which = blockIdx.z & 1, b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int which = blockIdx.z & 1, b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
     if (blk >= D.nblk) return;
     int* c = ws + (which ? D.rcnt : D.cnt) + (size_t)b * (D.nd + 1);
     const int i = blk * 1024 + tid;
     const int v = i <= D.nd ? c[i] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-        const int t = wtot[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    if (i <= D.nd) c[i] = before + incl - v;
+    int total;
+    const int before = sc_scan::block_exclusive<16>(v, wtot, total);
+    if (i <= D.nd) c[i] = before;
     if (tid == 0) ws[D.block_tot + ((size_t)b * 2 + which) * D.nblk + blk] = total;
 }
 

@@ -3,8 +3,8 @@
 // The reference (external/chamfer3D/chamfer3D.cu:12-134) and chamfer.hip evaluate all N x M ordered pairs: 8 FLOP per pair at the
 // packed-fp32 issue floor of 4 vector instructions per pair (0.39 of the VALU peak, 82 ms for B=32 x 100k x 100k).  The result of
 // the search -- for every query the smallest d = fmaf(dy, dy, dx*dx) + dz*dz over the other cloud and the LOWEST index attaining
-// it -- does not need all pairs.  Here the target cloud is binned into a uniform grid (about CG_TPC targets per cell) and every
-// query walks Chebyshev rings of cells around its own cell:
+// it -- does not need all pairs.  Here the target cloud is binned into a uniform grid (uniform_grid.hpp; about CG_TPC targets per
+// cell) and every query walks Chebyshev rings of cells around its own cell:
 //   * a candidate is evaluated with the SAME expression (dist2 of chamfer_common.hpp, contraction off) and accepted on
 //     d < best || (d == best && index < best_index): the order candidates are met in does not matter, the result is the
 //     reference's "first strict minimum in index order" (chamfer3D.cu:36,46,126);
@@ -30,7 +30,9 @@
 // target within 2-4 cells straight to the scan -- the walk is not where those cases spend their time, and at 0.05-0.09 it made the search
 // 1.3-2x slower (profiles/r04_chamfer_far_tile_rule_experiment.txt).
 // Bound: latency / L2 gathers; the brute-force line stays in bench.py's workloads.
+#include "block_scan.hpp"
 #include "chamfer_common.hpp"
+#include "uniform_grid.hpp"
 #include <limits.h>
 #include <stdlib.h>
 
@@ -46,118 +48,30 @@ constexpr int CG_WAVE_RMAX = 6;     // rings of the wave walk (its candidates co
 constexpr int CG_WAVE_REMPTY = 4;   // rings without any candidate before the wave gives up
 constexpr int CG_WAVE_BUDGET = 16384;   // candidates per WAVE (64 queries of one cell) before its open queries are handed to the scan
 
-struct GridMeta {                  // one per batch element
-    float lo[3], h[3], inv_h[3];
-    int g[3];
-    float slack;
-    int valid;
+struct GridMeta : sc_grid::Geometry {     // one per batch element
     int dense;                     // >= CG_DENSE targets per OCCUPIED cell (a surface, not a volume): the queries walk in waves (5b)
 };
 
 __host__ __device__ inline int cg_cells_capacity(int m) { return m / CG_TPC * 2 + 64; }
 
-// ---- 1. bounding box of the target cloud -> grid geometry ---------------------------------------------------------------------
-// Many workgroups per image: per-wave minima / maxima go into six order-preserving integer keys with atomicMax (the minima as the
-// complement of their key, so that the all-zero state the workspace memset leaves means "nothing yet" for all six); box[6] collects
-// the "not a plain finite coordinate" flag.  One thread per image turns the box into the grid geometry.  (One 1024-thread workgroup
-// per image took 40 us for 100,000 points -- a tenth of a whole batch-1 search.)
-__device__ __forceinline__ unsigned cg_key(float f) {
-    const unsigned u = __float_as_uint(f);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float cg_unkey(unsigned k) {
-    return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
-__global__ __launch_bounds__(256) void cg_bbox_kernel(int m, const float* __restrict__ tgt, unsigned* __restrict__ box_all) {
-    const int b = blockIdx.y, tid = threadIdx.x;
-    const float* t = tgt + (size_t)b * m * 3;
-    float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    int bad = 0, any = 0;
-    for (int k = blockIdx.x * 256 + tid; k < m; k += gridDim.x * 256) {
-        any = 1;
-        for (int a = 0; a < 3; ++a) {
-            const float v = t[(size_t)k * 3 + a];
-            bad |= !(fabsf(v) < 1.0e15f);          // NaN, Inf and magnitudes the padding / slack arithmetic is not made for
-            mn[a] = fminf(mn[a], v); mx[a] = fmaxf(mx[a], v);
-        }
-    }
-    for (int a = 0; a < 3; ++a)
-        for (int d = 32; d >= 1; d >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], d)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], d)); }
-    any = __any(any);
-    bad = __any(bad);
-    unsigned* box = box_all + (size_t)b * 8;
-    if ((tid & 63) == 0 && any) {
-        for (int a = 0; a < 3; ++a) { atomicMax(&box[a], ~cg_key(mn[a])); atomicMax(&box[3 + a], cg_key(mx[a])); }
-        if (bad) atomicOr(&box[6], 1u);
-    }
-}
+// ---- 1, 2, 4. bounding box of the target cloud -> grid geometry; cell of every target + histogram; targets into cell order as
+// {x, y, z, original index} (the order inside a cell is arbitrary, see the acceptance rule): uniform_grid.hpp.  One thread per image
+// turns the box into the geometry with this file's constants.
+using sc_grid::axis_cell;
 
 __global__ void cg_meta_kernel(int m, int n_images, const unsigned* __restrict__ box_all, GridMeta* __restrict__ meta) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_images) return;
-    const unsigned* box = box_all + (size_t)b * 8;
-    {
-        GridMeta g;
-        float ext[3], scale = 0.f, emax = 0.f;
-        for (int a = 0; a < 3; ++a) {
-            const float lo = cg_unkey(~box[a]), hi = cg_unkey(box[3 + a]);
-            g.lo[a] = lo;
-            ext[a] = hi - lo;
-            emax = fmaxf(emax, ext[a]);
-            scale = fmaxf(scale, fmaxf(fabsf(lo), fabsf(hi)));
-        }
-        g.valid = (!box[6] && m > 0 && emax > 0.f) ? 1 : 0;
-        // a flat or thin cloud still gets cells of a sensible size along its thin axes
-        float vol = 1.f;
-        for (int a = 0; a < 3; ++a) { ext[a] = fmaxf(ext[a], emax * 1.0e-3f); vol *= ext[a]; }
-        float h = cbrtf(vol * (float)CG_TPC / (float)(m > 0 ? m : 1));
-        const int cap = cg_cells_capacity(m);
-        for (int it = 0; it < 8; ++it) {           // the per-axis ceil can overshoot the cell budget: grow h until it fits
-            long long cells = 1;
-            for (int a = 0; a < 3; ++a) {
-                int n = (int)ceilf(ext[a] / h);
-                n = n < 1 ? 1 : (n > CG_GMAX ? CG_GMAX : n);
-                g.g[a] = n;
-                cells *= n;
-            }
-            if (cells <= cap) break;
-            h *= 1.26f;
-        }
-        if ((long long)g.g[0] * g.g[1] * g.g[2] > cap) g.valid = 0;
-        for (int a = 0; a < 3; ++a) {
-            g.h[a] = ext[a] / (float)g.g[a];       // cells tile the extent exactly (the last cell also takes x == hi by clamping)
-            g.inv_h[a] = (float)g.g[a] / ext[a];
-        }
-        g.slack = 16.f * 1.1920929e-7f * (scale + emax);
-        if (!g.valid) { g.g[0] = g.g[1] = g.g[2] = 1; }
-        g.dense = 0;                                   // set by the scan of the target histogram
-        meta[b] = g;
-    }
-}
-
-__device__ __forceinline__ int cg_axis_cell(float v, float lo, float inv_h, int g) {
-    const int c = (int)floorf((v - lo) * inv_h);
-    return c < 0 ? 0 : (c >= g ? g - 1 : c);
-}
-
-// ---- 2. cell of every target + histogram -----------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void cg_count_kernel(int m, const float* __restrict__ tgt, const GridMeta* __restrict__ meta, int cap,
-                                                       int* __restrict__ cell_of, int* __restrict__ counts, int only_dense) {
-    const int b = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= m) return;
-    const GridMeta& g = meta[b];
-    if (only_dense && !g.dense) return;            // the query-side binning is for the wave walk only
-    const float* t = tgt + ((size_t)b * m + k) * 3;
-    int c = 0;
-    if (g.valid) {
-        const int cx = cg_axis_cell(t[0], g.lo[0], g.inv_h[0], g.g[0]), cy = cg_axis_cell(t[1], g.lo[1], g.inv_h[1], g.g[1]);
-        const int cz = cg_axis_cell(t[2], g.lo[2], g.inv_h[2], g.g[2]);
-        c = (cz * g.g[1] + cy) * g.g[0] + cx;       // x fastest: a run of cells along x is one contiguous run of sorted targets
-        if (only_dense)                             // the QUERY side is binned by 2 x 2 x 2 TILE of cells (cg_query_wave_kernel)
-            c = ((cz >> 1) * ((g.g[1] + 1) >> 1) + (cy >> 1)) * ((g.g[0] + 1) >> 1) + (cx >> 1);
-    }
-    cell_of[(size_t)b * m + k] = c;
-    atomicAdd(&counts[(size_t)b * (cap + 1) + c], 1);
+    GridMeta g;
+    const float count = (float)(m > 0 ? m : 1);
+    sc_grid::geometry_from_box(box_all + (size_t)b * sc_grid::BOX_WORDS, cg_cells_capacity(m), CG_GMAX, 8,
+                               [=](float vol, float) { return cbrtf(vol * (float)CG_TPC / count); }, g);
+    // (no `h > 0` condition here, unlike the two other searches: a box so small that its volume underflows gets CG_GMAX cells per axis
+    // and is valid when they fit.  Looks like drift between the copies; kept, the geometry is not to change.)
+    g.valid = (g.valid && m > 0) ? 1 : 0;
+    if (!g.valid) { g.g[0] = g.g[1] = g.g[2] = 1; }
+    g.dense = 0;                                       // set by the scan of the target histogram
+    meta[b] = g;
 }
 
 // ---- 3. exclusive scan of the histogram, in place; start[cells] = total -----------------------------------------------------
@@ -169,7 +83,7 @@ __global__ __launch_bounds__(256) void cg_count_kernel(int m, const float* __res
 __global__ __launch_bounds__(1024) void cg_scan_local_kernel(const GridMeta* __restrict__ meta, int cap, int* __restrict__ counts,
                                                              int* __restrict__ block_tot, int nblk, int* __restrict__ occupied, int targets) {
     __shared__ int wtot[16];
-    const int b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const GridMeta& g = meta[b];
     if (!targets && !g.dense) return;
     const int cells = g.g[0] * g.g[1] * g.g[2];
@@ -177,22 +91,9 @@ __global__ __launch_bounds__(1024) void cg_scan_local_kernel(const GridMeta* __r
     int* c = counts + (size_t)b * (cap + 1);
     const int i = blk * 1024 + tid;
     const int v = i <= cells ? c[i] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-        const int t = wtot[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    if (i <= cells) c[i] = before + incl - v;
+    int total;
+    const int before = sc_scan::block_exclusive<16>(v, wtot, total);
+    if (i <= cells) c[i] = before;
     if (tid == 0) block_tot[(size_t)b * nblk + blk] = total;
     if (targets) {
         const unsigned long long nz = __ballot(v > 0);
@@ -223,19 +124,6 @@ __global__ __launch_bounds__(1024) void cg_scan_add_kernel(GridMeta* __restrict_
     if (targets && blk == 0 && tid == 0) meta[b].dense = (g.valid && (long long)targets >= (long long)occupied[b] * dense_min) ? 1 : 0;
 }
 
-// ---- 4. targets into cell order as {x, y, z, original index}; order inside a cell is arbitrary (see the acceptance rule) ----
-__global__ __launch_bounds__(256) void cg_scatter_kernel(int m, const float* __restrict__ tgt, int cap, const int* __restrict__ cell_of,
-                                                         const int* __restrict__ start, int* __restrict__ cursor,
-                                                         float4* __restrict__ sorted, const GridMeta* __restrict__ only_dense) {
-    const int b = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= m) return;
-    if (only_dense && !only_dense[b].dense) return;
-    const int c = cell_of[(size_t)b * m + k];
-    const int pos = start[(size_t)b * (cap + 1) + c] + atomicAdd(&cursor[(size_t)b * cap + c], 1);
-    const float* t = tgt + ((size_t)b * m + k) * 3;
-    sorted[(size_t)b * m + pos] = make_float4(t[0], t[1], t[2], __int_as_float(k));
-}
-
 // ---- 5. the ring walk --------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void cg_query_kernel(int n, const float* __restrict__ qry, int m, const GridMeta* __restrict__ meta, int cap,
                                                        const int* __restrict__ start_all, const float4* __restrict__ sorted_all,
@@ -257,7 +145,7 @@ __global__ __launch_bounds__(256) void cg_query_kernel(int n, const float* __res
         int c[3];
         bool outside = false;          // more than CG_REMPTY cells off the targets' bounding box: the walk could only confirm a candidate
         for (int a = 0; a < 3; ++a) {  // after many rings (its bound grows by one cell per ring, the lateral offsets do not shrink)
-            c[a] = cg_axis_cell(q[a], g.lo[a], g.inv_h[a], g.g[a]);
+            c[a] = axis_cell(q[a], g.lo[a], g.inv_h[a], g.g[a]);
             const float off = fmaxf(g.lo[a] - q[a], q[a] - (g.lo[a] + (float)g.g[a] * g.h[a]));
             outside |= off > (float)CG_REMPTY * g.h[a];
         }
@@ -549,28 +437,27 @@ struct CgCarve {
 inline CgCarve cg_carve(int b, int n, int m) {
     CgCarve c;
     const size_t cap = (size_t)cg_cells_capacity(m);
-    size_t o = 0;
-    auto take = [&](size_t words) { const size_t at = o; o += (words + 3) & ~(size_t)3; return at; };
-    c.counts = take((size_t)b * (cap + 1));      // counts, cursors and the two list counters are cleared by ONE memset: first and adjacent
-    c.cursor = take((size_t)b * cap);
-    c.todo_count = take((size_t)b);
-    c.qcounts = take((size_t)b * (cap + 1));     // the query cloud binned into the same grid (histogram -> starts)
-    c.qcursor = take((size_t)b * cap);
-    c.item_count = take((size_t)b);
-    c.occupied = take((size_t)b);
-    c.box = take((size_t)b * 8);                 // bounding-box keys (zero = nothing yet)
-    c.meta = take((size_t)b * (sizeof(GridMeta) / 4));
-    c.cell_of = take((size_t)b * m);
-    c.todo = take((size_t)b * n);
-    c.sorted = take((size_t)b * m * 4);
-    c.keys = take((size_t)b * n * 2);            // 64-bit (distance bits, index) of the listed queries (offsets are multiples of 4 words)
-    c.qcell_of = take((size_t)b * n);
-    c.qsorted = take((size_t)b * n * 4);
+    sc_grid::WordCarver w;
+    c.counts = w.take((size_t)b * (cap + 1));      // counts, cursors and the two list counters are cleared by ONE memset: first and adjacent
+    c.cursor = w.take((size_t)b * cap);
+    c.todo_count = w.take((size_t)b);
+    c.qcounts = w.take((size_t)b * (cap + 1));     // the query cloud binned into the same grid (histogram -> starts)
+    c.qcursor = w.take((size_t)b * cap);
+    c.item_count = w.take((size_t)b);
+    c.occupied = w.take((size_t)b);
+    c.box = w.take((size_t)b * sc_grid::BOX_WORDS);                // bounding-box keys (zero = nothing yet)
+    c.meta = w.take((size_t)b * (sizeof(GridMeta) / 4));
+    c.cell_of = w.take((size_t)b * m);
+    c.todo = w.take((size_t)b * n);
+    c.sorted = w.take((size_t)b * m * 4);
+    c.keys = w.take((size_t)b * n * 2);            // 64-bit (distance bits, index) of the listed queries (offsets are multiples of 4 words)
+    c.qcell_of = w.take((size_t)b * n);
+    c.qsorted = w.take((size_t)b * n * 4);
     c.max_items = (size_t)n / 64 + 1 + ((size_t)n < cap ? (size_t)n : cap);      // sum over cells of ceil(count / 64)
-    c.items = take((size_t)b * c.max_items * 2);
+    c.items = w.take((size_t)b * c.max_items * 2);
     c.nblk = cap / 1024 + 1;
-    c.block_tot = take((size_t)b * c.nblk);
-    c.total = o;
+    c.block_tot = w.take((size_t)b * c.nblk);
+    c.total = w.words;
     return c;
 }
 
@@ -580,25 +467,25 @@ int cg_one_direction(const float* qry, int n, const float* tgt, int m, int b, fl
     GridMeta* meta = reinterpret_cast<GridMeta*>(ws + c.meta);
     (void)hipMemsetAsync(ws, 0, c.meta * sizeof(int), stream);
     const int bbox_blocks = (m + 256 * 8 - 1) / (256 * 8);
-    hipLaunchKernelGGL(cg_bbox_kernel, dim3(bbox_blocks < 64 ? bbox_blocks : 64, b), dim3(256), 0, stream, m, tgt, reinterpret_cast<unsigned*>(ws + c.box));
+    hipLaunchKernelGGL(sc_grid::bbox_kernel, dim3(bbox_blocks < 64 ? bbox_blocks : 64, b), dim3(256), 0, stream, m, tgt, reinterpret_cast<unsigned*>(ws + c.box));
     hipLaunchKernelGGL(cg_meta_kernel, dim3((b + 63) / 64), dim3(64), 0, stream, m, b, reinterpret_cast<const unsigned*>(ws + c.box), meta);
-    hipLaunchKernelGGL(cg_count_kernel, dim3((m + 255) / 256, b), dim3(256), 0, stream, m, tgt, meta, cap, ws + c.cell_of, ws + c.counts, 0);
+    hipLaunchKernelGGL((sc_grid::count_kernel<false, GridMeta>), dim3((m + 255) / 256, b), dim3(256), 0, stream, m, tgt, meta, cap, ws + c.cell_of, ws + c.counts);
     hipLaunchKernelGGL(cg_scan_local_kernel, dim3((unsigned)c.nblk, b), dim3(1024), 0, stream, meta, cap, ws + c.counts, ws + c.block_tot, (int)c.nblk,
                        ws + c.occupied, m);
     static const int dense_min = [] { const char* e = getenv("SC_CHAMFER_GRID_DENSE"); return e ? atoi(e) : CG_DENSE; }();      // tuning override
     hipLaunchKernelGGL(cg_scan_add_kernel, dim3((unsigned)c.nblk, b), dim3(1024), 0, stream, meta, cap, ws + c.counts, ws + c.block_tot, (int)c.nblk,
                        ws + c.occupied, m, dense_min);
-    hipLaunchKernelGGL(cg_scatter_kernel, dim3((m + 255) / 256, b), dim3(256), 0, stream, m, tgt, cap, ws + c.cell_of, ws + c.counts,
-                       ws + c.cursor, reinterpret_cast<float4*>(ws + c.sorted), nullptr);
+    hipLaunchKernelGGL((sc_grid::scatter_kernel<false, GridMeta>), dim3((m + 255) / 256, b), dim3(256), 0, stream, m, tgt, cap, ws + c.cell_of,
+                       ws + c.counts, ws + c.cursor, reinterpret_cast<float4*>(ws + c.sorted), meta);
     static const int wave_walk = [] { const char* e = getenv("SC_CHAMFER_GRID_WAVE"); return e ? atoi(e) : 1; }();      // A/B: 0 = thread per query
     if (wave_walk) {       // images whose targets are surface-like (meta.dense): queries binned into the same grid, one wave per (cell, 64 queries)
-        hipLaunchKernelGGL(cg_count_kernel, dim3((n + 255) / 256, b), dim3(256), 0, stream, n, qry, meta, cap, ws + c.qcell_of, ws + c.qcounts, 1);
+        hipLaunchKernelGGL((sc_grid::count_kernel<true, GridMeta>), dim3((n + 255) / 256, b), dim3(256), 0, stream, n, qry, meta, cap, ws + c.qcell_of, ws + c.qcounts);
         hipLaunchKernelGGL(cg_scan_local_kernel, dim3((unsigned)c.nblk, b), dim3(1024), 0, stream, meta, cap, ws + c.qcounts, ws + c.block_tot,
                            (int)c.nblk, ws + c.occupied, 0);
         hipLaunchKernelGGL(cg_scan_add_kernel, dim3((unsigned)c.nblk, b), dim3(1024), 0, stream, meta, cap, ws + c.qcounts, ws + c.block_tot,
                            (int)c.nblk, ws + c.occupied, 0, 0);
-        hipLaunchKernelGGL(cg_scatter_kernel, dim3((n + 255) / 256, b), dim3(256), 0, stream, n, qry, cap, ws + c.qcell_of, ws + c.qcounts,
-                           ws + c.qcursor, reinterpret_cast<float4*>(ws + c.qsorted), meta);
+        hipLaunchKernelGGL((sc_grid::scatter_kernel<true, GridMeta>), dim3((n + 255) / 256, b), dim3(256), 0, stream, n, qry, cap, ws + c.qcell_of,
+                           ws + c.qcounts, ws + c.qcursor, reinterpret_cast<float4*>(ws + c.qsorted), meta);
         hipLaunchKernelGGL(cg_items_kernel, dim3((cap + 255) / 256, b), dim3(256), 0, stream, meta, cap, ws + c.qcounts, ws + c.items,
                            ws + c.item_count, (int)c.max_items);
         hipLaunchKernelGGL(cg_query_wave_kernel, dim3((unsigned)((c.max_items + 3) / 4 < 4096 ? (c.max_items + 3) / 4 : 4096), b), dim3(256), 0, stream, n, m, meta, cap, ws + c.counts,

@@ -17,6 +17,7 @@
 // comparisons (a NaN fails them all), plain vector stores, no atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "block_scan.hpp"
 #include "../../include/shapeclipper_hip.h"
 
 namespace sc {
@@ -207,7 +208,7 @@ __global__ __launch_bounds__(256) void dc_face_emit_kernel(const unsigned char* 
     __shared__ unsigned char flag_s[256];                       // dc_quad_axes | (corner 0 inside) << 3
     const int Nc = S - 1, per = Nc * Nc * Nc;
     const int b = blockIdx.x / bpi, blk = blockIdx.x - b * bpi;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     long long running = block_offsets[blockIdx.x];              // in triangles
     if (block_offsets[blockIdx.x + 1] == running) return;
     const int* cm = cell_map + (size_t)b * per;
@@ -221,22 +222,8 @@ __global__ __launch_bounds__(256) void dc_face_emit_kernel(const unsigned char* 
             fl = dc_quad_axes(m, gx, gy, gz) | ((m & 1) << 3);
         }
         const int n = __popc(fl & 7);
-        int incl = n;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) wave_tot[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const int t = wave_tot[w];
-            if (w < wave) before += t;
-            total += t;
-        }
-        excl[tid] = before + incl - n;
+        int total;
+        excl[tid] = sc_scan::block_exclusive<4>(n, wave_tot, total);            // the round's closing barrier frees wave_tot for the next
         flag_s[tid] = (unsigned char)fl;
         __syncthreads();
         for (int qd = tid; qd < total; qd += 256) {

@@ -21,8 +21,9 @@
 //     face that is not a face of the grid.  Every region of the pair arithmetic returns a point within a few ulp of the triangle (vertex
 //     regions exactly, edge and interior regions with weights in [0, 1]; a triangle too thin for its interior weights to mean anything is
 //     taken as its three edges), so its computed d is at least (lb - slack)^2 up to the rounding
-//     of d: the walk stops when  best < (lb - slack)^2 * 0.9999  (slack = 16 ulp of the coordinate scale, as GridMeta.slack of
-//     chamfer_grid.hip) or when the block covers the grid.  No unseen triangle can beat or tie `best`.
+//     of d: the walk stops when  best < (lb - slack)^2 * 0.9999  (slack = 16 ulp of the coordinate scale: Geometry.slack of
+//     uniform_grid.hpp, where the box, the geometry and the cell of a coordinate live) or when the block covers the grid.  No unseen
+//     triangle can beat or tie `best`.
 //   * queries that do not stop within PM_RMAX rings or PM_BUDGET candidates, that start more than PM_REMPTY cells outside the box, and
 //     every query of an image whose grid is invalid (a non-finite or huge vertex, a mesh of zero extent) go on a list and are answered by
 //     the brute kernel's inner loop, split over PM_SLICES slices of the faces and merged with 64-bit atomicMin keys
@@ -34,7 +35,9 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "block_scan.hpp"
 #include "shapeclipper_hip.h"
+#include "uniform_grid.hpp"
 
 #pragma clang fp contract(off)
 
@@ -54,11 +57,7 @@ constexpr float PM_FLAT = 1.0e-5f;   // den = |ab|^2 |ac|^2 sin^2: below this si
 constexpr float PM_HUGE = 1.0e15f;    // magnitudes the padding / slack arithmetic is not made for
 constexpr unsigned long long EMPTY = ~0ull;
 
-struct Meta {                         // one per image
-    float lo[3], h[3], inv_h[3];
-    int g[3];
-    float slack;
-    int valid;                        // the grid is usable: finite vertices of sensible magnitude, a box of positive extent
+struct Meta : sc_grid::Geometry {     // one per image; valid: finite vertices of sensible magnitude, a box of positive extent
     int cbase;                        // first cell of the image in the packed cell arrays
 };
 
@@ -192,13 +191,6 @@ __device__ __forceinline__ bool pm_load(int k, int b, const float* __restrict__ 
     return true;
 }
 
-// order-preserving integer keys of floats (chamfer_grid.hip): the all-zero state of the cleared workspace means "nothing yet"
-__device__ __forceinline__ unsigned pm_key(float f) {
-    const unsigned u = __float_as_uint(f);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float pm_unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
-
 // the lanes of a wave whose `ok` is set: all of one image -> the first such lane (it issues the wave's atomics after a reduction);
 // of several images -> -1 (every lane issues its own); none -> -2.  Every lane of the wave calls it.
 __device__ __forceinline__ int pm_wave_leader(bool ok, int b) {
@@ -209,7 +201,7 @@ __device__ __forceinline__ int pm_wave_leader(bool ok, int b) {
     return __all(!ok || b == b0) ? first : -1;
 }
 
-// ---- 1. bounding box of the valid triangles; box[b] = {~key(min) x3, key(max) x3, bad flag, valid faces} --------------------------------
+// ---- 1. bounding box of the valid triangles (the box of uniform_grid.hpp; its free word counts the valid faces) ------------------------------
 __global__ __launch_bounds__(THREADS) void pm_bbox_kernel(int n_images, int f_total, const float* __restrict__ verts,
                                                           const int32_t* __restrict__ faces, const int* __restrict__ v_start,
                                                           const int* __restrict__ f_start, unsigned* __restrict__ box_all,
@@ -234,16 +226,14 @@ __global__ __launch_bounds__(THREADS) void pm_bbox_kernel(int n_images, int f_to
     const int leader = pm_wave_leader(ok, b);
     unsigned count = ok ? 1u : 0u;
     if (leader >= 0) {
-        for (int i = 0; i < 3; ++i)
-            for (int d = 32; d >= 1; d >>= 1) { mn[i] = fminf(mn[i], __shfl_xor(mn[i], d)); mx[i] = fmaxf(mx[i], __shfl_xor(mx[i], d)); }
+        sc_grid::wave_minmax(mn, mx);
         bad = __any(bad);
         count = (unsigned)__builtin_popcountll(__ballot(ok));
     }
     if (ok && (leader == -1 || lane == leader)) {
-        unsigned* box = box_all + (size_t)b * 8;
-        for (int i = 0; i < 3; ++i) { atomicMax(&box[i], ~pm_key(mn[i])); atomicMax(&box[3 + i], pm_key(mx[i])); }
-        if (bad) atomicOr(&box[6], 1u);
-        atomicAdd(&box[7], count);
+        unsigned* box = box_all + (size_t)b * sc_grid::BOX_WORDS;
+        sc_grid::box_merge(box, mn, mx, bad);
+        atomicAdd(&box[sc_grid::BOX_USER], count);
     }
 }
 
@@ -258,10 +248,10 @@ __global__ __launch_bounds__(THREADS) void pm_extent_kernel(int n_images, int f_
     const int b = ok ? pm_image_of(k, f_start, n_images) : 0;
     unsigned q = 0;
     if (ok) {
-        const unsigned* box = box_all + (size_t)b * 8;
-        float emax = 0.f;
-        for (int i = 0; i < 3; ++i) emax = fmaxf(emax, pm_unkey(box[3 + i]) - pm_unkey(~box[i]));
-        ok = !box[6] && emax > 0.f;
+        float lo[3], hi[3], emax = 0.f;
+        const bool bad = sc_grid::box_read(box_all + (size_t)b * sc_grid::BOX_WORDS, lo, hi);
+        for (int i = 0; i < 3; ++i) emax = fmaxf(emax, hi[i] - lo[i]);
+        ok = !bad && emax > 0.f;
         if (ok) {
             const float4 bb = tris[(size_t)k * 3 + 1], c = tris[(size_t)k * 3 + 2];
             const float ex = fmaxf(a.x, fmaxf(bb.x, c.x)) - fminf(a.x, fminf(bb.x, c.x));
@@ -281,44 +271,17 @@ __global__ __launch_bounds__(THREADS) void pm_extent_kernel(int n_images, int f_
 __global__ __launch_bounds__(THREADS) void pm_meta_kernel(int n_images, const unsigned* __restrict__ box_all,
                                                           const unsigned long long* __restrict__ ext_sum, Meta* __restrict__ meta) {
     for (int b = threadIdx.x; b < n_images; b += THREADS) {
-        const unsigned* box = box_all + (size_t)b * 8;
-        const int nf = (int)box[7];
+        const unsigned* box = box_all + (size_t)b * sc_grid::BOX_WORDS;
+        const int nf = (int)box[sc_grid::BOX_USER];
+        const float count = (float)(nf > 0 ? nf : 1), ext_units = (float)ext_sum[b];
         Meta g;
-        float ext[3], scale = 0.f, emax = 0.f;
-        for (int a = 0; a < 3; ++a) {
-            const float lo = pm_unkey(~box[a]), hi = pm_unkey(box[3 + a]);
-            g.lo[a] = lo;
-            ext[a] = hi - lo;
-            emax = fmaxf(emax, ext[a]);
-            scale = fmaxf(scale, fmaxf(fabsf(lo), fabsf(hi)));
-        }
-        g.valid = (!box[6] && nf > 0 && emax > 0.f) ? 1 : 0;
-        float vol = 1.f;
-        for (int a = 0; a < 3; ++a) { ext[a] = fmaxf(ext[a], emax * 1.0e-3f); vol *= ext[a]; }     // a flat mesh still gets cells of a sensible size
-        const float mean_ext = emax * ((float)ext_sum[b] / (65536.f * (float)(nf > 0 ? nf : 1)));
-        float h = fmaxf(2.f * mean_ext, cbrtf(vol / (float)(nf > 0 ? nf : 1)));
-        const long long cap = 2ll * nf + 64;
-        g.g[0] = g.g[1] = g.g[2] = 1;
-        if (g.valid && h > 0.f) {
-            for (int it = 0; it < 24; ++it) {           // the per-axis ceil can overshoot the cell budget: grow h until it fits
-                long long cells = 1;
-                for (int a = 0; a < 3; ++a) {
-                    int n = (int)fminf(ceilf(ext[a] / h), (float)PM_GMAX);
-                    n = n < 1 ? 1 : (n > PM_GMAX ? PM_GMAX : n);
-                    g.g[a] = n;
-                    cells *= n;
-                }
-                if (cells <= cap) break;
-                h *= 1.26f;
-            }
-        }
-        if (!(h > 0.f) || (long long)g.g[0] * g.g[1] * g.g[2] > cap) g.valid = 0;
+        // (24 growth rounds where the two point grids take 8: possibly drift between the copies; kept, the geometry is not to change)
+        const float h = sc_grid::geometry_from_box(box, 2ll * nf + 64, PM_GMAX, 24, [=](float vol, float emax) {
+            const float mean_ext = emax * (ext_units / (65536.f * count));
+            return fmaxf(2.f * mean_ext, cbrtf(vol / count));
+        }, g);
+        g.valid = (g.valid && nf > 0 && h > 0.f) ? 1 : 0;
         if (!g.valid) g.g[0] = g.g[1] = g.g[2] = 1;
-        for (int a = 0; a < 3; ++a) {
-            g.h[a] = ext[a] / (float)g.g[a];            // cells tile the extent exactly (the last cell also takes x == hi by clamping)
-            g.inv_h[a] = (float)g.g[a] / ext[a];
-        }
-        g.slack = 16.f * 1.1920929e-7f * (scale + emax);
         g.cbase = 0;
         meta[b] = g;
     }
@@ -327,11 +290,6 @@ __global__ __launch_bounds__(THREADS) void pm_meta_kernel(int n_images, const un
         int base = 0;                                   // at most 2 F_b + 64 cells each: the sum fits the packed arrays (and an int)
         for (int b = 0; b < n_images; ++b) { meta[b].cbase = base; base += meta[b].g[0] * meta[b].g[1] * meta[b].g[2]; }
     }
-}
-
-__device__ __forceinline__ int pm_axis_cell(float v, float lo, float inv_h, int g) {
-    const int c = (int)fminf(fmaxf(floorf((v - lo) * inv_h), -1.f), (float)g);
-    return c < 0 ? 0 : (c >= g ? g - 1 : c);
 }
 
 // ---- 4. references: count pass (FILL = false; also builds the large lists) and fill pass (FILL = true) -----------------------------------
@@ -353,8 +311,8 @@ __global__ __launch_bounds__(THREADS) void pm_bin_kernel(int n_images, int f_tot
     int c0[3], c1[3];
     long long ncells = 1;
     for (int i = 0; i < 3; ++i) {
-        c0[i] = pm_axis_cell(mn[i] - g.slack, g.lo[i], g.inv_h[i], g.g[i]);
-        c1[i] = pm_axis_cell(mx[i] + g.slack, g.lo[i], g.inv_h[i], g.g[i]);
+        c0[i] = sc_grid::axis_cell_far(mn[i] - g.slack, g.lo[i], g.inv_h[i], g.g[i]);
+        c1[i] = sc_grid::axis_cell_far(mx[i] + g.slack, g.lo[i], g.inv_h[i], g.g[i]);
         ncells *= (c1[i] - c0[i] + 1);
     }
     const int local = k - f_start[b];
@@ -374,25 +332,12 @@ __global__ __launch_bounds__(THREADS) void pm_bin_kernel(int n_images, int f_tot
 // ---- 5. exclusive scan of the packed histogram, in place, over [0, n): entry `cells` of the last image ends up holding the total ---------
 __global__ __launch_bounds__(1024) void pm_scan_local_kernel(int n, int* __restrict__ counts, int* __restrict__ block_tot) {
     __shared__ int wtot[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int i = blockIdx.x * 1024 + tid;
     const int v = i < n ? counts[i] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-        const int t = wtot[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    if (i < n) counts[i] = before + incl - v;
+    int total;
+    const int before = sc_scan::block_exclusive<16>(v, wtot, total);
+    if (i < n) counts[i] = before;
     if (tid == 0) block_tot[blockIdx.x] = total;
 }
 
@@ -400,29 +345,16 @@ __global__ __launch_bounds__(1024) void pm_scan_local_kernel(int n, int* __restr
 __global__ __launch_bounds__(1024) void pm_scan_totals_kernel(int nblk, int* __restrict__ block_tot) {
     __shared__ int wtot[16];
     __shared__ int carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid == 0) carry_s = 0;
     __syncthreads();
     for (int base = 0; base < nblk; base += 1024) {
         const int i = base + tid;
         const int v = i < nblk ? block_tot[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) wtot[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-            const int t = wtot[w];
-            if (w < wave) before += t;
-            total += t;
-        }
+        int total;
+        const int before = sc_scan::block_exclusive<16>(v, wtot, total);      // the round's two barriers below free wtot for the next
         const int carry = carry_s;
-        if (i < nblk) block_tot[i] = carry + before + incl - v;
+        if (i < nblk) block_tot[i] = carry + before;
         __syncthreads();
         if (tid == 0) carry_s = carry + total;
         __syncthreads();
@@ -463,7 +395,7 @@ __global__ __launch_bounds__(THREADS) void pm_query_kernel(int n, const float* _
         int c[3];
         bool outside = false;          // more than PM_REMPTY cells off the box: the walk could only confirm a candidate after many rings
         for (int a = 0; a < 3; ++a) {
-            c[a] = pm_axis_cell(q[a], g.lo[a], g.inv_h[a], g.g[a]);
+            c[a] = sc_grid::axis_cell_far(q[a], g.lo[a], g.inv_h[a], g.g[a]);
             const float off = fmaxf(g.lo[a] - q[a], q[a] - (g.lo[a] + (float)g.g[a] * g.h[a]));
             outside |= off > (float)PM_REMPTY * g.h[a];
         }
@@ -607,27 +539,26 @@ struct Carve {
 };
 inline Carve carve(int b, int n, int f_total) {
     Carve c;
-    size_t o = 0;
-    auto take = [&](size_t words) { const size_t at = o; o += (words + 3) & ~(size_t)3; return at; };
+    sc_grid::WordCarver w;
     c.n_cells = 2 * (size_t)f_total + 64 * (size_t)b + 1;           // sum of the images' cell budgets, and the entry behind the last cell
     c.nblk = (c.n_cells + 1023) / 1024;
-    c.box = take((size_t)b * 8);
-    c.ext_sum = take((size_t)b * 2);
-    c.large_count = take((size_t)b);
-    c.todo_count = take((size_t)b);
-    c.counts = take(c.n_cells);
-    c.cursor = take(c.n_cells);
-    c.cleared = o;
-    c.v_start = take((size_t)b + 1);
-    c.f_start = take((size_t)b + 1);
-    c.meta = take((size_t)b * (sizeof(Meta) / 4));
-    c.block_tot = take(c.nblk);
-    c.large = take((size_t)f_total);
-    c.todo = take((size_t)b * n);
-    c.keys = take((size_t)b * n * 2);                               // 64-bit: offsets are multiples of 4 words
-    c.tris = take((size_t)f_total * 12);
-    c.refs = take((size_t)f_total * PM_CELL_CAP);
-    c.total = o;
+    c.box = w.take((size_t)b * sc_grid::BOX_WORDS);
+    c.ext_sum = w.take((size_t)b * 2);
+    c.large_count = w.take((size_t)b);
+    c.todo_count = w.take((size_t)b);
+    c.counts = w.take(c.n_cells);
+    c.cursor = w.take(c.n_cells);
+    c.cleared = w.words;
+    c.v_start = w.take((size_t)b + 1);
+    c.f_start = w.take((size_t)b + 1);
+    c.meta = w.take((size_t)b * (sizeof(Meta) / 4));
+    c.block_tot = w.take(c.nblk);
+    c.large = w.take((size_t)f_total);
+    c.todo = w.take((size_t)b * n);
+    c.keys = w.take((size_t)b * n * 2);                               // 64-bit: offsets are multiples of 4 words
+    c.tris = w.take((size_t)f_total * 12);
+    c.refs = w.take((size_t)f_total * PM_CELL_CAP);
+    c.total = w.words;
     return c;
 }
 

@@ -4,8 +4,9 @@
 //
 // sc_knn_points is EXACT: for every point the k smallest keys (float bits of d) << 32 | index over its own cloud, ascending, with
 // d = (dx*dx + dy*dy) + dz*dz in fp32.  The key order is total, so the result does not depend on the order candidates are met in.
-//   * the cloud is binned into a uniform grid of its own (bounding box by integer atomicMax on order-preserving keys, histogram and
-//     cursors by integer atomicAdd; the order inside a cell is arbitrary) and copied into cell order as {x, y, z, original index};
+//   * the cloud is binned into a uniform grid of its own (uniform_grid.hpp: bounding box by integer atomicMax on order-preserving keys,
+//     histogram and cursors by integer atomicAdd; the order inside a cell is arbitrary) and copied into cell order as
+//     {x, y, z, original index};
 //   * the queries ARE that sorted array: thread t of the walk answers sorted point t, so the lanes of a wave sit in the same or
 //     neighbouring cells and walk the same rows of cells;
 //   * a thread keeps its k keys ascending in LDS, laid out [k][thread]: slot i of lane l is at ((i * KNN_THREADS) + l) * 8 bytes, so a wave's
@@ -24,7 +25,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "block_scan.hpp"
 #include "shapeclipper_hip.h"
+#include "uniform_grid.hpp"
 
 namespace sc_pn {
 
@@ -43,111 +46,28 @@ constexpr unsigned long long EMPTY = ~0ull;
 
 static_assert(CHUNK == SC_ICP_CHUNK, "sc_normal_consistency sums in the chunks the header states for sc_icp_objective");
 
-struct GridMeta {                     // one per image
-    float lo[3], h[3], inv_h[3];
-    int g[3];
-    float slack;
-    int valid;
-};
+using GridMeta = sc_grid::Geometry;    // one per image
 constexpr int META_WORDS = sizeof(GridMeta) / 4;
 
 __host__ __device__ inline int cells_capacity(int n) { return n / KNN_TPC * 2 + 64; }
 
-// ---- 1. bounding box -> grid geometry --------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned box_key(float f) {
-    const unsigned u = __float_as_uint(f);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float box_unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
-
-// box[0..2] = ~key(min), box[3..5] = key(max), box[6] = "a coordinate is not a plain finite number"; all zero = nothing yet
-__global__ __launch_bounds__(256) void knn_bbox_kernel(int n, const float* __restrict__ pts, unsigned* __restrict__ box_all) {
-    const int b = blockIdx.y, tid = threadIdx.x;
-    const float* p = pts + (size_t)b * n * 3;
-    float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    int bad = 0, any = 0;
-    for (int i = blockIdx.x * 256 + tid; i < n; i += gridDim.x * 256) {
-        any = 1;
-        for (int a = 0; a < 3; ++a) {
-            const float v = p[(size_t)i * 3 + a];
-            bad |= !(fabsf(v) < 1.0e15f);
-            mn[a] = fminf(mn[a], v); mx[a] = fmaxf(mx[a], v);
-        }
-    }
-    for (int a = 0; a < 3; ++a)
-        for (int d = 32; d >= 1; d >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], d)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], d)); }
-    any = __any(any);
-    bad = __any(bad);
-    unsigned* box = box_all + (size_t)b * 8;
-    if ((tid & 63) == 0 && any) {
-        for (int a = 0; a < 3; ++a) { atomicMax(&box[a], ~box_key(mn[a])); atomicMax(&box[3 + a], box_key(mx[a])); }
-        if (bad) atomicOr(&box[6], 1u);
-    }
-}
+// ---- 1, 2, 4. bounding box -> grid geometry; cell of every point + histogram; points into cell order as {x, y, z, original index}:
+// uniform_grid.hpp.  One thread per image turns the box into the geometry with this file's constants.
+using sc_grid::axis_cell;
 
 __global__ void knn_meta_kernel(int n, int n_images, int force_scan, const unsigned* __restrict__ box_all, GridMeta* __restrict__ meta) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_images) return;
-    const unsigned* box = box_all + (size_t)b * 8;
     GridMeta g;
-    float ext[3], scale = 0.f, emax = 0.f;
-    for (int a = 0; a < 3; ++a) {
-        const float lo = box_unkey(~box[a]), hi = box_unkey(box[3 + a]);
-        g.lo[a] = lo;
-        ext[a] = hi - lo;
-        emax = fmaxf(emax, ext[a]);
-        scale = fmaxf(scale, fmaxf(fabsf(lo), fabsf(hi)));
-    }
-    g.valid = (!box[6] && !force_scan && emax > 0.f) ? 1 : 0;
-    float vol = 1.f;                               // a flat or thin cloud still gets cells of a sensible size along its thin axes
-    for (int a = 0; a < 3; ++a) { ext[a] = fmaxf(ext[a], emax * 1.0e-3f); vol *= ext[a]; }
-    float h = cbrtf(vol * (float)KNN_TPC / (float)n);
-    const int cap = cells_capacity(n);
-    for (int it = 0; it < 8; ++it) {               // the per-axis ceil can overshoot the cell budget: grow h until it fits
-        long long cells = 1;
-        for (int a = 0; a < 3; ++a) {
-            int c = (int)ceilf(ext[a] / h);
-            c = c < 1 ? 1 : (c > KNN_GMAX ? KNN_GMAX : c);
-            g.g[a] = c;
-            cells *= c;
-        }
-        if (cells <= cap) break;
-        h *= 1.26f;
-    }
-    if (!(h > 0.f) || (long long)g.g[0] * g.g[1] * g.g[2] > cap) g.valid = 0;
-    for (int a = 0; a < 3; ++a) {
-        g.h[a] = ext[a] / (float)g.g[a];
-        g.inv_h[a] = (float)g.g[a] / ext[a];
-    }
-    g.slack = 16.f * 1.1920929e-7f * (scale + emax);
+    const float h = sc_grid::geometry_from_box(box_all + (size_t)b * sc_grid::BOX_WORDS, cells_capacity(n), KNN_GMAX, 8,
+                                               [=](float vol, float) { return cbrtf(vol * (float)KNN_TPC / (float)n); }, g);
+    g.valid = (g.valid && !force_scan && h > 0.f) ? 1 : 0;
     if (!g.valid) {
         g.g[0] = g.g[1] = g.g[2] = 1;
         for (int a = 0; a < 3; ++a) { g.lo[a] = 0.f; g.h[a] = 1.f; g.inv_h[a] = 1.f; }
         g.slack = 0.f;
     }
     meta[b] = g;
-}
-
-__device__ __forceinline__ int axis_cell(float v, float lo, float inv_h, int g) {
-    const int c = (int)floorf((v - lo) * inv_h);
-    return c < 0 ? 0 : (c >= g ? g - 1 : c);
-}
-
-// ---- 2. cell of every point + histogram ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void knn_count_kernel(int n, const float* __restrict__ pts, const GridMeta* __restrict__ meta, int cap,
-                                                        int* __restrict__ cell_of, int* __restrict__ counts) {
-    const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const GridMeta& g = meta[b];
-    const float* p = pts + ((size_t)b * n + i) * 3;
-    int c = 0;
-    if (g.valid) {
-        const int cx = axis_cell(p[0], g.lo[0], g.inv_h[0], g.g[0]), cy = axis_cell(p[1], g.lo[1], g.inv_h[1], g.g[1]);
-        const int cz = axis_cell(p[2], g.lo[2], g.inv_h[2], g.g[2]);
-        c = (cz * g.g[1] + cy) * g.g[0] + cx;       // x fastest: a run of cells along x is one contiguous run of sorted points
-    }
-    cell_of[(size_t)b * n + i] = c;
-    atomicAdd(&counts[(size_t)b * (cap + 1) + c], 1);
 }
 
 // ---- 3. exclusive scan of the histogram in place over [0, cells] inclusive (the last entry receives the total) ---------------------
@@ -162,28 +82,12 @@ __global__ __launch_bounds__(SCAN_THREADS) void knn_scan_cells_kernel(const Grid
     const int first = tid * per, last = min(first + per, entries);
     int sum = 0;
     for (int i = first; i < last; ++i) sum += c[i];
-    int incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
+    const int incl = sc_scan::wave_inclusive(sum);         // the run totals: wave scan, then the totals of the waves in front (no block total needed)
     if (lane == 63) wtot[wave] = incl;
     __syncthreads();
     int run = incl - sum;
     for (int w = 0; w < wave; ++w) run += wtot[w];
     for (int i = first; i < last; ++i) { const int v = c[i]; c[i] = run; run += v; }
-}
-
-// ---- 4. points into cell order as {x, y, z, original index} ----------------------------------------------------------------------
-__global__ __launch_bounds__(256) void knn_scatter_kernel(int n, const float* __restrict__ pts, int cap, const int* __restrict__ cell_of,
-                                                          const int* __restrict__ start, int* __restrict__ cursor, float4* __restrict__ sorted) {
-    const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int c = cell_of[(size_t)b * n + i];
-    const int pos = start[(size_t)b * (cap + 1) + c] + atomicAdd(&cursor[(size_t)b * cap + c], 1);
-    const float* p = pts + ((size_t)b * n + i) * 3;
-    sorted[(size_t)b * n + pos] = make_float4(p[0], p[1], p[2], __int_as_float(i));
 }
 
 // ---- the k-entry list of one thread: keys ascending, slot i at list[i * KNN_THREADS] -----------------------------------------------
@@ -319,18 +223,17 @@ struct Carve { size_t box, counts, cursor, todo_count, zeroed, meta, cell_of, to
 inline Carve carve(int b, int n) {
     Carve c;
     const size_t cap = (size_t)cells_capacity(n);
-    size_t o = 0;
-    auto take = [&](size_t words) { const size_t at = o; o += (words + 3) & ~(size_t)3; return at; };
-    c.box = take((size_t)b * 8);                   // the first four are cleared by one memset
-    c.counts = take((size_t)b * (cap + 1));
-    c.cursor = take((size_t)b * cap);
-    c.todo_count = take((size_t)b);
-    c.zeroed = o;
-    c.meta = take((size_t)b * META_WORDS);
-    c.cell_of = take((size_t)b * n);
-    c.todo = take((size_t)b * n);
-    c.sorted = take((size_t)b * n * 4);            // float4: offsets are multiples of 4 words
-    c.total = o;
+    sc_grid::WordCarver w;
+    c.box = w.take((size_t)b * sc_grid::BOX_WORDS);                 // the first four are cleared by one memset
+    c.counts = w.take((size_t)b * (cap + 1));
+    c.cursor = w.take((size_t)b * cap);
+    c.todo_count = w.take((size_t)b);
+    c.zeroed = w.words;
+    c.meta = w.take((size_t)b * META_WORDS);
+    c.cell_of = w.take((size_t)b * n);
+    c.todo = w.take((size_t)b * n);
+    c.sorted = w.take((size_t)b * n * 4);            // float4: offsets are multiples of 4 words
+    c.total = w.words;
     return c;
 }
 
@@ -496,11 +399,12 @@ extern "C" int sc_knn_points(const float* points, int n_images, int n, int k, vo
     (void)hipMemsetAsync(ws, 0, c.zeroed * sizeof(int), s);
     const int bbox_blocks = (n + 256 * 8 - 1) / (256 * 8);
     const dim3 per_point((unsigned)((n + 255) / 256), (unsigned)b);
-    hipLaunchKernelGGL(knn_bbox_kernel, dim3(bbox_blocks < 64 ? bbox_blocks : 64, b), dim3(256), 0, s, n, points, reinterpret_cast<unsigned*>(ws + c.box));
+    hipLaunchKernelGGL(sc_grid::bbox_kernel, dim3(bbox_blocks < 64 ? bbox_blocks : 64, b), dim3(256), 0, s, n, points, reinterpret_cast<unsigned*>(ws + c.box));
     hipLaunchKernelGGL(knn_meta_kernel, dim3((b + 63) / 64), dim3(64), 0, s, n, b, force_scan, reinterpret_cast<const unsigned*>(ws + c.box), meta);
-    hipLaunchKernelGGL(knn_count_kernel, per_point, dim3(256), 0, s, n, points, meta, cap, ws + c.cell_of, ws + c.counts);
+    hipLaunchKernelGGL((sc_grid::count_kernel<false, GridMeta>), per_point, dim3(256), 0, s, n, points, meta, cap, ws + c.cell_of, ws + c.counts);
     hipLaunchKernelGGL(knn_scan_cells_kernel, dim3(b), dim3(SCAN_THREADS), 0, s, meta, cap, ws + c.counts);
-    hipLaunchKernelGGL(knn_scatter_kernel, per_point, dim3(256), 0, s, n, points, cap, ws + c.cell_of, ws + c.counts, ws + c.cursor, sorted);
+    hipLaunchKernelGGL((sc_grid::scatter_kernel<false, GridMeta>), per_point, dim3(256), 0, s, n, points, cap, ws + c.cell_of, ws + c.counts,
+                       ws + c.cursor, sorted, meta);
     const dim3 per_query((unsigned)((n + KNN_THREADS - 1) / KNN_THREADS), (unsigned)b);
     const size_t list_bytes = (size_t)k * KNN_THREADS * sizeof(unsigned long long);
     hipLaunchKernelGGL(knn_walk_kernel, per_query, dim3(KNN_THREADS), list_bytes, s, n, k, meta, cap, ws + c.counts, sorted, idx, dist,
