@@ -1001,6 +1001,74 @@ int sc_mesh_topology(const float* verts, const int32_t* faces, const int64_t* v_
                      int n_faces, int table_slots, void* scratch, int64_t* counts, double* area, double* volume, int32_t* face_component,
                      int32_t* bad_index, void* stream);
 
+/* ---- evaluation: decimation by vertex clustering with quadric placement (csrc/mesh_simplify.hip) -------------------------------------
+ * What ops.mesh_cluster_simplify runs and {idx}_mesh_simplified.ply holds (`--eval.simplify`).  A batch of packed meshes in the form of
+ * sc_mesh_topology above (verts, faces with image-local indices, v_off / f_off).  A box of `cells` = G cells per axis (1 <= G <=
+ * SC_MESH_SIMPLIFY_MAX_CELLS = 128, so G^3 <= 2^21), each of side `pitch` = h > 0, with its lower corner at origin = o (three fp32
+ * values, like h widened exactly to float64), is laid over every image; all vertices of an image that fall into one cell (Rossignac and
+ * Borrel) become ONE vertex, placed by the cell's quadric (Lindstrom).  tests/mesh_simplify_ref.py restates every rule in numpy.  All
+ * arithmetic is float64, every operation rounded once (the file is built without contraction; the divisions are correctly rounded).
+ *
+ * Vertices.  p = the vertex widened exactly to float64;  q_j = (p_j - o_j) / h  (j = 0, 1, 2).  A vertex with a p_j that is not finite
+ *   or a q_j outside [0, G] sets *bad_vertex to 1, gets vertex_cluster -1 and takes part in nothing, and neither does a face that holds
+ *   it (the caller raises; the other outputs of the call are then unspecified).  Otherwise its cell is g_j = min(floor(q_j), G - 1) (a
+ *   vertex on the upper face of the box belongs to the last cell), its cell id (g_0 G + g_1) G + g_2, and u_j = q_j - (g_j + 0.5).
+ * Clusters.  The clusters of an image are its occupied cells, numbered from 0 in ascending cell id (a bit per cell in a mask, an integer
+ *   block scan over the mask's popcounts).  vertex_cluster [n_verts] int32 = the cluster number of every vertex, local to the image.
+ * Accumulators, SC_MESH_SIMPLIFY_ACC = 13 per cluster, all int64, fed by 64-bit integer atomic adds only:
+ *   n += 1 and s_j += llrint(u_j 2^24) for every vertex of the cluster (round to nearest, ties to even; |u_j| <= 0.5, so |s_j| <= 2^54);
+ *   a face TAKES PART if its three indices lie in [0, v_off[b+1] - v_off[b]) -- else it sets *bad_index to 1 and is never
+ *   dereferenced -- and are pairwise distinct.  With a, b, c its corners in the order it lists them:
+ *       e1 = q_b - q_a,  e2 = q_c - q_a;   N = (e1_1 e2_2 - e1_2 e2_1,  e1_2 e2_0 - e1_0 e2_2,  e1_0 e2_1 - e1_1 e2_0)
+ *   and, once for each DISTINCT cluster among the three corners' clusters, with g the cell of that cluster:
+ *       w_j = q_a,j - (g_j + 0.5);   d = (N_0 w_0 + N_1 w_1) + N_2 w_2;
+ *       A_ij += fix(N_i N_j) for (i,j) = (0,0) (0,1) (0,2) (1,1) (1,2) (2,2);    b_j += fix(N_j d)
+ *       fix(t) = llrint(clamp(t, -2^12, 2^12) 2^24)          (t > 2^12 ? 2^12 : t < -2^12 ? -2^12 : t;  the scaling is exact)
+ *   N is twice the face's area vector in cell units, so a face that spans more than about 8 cells saturates instead of overflowing.
+ *   A face whose three corners fall into ONE cluster still adds its terms there: it carries the plane.  No sum can leave int64:
+ *   |fix| <= 2^36 and the entry point refuses more than 2^26 faces, so every |A_ij|, |b_j| <= 2^62.
+ * Solve, per cluster.  A_ij, b_j, s_j converted to float64 (round to nearest, ties to even) and scaled by 2^-24 (exact);
+ *       c_j = s_j / (double)n;    lam = reg * ((A_00 + A_11) + A_22);
+ *   if !(lam > 0) then x = c, else with a00 = A_00 + lam, a11 = A_11 + lam, a22 = A_22 + lam, a01 = A_01, a02 = A_02, a12 = A_12 and
+ *   b_j = b_j + lam c_j, the division-only LDL^T of the dual-contouring block above:
+ *       l10 = a01 / a00;   l20 = a02 / a00;   e1 = a11 - l10 a01;   t21 = a12 - l20 a01;   l21 = t21 / e1;
+ *       e2 = (a22 - l20 a02) - l21 t21;   z1 = b_1 - l10 b_0;   z2 = (b_2 - l20 b_0) - l21 z1;
+ *       x_2 = z2 / e2;   x_1 = z1 / e1 - l21 x_2;   x_0 = (b_0 / a00 - l10 x_1) - l20 x_2
+ *   which solves (sum N N^T + lam I) x = sum N d + lam c: the point nearest the planes of the cluster's faces, drawn towards the mean
+ *   of its vertices.  Then  if !(x_j >= -0.5) x_j = -0.5;  if !(x_j <= 0.5) x_j = 0.5  (a NaN lands on a bound), and
+ *       verts_out_j = (float)(o_j + ((g_j + 0.5) + x_j) h)
+ *   so every output vertex lies in its own cell.  verts_out is packed image after image in cluster order.  A cluster whose faces all
+ *   vanished stays as an unreferenced vertex.
+ * Faces.  A face that takes part maps to the cluster numbers (k_a, k_b, k_c) of its corners, keeping its rotation.  It is COLLAPSED, and
+ *   dropped, when two of them are equal.  The others are grouped by their unordered triple (an open-addressing table in scratch, image
+ *   b owning slots [2 f_off[b] + b, 2 f_off[b+1] + b + 1): more slots than faces, so a linear probe always meets an empty or matching
+ *   slot; the key (lo << 42) | (mid << 21) | hi of the ascending triple is claimed by a 64-bit compare-and-swap on the empty key).  A
+ *   face is EVEN when (k_a, k_b, k_c) is a rotation of (lo, mid, hi), ODD otherwise.  Per group and parity: the number of faces (integer
+ *   add) and the lowest face number (integer min).  A face is WRITTEN iff it is the lowest face of its parity in its group and that
+ *   parity has strictly more faces than the other: opposite faces cancel -- a sheet folded onto itself vanishes and the surface stays
+ *   closed -- and of several like-oriented copies one stays.  faces_out [.][3] int32 holds the written faces' image-local cluster
+ *   triples, packed image after image in ascending source face number (block-scan compaction); face_source [.] int32 their image-local
+ *   source face numbers.
+ * counts [SC_MESH_SIMPLIFY_FIELDS][n_images] int64, row by row: 0 vertices_out (clusters), 1 faces_out (written faces), 2 collapsed
+ *   faces, 3 cancelled faces = the faces that take part, are not collapsed and are not written.
+ * The caller allocates verts_out [n_verts][3], faces_out [n_faces][3] and face_source [n_faces] (the outputs cannot be larger) and reads
+ * counts to see how much of each was written.  Only integer atomics decide anything: every output has the same bits from run to run,
+ * for any batch, stream and face order (the face list follows the source order by definition).  Ten launches on `stream` (six when
+ * n_faces == 0), no wait on another workgroup, no host synchronisation.  scratch: sc_mesh_cluster_simplify_scratch_bytes(n_images,
+ * n_verts, n_faces, cells) bytes of device memory, 16-byte aligned, contents irrelevant on entry (the query gives 0 for sizes the entry
+ * point refuses).  n_images <= 0 returns 0 and launches nothing; hipErrorInvalidValue for n_images > 65535, n_faces > 2^26, a negative
+ * count, cells outside 1..128, n_images ceil(cells^3 / 64) > 2^28, an origin, pitch or reg that is not finite, pitch <= 0, reg <= 0, a
+ * NULL pointer or a misaligned scratch (verts, verts_out and vertex_cluster may be NULL when n_verts == 0; faces, faces_out and
+ * face_source when n_faces == 0).                                                                                                        */
+#define SC_MESH_SIMPLIFY_MAX_CELLS 128
+#define SC_MESH_SIMPLIFY_ACC 13
+#define SC_MESH_SIMPLIFY_FIELDS 4
+long long sc_mesh_cluster_simplify_scratch_bytes(int n_images, int n_verts, int n_faces, int cells);
+int sc_mesh_cluster_simplify(const float* verts, const int32_t* faces, const int64_t* v_off, const int64_t* f_off, int n_images, int n_verts,
+                             int n_faces, float origin_x, float origin_y, float origin_z, float pitch, int cells, double reg, void* scratch,
+                             float* verts_out, int32_t* faces_out, int64_t* counts, int32_t* vertex_cluster, int32_t* face_source,
+                             int32_t* bad_vertex, int32_t* bad_index, void* stream);
+
 /* ---- camera algebra of a render -------------------------------------------------------------------
  * sc_camera_rays_*: utils/camera.py:157-196 (get_center_and_ray on the rendered pixels only) + the normalisation of
  * model/renderer.py:69-76.  pose [n_images][3][4] = [R|t] world->camera, intr [n_images][3][3], ray_idx

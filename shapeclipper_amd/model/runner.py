@@ -159,6 +159,33 @@ def _write_mesh_stats_lines(path, rows, mode="w"):
                 f.write(mesh_stats_line(r, first))
 
 
+# a line of simplify.txt: idx cell vertices_in vertices_out faces_in faces_out collapsed cancelled dist_mean dist_max
+SIMPLIFY_LINE = "%d" + " %d" * 7 + " %.8f %.8f\n"
+SIMPLIFY_KEYS = ("vertices_in", "v_count", "faces_in", "f_count", "collapsed", "cancelled", "dist_mean", "dist_max")
+
+
+def _simplify_records(var):
+    """[B,11] float64 on the host, a record per sample of eval_3D.meshes_simplified's result: idx, cell, the eight values of
+    SIMPLIFY_KEYS (the counts are exact in float64), category; [B,29] with the 18 values of MESH_STATS_KEYS of the simplified mesh behind
+    them when --eval.mesh_stats gave var.mesh_stats_simplified."""
+    B, res = len(var.idx), var.mesh_simplified
+    cols = [var.idx, torch.full((B,), res["cell"])] + [res[k] for k in SIMPLIFY_KEYS] + [var.category_label]
+    rec = torch.stack([c.detach().double().view(-1).cpu() for c in cols], dim=1)
+    return rec if "mesh_stats_simplified" not in var else torch.cat([rec, _mesh_stats_records(var, "mesh_stats_simplified")[:, 1:19]], dim=1)
+
+
+def _write_simplify_lines(path, rows, mode="w"):
+    """simplify.txt at `path` (and mesh_stats_simplified.txt beside it, in mesh_stats.txt's format, for rows that carry the simplified
+    mesh's statistics) from _simplify_records."""
+    with open(os.path.join(path, "simplify.txt"), mode) as f:
+        for r in rows:
+            f.write(SIMPLIFY_LINE % (*(int(r[c]) for c in range(8)), float(r[8]), float(r[9])))
+    if rows.shape[1] >= 29:
+        with open(os.path.join(path, "mesh_stats_simplified.txt"), mode) as f:
+            for r in rows:
+                f.write(mesh_stats_line(r, 11))
+
+
 TEXTURE_LINE = "%d %d %d %d %.6f %.6f\n"     # a line of texture.txt: idx faces atlas rows err_mean err_max
 
 
@@ -600,7 +627,8 @@ class Runner:
         cd_cat_mesh.txt / f_score_mesh.txt and, with --eval.dual_mesh, their _dual namesakes, from one more gather; with --eval.emd
         also emd.txt / emd_cat.txt and, with --eval.icp, their _icp namesakes, from one more gather; with --eval.iou also iou.txt /
         iou_cat.txt and, with --eval.icp, their _icp namesakes, from one more gather; with --eval.mesh_stats also mesh_stats.txt /
-        mesh_stats_cat.txt and, with --eval.dual_mesh, their _dual namesakes, from one more gather).  The value
+        mesh_stats_cat.txt and, with --eval.dual_mesh, their _dual namesakes, from one more gather; with --eval.simplify also
+        simplify.txt and, with --eval.mesh_stats, mesh_stats_simplified.txt, from one more gather).  The value
         returned is the raw one.  Every rank
         writes the per-sample files of its own samples (dump_visuals: PNGs, mesh and point-cloud PLYs)."""
         from ..parallel import gather_eval_records
@@ -610,6 +638,7 @@ class Runner:
         # right when ranks and devices are numbered differently (several nodes; tests/test_gpu_two_ranks.py: two ranks on one GPU)
         rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else util.get_rank(opt)
         recs, comps, icps, ncs, meshes, emds, texs, mrs, ious, stats = [], [], [], [], [], [], [], [], [], []
+        simps = []                                      # --eval.simplify: _simplify_records of this rank's samples
         for it in range(rank, len(self.test_data), opt.world_size):
             sample = self.test_data[it]
             batch = {k: ({kk: vv[None] for kk, vv in v.items()} if isinstance(v, dict) else torch.as_tensor(v)[None]) for k, v in sample.items()}
@@ -633,6 +662,8 @@ class Runner:
                 ious.append(_iou_records(var))
             if "mesh_stats" in var:                     # --eval.mesh_stats: _mesh_stats_rows' columns
                 stats.append(_mesh_stats_rows(var))
+            if "mesh_simplified" in var:                # --eval.simplify: _simplify_records' columns
+                simps.append(_simplify_records(var))
             if "texture" in var and options.texture_texels(opt) is not None:    # --eval.texture: _texture_records' columns (dump_geometry baked the atlas)
                 texs.append(_texture_records(var))
             if "mesh_render" in var:                    # --eval.mesh_render: _mesh_render_records' columns (dump_geometry rendered)
@@ -674,6 +705,11 @@ class Runner:
             width = 20 if options.dual_mesh_reg(opt) is None else 38
             alls = gather_eval_records(torch.cat(stats).to(dev) if stats else torch.zeros(0, width, device=dev, dtype=torch.float64),
                                        opt.world_size).cpu()
+        allsi = None
+        if options.simplify_settings(opt) is not None:  # likewise
+            width = 29 if options.mesh_stats_settings(opt) else 11
+            allsi = gather_eval_records(torch.cat(simps).to(dev) if simps else torch.zeros(0, width, device=dev, dtype=torch.float64),
+                                        opt.world_size).cpu()
         allt = None
         if options.texture_texels(opt) is not None and util_vis is not None:      # likewise
             allt = gather_eval_records(torch.cat(texs).to(dev) if texs else torch.zeros(0, 6, device=dev, dtype=torch.float64),
@@ -689,6 +725,8 @@ class Runner:
             _write_texture(opt, allt)
         if rank == 0 and alls is not None:
             self._write_mesh_stats(opt, alls)
+        if rank == 0 and allsi is not None:
+            _write_simplify_lines(opt.output_path, allsi)
         if rank == 0 and allv is not None:
             self._write_iou(opt, allv)
         if rank == 0 and alle is not None:
@@ -1023,6 +1061,8 @@ class Runner:
         """{idx}_mesh.ply (the predicted mesh) and {idx}_pointclouds_comp.ply (prediction red, ground truth green) of an evaluated batch;
         with --hip.mesh_color also {idx}_mesh_color.ply (the device mesh with vertex normals and the sample's predicted colours); with
         --eval.dual_mesh also {idx}_mesh_dual.ply (eval_3D.meshes_dual: the dual-contouring mesh of the same grid, positions and faces);
+        with --eval.simplify also {idx}_mesh_simplified.ply (eval_3D.meshes_simplified: the mesh of {idx}_mesh.ply decimated by vertex
+        clustering, positions and faces);
         with --eval.icp also {idx}_pointclouds_comp_icp.ply (the ICP-aligned prediction of eval_3D.icp_metrics red, ground truth green);
         with --eval.normals also {idx}_pointclouds_normals.ply (pointclouds_comp's vertices as x y z nx ny nz red green blue: the SDF's
         normals on the prediction, the estimated PCA normals on the ground truth); with --eval.emd also {idx}_pointclouds_emd.ply (the
@@ -1051,6 +1091,10 @@ class Runner:
             # (--eval.mesh_dist measured against this mesh already and left it in var)
             dual = var.mesh_dual if "mesh_dual" in var else eval_3D.meshes_dual(opt, net.sdf_network, var.proj_latent_sdf, var.level_vox, reg)
             util_vis.dump_meshes(opt, var.idx, "mesh_dual", dual, folder=folder)
+        if options.simplify_settings(opt) is not None:
+            # (eval_metrics decimated the mesh already and left it in var)
+            simple = var.mesh_simplified_world if "mesh_simplified_world" in var else eval_3D.meshes_simplified(opt, var)
+            util_vis.dump_meshes(opt, var.idx, "mesh_simplified", simple, folder=folder)
         if options.texture_texels(opt) is not None:
             net = self.graph.module
             var.texture = eval_3D.mesh_texture(opt, net.sdf_network, net.rgb_network, var.proj_latent_sdf, var.proj_latent_rgb, var.level_vox)
@@ -1126,6 +1170,8 @@ class Runner:
                             f.write(iou_line(r, cols))
             if "mesh_stats" in var:                     # --eval.mesh_stats: MESH_STATS_LINE (and the same for the dual mesh)
                 _write_mesh_stats_lines(opt.output_path, _mesh_stats_rows(var), "w" if write_new else "a")
+            if "mesh_simplified" in var:                # --eval.simplify: SIMPLIFY_LINE (and MESH_STATS_LINE of the simplified mesh)
+                _write_simplify_lines(opt.output_path, _simplify_records(var), "w" if write_new else "a")
             if "emd" in var:                            # --eval.emd: idx n emd rounds converged (and the same after ICP)
                 rec = _emd_records(var)
                 for suffix, cols in (("", [2, 3, 4]), ("_icp", [6, 7, 8]))[:1 if rec.shape[1] < 9 else 2]:

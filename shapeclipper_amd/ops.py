@@ -2418,3 +2418,99 @@ def mesh_topology(verts, faces, v_count, f_count, table_slots=None):
     n = len(MESH_TOPOLOGY_COUNTS)
     return MeshTopology(*counts[:n].unbind(0), *(counts[n + k] != 0 for k in range(len(MESH_TOPOLOGY_FLAGS))), measures[0], measures[1],
                         face_component)
+
+
+# ---- evaluation: decimation by vertex clustering with quadric placement (csrc/mesh_simplify.hip) ----------------------------------------
+MESH_SIMPLIFY_MAX_CELLS = 128               # SC_MESH_SIMPLIFY_MAX_CELLS
+MESH_SIMPLIFY_MAX_WORDS = 1 << 28           # mask words of a whole batch: B ceil(G^3 / 64)
+SimplifiedMesh = collections.namedtuple("SimplifiedMesh", ["verts", "faces", "v_count", "f_count", "vertex_cluster", "face_source",
+                                                           "collapsed", "cancelled"])
+
+
+def mesh_cluster_simplify(verts, faces, v_count, f_count, origin, pitch, cells, reg=0.05):
+    """Decimates B packed triangle meshes -- exactly what isosurface_mesh and dual_contour_mesh return: verts [V,3] fp32 and faces [F,3]
+    int32 on the device, indices LOCAL to the image's vertex slice, v_count / f_count [B] int64 or int32 (host or device) -- by vertex
+    clustering: a box of `cells` = G cells per axis (1..128) of side `pitch` > 0 with its lower corner at `origin` (three numbers) is laid
+    over every image, the vertices of a cell become one vertex at the minimiser of the cell's quadric (the planes of the faces that
+    touch it, regularised towards the mean of its vertices by `reg` > 0, clamped into the cell), faces with two corners in one cell
+    collapse, and of the faces left on one cluster triple opposite ones cancel and like-oriented copies leave one.
+    include/shapeclipper_hip.h states every rule (sc_mesh_cluster_simplify); tests/mesh_simplify_ref.py restates them in numpy.
+
+    -> SimplifiedMesh(verts [V',3] fp32, faces [F',3] int32 image-local, v_count, f_count [B] int64 on the host -- the packed form again,
+    so the result goes into mesh_topology, point_mesh_distance or this op --, vertex_cluster [V] int32 (old vertex -> new vertex of its
+    image), face_source [F'] int32 (new face -> image-local old face), collapsed, cancelled [B] int64 on the device).  Output faces keep
+    the source order; a cluster whose faces all vanished stays as an unreferenced vertex.  Only integer atomics decide anything: the
+    same bits from run to run, for any batch, stream and face order.  Scratch comes from the scratch cache ("mesh simplify").
+
+    ValueError for wrong dtypes, shapes or devices, counts that are negative or do not sum to the packed lengths, a bad origin, pitch,
+    cells or reg -- all before any launch -- and, checked on the device and raised after the launches, for a vertex that is not finite
+    or lies outside the box [origin, origin + G pitch] and for a face index outside its image's vertex range (neither is dereferenced).
+
+    Host synchronisation: one read of the two flags and the per-image counts, which sizes the outputs.  Runs on the current stream."""
+    who = "shapeclipper_amd: mesh_cluster_simplify"
+    for name, t, dtypes in (("verts", verts, (torch.float32,)), ("faces", faces, (torch.int32,)),
+                            ("v_count", v_count, (torch.int64, torch.int32)), ("f_count", f_count, (torch.int64, torch.int32))):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
+        if t.dtype not in dtypes:
+            raise ValueError("%s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype))
+    for name, t in (("verts", verts), ("faces", faces)):
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("%s: %s must be [n,3], got %s" % (who, name, tuple(t.shape)))
+        if not t.is_cuda:
+            raise ValueError("%s: %s is a CPU tensor; the HIP kernels need device tensors (no CPU fallback)" % (who, name))
+    if faces.device != verts.device:
+        raise ValueError("%s: faces is on %s, verts is on %s" % (who, faces.device, verts.device))
+    if v_count.dim() != 1 or v_count.shape != f_count.shape:
+        raise ValueError("%s: v_count and f_count must be [B], got %s and %s" % (who, tuple(v_count.shape), tuple(f_count.shape)))
+    for name, t in (("v_count", v_count), ("f_count", f_count)):
+        if t.is_cuda and t.device != verts.device:
+            raise ValueError("%s: %s is on %s, verts is on %s" % (who, name, t.device, verts.device))
+    number = lambda x: isinstance(x, (int, float)) and not isinstance(x, bool) and x == x and abs(x) != float("inf")
+    if isinstance(origin, torch.Tensor):
+        origin = origin.detach().cpu().reshape(-1).tolist()
+    if not isinstance(origin, (list, tuple)) or len(origin) != 3 or not all(number(x) for x in origin):
+        raise ValueError("%s: origin must be three finite numbers, got %r" % (who, origin))
+    if not number(pitch) or not pitch > 0 or not float(torch.tensor(float(pitch), dtype=torch.float32)) > 0:
+        raise ValueError("%s: pitch must be a finite number > 0 (as fp32), got %r" % (who, pitch))
+    if isinstance(cells, bool) or not isinstance(cells, int) or not 1 <= cells <= MESH_SIMPLIFY_MAX_CELLS:
+        raise ValueError("%s: cells must be an integer in 1..%d, got %r" % (who, MESH_SIMPLIFY_MAX_CELLS, cells))
+    if not number(reg) or not reg > 0:
+        raise ValueError("%s: reg must be a finite number > 0, got %r" % (who, reg))
+    B, V, F, dev = v_count.shape[0], verts.shape[0], faces.shape[0], verts.device
+    if B > MESH_TOPOLOGY_MAX_IMAGES or F > MESH_TOPOLOGY_MAX_FACES or V > 2 ** 31 - 1 or B * ((cells ** 3 + 63) // 64) > MESH_SIMPLIFY_MAX_WORDS:
+        raise ValueError("%s takes at most %d images, 2^26 faces, 2^31 - 1 vertices and B ceil(cells^3 / 64) <= 2^28 per call, got %d, %d, %d "
+                         "and cells = %d" % (who, MESH_TOPOLOGY_MAX_IMAGES, B, F, V, cells))
+    counts_host = torch.stack([v_count.long(), f_count.long()]).cpu()               # free for host counts, the form the meshers return
+    if B and int(counts_host.min()) < 0 or int(counts_host[0].sum()) != V or int(counts_host[1].sum()) != F:
+        raise ValueError("%s: v_count / f_count must be non-negative and sum to the packed lengths (%d vertices, %d faces), got sums %d and %d"
+                         % (who, V, F, int(counts_host[0].sum()), int(counts_host[1].sum())))
+    verts_out = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    faces_out = torch.empty(F, 3, device=dev, dtype=torch.int32)
+    vertex_cluster = torch.empty(V, device=dev, dtype=torch.int32)
+    face_source = torch.empty(F, device=dev, dtype=torch.int32)
+    back = torch.zeros(4 * B + 1, device=dev, dtype=torch.int64)                    # what the host reads: the counts, then the two flags
+    counts, bad = back[:4 * B].view(4, B), back[4 * B:].view(torch.int32)           # SC_MESH_SIMPLIFY_FIELDS rows; bad_vertex, bad_index
+    if B == 0:
+        return SimplifiedMesh(verts_out, faces_out, counts_host[0], counts_host[1], vertex_cluster, face_source, counts[2], counts[3])
+    offsets = torch.zeros(2, B + 1, dtype=torch.int64)
+    offsets[:, 1:] = counts_host.cumsum(1)
+    offsets = offsets.to(dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = _scratch("mesh simplify", dev, (lib.sc_mesh_cluster_simplify_scratch_bytes(B, V, F, cells) + 3) // 4)
+        code = lib.sc_mesh_cluster_simplify(_lib.ptr(verts.contiguous()) if V else None, _lib.ptr(faces.contiguous()) if F else None,
+                                            _lib.ptr(offsets[0]), _lib.ptr(offsets[1]), B, V, F, float(origin[0]), float(origin[1]),
+                                            float(origin[2]), float(pitch), cells, float(reg), _lib.ptr(ws),
+                                            _lib.ptr(verts_out) if V else None, _lib.ptr(faces_out) if F else None, _lib.ptr(counts),
+                                            _lib.ptr(vertex_cluster) if V else None, _lib.ptr(face_source) if F else None,
+                                            _lib.ptr(bad[:1]), _lib.ptr(bad[1:]), _lib.stream())
+    _lib.check(code, "sc_mesh_cluster_simplify")
+    host = back.cpu()
+    flags, sizes = host[4 * B:].view(torch.int32).tolist(), host[:2 * B].view(2, B)
+    if flags[0]:
+        raise ValueError("%s: a vertex is not finite or lies outside the box [origin, origin + cells * pitch]" % who)
+    if flags[1]:
+        raise ValueError("%s: a face index lies outside its image's vertex range [0, v_count[b])" % who)
+    return SimplifiedMesh(verts_out[:int(sizes[0].sum())], faces_out[:int(sizes[1].sum())], sizes[0], sizes[1], vertex_cluster,
+                          face_source[:int(sizes[1].sum())], counts[2], counts[3])

@@ -27,6 +27,8 @@ Call surface of the reference's utils/eval_3D.py.
     are written, from an edge table and two union-finds on the device (ops.mesh_topology, csrc/mesh_topology.hip).
   * meshes_dual (`--eval.dual_mesh`): the dual-contouring mesh of the same grid from the SDF gradients at the crossings
     (csrc/dual_contour.hip), which keeps corners and creases that marching cubes chamfers at the grid pitch.
+  * meshes_simplified (`--eval.simplify=k`): the marching-cubes mesh decimated by vertex clustering in cells of k grid pitches with
+    quadric placement (ops.mesh_cluster_simplify, csrc/mesh_simplify.hip), and what the smaller file costs in distance.
 """
 from __future__ import annotations
 
@@ -781,6 +783,56 @@ def mesh_stats(opt, var, sdf_network=None):
         var.mesh_stats_dual = measure(var.mesh_dual_packed)
 
 
+@torch.no_grad()
+def meshes_simplified(opt, var):
+    """`--eval.simplify=k`: the mesh that is written, decimated.  ops.mesh_cluster_simplify (csrc/mesh_simplify.hip) on the packed mesh of
+    ops.isosurface_mesh(var.level_vox) -- var.mesh_packed, built here as mesh_stats does when it is absent -- in grid-index units with
+    origin 0, cells of k grid pitches and G = ceil((S - 1) / k) cells per axis (a ValueError naming eval.simplify when G > 128).
+    Sets var.mesh_simplified, a dict (var keeps dicts with attribute access): the fields of ops.SimplifiedMesh (verts in grid-index units),
+    cell = k, vertices_in, faces_in [B] and dist_mean, dist_max [B] float32 -- the distance from every ORIGINAL vertex to the simplified
+    mesh (ops.point_mesh_distance), both at the positions the level grid was sampled at, lo + v (hi - lo) / (S - 1), in object units: the
+    one-sided deviation paid for the smaller file; nan for an image whose simplified mesh has no face.  With `--eval.mesh_stats` also
+    var.mesh_stats_simplified, ops.mesh_topology of the simplified mesh at those positions, as a dict.  Returns, and keeps in
+    var.mesh_simplified_world for the dump, the per-image list of (vertices, faces) with meshes_device's v / S rescale, which overlays
+    {idx}_mesh.ply.  Nothing is repaired, nothing enters a loss."""
+    k, reg = options.simplify_settings(opt)
+    lo, hi = opt.eval.range
+    B, S = var.level_vox.shape[0], var.level_vox.shape[1]
+    dev = var.level_vox.device
+    G = -(-(S - 1) // k)
+    if G > ops.MESH_SIMPLIFY_MAX_CELLS:
+        raise ValueError("eval.simplify = %d gives %d cells per axis at a level grid of %d points; at most %d (choose eval.simplify >= %d)"
+                         % (k, G, S, ops.MESH_SIMPLIFY_MAX_CELLS, -(-(S - 1) // ops.MESH_SIMPLIFY_MAX_CELLS)))
+    if "mesh_packed" not in var:
+        var.mesh_packed = list(ops.isosurface_mesh(var.level_vox))
+    verts, faces, v_count, f_count = var.mesh_packed
+    res = ops.mesh_cluster_simplify(verts, faces, v_count, f_count, (0.0, 0.0, 0.0), float(k), G, reg)
+    to_object = lambda v: (lo + v * ((hi - lo) / (S - 1))).contiguous()
+    v_in, v_out, f_out = v_count.tolist(), res.v_count.tolist(), res.f_count.tolist()
+    dist_mean = torch.full((B,), float("nan"), device=dev)
+    dist_max = torch.full((B,), float("nan"), device=dev)
+    N = max(v_in, default=0)
+    if N > 0 and res.faces.shape[0] > 0:
+        start = (torch.cumsum(v_count, 0) - v_count).to(dev).clamp_max(verts.shape[0] - 1)
+        j = torch.arange(N, device=dev)
+        real = j[None] < v_count.to(dev)[:, None]                       # padding rows repeat the image's first vertex
+        rows = torch.where(real, start[:, None] + j[None], start[:, None])
+        i32 = dict(dtype=torch.int32, device=dev)
+        dist = ops.point_mesh_distance(to_object(verts)[rows].contiguous(), to_object(res.verts), res.faces.contiguous(),
+                                       torch.tensor(v_out, **i32), torch.tensor(f_out, **i32), search="grid").dist2.sqrt()
+        for b in range(B):
+            if v_in[b] > 0 and f_out[b] > 0:
+                dist_mean[b], dist_max[b] = dist[b, :v_in[b]].mean(), dist[b, :v_in[b]].max()
+    var.mesh_simplified = dict(res._asdict(), cell=k, vertices_in=v_count.clone(), faces_in=f_count.clone(), dist_mean=dist_mean,
+                               dist_max=dist_max)
+    if options.mesh_stats_settings(opt):
+        var.mesh_stats_simplified = ops.mesh_topology(to_object(res.verts), res.faces, res.v_count, res.f_count)._asdict()
+    world = res.verts / S * (hi - lo) + lo
+    v_end, f_end = torch.cumsum(res.v_count, 0).tolist(), torch.cumsum(res.f_count, 0).tolist()
+    var.mesh_simplified_world = [(world[e - n:e], res.faces[fe - fn:fe]) for e, n, fe, fn in zip(v_end, v_out, f_end, f_out)]
+    return var.mesh_simplified_world
+
+
 def icp_summary(var):
     """[B,5] float64 on the host, a row of icp.txt per sample: s, the rotation angle in degrees, |t|, the first and the last objective."""
     T, s, obj = (var.icp[k].detach().cpu().double() for k in ("transform", "s", "objective"))
@@ -833,6 +885,8 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     if vis_only:
         if options.mesh_stats_settings(opt):    # vis_{ep}/mesh_stats.txt of --hip.train_vis
             mesh_stats(opt, var, sdf_network)
+        if options.simplify_settings(opt) is not None:      # vis_{ep}/{idx}_mesh_simplified.ply
+            meshes_simplified(opt, var)
         return
     dist_acc, dist_comp, idx1, idx2 = chamfer_distance(opt, X1=var.dpc_pred, X2=var.dpc.points)
     var.f_score = compute_fscore(dist_acc, dist_comp, opt.eval.f_thresholds)
@@ -857,4 +911,6 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
         iou_metrics(opt, var, *iou, icp=aligned)
     if options.mesh_stats_settings(opt):    # likewise
         mesh_stats(opt, var, sdf_network)
+    if options.simplify_settings(opt) is not None:          # likewise
+        meshes_simplified(opt, var)
     return dist_acc.mean(), dist_comp.mean()

@@ -211,6 +211,26 @@ def mesh_stats_settings(opt):
     return on
 
 
+def simplify_settings(opt):
+    """The evaluation's decimated mesh: None unless `--eval.simplify=k` is given (absent means off), else (k, reg): k, an integer in
+    2..16, is the side of a cluster cell in grid pitches and reg, `--eval.simplify_reg` (default 0.05, a float in (0, 1]), the pull of a
+    cluster's vertex towards the mean of its vertices -- the arguments of eval_3D.meshes_simplified (ops.mesh_cluster_simplify).
+    Evaluation settings beside eval.vox_res, not hip.* switches.  A bool or any other bad value is a ValueError, whether or not the
+    switch is on.  (A string that float() reads is taken as that number, as for eval.emd_eps.)"""
+    ev = opt.get("eval", None) or {}
+    k, reg = ev.get("simplify", None), ev.get("simplify_reg", 0.05)
+    if isinstance(reg, str):
+        try:
+            reg = float(reg)
+        except ValueError:
+            pass
+    if k is not None and (isinstance(k, bool) or not isinstance(k, int) or not 2 <= k <= 16):
+        raise ValueError("eval.simplify must be an integer in 2..16, got %r" % (k,))
+    if isinstance(reg, bool) or not isinstance(reg, (int, float)) or not 0.0 < reg <= 1.0:
+        raise ValueError("eval.simplify_reg must be a float in (0, 1], got %r" % (reg,))
+    return None if k is None else (k, float(reg))
+
+
 def parse_arguments(args):
     """--key1.key2=value ; --flag (true) ; --flag! (false)"""
     opt_cmd = {}
@@ -309,6 +329,7 @@ def process_options(opt):
     emd_settings(opt)
     iou_settings(opt)
     mesh_stats_settings(opt)
+    simplify_settings(opt)
     torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
     for row in HIP_TABLE:
         if row.drives is not None:
