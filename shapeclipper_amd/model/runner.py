@@ -11,6 +11,7 @@ train, evaluate, ...).  Differences that matter on MI355X:
 from __future__ import annotations
 
 import contextlib
+import functools
 import importlib
 import os
 import shutil
@@ -26,6 +27,10 @@ from ..parallel import FlatGradAllReduce, ModuleHolder
 from ..utils import eval_3D, options, util
 from ..utils.util import EasyDict as edict
 from ..utils.util import cleanup, log, setup
+# the optional evaluation outputs are declared in utils/eval_reports.py; the names the per-output tests and tools import stay reachable here
+from ..utils.eval_reports import (ICP_KEYS, IOU_COLS, IOU_KEYS, MESH_LINE, MESH_STATS_KEYS, MESH_STATS_LINE, NC_LINE, REPORT, REPORTS,  # noqa: F401
+                                  _component_counts, _iou_records, _mesh_records, _mesh_stats_records, _mesh_stats_rows, _normal_records,
+                                  _write_mesh_stats_lines, iou_line, mesh_stats_line)
 
 try:
     from ..utils import util_vis
@@ -56,168 +61,6 @@ def _surface_render(opt):
     (Renderer.render_surface with `--hip.surface_refine` rounds at `--hip.surface_scale` times the evaluation resolution):
     {idx}_image_surface.png, _mask_surface.png, _normal_surface.png, _depth_surface.png and _depth_surface.npy."""
     return bool(options.hip(opt, "surface_render"))
-
-
-def _component_counts(var):
-    """(n_components, inside_voxels, kept_voxels) [B] of var.component_stats (eval_3D.eval_metrics with `--hip.largest_component`)."""
-    return tuple(var.component_stats[k] for k in ("n_components", "inside_voxels", "kept_voxels"))
-
-
-NC_LINE = "%d %.8f %.8f %.8f\n"              # a line of normal_consistency.txt: idx nc_acc nc_comp nc
-
-
-def _normal_records(var):
-    """[B,5] float64 on the host, a record per sample of eval_3D.normal_metrics' results: idx, nc_acc, nc_comp, nc, category; [B,8]
-    with the three values after ICP behind them when --eval.icp ran as well."""
-    cols = [var.idx, var.nc_acc, var.nc_comp, var.nc, var.category_label]
-    if "nc_icp" in var:
-        cols += [var.nc_acc_icp, var.nc_comp_icp, var.nc_icp]
-    return torch.stack([c.detach().double().view(-1).cpu() for c in cols], dim=1)
-
-
-MESH_LINE = "%d %.8f %.8f\n"                  # a line of completeness_mesh.txt: idx cd_comp cd_comp_mesh
-
-
-def _mesh_records(var):
-    """[B, 5 + T] float64 on the host, a record per sample of eval_3D.mesh_metrics' results: idx, cd_acc, cd_comp, cd_comp_mesh,
-    f_score_mesh [T], category; [B, 6 + 2 T] with cd_comp_dual and f_score_dual [T] behind them when --eval.dual_mesh is on as well."""
-    cols = [var.idx, var.cd_acc, var.cd_comp, var.cd_comp_mesh, var.f_score_mesh, var.category_label]
-    if "cd_comp_dual" in var:
-        cols += [var.cd_comp_dual, var.f_score_dual]
-    B = len(var.idx)
-    return torch.cat([c.detach().double().view(B, -1).cpu() for c in cols], dim=1)
-
-
-EMD_LINE = "%d %d %.8f %d %d\n"              # a line of emd.txt: idx n emd rounds converged
-
-
-def _emd_records(var):
-    """[B,6] float64 on the host, a record per sample of eval_3D.emd_metrics' results: idx, n, emd, rounds, converged, category; [B,9]
-    with emd, rounds and converged of the ICP-aligned prediction behind them when --eval.icp ran as well."""
-    B = len(var.idx)
-    cols = [var.idx, torch.full((B,), var.emd_n), var.emd, var.emd_rounds, var.emd_converged, var.category_label]
-    if "emd_icp" in var:
-        cols += [var.emd_icp, var.emd_rounds_icp, var.emd_converged_icp]
-    return torch.stack([c.detach().double().view(-1).cpu() for c in cols], dim=1)
-
-
-IOU_LINE = "%d %d %.8f %d %d %d %d %d %d\n"  # a line of iou.txt: idx res iou inter union vox_pred vox_gt shell_pred shell_gt
-IOU_KEYS = ("iou", "iou_inter", "iou_union", "iou_vox_pred", "iou_vox_gt", "iou_shell_pred", "iou_shell_gt")
-IOU_COLS = (("", [2, 3, 4, 5, 6, 7, 8]), ("_icp", [10, 11, 12, 13, 14, 15, 16]))      # the columns of a line behind idx and res
-
-
-def _iou_records(var):
-    """[B,10] float64 on the host, a record per sample of eval_3D.iou_metrics' results: idx, res, the seven values of IOU_KEYS, category;
-    [B,17] with the seven values of the ICP-aligned prediction behind them when --eval.icp ran as well."""
-    B = len(var.idx)
-    cols = [var.idx, torch.full((B,), var.iou_res)] + [var[k] for k in IOU_KEYS] + [var.category_label]
-    if "iou_icp" in var:
-        cols += [var[k + "_icp"] for k in IOU_KEYS]
-    return torch.stack([c.detach().double().view(-1).cpu() for c in cols], dim=1)
-
-
-def iou_line(r, cols):
-    """The line of iou.txt (or iou_icp.txt) of one row of _iou_records."""
-    return IOU_LINE % (int(r[0]), int(r[1]), float(r[cols[0]]), *(int(r[c]) for c in cols[1:]))
-
-
-# a line of mesh_stats.txt: idx vertices faces edges boundary nonmanifold_edges nonmanifold_vertices inconsistent degenerate unreferenced
-# components largest_faces euler genus watertight oriented manifold area volume
-MESH_STATS_LINE = "%d" + " %d" * 16 + " %.8f %.8f\n"
-MESH_STATS_KEYS = ("vertices", "faces", "edges", "boundary_edges", "nonmanifold_edges", "nonmanifold_vertices", "inconsistent_edges",
-                   "degenerate_faces", "unreferenced_vertices", "components", "largest_component_faces", "euler", "genus", "watertight",
-                   "oriented", "manifold", "area", "volume")
-MESH_STATS_COLS = (("", 1), ("_dual", 20))      # the first of a mesh's 18 columns in a row of _mesh_stats_records
-
-
-def _mesh_stats_records(var, key="mesh_stats"):
-    """[B,20] float64 on the host, a record per sample of eval_3D.mesh_stats' result var[key]: idx, the 18 values of MESH_STATS_KEYS (the
-    counts are exact in float64), category."""
-    stats = var[key]
-    stats = stats._asdict() if hasattr(stats, "_asdict") else stats
-    cols = [var.idx] + [stats[k] for k in MESH_STATS_KEYS] + [var.category_label]
-    return torch.stack([c.detach().double().view(-1).cpu() for c in cols], dim=1)
-
-
-def _mesh_stats_rows(var):
-    """_mesh_stats_records of the marching-cubes mesh; [B,38] with the 18 values of the dual-contouring mesh behind them when
-    --eval.dual_mesh gave var.mesh_stats_dual."""
-    rec = _mesh_stats_records(var)
-    return rec if "mesh_stats_dual" not in var else torch.cat([rec, _mesh_stats_records(var, "mesh_stats_dual")[:, 1:19]], dim=1)
-
-
-def mesh_stats_line(r, first=1):
-    """The line of mesh_stats.txt (or mesh_stats_dual.txt) of one row of _mesh_stats_records."""
-    return MESH_STATS_LINE % (int(r[0]), *(int(r[c]) for c in range(first, first + 16)), float(r[first + 16]), float(r[first + 17]))
-
-
-def _write_mesh_stats_lines(path, rows, mode="w"):
-    """mesh_stats.txt at `path` (and mesh_stats_dual.txt beside it for rows that carry the dual mesh's columns) from _mesh_stats_rows."""
-    for suffix, first in MESH_STATS_COLS[:1 if rows.shape[1] < 38 else 2]:
-        with open(os.path.join(path, "mesh_stats{}.txt".format(suffix)), mode) as f:
-            for r in rows:
-                f.write(mesh_stats_line(r, first))
-
-
-# a line of simplify.txt: idx cell vertices_in vertices_out faces_in faces_out collapsed cancelled dist_mean dist_max
-SIMPLIFY_LINE = "%d" + " %d" * 7 + " %.8f %.8f\n"
-SIMPLIFY_KEYS = ("vertices_in", "v_count", "faces_in", "f_count", "collapsed", "cancelled", "dist_mean", "dist_max")
-
-
-def _simplify_records(var):
-    """[B,11] float64 on the host, a record per sample of eval_3D.meshes_simplified's result: idx, cell, the eight values of
-    SIMPLIFY_KEYS (the counts are exact in float64), category; [B,29] with the 18 values of MESH_STATS_KEYS of the simplified mesh behind
-    them when --eval.mesh_stats gave var.mesh_stats_simplified."""
-    B, res = len(var.idx), var.mesh_simplified
-    cols = [var.idx, torch.full((B,), res["cell"])] + [res[k] for k in SIMPLIFY_KEYS] + [var.category_label]
-    rec = torch.stack([c.detach().double().view(-1).cpu() for c in cols], dim=1)
-    return rec if "mesh_stats_simplified" not in var else torch.cat([rec, _mesh_stats_records(var, "mesh_stats_simplified")[:, 1:19]], dim=1)
-
-
-def _write_simplify_lines(path, rows, mode="w"):
-    """simplify.txt at `path` (and mesh_stats_simplified.txt beside it, in mesh_stats.txt's format, for rows that carry the simplified
-    mesh's statistics) from _simplify_records."""
-    with open(os.path.join(path, "simplify.txt"), mode) as f:
-        for r in rows:
-            f.write(SIMPLIFY_LINE % (*(int(r[c]) for c in range(8)), float(r[8]), float(r[9])))
-    if rows.shape[1] >= 29:
-        with open(os.path.join(path, "mesh_stats_simplified.txt"), mode) as f:
-            for r in rows:
-                f.write(mesh_stats_line(r, 11))
-
-
-TEXTURE_LINE = "%d %d %d %d %.6f %.6f\n"     # a line of texture.txt: idx faces atlas rows err_mean err_max
-
-
-def _texture_records(var):
-    """[B,6] float64 on the host, a record per sample of eval_3D.mesh_texture's stats (var.texture, left by dump_geometry with
-    --eval.texture): idx, faces, atlas, rows, err_mean, err_max."""
-    return torch.tensor([[float(i)] + [float(m.stats[k]) for k in ("faces", "atlas", "rows", "err_mean", "err_max")]
-                         for i, m in zip(var.idx.tolist(), var.texture)], dtype=torch.float64).view(-1, 6)
-
-
-def _write_texture(opt, rec, mode="w"):
-    with open("{}/texture.txt".format(opt.output_path), mode) as f:
-        for r in rec:
-            f.write(TEXTURE_LINE % (int(r[0]), int(r[1]), int(r[2]), int(r[3]), float(r[4]), float(r[5])))
-
-
-MESH_RENDER_LINE = "%d %d %d %.6f %.6f\n"   # a line of mesh_render.txt: idx faces pixels iou_input iou_volume
-
-
-def _mesh_render_records(var):
-    """[B,5] float64 on the host, a record per sample of eval_3D.mesh_render_sample (var.mesh_render, left by dump_geometry with
-    --eval.mesh_render): idx, faces, pixels, iou_input, iou_volume (nan where the map to compare with is missing)."""
-    m = var.mesh_render
-    cols = [var.idx.double().view(-1).cpu(), torch.tensor(m.faces, dtype=torch.float64), torch.tensor(m.pixels, dtype=torch.float64),
-            m.iou_input.double().view(-1).cpu(), m.iou_volume.double().view(-1).cpu()]
-    return torch.stack(cols, dim=1)
-
-
-def _write_mesh_render(opt, rec, mode="w"):
-    with open("{}/mesh_render.txt".format(opt.output_path), mode) as f:
-        for r in rec:
-            f.write(MESH_RENDER_LINE % (int(r[0]), int(r[1]), int(r[2]), float(r[3]), float(r[4])))
 
 
 class Runner:
@@ -542,11 +385,8 @@ class Runner:
         C = opt.data.num_classes
         acc_cat, comp_cat, counts = [0.] * C, [0.] * C, [0.001] * C
         f_scores_icp, acc_cat_icp, comp_cat_icp = [], [0.] * C, [0.] * C     # --eval.icp: the same tallies of the ICP-aligned metrics
-        nc_recs = []                                    # --eval.normals: _normal_records of every batch
-        mesh_recs = []                                  # --eval.mesh_dist: _mesh_records of every batch
-        emd_recs = []                                   # --eval.emd: _emd_records of every batch
-        iou_recs = []                                   # --eval.iou: _iou_records of every batch
-        stats_recs = []                                 # --eval.mesh_stats: _mesh_stats_rows of every batch
+        tabled = [rep for rep in REPORTS if rep.base.tables]                 # dump_results writes the per-sample lines of every report
+        recs = {rep.key: [] for rep in tabled}                               # the records of every batch, for the per-category tables
         loader = tqdm.tqdm(self.test_loader, desc="evaluating", leave=False)
         for it, batch in enumerate(loader):
             var = self.evaluate_batch(opt, edict(batch), ep, it, single_gpu=True)
@@ -559,16 +399,9 @@ class Runner:
                     acc_cat_icp[c] += var.cd_acc_icp[i].item(); comp_cat_icp[c] += var.cd_comp_icp[i].item()
             if "icp" in var:
                 f_scores_icp.append(var.f_score_icp)
-            if "nc" in var:
-                nc_recs.append(_normal_records(var))
-            if "cd_comp_mesh" in var:
-                mesh_recs.append(_mesh_records(var))
-            if "emd" in var:
-                emd_recs.append(_emd_records(var))
-            if "iou" in var:
-                iou_recs.append(_iou_records(var))
-            if "mesh_stats" in var:
-                stats_recs.append(_mesh_stats_rows(var))
+            for rep in tabled:
+                if rep.present(var, opt):
+                    recs[rep.key].append(rep.records(var))
             metric["dist_acc"] += dist_acc * len(var.idx)
             metric["dist_cov"] += dist_cov * len(var.idx)
             loader.set_postfix(CD="{:.3f}".format(float((dist_acc + dist_cov) / 2)))
@@ -577,9 +410,9 @@ class Runner:
             if not training:
                 self.dump_results(opt, var, ep, write_new=(it == 0))
         if not training:
+            names = self._category_names(opt)
             with open(os.path.join(opt.output_path, "cd_cat.txt"), "w") as f:
                 f.write("CD     Acc    Comp   Count Cat\n")
-                names = getattr(self.test_data, "label2cat", {i: str(i) for i in range(C)})
                 for i in range(C):
                     a, c = acc_cat[i] / counts[i], comp_cat[i] / counts[i]
                     f.write("%.4f %.4f %.4f %5d %s\n" % ((a + c) / 2, a, c, counts[i], names[i]))
@@ -598,16 +431,9 @@ class Runner:
                 with open(os.path.join(opt.output_path, "f_score_icp.txt"), "w") as f:
                     for i, th in enumerate(opt.eval.f_thresholds):
                         f.write("F-score @ %.2f: %.4f\n" % (th * 100, fs[i].item()))
-            if nc_recs:                                 # nc_cat.txt (and nc_cat_icp.txt); dump_results wrote the per-sample lines
-                self._write_normals(opt, torch.cat(nc_recs), per_sample=False)
-            if mesh_recs:                               # cd_cat_mesh.txt / f_score_mesh.txt (and the _dual namesakes); likewise
-                self._write_mesh(opt, torch.cat(mesh_recs), per_sample=False)
-            if emd_recs:                                # emd_cat.txt (and emd_cat_icp.txt); likewise
-                self._write_emd(opt, torch.cat(emd_recs), per_sample=False)
-            if iou_recs:                                # iou_cat.txt (and iou_cat_icp.txt); likewise
-                self._write_iou(opt, torch.cat(iou_recs), per_sample=False)
-            if stats_recs:                              # mesh_stats_cat.txt (and mesh_stats_cat_dual.txt); likewise
-                self._write_mesh_stats(opt, torch.cat(stats_recs), per_sample=False)
+            for rep in tabled:
+                if recs[rep.key]:
+                    self._write_report(opt, torch.cat(recs[rep.key]), per_sample=False, key=rep.key)
         n = max(len(self.test_data), 1)
         for k in metric:
             metric[k] /= n
@@ -617,137 +443,50 @@ class Runner:
 
     @torch.no_grad()
     def evaluate_sharded(self, opt, ep=0):
-        """Evaluation over all ranks (BASELINE config[4]; the reference evaluates on one GPU, evaluate.py:16-18):
-        rank r takes the test samples with index % world == r (eval.batch_size = 1), per-sample records are
-        gathered once, rank 0 writes chamfer.txt / cd_cat.txt / f_score.txt in sample order (with --hip.largest_component also
-        components.txt, from a second gather of the per-sample counts; with --eval.texture also texture.txt, from one more gather of
-        the bake's per-sample records; with --eval.mesh_render also mesh_render.txt, likewise; with --eval.icp also chamfer_icp.txt / cd_cat_icp.txt /
-        f_score_icp.txt / icp.txt, from one more gather of the ICP-aligned records; with --eval.normals also normal_consistency.txt /
-        nc_cat.txt and their _icp namesakes, from one more gather again; with --eval.mesh_dist also completeness_mesh.txt /
-        cd_cat_mesh.txt / f_score_mesh.txt and, with --eval.dual_mesh, their _dual namesakes, from one more gather; with --eval.emd
-        also emd.txt / emd_cat.txt and, with --eval.icp, their _icp namesakes, from one more gather; with --eval.iou also iou.txt /
-        iou_cat.txt and, with --eval.icp, their _icp namesakes, from one more gather; with --eval.mesh_stats also mesh_stats.txt /
-        mesh_stats_cat.txt and, with --eval.dual_mesh, their _dual namesakes, from one more gather; with --eval.simplify also
-        simplify.txt and, with --eval.mesh_stats, mesh_stats_simplified.txt, from one more gather).  The value
-        returned is the raw one.  Every rank
-        writes the per-sample files of its own samples (dump_visuals: PNGs, mesh and point-cloud PLYs)."""
+        """Evaluation over all ranks (BASELINE config[4]; the reference evaluates on one GPU, evaluate.py:16-18): rank r takes the test
+        samples with index % world == r (eval.batch_size = 1), the per-sample records are gathered, and rank 0 writes chamfer.txt /
+        cd_cat.txt / f_score.txt in sample order.  Every optional output that is enabled (eval_reports.REPORTS, in that order) costs one
+        more gather of its records, which every rank joins, also one that evaluated no sample; rank 0 writes its files.  The value
+        returned is the raw one.  Every rank writes the per-sample files of its own samples (dump_visuals: PNGs, mesh and point-cloud PLYs)."""
         from ..parallel import gather_eval_records
         self.graph.eval()
         opt.H, opt.W = opt.eval.image_size
         # the reference's single-node convention is rank == device index; the process group's rank is the same number there and stays
         # right when ranks and devices are numbered differently (several nodes; tests/test_gpu_two_ranks.py: two ranks on one GPU)
         rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else util.get_rank(opt)
-        recs, comps, icps, ncs, meshes, emds, texs, mrs, ious, stats = [], [], [], [], [], [], [], [], [], []
-        simps = []                                      # --eval.simplify: _simplify_records of this rank's samples
+        raw, recs = [], {rep.key: [] for rep in REPORTS}
         for it in range(rank, len(self.test_data), opt.world_size):
             sample = self.test_data[it]
             batch = {k: ({kk: vv[None] for kk, vv in v.items()} if isinstance(v, dict) else torch.as_tensor(v)[None]) for k, v in sample.items()}
             var = self.evaluate_batch(opt, edict(batch), ep, it, single_gpu=True)
             eval_3D.eval_metrics(opt, var, self.graph.module.sdf_network)
-            self.dump_visuals(opt, var, ep)             # this rank's samples only; rank 0 writes chamfer.txt once below
-            recs.append(torch.cat([var.idx.float().view(1), var.cd_acc.view(1), var.cd_comp.view(1), var.f_score.view(-1),
-                                   var.category_label.float().view(1)]))
-            if "component_stats" in var:                # --hip.largest_component: (idx, n_components, inside_voxels, kept_voxels), exact in float64
-                comps.append(torch.cat([t.view(1).double() for t in (var.idx, *_component_counts(var))]))
-            if "icp" in var:                            # --eval.icp: the record above of the aligned metrics, then icp.txt's five numbers
-                icps.append(torch.cat([t.double().view(-1).cpu() for t in (var.idx, var.cd_acc_icp, var.cd_comp_icp, var.f_score_icp,
-                                                                           var.category_label, eval_3D.icp_summary(var))]))
-            if "nc" in var:                             # --eval.normals: (idx, nc_acc, nc_comp, nc, category[, the three after ICP])
-                ncs.append(_normal_records(var))
-            if "cd_comp_mesh" in var:                   # --eval.mesh_dist: _mesh_records' columns
-                meshes.append(_mesh_records(var))
-            if "emd" in var:                            # --eval.emd: _emd_records' columns
-                emds.append(_emd_records(var))
-            if "iou" in var:                            # --eval.iou: _iou_records' columns
-                ious.append(_iou_records(var))
-            if "mesh_stats" in var:                     # --eval.mesh_stats: _mesh_stats_rows' columns
-                stats.append(_mesh_stats_rows(var))
-            if "mesh_simplified" in var:                # --eval.simplify: _simplify_records' columns
-                simps.append(_simplify_records(var))
-            if "texture" in var and options.texture_texels(opt) is not None:    # --eval.texture: _texture_records' columns (dump_geometry baked the atlas)
-                texs.append(_texture_records(var))
-            if "mesh_render" in var:                    # --eval.mesh_render: _mesh_render_records' columns (dump_geometry rendered)
-                mrs.append(_mesh_render_records(var))
+            self.dump_visuals(opt, var, ep)             # this rank's samples only (dump_geometry leaves var.texture / var.mesh_render)
+            raw.append(torch.cat([var.idx.float().view(1), var.cd_acc.view(1), var.cd_comp.view(1), var.f_score.view(-1),
+                                  var.category_label.float().view(1)]))
+            for rep in REPORTS:
+                if rep.present(var, opt):
+                    recs[rep.key].append(rep.records(var))
         dev = next(self.graph.parameters()).device
-        records = torch.stack(recs) if recs else torch.zeros(0, 10, device=dev)
+        records = torch.stack(raw) if raw else torch.zeros(0, 10, device=dev)
         allr = gather_eval_records(records.to(dev), opt.world_size).cpu()
-        allc = None
-        if eval_3D.largest_component_enabled(opt):      # every rank joins the second gather, also one that evaluated no sample
-            allc = gather_eval_records(torch.stack(comps).to(dev) if comps else torch.zeros(0, 4, device=dev, dtype=torch.float64),
-                                       opt.world_size).cpu()
-        alli = None
-        if options.icp_settings(opt) is not None:       # likewise: every rank joins
-            alli = gather_eval_records(torch.stack(icps).to(dev) if icps else torch.zeros(0, 15, device=dev, dtype=torch.float64),
-                                       opt.world_size).cpu()
-        alln = None
-        if options.normal_settings(opt) is not None:    # likewise
-            width = 5 if options.icp_settings(opt) is None else 8
-            alln = gather_eval_records(torch.cat(ncs).to(dev) if ncs else torch.zeros(0, width, device=dev, dtype=torch.float64),
-                                       opt.world_size).cpu()
-        allm = None
-        if options.mesh_dist_settings(opt) is not None:     # likewise
-            T = len(opt.eval.f_thresholds)
-            width = 5 + T if options.dual_mesh_reg(opt) is None else 6 + 2 * T
-            allm = gather_eval_records(torch.cat(meshes).to(dev) if meshes else torch.zeros(0, width, device=dev, dtype=torch.float64),
-                                       opt.world_size).cpu()
-        alle = None
-        if options.emd_settings(opt) is not None:       # likewise
-            width = 6 if options.icp_settings(opt) is None else 9
-            alle = gather_eval_records(torch.cat(emds).to(dev) if emds else torch.zeros(0, width, device=dev, dtype=torch.float64),
-                                       opt.world_size).cpu()
-        allv = None
-        if options.iou_settings(opt) is not None:       # likewise
-            width = 10 if options.icp_settings(opt) is None else 17
-            allv = gather_eval_records(torch.cat(ious).to(dev) if ious else torch.zeros(0, width, device=dev, dtype=torch.float64),
-                                       opt.world_size).cpu()
-        alls = None
-        if options.mesh_stats_settings(opt):            # likewise
-            width = 20 if options.dual_mesh_reg(opt) is None else 38
-            alls = gather_eval_records(torch.cat(stats).to(dev) if stats else torch.zeros(0, width, device=dev, dtype=torch.float64),
-                                       opt.world_size).cpu()
-        allsi = None
-        if options.simplify_settings(opt) is not None:  # likewise
-            width = 29 if options.mesh_stats_settings(opt) else 11
-            allsi = gather_eval_records(torch.cat(simps).to(dev) if simps else torch.zeros(0, width, device=dev, dtype=torch.float64),
-                                        opt.world_size).cpu()
-        allt = None
-        if options.texture_texels(opt) is not None and util_vis is not None:      # likewise
-            allt = gather_eval_records(torch.cat(texs).to(dev) if texs else torch.zeros(0, 6, device=dev, dtype=torch.float64),
-                                       opt.world_size).cpu()
-        allmr = None
-        if options.mesh_render(opt) and util_vis is not None:                     # likewise
-            allmr = gather_eval_records(torch.cat(mrs).to(dev) if mrs else torch.zeros(0, 5, device=dev, dtype=torch.float64),
-                                        opt.world_size).cpu()
+        gathered = {}
+        for rep in REPORTS:
+            if rep.enabled(opt):
+                mine = torch.cat(recs[rep.key]) if recs[rep.key] else torch.zeros(0, rep.width(opt), dtype=torch.float64)
+                gathered[rep.key] = gather_eval_records(mine.to(dev), opt.world_size).cpu()
         opt.H, opt.W = opt.image_size
-        if rank == 0 and allmr is not None:
-            _write_mesh_render(opt, allmr)
-        if rank == 0 and allt is not None:
-            _write_texture(opt, allt)
-        if rank == 0 and alls is not None:
-            self._write_mesh_stats(opt, alls)
-        if rank == 0 and allsi is not None:
-            _write_simplify_lines(opt.output_path, allsi)
-        if rank == 0 and allv is not None:
-            self._write_iou(opt, allv)
-        if rank == 0 and alle is not None:
-            self._write_emd(opt, alle)
-        if rank == 0 and allm is not None:
-            self._write_mesh(opt, allm)
-        if rank == 0 and alln is not None:
-            self._write_normals(opt, alln)
-        if rank == 0 and alli is not None:
-            self._write_gathered(opt, alli[:, :10].float(), "_icp")     # the metrics are fp32 values: tallied as the raw records are
-            with open("{}/icp.txt".format(opt.output_path), "w") as f:
-                for r in alli:
-                    f.write("%d %.8f %.8f %.8f %.8f %.8f\n" % (int(r[0]), *(float(x) for x in r[10:15])))
-        if rank == 0 and allc is not None:
-            with open("{}/components.txt".format(opt.output_path), "w") as f:
-                for r in allc:
-                    f.write("{} {} {} {}\n".format(*(int(x) for x in r)))
         if rank == 0:
+            for key, rows in gathered.items():
+                self._write_report(opt, rows, key=key)
+            if "icp" in gathered:                       # the metrics are fp32 values: tallied as the raw records are
+                self._write_gathered(opt, gathered["icp"][:, :REPORT["icp"].layout(opt)[ICP_KEYS[0]]].float(), "_icp")
             self._write_gathered(opt, allr)
             log.loss_eval(opt, loss=None, chamfer=(allr[:, 1].mean(), allr[:, 2].mean()))
         return float((allr[:, 1].mean() + allr[:, 2].mean()) / 2) if allr.shape[0] else float("nan")
+
+    def _category_names(self, opt):
+        return getattr(self.test_data, "label2cat", {i: str(i) for i in range(opt.data.num_classes)})
+
 
     def _write_gathered(self, opt, allr, suffix=""):
         """chamfer{suffix}.txt, cd_cat{suffix}.txt and f_score{suffix}.txt from gathered records [N,10] = (idx, cd_acc, cd_comp, f_score[6],
@@ -769,109 +508,14 @@ class Runner:
             for i, th in enumerate(opt.eval.f_thresholds):
                 f.write("F-score @ %.2f: %.4f\n" % (th * 100, fs[i].item()))
 
-    def _write_normals(self, opt, alln, per_sample=True):
-        """The files of --eval.normals from records [N,5] = (idx, nc_acc, nc_comp, nc, category) in sample order, float64:
-        normal_consistency.txt (`idx nc_acc nc_comp nc` per sample; per_sample=False leaves it to dump_results) and nc_cat.txt, the
-        per-category means in cd_cat.txt's format.  Records [N,8] (with --eval.icp) carry the three values after ICP in columns 5..7,
-        which go to normal_consistency_icp.txt and nc_cat_icp.txt."""
-        C = opt.data.num_classes
-        names = getattr(self.test_data, "label2cat", {i: str(i) for i in range(C)})
-        for suffix, cols in (("", [1, 2, 3]), ("_icp", [5, 6, 7]))[:1 if alln.shape[1] < 8 else 2]:
-            if per_sample:
-                with open("{}/normal_consistency{}.txt".format(opt.output_path, suffix), "w") as f:
-                    for r in alln:
-                        f.write(NC_LINE % (int(r[0]), *(float(r[c]) for c in cols)))
-            with open(os.path.join(opt.output_path, "nc_cat{}.txt".format(suffix)), "w") as f:
-                f.write("NC     Acc    Comp   Count Cat\n")
-                for c in range(C):
-                    sel = alln[alln[:, 4] == c]
-                    n = sel.shape[0] + 0.001
-                    a_, c_ = float(sel[:, cols[0]].sum()) / n, float(sel[:, cols[1]].sum()) / n
-                    f.write("%.4f %.4f %.4f %5d %s\n" % ((a_ + c_) / 2, a_, c_, n, names[c]))
+    def _write_report(self, opt, rows, per_sample=True, key=None):
+        """The files of one report from its records in sample order (eval_reports.Report.write)."""
+        REPORT[key].write(opt, rows, Runner._category_names(self, opt), per_sample)
 
-    def _write_mesh(self, opt, allm, per_sample=True):
-        """The files of --eval.mesh_dist from _mesh_records' rows in sample order, float64: completeness_mesh.txt (`idx cd_comp
-        cd_comp_mesh` per sample; per_sample=False leaves it to dump_results), cd_cat_mesh.txt (cd_cat.txt's format with Comp replaced by
-        the mesh value) and f_score_mesh.txt (f_score.txt's format: precision from the samples, recall from the mesh).  Rows that carry
-        the dual-contouring mesh's columns also give completeness_mesh_dual.txt, cd_cat_mesh_dual.txt and f_score_mesh_dual.txt."""
-        C, T = opt.data.num_classes, len(opt.eval.f_thresholds)
-        names = getattr(self.test_data, "label2cat", {i: str(i) for i in range(C)})
-        for suffix, comp, fs0 in (("", 3, 4), ("_dual", 5 + T, 6 + T))[:1 if allm.shape[1] < 6 + 2 * T else 2]:
-            if per_sample:
-                with open("{}/completeness_mesh{}.txt".format(opt.output_path, suffix), "w") as f:
-                    for r in allm:
-                        f.write(MESH_LINE % (int(r[0]), float(r[2]), float(r[comp])))
-            with open(os.path.join(opt.output_path, "cd_cat_mesh{}.txt".format(suffix)), "w") as f:
-                f.write("CD     Acc    Comp   Count Cat\n")
-                for c in range(C):
-                    sel = allm[allm[:, 4 + T] == c]
-                    n = sel.shape[0] + 0.001
-                    a_, c_ = float(sel[:, 1].sum()) / n, float(sel[:, comp].sum()) / n
-                    f.write("%.4f %.4f %.4f %5d %s\n" % ((a_ + c_) / 2, a_, c_, n, names[c]))
-            fs = allm[:, fs0:fs0 + T].mean(dim=0) if allm.shape[0] else torch.zeros(T, dtype=torch.float64)
-            with open(os.path.join(opt.output_path, "f_score_mesh{}.txt".format(suffix)), "w") as f:
-                for i, th in enumerate(opt.eval.f_thresholds):
-                    f.write("F-score @ %.2f: %.4f\n" % (th * 100, fs[i].item()))
-
-    def _write_emd(self, opt, alle, per_sample=True):
-        """The files of --eval.emd from _emd_records' rows in sample order, float64: emd.txt (`idx n emd rounds converged` per sample;
-        per_sample=False leaves it to dump_results) and emd_cat.txt, the per-category mean in cd_cat.txt's format with the one column.
-        Rows [N,9] (with --eval.icp) carry the values of the ICP-aligned prediction in columns 6..8, which go to emd_icp.txt and
-        emd_cat_icp.txt."""
-        C = opt.data.num_classes
-        names = getattr(self.test_data, "label2cat", {i: str(i) for i in range(C)})
-        for suffix, cols in (("", [2, 3, 4]), ("_icp", [6, 7, 8]))[:1 if alle.shape[1] < 9 else 2]:
-            if per_sample:
-                with open("{}/emd{}.txt".format(opt.output_path, suffix), "w") as f:
-                    for r in alle:
-                        f.write(EMD_LINE % (int(r[0]), int(r[1]), float(r[cols[0]]), int(r[cols[1]]), int(r[cols[2]])))
-            with open(os.path.join(opt.output_path, "emd_cat{}.txt".format(suffix)), "w") as f:
-                f.write("EMD    Count Cat\n")
-                for c in range(C):
-                    sel = alle[alle[:, 5] == c]
-                    n = sel.shape[0] + 0.001
-                    f.write("%.4f %5d %s\n" % (float(sel[:, cols[0]].sum()) / n, n, names[c]))
-
-    def _write_iou(self, opt, allv, per_sample=True):
-        """The files of --eval.iou from _iou_records' rows in sample order, float64: iou.txt (`idx res iou inter union vox_pred vox_gt
-        shell_pred shell_gt` per sample; per_sample=False leaves it to dump_results) and iou_cat.txt, the per-category mean in
-        cd_cat.txt's format with the one column.  Rows [N,17] (with --eval.icp) carry the values of the ICP-aligned prediction in
-        columns 10..16, which go to iou_icp.txt and iou_cat_icp.txt."""
-        C = opt.data.num_classes
-        names = getattr(self.test_data, "label2cat", {i: str(i) for i in range(C)})
-        for suffix, cols in IOU_COLS[:1 if allv.shape[1] < 17 else 2]:
-            if per_sample:
-                with open("{}/iou{}.txt".format(opt.output_path, suffix), "w") as f:
-                    for r in allv:
-                        f.write(iou_line(r, cols))
-            with open(os.path.join(opt.output_path, "iou_cat{}.txt".format(suffix)), "w") as f:
-                f.write("IoU    Count Cat\n")
-                for c in range(C):
-                    sel = allv[allv[:, 9] == c]
-                    n = sel.shape[0] + 0.001
-                    f.write("%.4f %5d %s\n" % (float(sel[:, cols[0]].sum()) / n, n, names[c]))
-
-    def _write_mesh_stats(self, opt, alls, per_sample=True):
-        """The files of --eval.mesh_stats from _mesh_stats_rows' rows in sample order, float64: mesh_stats.txt (MESH_STATS_LINE per sample;
-        per_sample=False leaves it to dump_results) and mesh_stats_cat.txt, per category in cd_cat.txt's style: the share of samples whose
-        mesh is watertight and manifold, the mean number of components, and the mean genus over the samples whose genus is >= 0 (0 when
-        there is none).  Rows [N,38] (with --eval.dual_mesh) carry the dual-contouring mesh in columns 20..37, which go to
-        mesh_stats_dual.txt and mesh_stats_cat_dual.txt."""
-        C = opt.data.num_classes
-        names = getattr(self.test_data, "label2cat", {i: str(i) for i in range(C)})
-        if per_sample:
-            _write_mesh_stats_lines(opt.output_path, alls)
-        for suffix, first in MESH_STATS_COLS[:1 if alls.shape[1] < 38 else 2]:
-            comps, genus, water, manifold = (first + MESH_STATS_KEYS.index(k) for k in ("components", "genus", "watertight", "manifold"))
-            with open(os.path.join(opt.output_path, "mesh_stats_cat{}.txt".format(suffix)), "w") as f:
-                f.write("Closed Comps   Genus  Count Cat\n")
-                for c in range(C):
-                    sel = alls[alls[:, 19] == c]
-                    n = sel.shape[0] + 0.001
-                    closed = float(((sel[:, water] != 0) & (sel[:, manifold] != 0)).sum()) / n
-                    g = sel[sel[:, genus] >= 0][:, genus]
-                    f.write("%.4f %.4f %.4f %5d %s\n" % (closed, float(sel[:, comps].sum()) / n, float(g.sum()) / (g.shape[0] + 0.001), n,
-                                                         names[c]))
+    _write_normals = functools.partialmethod(_write_report, key="normals")
+    _write_mesh = functools.partialmethod(_write_report, key="mesh_dist")
+    _write_iou = functools.partialmethod(_write_report, key="iou")
+    _write_mesh_stats = functools.partialmethod(_write_report, key="mesh_stats")
 
     def evaluate_batch(self, opt, var, ep=None, it=None, single_gpu=False, visualize=False):
         var = util.move_to_device(var, opt.device)
@@ -1129,55 +773,18 @@ class Runner:
 
     @torch.no_grad()
     def dump_results(self, opt, var, ep, write_new=False, train=False):
+        """The per-sample files of a batch (dump_visuals) and, outside training, its lines of chamfer.txt and of the per-sample files of
+        every report of eval_reports.REPORTS that the batch carries."""
         self.dump_visuals(opt, var, ep, train=train)
         if not train:
-            with open("{}/chamfer.txt".format(opt.output_path), "w" if write_new else "a") as f:
+            mode = "w" if write_new else "a"
+            with open("{}/chamfer.txt".format(opt.output_path), mode) as f:
                 for i, acc, comp in zip(var.idx, var.cd_acc, var.cd_comp):
                     f.write("{} {:.8f} {:.8f}\n".format(i, acc, comp))
-            if "component_stats" in var:                # --hip.largest_component: idx n_components inside_voxels kept_voxels
-                with open("{}/components.txt".format(opt.output_path), "w" if write_new else "a") as f:
-                    for row in zip(var.idx.tolist(), *(c.tolist() for c in _component_counts(var))):
-                        f.write("{} {} {} {}\n".format(*row))
-            # --eval.texture: idx faces atlas rows err_mean err_max (--eval.mesh_render alone bakes var.texture too and writes no texture.txt)
-            if "texture" in var and options.texture_texels(opt) is not None:
-                _write_texture(opt, _texture_records(var), "w" if write_new else "a")
-            if "mesh_render" in var:                    # --eval.mesh_render: idx faces pixels iou_input iou_volume
-                _write_mesh_render(opt, _mesh_render_records(var), "w" if write_new else "a")
-            if "icp" in var:                            # --eval.icp: chamfer.txt's line of the aligned metrics; idx s angle_deg |t| objective first, last
-                with open("{}/chamfer_icp.txt".format(opt.output_path), "w" if write_new else "a") as f:
-                    for i, acc, comp in zip(var.idx, var.cd_acc_icp, var.cd_comp_icp):
-                        f.write("{} {:.8f} {:.8f}\n".format(i, acc, comp))
-                with open("{}/icp.txt".format(opt.output_path), "w" if write_new else "a") as f:
-                    for i, row in zip(var.idx.tolist(), eval_3D.icp_summary(var).tolist()):
-                        f.write("%d %.8f %.8f %.8f %.8f %.8f\n" % (i, *row))
-            if "cd_comp_mesh" in var:                   # --eval.mesh_dist: idx cd_comp cd_comp_mesh (and the same for the dual mesh)
-                rec, T = _mesh_records(var), len(opt.eval.f_thresholds)
-                for suffix, comp in (("", 3), ("_dual", 5 + T))[:1 if rec.shape[1] < 6 + 2 * T else 2]:
-                    with open("{}/completeness_mesh{}.txt".format(opt.output_path, suffix), "w" if write_new else "a") as f:
-                        for r in rec:
-                            f.write(MESH_LINE % (int(r[0]), float(r[2]), float(r[comp])))
-            if "nc" in var:                             # --eval.normals: idx nc_acc nc_comp nc (and the same after ICP)
-                rec = _normal_records(var)
-                for suffix, cols in (("", [1, 2, 3]), ("_icp", [5, 6, 7]))[:1 if rec.shape[1] < 8 else 2]:
-                    with open("{}/normal_consistency{}.txt".format(opt.output_path, suffix), "w" if write_new else "a") as f:
-                        for r in rec:
-                            f.write(NC_LINE % (int(r[0]), *(float(r[c]) for c in cols)))
-            if "iou" in var:                            # --eval.iou: idx res iou inter union and the voxel counts (and the same after ICP)
-                rec = _iou_records(var)
-                for suffix, cols in IOU_COLS[:1 if rec.shape[1] < 17 else 2]:
-                    with open("{}/iou{}.txt".format(opt.output_path, suffix), "w" if write_new else "a") as f:
-                        for r in rec:
-                            f.write(iou_line(r, cols))
-            if "mesh_stats" in var:                     # --eval.mesh_stats: MESH_STATS_LINE (and the same for the dual mesh)
-                _write_mesh_stats_lines(opt.output_path, _mesh_stats_rows(var), "w" if write_new else "a")
-            if "mesh_simplified" in var:                # --eval.simplify: SIMPLIFY_LINE (and MESH_STATS_LINE of the simplified mesh)
-                _write_simplify_lines(opt.output_path, _simplify_records(var), "w" if write_new else "a")
-            if "emd" in var:                            # --eval.emd: idx n emd rounds converged (and the same after ICP)
-                rec = _emd_records(var)
-                for suffix, cols in (("", [2, 3, 4]), ("_icp", [6, 7, 8]))[:1 if rec.shape[1] < 9 else 2]:
-                    with open("{}/emd{}.txt".format(opt.output_path, suffix), "w" if write_new else "a") as f:
-                        for r in rec:
-                            f.write(EMD_LINE % (int(r[0]), int(r[1]), float(r[cols[0]]), int(r[cols[1]]), int(r[cols[2]])))
+            for rep in REPORTS:
+                if rep.present(var, opt):
+                    rep.write_lines(opt.output_path, rep.records(var), mode, opt)
+
 
     def save_checkpoint(self, opt, ep=0, it=0, best_val=np.inf, latest=False, best=False):
         assert _rank0(opt)

@@ -833,20 +833,16 @@ def meshes_simplified(opt, var):
     return var.mesh_simplified_world
 
 
-def icp_summary(var):
-    """[B,5] float64 on the host, a row of icp.txt per sample: s, the rotation angle in degrees, |t|, the first and the last objective."""
-    T, s, obj = (var.icp[k].detach().cpu().double() for k in ("transform", "s", "objective"))
-    cos = ((T[:, 0, 0] + T[:, 1, 1] + T[:, 2, 2]) / s - 1) / 2
-    angle = torch.rad2deg(torch.acos(cos.clamp(-1, 1)))
-    return torch.stack([s, angle, T[:, :3, 3].norm(dim=1), obj[:, 0], obj[:, -1]], dim=1)
-
-
 _FLIP_PRED = [[1, 0, 0], [0, -1, 0], [0, 0, -1]]
 _FLIP_GT = [[-1, 0, 0], [0, 1, 0], [0, 0, 1]]
 
 
 @torch.no_grad()
 def eval_metrics(opt, var, sdf_network, vis_only=False):
+    # every optional metric's setting, read once: None (or False) while its switch is off, else the arguments of its function
+    icp, normals_k, emd, iou = (f(opt) for f in (options.icp_settings, options.normal_settings, options.emd_settings, options.iou_settings))
+    mesh_dist = None if vis_only else options.mesh_dist_settings(opt)
+    want_stats, simplify = options.mesh_stats_settings(opt), options.simplify_settings(opt)
     points_3D = get_dense_3D_grid(opt, var)
     B = points_3D.shape[0]
     level_vox = compute_level_grid(opt, sdf_network, var.proj_latent_sdf, points_3D)
@@ -878,14 +874,13 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
         fg = torch.tensor(_FLIP_GT).float().to(dev).unsqueeze(0).expand(B, 3, 3)
         var.dpc_pred = rot(fp, var.dpc_pred)
         var.dpc.points = rot(fg, var.dpc.points)
-    mesh_dist = None if vis_only else options.mesh_dist_settings(opt)
     frame = normalize_pc_params(var.dpc_pred) if mesh_dist is not None else None      # the samples' centre and scale (mesh_metrics)
     var.dpc_pred = normalize_pc(var.dpc_pred)
     var.dpc.points = normalize_pc(var.dpc.points)
     if vis_only:
-        if options.mesh_stats_settings(opt):    # vis_{ep}/mesh_stats.txt of --hip.train_vis
+        if want_stats:                          # vis_{ep}/mesh_stats.txt of --hip.train_vis
             mesh_stats(opt, var, sdf_network)
-        if options.simplify_settings(opt) is not None:      # vis_{ep}/{idx}_mesh_simplified.ply
+        if simplify is not None:                # vis_{ep}/{idx}_mesh_simplified.ply
             meshes_simplified(opt, var)
         return
     dist_acc, dist_comp, idx1, idx2 = chamfer_distance(opt, X1=var.dpc_pred, X2=var.dpc.points)
@@ -893,24 +888,20 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     assert dist_acc.shape[1] == opt.eval.num_points
     var.cd_acc = dist_acc.mean(dim=1)
     var.cd_comp = dist_comp.mean(dim=1)
-    icp = options.icp_settings(opt)
     aligned = None
     if icp is not None:                     # beside the raw metrics, never in their place
         aligned = icp_metrics(opt, var, *icp)
-    normals_k = options.normal_settings(opt)
     if normals_k is not None:               # likewise
         normal_metrics(opt, var, sdf_network, points_object, idx1, idx2, normals_k, icp=aligned)
     if mesh_dist is not None:               # likewise
         var.dist_acc, var.dist_comp = dist_acc, dist_comp
         mesh_metrics(opt, var, sdf_network, frame)
-    emd = options.emd_settings(opt)
     if emd is not None:                     # likewise
         emd_metrics(opt, var, *emd, icp=aligned)
-    iou = options.iou_settings(opt)
     if iou is not None:                     # likewise
         iou_metrics(opt, var, *iou, icp=aligned)
-    if options.mesh_stats_settings(opt):    # likewise
+    if want_stats:                          # likewise
         mesh_stats(opt, var, sdf_network)
-    if options.simplify_settings(opt) is not None:          # likewise
+    if simplify is not None:                # likewise
         meshes_simplified(opt, var)
     return dist_acc.mean(), dist_comp.mean()

@@ -86,149 +86,121 @@ def hip(opt, key):
     return opt.get("hip", {}).get(key, default)
 
 
+# The `eval.*` settings of the optional evaluation outputs, one row each: (key, default, kind, what it sets[, flag]).  kind is bool, (lo, hi)
+# with integer bounds for an integer in lo..hi, or (lo, hi) with float bounds for a real number in (lo, hi].  flag "absent": None (the key
+# missing) is a value too and means off; flag "str": a string that float() reads counts as that number (`--eval.emd_eps=1e-4` arrives as
+# the string "1e-4" -- YAML 1.1 reads a float only with a dot, "1.0e-4").  These are evaluation settings beside eval.vox_res, not hip.*
+# switches; an absent key means its default, so a reference YAML loads unchanged.  eval_setting() is the one place a value is checked: a
+# bad value is a ValueError whether or not the switch it belongs to is on, and process_options asks for every row.  The functions below
+# it answer what each output needs: None (or False) while its switch is off, else the arguments of its metric function.
+Setting = collections.namedtuple("Setting", ["key", "default", "kind", "text", "flag"], defaults=("",))
+EVAL_TABLE = tuple(Setting(*row) for row in (
+    ("texture", False, bool, "textured OBJ dump: {idx}_mesh_tex.obj / .mtl / .png and texture.txt (eval_3D.mesh_texture)"),
+    ("texture_texels", 8, (4, 32), "... the side in texels of the square atlas cell that two faces share (include/shapeclipper_hip.h)"),
+    ("mesh_render", False, bool, "pictures of the textured mesh and their mask IoU, mesh_render.txt; bakes the texture when eval.texture is off"),
+    ("dual_mesh", False, bool, "dual-contouring dump {idx}_mesh_dual.ply (read by its truth value)"),
+    ("dual_reg", 0.05, (0.0, 1.0), "... the weight that holds a cell's vertex near the mean of its crossings (ops.dual_contour_mesh)"),
+    ("icp", False, bool, "ICP-aligned metrics beside the raw ones (ops.icp_align)"),
+    ("icp_iters", 30, (1, 100), "... iterations"),
+    ("icp_scale", True, bool, "... fit a similarity; false: a rigid motion"),
+    ("normals", False, bool, "normal consistency (eval_3D.normal_metrics)"),
+    ("normals_k", 16, (3, 32), "... the neighbour count of ops.point_normals for the ground truth's PCA normals"),
+    ("mesh_dist", False, bool, "completeness from every ground-truth point to the predicted MESH (ops.point_mesh_distance)"),
+    ("emd", False, bool, "Earth Mover's Distance (eval_3D.emd_metrics)"),
+    ("emd_points", 1024, (2, 2048), "... points matched, the sizes ops.emd_match takes; 1024 is the Pix3D benchmark's count"),
+    ("emd_eps", 1e-4, (0.0, 0.25), "... the last epsilon of the auction, which starts at 0.25", "str"),
+    ("iou", False, bool, "volumetric IoU (eval_3D.iou_metrics)"),
+    ("iou_res", 32, (8, 64), "... voxels per side, the grids ops.voxel_solid takes; 32 is Pix3D's resolution"),
+    ("iou_close", 1, (0, 2), "... dilations that close the voxel shell before it is filled"),
+    ("mesh_stats", False, bool, "watertightness, manifoldness, orientation, components, genus, area and volume of the written meshes (ops.mesh_topology)"),
+    ("simplify", None, (2, 16), "decimated mesh {idx}_mesh_simplified.ply: the side of a cluster cell in grid pitches (ops.mesh_cluster_simplify)",
+     "absent"),
+    ("simplify_reg", 0.05, (0.0, 1.0), "... the pull of a cluster's vertex towards the mean of its vertices", "str"),
+))
+EVAL = {row.key: row for row in EVAL_TABLE}
+
+
+def eval_setting(opt, key):
+    """opt.eval[key] checked against its row of EVAL_TABLE, the row's default where the option tree has no such key."""
+    row = EVAL[key]
+    v = (opt.get("eval", None) or {}).get(key, row.default)
+    if row.kind is bool:
+        if not isinstance(v, bool):
+            raise ValueError("eval.%s must be a bool, got %r" % (key, v))
+        return v
+    if v is None and row.flag == "absent":
+        return None
+    lo, hi = row.kind
+    if isinstance(lo, int):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError("eval.%s must be an integer in %d..%d, got %r" % (key, lo, hi, v))
+        return v
+    if row.flag == "str" and isinstance(v, str):
+        try:
+            v = float(v)
+        except ValueError:
+            pass
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo < v <= hi:
+        raise ValueError("eval.%s must be a float in (%g, %g], got %r" % (key, lo, hi, v))
+    return float(v)
+
+
 def dual_mesh_reg(opt):
-    """The evaluation's dual-contouring dump: None unless `--eval.dual_mesh` is set (absent means off), else `--eval.dual_reg` (default
-    0.05), the weight that holds a cell's vertex near the mean of its crossings (ops.dual_contour_mesh).  An evaluation setting beside
-    eval.vox_res, not a hip.* switch.  A dual_reg that is not a real number in (0, 1] is a ValueError, whether or not the dump is on."""
-    ev = opt.get("eval", None) or {}
-    reg = ev.get("dual_reg", 0.05)
-    if isinstance(reg, bool) or not isinstance(reg, (int, float)) or not 0.0 < reg <= 1.0:
-        raise ValueError("eval.dual_reg must be a float in (0, 1], got %r" % (reg,))
-    return float(reg) if ev.get("dual_mesh", False) else None
+    """None unless `--eval.dual_mesh` is set, else eval.dual_reg."""
+    reg = eval_setting(opt, "dual_reg")
+    return reg if (opt.get("eval", None) or {}).get("dual_mesh", False) else None
 
 
 def texture_texels(opt, always=False):
-    """The evaluation's textured OBJ dump: None unless `--eval.texture` is set (absent means off), else `--eval.texture_texels` (default
-    8, an integer in 4..32), the side T in texels of the square atlas cell that two faces share (eval_3D.mesh_texture;
-    include/shapeclipper_hip.h states the layout).  Evaluation settings beside eval.vox_res, not hip.* switches.  A bad value is a
-    ValueError, whether or not the switch is on.  always=True returns T whatever the switch says (a direct call of mesh_texture)."""
-    ev = opt.get("eval", None) or {}
-    on, texels = ev.get("texture", False), ev.get("texture_texels", 8)
-    if not isinstance(on, bool):
-        raise ValueError("eval.texture must be a bool, got %r" % (on,))
-    if isinstance(texels, bool) or not isinstance(texels, int) or not 4 <= texels <= 32:
-        raise ValueError("eval.texture_texels must be an integer in 4..32, got %r" % (texels,))
+    """None unless `--eval.texture` is set, else eval.texture_texels; always=True returns it whatever the switch says (a direct call of
+    eval_3D.mesh_texture)."""
+    on, texels = eval_setting(opt, "texture"), eval_setting(opt, "texture_texels")
     return texels if on or always else None
 
 
 def mesh_render(opt):
-    """The evaluation's picture of the textured mesh and its mask IoU (eval_3D.mesh_render, mesh_render.txt): `--eval.mesh_render`, absent
-    means off.  An evaluation setting beside eval.texture, not a hip.* switch; it bakes the texture (eval.texture_texels) when
-    `--eval.texture` has not.  A value that is not a bool is a ValueError, whether or not the switch is on."""
-    on = (opt.get("eval", None) or {}).get("mesh_render", False)
-    if not isinstance(on, bool):
-        raise ValueError("eval.mesh_render must be a bool, got %r" % (on,))
-    return on
+    """`--eval.mesh_render`, a bool."""
+    return eval_setting(opt, "mesh_render")
 
 
 def icp_settings(opt):
-    """The evaluation's ICP-aligned metrics: None unless `--eval.icp` is set (absent means off), else (iters, scale) from
-    `--eval.icp_iters` (default 30, an integer in 1..100) and `--eval.icp_scale` (default true: fit a similarity; false: a rigid motion),
-    the arguments of ops.icp_align.  Evaluation settings beside eval.vox_res, not hip.* switches.  A bad value is a ValueError, whether
-    or not the switch is on."""
-    ev = opt.get("eval", None) or {}
-    on, iters, scale = ev.get("icp", False), ev.get("icp_iters", 30), ev.get("icp_scale", True)
-    if not isinstance(on, bool):
-        raise ValueError("eval.icp must be a bool, got %r" % (on,))
-    if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= 100:
-        raise ValueError("eval.icp_iters must be an integer in 1..100, got %r" % (iters,))
-    if not isinstance(scale, bool):
-        raise ValueError("eval.icp_scale must be a bool, got %r" % (scale,))
+    """None unless `--eval.icp` is set, else (iters, scale), the arguments of ops.icp_align."""
+    on, iters, scale = (eval_setting(opt, k) for k in ("icp", "icp_iters", "icp_scale"))
     return (iters, scale) if on else None
 
 
 def normal_settings(opt):
-    """The evaluation's normal consistency: None unless `--eval.normals` is set (absent means off), else `--eval.normals_k` (default 16,
-    an integer in 3..32), the neighbour count of ops.point_normals for the ground truth's PCA normals.  Evaluation settings beside
-    eval.vox_res, not hip.* switches.  A bad value is a ValueError, whether or not the switch is on."""
-    ev = opt.get("eval", None) or {}
-    on, k = ev.get("normals", False), ev.get("normals_k", 16)
-    if not isinstance(on, bool):
-        raise ValueError("eval.normals must be a bool, got %r" % (on,))
-    if isinstance(k, bool) or not isinstance(k, int) or not 3 <= k <= 32:
-        raise ValueError("eval.normals_k must be an integer in 3..32, got %r" % (k,))
+    """None unless `--eval.normals` is set, else eval.normals_k."""
+    on, k = eval_setting(opt, "normals"), eval_setting(opt, "normals_k")
     return k if on else None
 
 
 def mesh_dist_settings(opt):
-    """The evaluation's mesh-based completeness: None unless `--eval.mesh_dist` is set (absent means off), else True -- the distance
-    from every ground-truth point to the predicted MESH (eval_3D.mesh_metrics, ops.point_mesh_distance) beside the sample-based
-    metrics.  An evaluation setting beside eval.vox_res, not a hip.* switch.  A value that is not a bool is a ValueError, whether or
-    not the switch is on."""
-    ev = opt.get("eval", None) or {}
-    on = ev.get("mesh_dist", False)
-    if not isinstance(on, bool):
-        raise ValueError("eval.mesh_dist must be a bool, got %r" % (on,))
-    return True if on else None
+    """None unless `--eval.mesh_dist` is set, else True."""
+    return True if eval_setting(opt, "mesh_dist") else None
 
 
 def emd_settings(opt):
-    """The evaluation's Earth Mover's Distance: None unless `--eval.emd` is set (absent means off), else (points, eps) from
-    `--eval.emd_points` (default 1024, the count of the Pix3D benchmark; an integer in 2..2048, the sizes ops.emd_match takes) and
-    `--eval.emd_eps` (default 1e-4, a float in (0, 0.25]: the last epsilon of the auction, which starts at 0.25), the arguments of
-    eval_3D.emd_metrics.  Evaluation settings beside eval.vox_res, not hip.* switches.  A bad value is a ValueError, whether or not the
-    switch is on.  (`--eval.emd_eps=1e-4` arrives as the string "1e-4" -- YAML 1.1 reads a float only with a dot, "1.0e-4" -- so a
-    string that float() reads is taken as that number.)"""
-    ev = opt.get("eval", None) or {}
-    on, points, eps = ev.get("emd", False), ev.get("emd_points", 1024), ev.get("emd_eps", 1e-4)
-    if isinstance(eps, str):
-        try:
-            eps = float(eps)
-        except ValueError:
-            pass
-    if not isinstance(on, bool):
-        raise ValueError("eval.emd must be a bool, got %r" % (on,))
-    if isinstance(points, bool) or not isinstance(points, int) or not 2 <= points <= 2048:
-        raise ValueError("eval.emd_points must be an integer in 2..2048, got %r" % (points,))
-    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 < eps <= 0.25:
-        raise ValueError("eval.emd_eps must be a float in (0, 0.25], got %r" % (eps,))
-    return (points, float(eps)) if on else None
+    """None unless `--eval.emd` is set, else (points, eps), the arguments of eval_3D.emd_metrics."""
+    on, points, eps = (eval_setting(opt, k) for k in ("emd", "emd_points", "emd_eps"))
+    return (points, eps) if on else None
 
 
 def iou_settings(opt):
-    """The evaluation's volumetric IoU: None unless `--eval.iou` is set (absent means off), else (res, close) from `--eval.iou_res`
-    (default 32, Pix3D's resolution; an integer in 8..64, the grids ops.voxel_solid takes) and `--eval.iou_close` (default 1, an
-    integer in 0..2: the dilations that close the voxel shell before it is filled), the arguments of eval_3D.iou_metrics.  Evaluation
-    settings beside eval.vox_res, not hip.* switches.  A bad value is a ValueError, whether or not the switch is on."""
-    ev = opt.get("eval", None) or {}
-    on, res, close = ev.get("iou", False), ev.get("iou_res", 32), ev.get("iou_close", 1)
-    if not isinstance(on, bool):
-        raise ValueError("eval.iou must be a bool, got %r" % (on,))
-    if isinstance(res, bool) or not isinstance(res, int) or not 8 <= res <= 64:
-        raise ValueError("eval.iou_res must be an integer in 8..64, got %r" % (res,))
-    if isinstance(close, bool) or not isinstance(close, int) or not 0 <= close <= 2:
-        raise ValueError("eval.iou_close must be an integer in 0..2, got %r" % (close,))
+    """None unless `--eval.iou` is set, else (res, close), the arguments of eval_3D.iou_metrics."""
+    on, res, close = (eval_setting(opt, k) for k in ("iou", "iou_res", "iou_close"))
     return (res, close) if on else None
 
 
 def mesh_stats_settings(opt):
-    """The evaluation's mesh statistics: True when `--eval.mesh_stats` is set (absent means off) -- eval_3D.mesh_stats then reports
-    watertightness, manifoldness, orientation, components, genus, area and volume of the meshes that are written (ops.mesh_topology).
-    An evaluation setting beside eval.vox_res, not a hip.* switch.  A value that is not a bool is a ValueError."""
-    on = (opt.get("eval", None) or {}).get("mesh_stats", False)
-    if not isinstance(on, bool):
-        raise ValueError("eval.mesh_stats must be a bool, got %r" % (on,))
-    return on
+    """`--eval.mesh_stats`, a bool."""
+    return eval_setting(opt, "mesh_stats")
 
 
 def simplify_settings(opt):
-    """The evaluation's decimated mesh: None unless `--eval.simplify=k` is given (absent means off), else (k, reg): k, an integer in
-    2..16, is the side of a cluster cell in grid pitches and reg, `--eval.simplify_reg` (default 0.05, a float in (0, 1]), the pull of a
-    cluster's vertex towards the mean of its vertices -- the arguments of eval_3D.meshes_simplified (ops.mesh_cluster_simplify).
-    Evaluation settings beside eval.vox_res, not hip.* switches.  A bool or any other bad value is a ValueError, whether or not the
-    switch is on.  (A string that float() reads is taken as that number, as for eval.emd_eps.)"""
-    ev = opt.get("eval", None) or {}
-    k, reg = ev.get("simplify", None), ev.get("simplify_reg", 0.05)
-    if isinstance(reg, str):
-        try:
-            reg = float(reg)
-        except ValueError:
-            pass
-    if k is not None and (isinstance(k, bool) or not isinstance(k, int) or not 2 <= k <= 16):
-        raise ValueError("eval.simplify must be an integer in 2..16, got %r" % (k,))
-    if isinstance(reg, bool) or not isinstance(reg, (int, float)) or not 0.0 < reg <= 1.0:
-        raise ValueError("eval.simplify_reg must be a float in (0, 1], got %r" % (reg,))
-    return None if k is None else (k, float(reg))
+    """None unless `--eval.simplify=k` is given, else (k, reg), the arguments of eval_3D.meshes_simplified."""
+    k, reg = eval_setting(opt, "simplify"), eval_setting(opt, "simplify_reg")
+    return None if k is None else (k, reg)
 
 
 def parse_arguments(args):
@@ -320,16 +292,9 @@ def process_options(opt):
             (lo, hi), v = row.kind, hip(opt, row.key)
             if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
                 raise ValueError("hip.%s must be an integer in %d..%d, got %r" % (row.key, lo, hi, v))
-    dual_mesh_reg(opt)
-    texture_texels(opt)
-    mesh_render(opt)
-    icp_settings(opt)
-    normal_settings(opt)
-    mesh_dist_settings(opt)
-    emd_settings(opt)
-    iou_settings(opt)
-    mesh_stats_settings(opt)
-    simplify_settings(opt)
+    for check in (dual_mesh_reg, texture_texels, mesh_render, icp_settings, normal_settings, mesh_dist_settings, emd_settings, iou_settings,
+                  mesh_stats_settings, simplify_settings):      # every eval.* value is checked here, whether or not its switch is on
+        check(opt)
     torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
     for row in HIP_TABLE:
         if row.drives is not None:
