@@ -1,0 +1,138 @@
+"""B triangle meshes packed one after the other: the form every mesh op of `ops` produces or consumes, and the checks of its two spellings.
+
+PackedMesh(verts [V,3] fp32, faces [F,3] int32, v_count [B], f_count [B]): image b's mesh is verts[vs:ve], faces[fs:fe] with the running
+sums of the two counts, and faces holds vertex numbers LOCAL to its image.  The producers (ops.isosurface_mesh, ops.dual_contour_mesh,
+ops.mesh_cluster_simplify) return the counts as int64 on the host; verts and faces live on the device.  The counts spelling
+(`*mesh`) goes into ops.mesh_topology, ops.mesh_cluster_simplify and ops.point_mesh_distance -- check_packed; the starts spelling
+(`*mesh.starts()`) into ops.texture_queries and ops.mesh_raster -- check_starts.  Pure torch: nothing here needs the library or a device."""
+import collections
+
+import torch
+
+
+def _host_counts(v_count, f_count):
+    """[2, B] int64 on the host; free for host counts, the form the meshers return, else the one read of the two counts."""
+    return torch.stack([v_count.long(), f_count.long()]).cpu()
+
+
+def _offsets(counts_host):
+    offsets = torch.zeros(2, counts_host.shape[1] + 1, dtype=torch.int64)
+    offsets[:, 1:] = counts_host.cumsum(1)
+    return offsets
+
+
+class PackedMesh(collections.namedtuple("PackedMesh", "verts faces v_count f_count")):
+    """The packed meshes of B images (see the module); a plain 4-tuple to every caller that unpacks it or passes `*mesh`."""
+    __slots__ = ()
+
+    @classmethod
+    def empty(cls, B, device):
+        """B images without a vertex or a face."""
+        return cls(torch.zeros(0, 3, device=device), torch.zeros(0, 3, dtype=torch.int32, device=device),
+                   torch.zeros(B, dtype=torch.int64), torch.zeros(B, dtype=torch.int64))
+
+    def offsets(self):
+        """[2, B + 1] int64 on the host: the exclusive running sums of v_count (row 0) and f_count (row 1), the totals last."""
+        return _offsets(_host_counts(self.v_count, self.f_count))
+
+    def starts(self):
+        """(v_start, f_start, f_count) as lists of B Python ints: what ops.texture_queries and ops.mesh_raster take."""
+        v_off, f_off = self.offsets().tolist()
+        return v_off[:-1], f_off[:-1], [e - s for s, e in zip(f_off, f_off[1:])]
+
+    def split(self, verts=None):
+        """Per image (verts[vs:ve], faces[fs:fe]); `verts` may be any other per-vertex tensor of V rows (positions in another frame,
+        normals, colours)."""
+        verts = self.verts if verts is None else verts
+        v_off, f_off = self.offsets().tolist()
+        return [(verts[v_off[b]:v_off[b + 1]], self.faces[f_off[b]:f_off[b + 1]]) for b in range(len(v_off) - 1)]
+
+    def padded_rows(self, multiple=1):
+        """(P, rows): the row gather of a padded one-launch layout with P = multiple * ceil(max V_b / multiple) rows per image.  rows
+        [B, P] int64 on verts' device holds image b's vertex rows, then its first vertex repeated (an image without a vertex repeats row
+        min(its start, V - 1), which the caller drops).  (0, None) when no image has a vertex."""
+        dev = self.verts.device
+        P = multiple * ((max(self.v_count.tolist(), default=0) + multiple - 1) // multiple)
+        if P == 0:
+            return 0, None
+        start = torch.tensor(self.starts()[0], device=dev).clamp_max(self.verts.shape[0] - 1)
+        j = torch.arange(P, device=dev)
+        return P, torch.where(j[None] < self.v_count.to(dev)[:, None], start[:, None] + j[None], start[:, None])
+
+
+def device_tensor(who, name, t, dtypes, dev=None):
+    """t, contiguous, if it is a device tensor of one of `dtypes` (on `dev`, when given); ValueError otherwise."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError("shapeclipper_amd: %s: %s must be a device tensor (no CPU fallback)" % (who, name))
+    if t.dtype not in dtypes:
+        raise ValueError("shapeclipper_amd: %s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype))
+    if dev is not None and t.device != dev:
+        raise ValueError("shapeclipper_amd: %s: %s is on %s, expected %s" % (who, name, t.device, dev))
+    return t.contiguous()
+
+
+def check_counts(who, v_count, f_count, V, F):
+    """The counts of a packed mesh of V vertices and F faces -> (counts [2, B], offsets [2, B + 1]), int64 on the host (one read when
+    the counts are on the device).  ValueError unless they are non-negative and sum to V and F."""
+    counts = _host_counts(v_count, f_count)
+    if counts.shape[1] and int(counts.min()) < 0 or int(counts[0].sum()) != V or int(counts[1].sum()) != F:
+        raise ValueError("%s: v_count / f_count must be non-negative and sum to the packed lengths (%d vertices, %d faces), got sums %d and %d"
+                         % (who, V, F, int(counts[0].sum()), int(counts[1].sum())))
+    return counts, _offsets(counts)
+
+
+def check_packed(who, verts, faces, v_count, f_count, *, max_images, max_faces):
+    """The counts spelling, as ops.mesh_topology and ops.mesh_cluster_simplify take it: verts [V,3] fp32 and faces [F,3] int32 on one
+    device, v_count / f_count [B] int64 or int32, on the host or on that device -> (B, V, F, counts, offsets) with check_counts' two
+    host tensors.  Every refusal is a ValueError that names the argument, in this order: not a tensor or a wrong dtype, a shape other
+    than [n,3], counts of different lengths, a CPU tensor, two devices, more than max_images images, max_faces faces or 2^31 - 1
+    vertices, and check_counts' (the only step that may read from the device)."""
+    for name, t, dtypes in (("verts", verts, (torch.float32,)), ("faces", faces, (torch.int32,)),
+                            ("v_count", v_count, (torch.int64, torch.int32)), ("f_count", f_count, (torch.int64, torch.int32))):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
+        if t.dtype not in dtypes:
+            raise ValueError("%s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype))
+    for name, t in (("verts", verts), ("faces", faces)):
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("%s: %s must be [n,3], got %s" % (who, name, tuple(t.shape)))
+    if v_count.dim() != 1 or v_count.shape != f_count.shape:
+        raise ValueError("%s: v_count and f_count must be [B], got %s and %s" % (who, tuple(v_count.shape), tuple(f_count.shape)))
+    for name, t in (("verts", verts), ("faces", faces)):
+        if not t.is_cuda:
+            raise ValueError("%s: %s is a CPU tensor; the HIP kernels need device tensors (no CPU fallback)" % (who, name))
+    if faces.device != verts.device:
+        raise ValueError("%s: faces is on %s, verts is on %s" % (who, faces.device, verts.device))
+    for name, t in (("v_count", v_count), ("f_count", f_count)):
+        if t.is_cuda and t.device != verts.device:
+            raise ValueError("%s: %s is on %s, verts is on %s" % (who, name, t.device, verts.device))
+    B, V, F = v_count.shape[0], verts.shape[0], faces.shape[0]
+    if B > max_images or F > max_faces or V > 2 ** 31 - 1:
+        raise ValueError("%s takes at most %d images, %d faces and 2^31 - 1 vertices per call, got %d, %d and %d"
+                         % (who, max_images, max_faces, B, F, V))
+    return (B, V, F) + check_counts(who, v_count, f_count, V, F)
+
+
+def check_mesh_tensors(who, verts, faces):
+    """verts [V,3] fp32 and faces [F,3] int32 on one device -> the two, contiguous; ValueError otherwise (the starts spelling's ops)."""
+    verts = device_tensor(who, "verts", verts, (torch.float32,))
+    faces = device_tensor(who, "faces", faces, (torch.int32,), verts.device)
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("shapeclipper_amd: %s takes verts [V,3] and faces [F,3], got %s and %s" % (who, tuple(verts.shape), tuple(faces.shape)))
+    return verts, faces
+
+
+def check_starts(who, v_start, f_start, f_count, V, F, max_images):
+    """The starts spelling, as ops.texture_queries and ops.mesh_raster take it beside verts [V,3] and faces [F,3]: v_start / f_start /
+    f_count sequences of B host integers -> (v_start, f_start, f_count) as lists of ints.  ValueError for sequences of different lengths
+    or more than max_images images, and for an image whose faces [f_start, f_start + f_count) or first vertex lie outside the F faces /
+    V vertices.  Nothing here needs a device."""
+    v_start, f_start, f_count = ([int(v) for v in s] for s in (v_start, f_start, f_count))
+    B = len(f_count)
+    if len(v_start) != B or len(f_start) != B or B > max_images:
+        raise ValueError("shapeclipper_amd: %s takes v_start, f_start and f_count of one length <= %d" % (who, max_images))
+    for b in range(B):
+        if f_count[b] < 0 or f_start[b] < 0 or f_start[b] + f_count[b] > F or not 0 <= v_start[b] <= V:
+            raise ValueError("shapeclipper_amd: %s: image %d's faces f_start + [0, f_count) = [%d, %d) / first vertex v_start = %d lie "
+                             "outside the %d faces / %d vertices given" % (who, b, f_start[b], f_start[b] + f_count[b], v_start[b], F, V))
+    return v_start, f_start, f_count

@@ -8,6 +8,7 @@ import weakref
 import torch
 
 from . import _lib
+from .mesh_pack import PackedMesh, check_counts, check_mesh_tensors, check_packed, check_starts, device_tensor
 from .packing import n_tiles
 
 _SCRATCH = {}       # (tag, device index, raw stream) -> fp32 buffer; every cached device scratch of this module lives here
@@ -722,11 +723,10 @@ def _mesh_state(level, iso, who):
 
 
 def isosurface_mesh(level: torch.Tensor, iso: float = 0.0):
-    """level [B,S,S,S] (device) -> (verts [V,3] fp32, faces [F,3] int32, v_count [B] int64, f_count [B] int64; counts on the host).
+    """level [B,S,S,S] (device) -> PackedMesh (mesh_pack.py) with verts in grid-index units and the counts as int64 on the host.
 
     The indexed form of isosurface_triangles(method="cubes"): one vertex per grid edge whose end values lie on different sides of iso,
-    ordered by image, owning grid point (its lower end, linear index) and axis, shared by every triangle around the edge; faces are
-    vertex numbers local to their image, so image b's mesh is verts[vs:ve], faces[fs:fe] with the offsets of the two counts.
+    ordered by image, owning grid point (its lower end, linear index) and axis, shared by every triangle around the edge.
     verts[faces] of an image equals its triangles from isosurface_triangles bit for bit, in the same order.  Two scans with one host
     read each (faces: the soup's count / scan over 1,024-cube blocks; vertices: 1,024-point blocks), vertex emit, face emit --
     csrc/isosurface.hip.  Scratch: a vertex-number map of 12 bytes per grid point, written at crossing edges only."""
@@ -737,12 +737,12 @@ def isosurface_mesh(level: torch.Tensor, iso: float = 0.0):
     if st.vmap is not None and F > 0:
         _lib.check(_lib.load().sc_marching_cubes_mesh_face_emit(B, S, _lib.ptr(st.offsets), _lib.ptr(st.masks), _lib.ptr(st.vmap),
                                                                 _lib.ptr(faces), _lib.stream()), "sc_marching_cubes_mesh_face_emit")
-    return st.verts, faces, st.v_count, st.f_count
+    return PackedMesh(st.verts, faces, st.v_count, st.f_count)
 
 
 def dual_contour_mesh(level: torch.Tensor, normals: torch.Tensor, iso: float = 0.0, reg: float = 0.05):
-    """level [B,S,S,S] (device), normals [V,3] fp32 (device) -> (verts [Vd,3] fp32 in grid-index units, faces [Fd,3] int32, v_count [B]
-    int64, f_count [B] int64; counts on the host): the dual-contouring mesh of the grid.
+    """level [B,S,S,S] (device), normals [V,3] fp32 (device) -> PackedMesh (verts in grid-index units, the counts as int64 on the host):
+    the dual-contouring mesh of the grid.
 
     normals belong to the vertices of isosurface_mesh(level, iso), in their order (V of them).  One vertex per cell whose corners lie
     on both sides of iso, where the tangent planes of the cell's crossings meet: the minimiser of sum (n_i . (x - p_i))^2 +
@@ -770,8 +770,7 @@ def dual_contour_mesh(level: torch.Tensor, normals: torch.Tensor, iso: float = 0
         raise ValueError("shapeclipper_amd: dual_contour_mesh: %d normals for the %d crossing vertices of isosurface_mesh(level, iso)"
                          % (normals.shape[0], st.verts.shape[0]))
     if st.vmap is None:                                                             # no crossing edge: no image has a surface
-        return (torch.empty(0, 3, device=dev, dtype=torch.float32), torch.empty(0, 3, device=dev, dtype=torch.int32),
-                torch.zeros(B, dtype=torch.int64), torch.zeros(B, dtype=torch.int64))
+        return PackedMesh.empty(B, dev)
     normals = normals.contiguous()
     bpi = int(lib.sc_isosurface_blocks_per_image(S))
     counts = torch.empty(2, B * bpi, device=dev, dtype=torch.int32)                 # owning cells / triangles per 1,024-cube block
@@ -794,7 +793,7 @@ def dual_contour_mesh(level: torch.Tensor, normals: torch.Tensor, iso: float = 0
     if Fd > 0:
         _lib.check(lib.sc_dual_contour_face_emit(_lib.ptr(st.masks), _lib.ptr(cell_map), B, S, _lib.ptr(offsets[1]), _lib.ptr(faces),
                                                  _lib.stream()), "sc_dual_contour_face_emit")
-    return verts, faces, v_count, f_count
+    return PackedMesh(verts, faces, v_count, f_count)
 
 
 # ---- evaluation: the largest connected component of a level grid's solid (csrc/level_components.hip) -------------------------------
@@ -1818,19 +1817,22 @@ def _point_mesh_args(points, verts, faces, v_count, f_count, search):
     who = "shapeclipper_amd: point_mesh_distance"
     if search not in ("grid", "brute"):
         raise ValueError("%s: search must be 'grid' or 'brute', got %r" % (who, search))
-    f32, i32 = torch.float32, torch.int32
-    for name, t, dtype in (("points", points, f32), ("verts", verts, f32), ("faces", faces, i32), ("v_count", v_count, i32),
-                           ("f_count", f_count, i32)):
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    for name, t, dtypes in (("points", points, (f32,)), ("verts", verts, (f32,)), ("faces", faces, (i32,)), ("v_count", v_count, (i32, i64)),
+                            ("f_count", f_count, (i32, i64))):
         if not isinstance(t, torch.Tensor):
             raise ValueError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
-        if not t.is_cuda:
+        if not t.is_cuda and not name.endswith("_count"):               # the counts may be on the host, where the producers leave them
             raise ValueError("%s: %s is a CPU tensor; the HIP kernels need device tensors (no CPU fallback)" % (who, name))
-        if t.device != points.device:
+        if t.is_cuda and t.device != points.device:
             raise ValueError("%s: %s is on %s, points is on %s" % (who, name, t.device, points.device))
-        if t.dtype != dtype:
-            raise ValueError("%s: %s must be %s, got %s" % (who, name, dtype, t.dtype))
+        if t.dtype not in dtypes:
+            raise ValueError("%s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype))
         if not t.is_contiguous():
             raise ValueError("%s: %s must be contiguous" % (who, name))
+    if v_count.dtype != f_count.dtype or v_count.device != f_count.device:
+        raise ValueError("%s: v_count and f_count must come in one form, got %s on %s and %s on %s"
+                         % (who, v_count.dtype, v_count.device, f_count.dtype, f_count.device))
     if points.dim() != 3 or points.shape[2] != 3 or points.shape[1] < 1:
         raise ValueError("%s: points must be [B,N,3] with N >= 1, got %s" % (who, tuple(points.shape)))
     B, N = points.shape[0], points.shape[1]
@@ -1847,8 +1849,9 @@ def _point_mesh_args(points, verts, faces, v_count, f_count, search):
 
 
 def point_mesh_distance(points, verts, faces, v_count, f_count, search="grid"):
-    """points [B,N,3] fp32 against B triangle meshes packed one after the other -- verts [Vtot,3] fp32, faces [Ftot,3] int32 with indices
-    LOCAL to the image's vertex slice, v_count / f_count [B] int32 on the device, the form isosurface_mesh and dual_contour_mesh return
+    """points [B,N,3] fp32 against the PackedMesh (mesh_pack.py) of B images, passed as `*mesh` -- verts [Vtot,3] fp32 and faces [Ftot,3]
+    int32 on points' device; v_count / f_count [B], both in one form: int64 or int32, on the host (as every producer returns them) or on
+    that device.  The C entry point takes int32 device counts; that form is passed through, any other is converted (two copies, no read)
     -> PointMesh(dist2 [B,N] fp32, face [B,N] int32, closest [B,N,3] fp32): for every point the squared distance to the nearest
     triangle of its image, that triangle's local index (the LOWEST among exact ties) and the closest point on it, in the fp32 arithmetic
     include/shapeclipper_hip.h states for sc_point_mesh_distance (PyTorch3D's point_mesh_face_distance keeps the distance only).
@@ -1867,7 +1870,9 @@ def point_mesh_distance(points, verts, faces, v_count, f_count, search="grid"):
     if B == 0:
         return PointMesh(dist2, face, closest)
     # the one reduction: (counts non-negative, sum of v_count, sum of f_count, faces inside their image's vertex range) -> 4 numbers
-    vc, fc = v_count.long(), f_count.long()
+    vc, fc = v_count.to(dev).long(), f_count.to(dev).long()
+    if not v_count.is_cuda or v_count.dtype != torch.int32:
+        v_count, f_count = vc.int(), fc.int()                           # the validated int64 values below bound them
     inside = torch.ones((), dtype=torch.bool, device=dev)
     if Ftot:        # the image of every packed face, from the running sum of f_count (no host read; meaningful only if the sums hold)
         owner = torch.searchsorted(torch.cumsum(fc.clamp_min(0), 0), torch.arange(Ftot, device=dev), right=True).clamp_max(B - 1)
@@ -2007,20 +2012,10 @@ def _texture_atlas_arg(who, A):
         raise ValueError("shapeclipper_amd: %s: the atlas side must be a power of two in %d..%d, got %r" % (who, *TEXTURE_ATLAS, A))
 
 
-def _texture_tensor(who, name, t, dtypes, dev=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError("shapeclipper_amd: %s: %s must be a device tensor (no CPU fallback)" % (who, name))
-    if t.dtype not in dtypes:
-        raise ValueError("shapeclipper_amd: %s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype))
-    if dev is not None and t.device != dev:
-        raise ValueError("shapeclipper_amd: %s: %s is on %s, expected %s" % (who, name, t.device, dev))
-    return t.contiguous()
-
-
 def texture_queries(verts, faces, v_start, f_start, f_count, A, T, lo, hi, S, rows, extra=0):
-    """The network query point of every atlas texel: verts [V,3] fp32 (grid-index units) and faces [F,3] int32 (vertex numbers local to
-    their image) as isosurface_mesh returns them, v_start / f_start / f_count sequences of B host integers (image b's faces are
-    faces[f_start[b]:f_start[b] + f_count[b]], its vertex k is verts[v_start[b] + k]) -> (query [B (rows A + extra), 3] fp32,
+    """The network query point of every atlas texel: mesh.verts (grid-index units), mesh.faces and *mesh.starts() of a PackedMesh
+    (mesh_pack.py) -- v_start / f_start / f_count sequences of B host integers: image b's faces are
+    faces[f_start[b]:f_start[b] + f_count[b]], its vertex k is verts[v_start[b] + k] -> (query [B (rows A + extra), 3] fp32,
     face_of_texel [B, rows A] int32).  Image b's texel (x, y) is row y A + x of its block of rows A + extra query rows, the padded
     one-launch layout of sdf_forward / rgb_points_forward with n_per_image = rows A + extra; the `extra` rows behind the texels are
     left unwritten for the caller (eval_3D.mesh_texture puts the face centroids there).  A used texel is queried at
@@ -2028,22 +2023,15 @@ def texture_queries(verts, faces, v_start, f_start, f_count, A, T, lo, hi, S, ro
     image's first texel.  include/shapeclipper_hip.h states layout and arithmetic (sc_texture_queries); texture_layout gives A and
     rows.  One launch on the current stream, no host synchronisation."""
     who = "texture_queries"
-    verts = _texture_tensor(who, "verts", verts, (torch.float32,))
-    faces = _texture_tensor(who, "faces", faces, (torch.int32,), verts.device)
-    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError("shapeclipper_amd: texture_queries takes verts [V,3] and faces [F,3], got %s and %s" % (tuple(verts.shape), tuple(faces.shape)))
+    verts, faces = check_mesh_tensors(who, verts, faces)
     _texture_atlas_arg(who, A)
-    v_start, f_start, f_count = ([int(v) for v in s] for s in (v_start, f_start, f_count))
-    B, V, F = len(f_count), verts.shape[0], faces.shape[0]
-    if len(v_start) != B or len(f_start) != B or B > TEXTURE_MAX_IMAGES:
-        raise ValueError("shapeclipper_amd: texture_queries takes v_start, f_start and f_count of one length <= %d" % TEXTURE_MAX_IMAGES)
+    V, F = verts.shape[0], faces.shape[0]
+    v_start, f_start, f_count = check_starts(who, v_start, f_start, f_count, V, F, TEXTURE_MAX_IMAGES)
+    B = len(f_count)
     if isinstance(T, bool) or not isinstance(T, int) or not TEXTURE_TEXELS[0] <= T <= TEXTURE_TEXELS[1]:
         raise ValueError("shapeclipper_amd: texture_queries: T must be an integer in %d..%d, got %r" % (*TEXTURE_TEXELS, T))
     n = A // T
     for b in range(B):
-        if f_count[b] < 0 or f_start[b] < 0 or f_start[b] + f_count[b] > F or not 0 <= v_start[b] <= V:
-            raise ValueError("shapeclipper_amd: texture_queries: image %d's faces [%d, %d) / first vertex %d lie outside the %d faces / %d "
-                             "vertices given" % (b, f_start[b], f_start[b] + f_count[b], v_start[b], F, V))
         if f_count[b] > 2 * n * (rows // T):
             raise ValueError("shapeclipper_amd: texture_queries: image %d has %d faces; %d rows of an atlas of %d hold %d at T = %d"
                              % (b, f_count[b], rows, A, 2 * n * (rows // T), T))
@@ -2071,10 +2059,10 @@ def texture_pack(rgb, normal, face_of_texel, A, rows):
     and the rows >= `rows` hold 127.  One launch (sc_texture_pack), no host synchronisation."""
     who = "texture_pack"
     _texture_atlas_arg(who, A)
-    face_of_texel = _texture_tensor(who, "face_of_texel", face_of_texel, (torch.int32,))
+    face_of_texel = device_tensor(who, "face_of_texel", face_of_texel, (torch.int32,))
     dev = face_of_texel.device
-    rgb = _texture_tensor(who, "rgb", rgb, (torch.float32,), dev)
-    normal = _texture_tensor(who, "normal", normal, (torch.float32,), dev)
+    rgb = device_tensor(who, "rgb", rgb, (torch.float32,), dev)
+    normal = device_tensor(who, "normal", normal, (torch.float32,), dev)
     if not 0 <= rows <= A or face_of_texel.dim() != 2 or face_of_texel.shape[1] != rows * A:
         raise ValueError("shapeclipper_amd: texture_pack takes face_of_texel [B, rows A] with 0 <= rows <= A, got %s at rows = %r, A = %d"
                          % (tuple(face_of_texel.shape), rows, A))
@@ -2100,10 +2088,10 @@ def texture_sample(atlas, uv, image_of_point):
     convention (u to the right, v upward, texel centres at (k + 0.5) / A), image_of_point [N] int32 -> [N, C] fp32.  Indices clamp to the
     atlas edge; include/shapeclipper_hip.h states the expression (sc_texture_sample).  One launch, no host synchronisation."""
     who = "texture_sample"
-    atlas = _texture_tensor(who, "atlas", atlas, (torch.float32, torch.uint8))
+    atlas = device_tensor(who, "atlas", atlas, (torch.float32, torch.uint8))
     dev = atlas.device
-    uv = _texture_tensor(who, "uv", uv, (torch.float32,), dev)
-    image_of_point = _texture_tensor(who, "image_of_point", image_of_point, (torch.int32,), dev)
+    uv = device_tensor(who, "uv", uv, (torch.float32,), dev)
+    image_of_point = device_tensor(who, "image_of_point", image_of_point, (torch.int32,), dev)
     if atlas.dim() != 4 or atlas.shape[1] != atlas.shape[2] or not 1 <= atlas.shape[3] <= 16 or atlas.shape[0] < 1:
         raise ValueError("shapeclipper_amd: texture_sample takes an atlas [B, A, A, C] with B >= 1 and 1 <= C <= 16, got %s" % (tuple(atlas.shape),))
     B, A, C = atlas.shape[0], atlas.shape[1], atlas.shape[3]
@@ -2125,14 +2113,15 @@ def texture_sample(atlas, uv, image_of_point):
 # ---- evaluation: triangle rasteriser (csrc/mesh_raster.hip) -----------------------------------------------------------------------------
 RASTER_MAX_SIDE = 4096
 RASTER_MAX_VIEWS = 65535
+RASTER_MAX_IMAGES = 65535
 RASTER_LARGE_PIXELS = 64            # a face whose box holds more pixel centres is walked by a wave, not by its own thread
 MeshRaster = collections.namedtuple("MeshRaster", ["face", "depth", "bary", "stats"])
 
 
 def mesh_raster(verts, faces, v_start, f_start, f_count, pose, intr, H, W, near, large_pixels=RASTER_LARGE_PIXELS):
-    """The packed meshes of B images, each seen from n_views cameras: verts [V,3] fp32 in world units, faces [F,3] int32 (vertex numbers
-    local to their image), v_start / f_start / f_count sequences of B host integers as texture_queries takes them (image b's vertices
-    are verts[v_start[b]:v_start[b + 1]], the last image's run to V), pose [B, n_views, 3, 4] world-to-camera (camera.world2cam's
+    """The PackedMesh (mesh_pack.py) of B images, each seen from n_views cameras: verts [V,3] fp32 in world units, mesh.faces and
+    *mesh.starts() -- v_start / f_start / f_count sequences of B host integers as texture_queries takes them, the images in order (image
+    b's vertices are verts[v_start[b]:v_start[b + 1]], the last image's run to V) --, pose [B, n_views, 3, 4] world-to-camera (camera.world2cam's
     convention), intr [B, 3, 3] -> MeshRaster(face [B, n_views, H, W] int32 -- the image's face nearest to the camera at the pixel's
     centre, -1 where none covers it --, depth [B, n_views, H, W] fp32 camera z (0 on a miss), bary [B, n_views, H, W, 3] fp32
     perspective-correct barycentrics (0 on a miss), stats [B, n_views, 4] int32: faces drawn, culled by `near`, culled by range or not
@@ -2142,17 +2131,13 @@ def mesh_raster(verts, faces, v_start, f_start, f_count, pose, intr, H, W, near,
     paths, which agree bit for bit.  Scratch from the `_scratch` cache (tag "mesh_raster"); three memsets and four launches on the
     current stream, no host synchronisation."""
     who = "mesh_raster"
-    verts = _texture_tensor(who, "verts", verts, (torch.float32,))
+    verts, faces = check_mesh_tensors(who, verts, faces)
     dev = verts.device
-    faces = _texture_tensor(who, "faces", faces, (torch.int32,), dev)
-    pose = _texture_tensor(who, "pose", pose, (torch.float32,), dev)
-    intr = _texture_tensor(who, "intr", intr, (torch.float32,), dev)
-    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError("shapeclipper_amd: mesh_raster takes verts [V,3] and faces [F,3], got %s and %s" % (tuple(verts.shape), tuple(faces.shape)))
-    v_start, f_start, f_count = ([int(v) for v in s] for s in (v_start, f_start, f_count))
-    B, V, F = len(f_count), verts.shape[0], faces.shape[0]
-    if len(v_start) != B or len(f_start) != B or B > TEXTURE_MAX_IMAGES:
-        raise ValueError("shapeclipper_amd: mesh_raster takes v_start, f_start and f_count of one length <= %d" % TEXTURE_MAX_IMAGES)
+    pose = device_tensor(who, "pose", pose, (torch.float32,), dev)
+    intr = device_tensor(who, "intr", intr, (torch.float32,), dev)
+    V, F = verts.shape[0], faces.shape[0]
+    v_start, f_start, f_count = check_starts(who, v_start, f_start, f_count, V, F, RASTER_MAX_IMAGES)
+    B = len(f_count)
     if pose.dim() != 4 or pose.shape[0] != B or tuple(pose.shape[2:]) != (3, 4) or not 1 <= pose.shape[1] <= RASTER_MAX_VIEWS:
         raise ValueError("shapeclipper_amd: mesh_raster takes pose [B, n_views, 3, 4] with B = %d and 1 <= n_views <= %d, got %s"
                          % (B, RASTER_MAX_VIEWS, tuple(pose.shape)))
@@ -2170,9 +2155,9 @@ def mesh_raster(verts, faces, v_start, f_start, f_count, pose, intr, H, W, near,
         v_end = v_start[b + 1] if b + 1 < B else V
         if not 0 <= v_start[b] <= v_end <= V:
             raise ValueError("shapeclipper_amd: mesh_raster: v_start must be non-decreasing within 0..%d, got %r" % (V, v_start))
-        if f_count[b] < 0 or f_start[b] < (f_start[b - 1] + f_count[b - 1] if b else 0) or f_start[b] + f_count[b] > F:
-            raise ValueError("shapeclipper_amd: mesh_raster: image %d's faces [%d, %d) overlap the image before or lie outside the %d "
-                             "faces given" % (b, f_start[b], f_start[b] + f_count[b], F))
+        if b and f_start[b] < f_start[b - 1] + f_count[b - 1]:
+            raise ValueError("shapeclipper_amd: mesh_raster: image %d's faces f_start + [0, f_count) = [%d, %d) overlap the image before"
+                             % (b, f_start[b], f_start[b] + f_count[b]))
         if f_count[b] > 0 and v_end == v_start[b]:
             raise ValueError("shapeclipper_amd: mesh_raster: image %d has %d faces and no vertex" % (b, f_count[b]))
     lib = _lib.load()
@@ -2345,9 +2330,9 @@ def mesh_topology_slots(n_faces: int) -> int:
 
 
 def mesh_topology(verts, faces, v_count, f_count, table_slots=None):
-    """B triangle meshes packed one after the other, exactly what isosurface_mesh and dual_contour_mesh return -- verts [V,3] fp32 and
-    faces [F,3] int32 on the device, indices LOCAL to the image's vertex slice, v_count / f_count [B] int64 or int32 (on the host, as
-    those two return them, or on the device) -> MeshTopology of [B] int64 device tensors vertices (referenced ones), unreferenced_vertices,
+    """A PackedMesh (mesh_pack.py) of B images, passed as `*mesh` -- verts and faces on the device, v_count / f_count [B] int64 or int32,
+    on the host (as every producer returns them) or on the device -> MeshTopology of [B] int64 device tensors vertices (referenced
+    ones), unreferenced_vertices,
     faces (non-degenerate), degenerate_faces, edges, boundary_edges (one face), nonmanifold_edges (three or more), inconsistent_edges
     (two faces that traverse the edge the same way), components (what trimesh.split returns), largest_component_faces,
     nonmanifold_vertices (more than one fan of corners), euler = V - E + F and genus (components - euler / 2 for a watertight, oriented,
@@ -2366,43 +2351,18 @@ def mesh_topology(verts, faces, v_count, f_count, table_slots=None):
 
     Host synchronisation: one read of a 4-byte flag after the launches (the index check).  Runs on the current stream."""
     who = "shapeclipper_amd: mesh_topology"
-    for name, t, dtypes in (("verts", verts, (torch.float32,)), ("faces", faces, (torch.int32,)),
-                            ("v_count", v_count, (torch.int64, torch.int32)), ("f_count", f_count, (torch.int64, torch.int32))):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
-        if t.dtype not in dtypes:
-            raise ValueError("%s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype))
-    for name, t in (("verts", verts), ("faces", faces)):
-        if t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError("%s: %s must be [n,3], got %s" % (who, name, tuple(t.shape)))
-        if not t.is_cuda:
-            raise ValueError("%s: %s is a CPU tensor; the HIP kernels need device tensors (no CPU fallback)" % (who, name))
-    if faces.device != verts.device:
-        raise ValueError("%s: faces is on %s, verts is on %s" % (who, faces.device, verts.device))
-    if v_count.dim() != 1 or v_count.shape != f_count.shape:
-        raise ValueError("%s: v_count and f_count must be [B], got %s and %s" % (who, tuple(v_count.shape), tuple(f_count.shape)))
-    for name, t in (("v_count", v_count), ("f_count", f_count)):
-        if t.is_cuda and t.device != verts.device:
-            raise ValueError("%s: %s is on %s, verts is on %s" % (who, name, t.device, verts.device))
-    B, V, F, dev = v_count.shape[0], verts.shape[0], faces.shape[0], verts.device
-    if B > MESH_TOPOLOGY_MAX_IMAGES or F > MESH_TOPOLOGY_MAX_FACES or V > 2 ** 31 - 1:
-        raise ValueError("%s takes at most %d images, 2^26 faces and 2^31 - 1 vertices per call, got %d, %d and %d"
-                         % (who, MESH_TOPOLOGY_MAX_IMAGES, B, F, V))
+    B, V, F, _, offsets = check_packed(who, verts, faces, v_count, f_count, max_images=MESH_TOPOLOGY_MAX_IMAGES,
+                                       max_faces=MESH_TOPOLOGY_MAX_FACES)
+    dev = verts.device
     if table_slots is None:
         table_slots = mesh_topology_slots(F)
     if (isinstance(table_slots, bool) or not isinstance(table_slots, int) or table_slots < 1 or table_slots & (table_slots - 1)
             or table_slots <= 3 * F or table_slots > MESH_TOPOLOGY_MAX_SLOTS):
         raise ValueError("%s: table_slots must be a power of two greater than 3 F = %d (and at most 2^30), got %r" % (who, 3 * F, table_slots))
-    counts_host = torch.stack([v_count.long(), f_count.long()]).cpu()               # free for host counts, the form the meshers return
-    if B and int(counts_host.min()) < 0 or int(counts_host[0].sum()) != V or int(counts_host[1].sum()) != F:
-        raise ValueError("%s: v_count / f_count must be non-negative and sum to the packed lengths (%d vertices, %d faces), got sums %d and %d"
-                         % (who, V, F, int(counts_host[0].sum()), int(counts_host[1].sum())))
     counts = torch.empty(len(MESH_TOPOLOGY_COUNTS) + len(MESH_TOPOLOGY_FLAGS), B, device=dev, dtype=torch.int64)
     measures = torch.empty(2, B, device=dev, dtype=torch.float64)
     face_component = torch.empty(F, device=dev, dtype=torch.int32)
     if B > 0:
-        offsets = torch.zeros(2, B + 1, dtype=torch.int64)
-        offsets[:, 1:] = counts_host.cumsum(1)
         offsets = offsets.to(dev)
         bad = torch.empty(1, device=dev, dtype=torch.int32)
         lib = _lib.load()
@@ -2423,22 +2383,25 @@ def mesh_topology(verts, faces, v_count, f_count, table_slots=None):
 # ---- evaluation: decimation by vertex clustering with quadric placement (csrc/mesh_simplify.hip) ----------------------------------------
 MESH_SIMPLIFY_MAX_CELLS = 128               # SC_MESH_SIMPLIFY_MAX_CELLS
 MESH_SIMPLIFY_MAX_WORDS = 1 << 28           # mask words of a whole batch: B ceil(G^3 / 64)
-SimplifiedMesh = collections.namedtuple("SimplifiedMesh", ["verts", "faces", "v_count", "f_count", "vertex_cluster", "face_source",
-                                                           "collapsed", "cancelled"])
+
+
+class SimplifiedMesh(collections.namedtuple("SimplifiedMesh", ["verts", "faces", "v_count", "f_count", "vertex_cluster", "face_source",
+                                                               "collapsed", "cancelled"])):
+    __slots__ = ()
+    packed = property(lambda self: PackedMesh(*self[:4]), doc="the simplified meshes alone, as a PackedMesh")
 
 
 def mesh_cluster_simplify(verts, faces, v_count, f_count, origin, pitch, cells, reg=0.05):
-    """Decimates B packed triangle meshes -- exactly what isosurface_mesh and dual_contour_mesh return: verts [V,3] fp32 and faces [F,3]
-    int32 on the device, indices LOCAL to the image's vertex slice, v_count / f_count [B] int64 or int32 (host or device) -- by vertex
-    clustering: a box of `cells` = G cells per axis (1..128) of side `pitch` > 0 with its lower corner at `origin` (three numbers) is laid
+    """Decimates a PackedMesh (mesh_pack.py) of B images, passed as `*mesh` -- verts and faces on the device, v_count / f_count [B] int64
+    or int32 (host or device) -- by vertex clustering.  A box of `cells` = G cells per axis (1..128) of side `pitch` > 0 with its lower corner at `origin` (three numbers) is laid
     over every image, the vertices of a cell become one vertex at the minimiser of the cell's quadric (the planes of the faces that
     touch it, regularised towards the mean of its vertices by `reg` > 0, clamped into the cell), faces with two corners in one cell
     collapse, and of the faces left on one cluster triple opposite ones cancel and like-oriented copies leave one.
     include/shapeclipper_hip.h states every rule (sc_mesh_cluster_simplify); tests/mesh_simplify_ref.py restates them in numpy.
 
-    -> SimplifiedMesh(verts [V',3] fp32, faces [F',3] int32 image-local, v_count, f_count [B] int64 on the host -- the packed form again,
-    so the result goes into mesh_topology, point_mesh_distance or this op --, vertex_cluster [V] int32 (old vertex -> new vertex of its
-    image), face_source [F'] int32 (new face -> image-local old face), collapsed, cancelled [B] int64 on the device).  Output faces keep
+    -> SimplifiedMesh(verts [V',3] fp32, faces [F',3] int32 image-local, v_count, f_count [B] int64 on the host -- `.packed` is these
+    four as a PackedMesh again, for mesh_topology, point_mesh_distance or this op --, vertex_cluster [V] int32 (old vertex -> new vertex
+    of its image), face_source [F'] int32 (new face -> image-local old face), collapsed, cancelled [B] int64 on the device).  Output faces keep
     the source order; a cluster whose faces all vanished stays as an unreferenced vertex.  Only integer atomics decide anything: the
     same bits from run to run, for any batch, stream and face order.  Scratch comes from the scratch cache ("mesh simplify").
 
@@ -2448,24 +2411,9 @@ def mesh_cluster_simplify(verts, faces, v_count, f_count, origin, pitch, cells, 
 
     Host synchronisation: one read of the two flags and the per-image counts, which sizes the outputs.  Runs on the current stream."""
     who = "shapeclipper_amd: mesh_cluster_simplify"
-    for name, t, dtypes in (("verts", verts, (torch.float32,)), ("faces", faces, (torch.int32,)),
-                            ("v_count", v_count, (torch.int64, torch.int32)), ("f_count", f_count, (torch.int64, torch.int32))):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
-        if t.dtype not in dtypes:
-            raise ValueError("%s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype))
-    for name, t in (("verts", verts), ("faces", faces)):
-        if t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError("%s: %s must be [n,3], got %s" % (who, name, tuple(t.shape)))
-        if not t.is_cuda:
-            raise ValueError("%s: %s is a CPU tensor; the HIP kernels need device tensors (no CPU fallback)" % (who, name))
-    if faces.device != verts.device:
-        raise ValueError("%s: faces is on %s, verts is on %s" % (who, faces.device, verts.device))
-    if v_count.dim() != 1 or v_count.shape != f_count.shape:
-        raise ValueError("%s: v_count and f_count must be [B], got %s and %s" % (who, tuple(v_count.shape), tuple(f_count.shape)))
-    for name, t in (("v_count", v_count), ("f_count", f_count)):
-        if t.is_cuda and t.device != verts.device:
-            raise ValueError("%s: %s is on %s, verts is on %s" % (who, name, t.device, verts.device))
+    B, V, F, counts_host, offsets = check_packed(who, verts, faces, v_count, f_count, max_images=MESH_TOPOLOGY_MAX_IMAGES,
+                                                 max_faces=MESH_TOPOLOGY_MAX_FACES)
+    dev = verts.device
     number = lambda x: isinstance(x, (int, float)) and not isinstance(x, bool) and x == x and abs(x) != float("inf")
     if isinstance(origin, torch.Tensor):
         origin = origin.detach().cpu().reshape(-1).tolist()
@@ -2477,14 +2425,8 @@ def mesh_cluster_simplify(verts, faces, v_count, f_count, origin, pitch, cells, 
         raise ValueError("%s: cells must be an integer in 1..%d, got %r" % (who, MESH_SIMPLIFY_MAX_CELLS, cells))
     if not number(reg) or not reg > 0:
         raise ValueError("%s: reg must be a finite number > 0, got %r" % (who, reg))
-    B, V, F, dev = v_count.shape[0], verts.shape[0], faces.shape[0], verts.device
-    if B > MESH_TOPOLOGY_MAX_IMAGES or F > MESH_TOPOLOGY_MAX_FACES or V > 2 ** 31 - 1 or B * ((cells ** 3 + 63) // 64) > MESH_SIMPLIFY_MAX_WORDS:
-        raise ValueError("%s takes at most %d images, 2^26 faces, 2^31 - 1 vertices and B ceil(cells^3 / 64) <= 2^28 per call, got %d, %d, %d "
-                         "and cells = %d" % (who, MESH_TOPOLOGY_MAX_IMAGES, B, F, V, cells))
-    counts_host = torch.stack([v_count.long(), f_count.long()]).cpu()               # free for host counts, the form the meshers return
-    if B and int(counts_host.min()) < 0 or int(counts_host[0].sum()) != V or int(counts_host[1].sum()) != F:
-        raise ValueError("%s: v_count / f_count must be non-negative and sum to the packed lengths (%d vertices, %d faces), got sums %d and %d"
-                         % (who, V, F, int(counts_host[0].sum()), int(counts_host[1].sum())))
+    if B * ((cells ** 3 + 63) // 64) > MESH_SIMPLIFY_MAX_WORDS:
+        raise ValueError("%s takes B ceil(cells^3 / 64) <= 2^28 mask words per call, got B = %d and cells = %d" % (who, B, cells))
     verts_out = torch.empty(V, 3, device=dev, dtype=torch.float32)
     faces_out = torch.empty(F, 3, device=dev, dtype=torch.int32)
     vertex_cluster = torch.empty(V, device=dev, dtype=torch.int32)
@@ -2493,8 +2435,6 @@ def mesh_cluster_simplify(verts, faces, v_count, f_count, origin, pitch, cells, 
     counts, bad = back[:4 * B].view(4, B), back[4 * B:].view(torch.int32)           # SC_MESH_SIMPLIFY_FIELDS rows; bad_vertex, bad_index
     if B == 0:
         return SimplifiedMesh(verts_out, faces_out, counts_host[0], counts_host[1], vertex_cluster, face_source, counts[2], counts[3])
-    offsets = torch.zeros(2, B + 1, dtype=torch.int64)
-    offsets[:, 1:] = counts_host.cumsum(1)
     offsets = offsets.to(dev)
     lib = _lib.load()
     with torch.cuda.device(dev):

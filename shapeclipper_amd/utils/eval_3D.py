@@ -116,7 +116,7 @@ def _edge_crossing_points(level, lo, hi, num_points, rng):
     if len(pts) == 0:
         return np.zeros([num_points, 3])
     pick = rng.randint(0, len(pts), num_points)
-    return pts[pick] / S * (hi - lo) + lo
+    return written_position(pts[pick], lo, hi, S)
 
 
 @torch.no_grad()
@@ -133,7 +133,7 @@ def surface_points_device(level, lo, hi, num_points, seed=0, iso=0.0, method="cu
     B, S = level.shape[0], level.shape[1]
     dev = level.device
     tris, per_image = ops.isosurface_triangles(level, iso, method=method)
-    t_all = tris / S * (hi - lo) + lo
+    t_all = written_position(tris, lo, hi, S)
     ends = torch.cumsum(per_image, 0)                                   # host: triangles up to and including image b
     starts = ends - per_image
     meshes = [t_all[int(starts[b]):int(ends[b])] for b in range(B)]
@@ -165,31 +165,33 @@ def surface_points_device(level, lo, hi, num_points, seed=0, iso=0.0, method="cu
     return torch.where(ok[:, None, None], pts, out), meshes
 
 
+def sampled_position(v, lo, hi, S):
+    """v in grid-index units -> where the level grid of S points per axis was sampled: where the surface is and the networks are asked."""
+    return lo + v * ((hi - lo) / (S - 1))
+
+
+def written_position(v, lo, hi, S):
+    """v in grid-index units -> the reference's rescale, which every written mesh and the surface samples carry (see mesh_attributes)."""
+    return v / S * (hi - lo) + lo
+
+
 @torch.no_grad()
 def meshes_device(level, lo, hi, iso=0.0):
     """level [B,S,S,S] on the GPU -> per-image list of (vertices [V,3] float32, faces [F,3] int32), both on the device, vertices in world
     units: the indexed marching-cubes mesh of ops.isosurface_mesh (the form `mcubes.marching_cubes` returns in the reference), rescaled
     with surface_points_device's expression, so its de-indexed triangles are exactly the surface the metrics were sampled from."""
-    S = level.shape[1]
-    verts, faces, v_count, f_count = ops.isosurface_mesh(level, iso)
-    verts = verts / S * (hi - lo) + lo
-    v_end, f_end = torch.cumsum(v_count, 0).tolist(), torch.cumsum(f_count, 0).tolist()
-    v_start, f_start = [0] + v_end[:-1], [0] + f_end[:-1]
-    return [(verts[v_start[b]:v_end[b]], faces[f_start[b]:f_end[b]]) for b in range(level.shape[0])]
+    mesh = ops.isosurface_mesh(level, iso)
+    return mesh.split(written_position(mesh.verts, lo, hi, level.shape[1]))
 
 
-def _padded_vertex_queries(verts, v_count, v_start, lo, hi, S):
-    """The one-launch layout of the per-vertex network queries: (P, query [B P, 3]) with P = 16 ceil(max V_b / 16) rows per image, image
-    b's vertices at rows [b P, b P + V_b), padding rows repeating the image's first vertex; positions are where the level grid was sampled,
-    lo + v (hi - lo) / (S - 1) with v in grid-index units.  (0, None) when no image has a vertex."""
-    dev = verts.device
-    P = 16 * ((max(v_count.tolist(), default=0) + 15) // 16)
+def _padded_vertex_queries(mesh, lo, hi, S):
+    """The one-launch layout of the per-vertex network queries of a PackedMesh: (P, query [B P, 3]) with P = 16 ceil(max V_b / 16) rows
+    per image, image b's vertices at rows [b P, b P + V_b), padding rows repeating the image's first vertex (mesh.padded_rows), at
+    sampled_position.  (0, None) when no image has a vertex."""
+    P, rows = mesh.padded_rows(16)
     if P == 0:
         return 0, None
-    start = torch.tensor(v_start, device=dev).clamp_max(verts.shape[0] - 1)
-    j = torch.arange(P, device=dev)
-    rows = torch.where(j[None] < v_count.to(dev)[:, None], start[:, None] + j[None], start[:, None]).reshape(-1)
-    return P, (lo + verts[rows] * ((hi - lo) / (S - 1))).contiguous()
+    return P, sampled_position(mesh.verts[rows.reshape(-1)], lo, hi, S).contiguous()
 
 
 def _colours_and_normals(sdf_network, rgb_network, proj_latent_sdf, proj_latent_rgb):
@@ -232,20 +234,17 @@ def mesh_attributes(opt, sdf_network, rgb_network, proj_latent_sdf, proj_latent_
     lo, hi = opt.eval.range
     B, S = level_vox.shape[0], level_vox.shape[1]
     dev = level_vox.device
-    verts, faces, v_count, f_count = ops.isosurface_mesh(level_vox)
-    written = verts / S * (hi - lo) + lo                                # meshes_device's expression: the same bytes as {idx}_mesh.ply
-    v_end, f_end = torch.cumsum(v_count, 0).tolist(), torch.cumsum(f_count, 0).tolist()
-    v_start, f_start = [0] + v_end[:-1], [0] + f_end[:-1]
-    V = v_count.tolist()
-    P, query = _padded_vertex_queries(verts, v_count, v_start, lo, hi, S)
+    mesh = ops.isosurface_mesh(level_vox)
+    written = mesh.split(written_position(mesh.verts, lo, hi, S))       # meshes_device's expression: the same bytes as {idx}_mesh.ply
+    V = mesh.v_count.tolist()
+    P, query = _padded_vertex_queries(mesh, lo, hi, S)
     if P == 0:
         empty = (torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.int32, device=dev),
                  torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.uint8, device=dev))
         return [empty] * B
     rgb, normal = _colours_and_normals(sdf_network, rgb_network, proj_latent_sdf, proj_latent_rgb)(query, B, P)
     colours = (rgb.clamp(0, 1) * 255).to(torch.uint8)
-    return [(written[v_start[b]:v_end[b]], faces[f_start[b]:f_end[b]], normal[b * P:b * P + V[b]], colours[b * P:b * P + V[b]])
-            for b in range(B)]
+    return [(*written[b], normal[b * P:b * P + V[b]], colours[b * P:b * P + V[b]]) for b in range(B)]
 
 
 TEXTURE_SLAB = 1 << 20     # texels per launch of mesh_texture's network chain: the feature tile costs 256 B a texel
@@ -287,27 +286,24 @@ def mesh_texture(opt, sdf_network, rgb_network, proj_latent_sdf, proj_latent_rgb
     T = options.texture_texels(opt, always=True)
     B, S = level_vox.shape[0], level_vox.shape[1]
     dev = level_vox.device
-    verts, faces, v_count, f_count = ops.isosurface_mesh(level_vox)
-    written = verts / S * (hi - lo) + lo                                # meshes_device's expression: the same bytes as {idx}_mesh.ply
-    v_end, f_end = torch.cumsum(v_count, 0).tolist(), torch.cumsum(f_count, 0).tolist()
-    v_start, f_start = [0] + v_end[:-1], [0] + f_end[:-1]
-    F = f_count.tolist()
+    mesh = ops.isosurface_mesh(level_vox)
+    written = mesh.split(written_position(mesh.verts, lo, hi, S))       # meshes_device's expression: the same bytes as {idx}_mesh.ply
+    v_start, f_start, F = mesh.starts()
     A, _, rows = ops.texture_layout(max(F, default=0), T)
     grey = torch.full((64, 64, 3), 127, dtype=torch.uint8, device=dev)
-    blank = lambda b: TexturedMesh(written[v_start[b]:v_end[b]], faces[f_start[b]:f_end[b]], torch.zeros(0, 3, 2, device=dev), grey, grey,
+    blank = lambda b: TexturedMesh(*written[b], torch.zeros(0, 3, 2, device=dev), grey, grey,
                                    dict(faces=0, atlas=64, rows=0, err_mean=0.0, err_max=0.0))
     if rows == 0:
         return [blank(b) for b in range(B)]
     n_tex = rows * A
     Pc = 16 * ((max(F) + 15) // 16)                                     # the centroid block
     P = n_tex + Pc
-    query, face_of_texel = ops.texture_queries(verts, faces, v_start, f_start, F, A, T, lo, hi, S, rows, extra=Pc)
+    query, face_of_texel = ops.texture_queries(mesh.verts, mesh.faces, v_start, f_start, F, A, T, lo, hi, S, rows, extra=Pc)
     q = query.view(B, P, 3)
-    scale = (hi - lo) / (S - 1)
-    for b in range(B):
-        tri = verts[v_start[b]:v_end[b]][faces[f_start[b]:f_end[b]].long()]            # [F_b,3,3] grid-index units
+    for b, (v, f) in enumerate(mesh.split()):
+        tri = v[f.long()]                                                              # [F_b,3,3] grid-index units
         q[b, n_tex:] = q[b, 0]                                                         # padding repeats the image's first texel
-        q[b, n_tex:n_tex + F[b]] = lo + (tri.sum(dim=1) / 3) * scale
+        q[b, n_tex:n_tex + F[b]] = sampled_position(tri.sum(dim=1) / 3, lo, hi, S)
     # the chain, slab by slab: rows [s, e) of every image's block are one padded launch of e - s points per image
     slab = TEXTURE_SLAB if slab is None else int(slab)
     step = max(16, (slab // B) // 16 * 16)
@@ -334,8 +330,8 @@ def mesh_texture(opt, sdf_network, rgb_network, proj_latent_sdf, proj_latent_rgb
         if F[b] == 0:
             out.append(blank(b))
             continue
-        e = err[f_start[b]:f_end[b]]
-        out.append(TexturedMesh(written[v_start[b]:v_end[b]], faces[f_start[b]:f_end[b]], uv[b], atlas[b], atlas_n[b],
+        e = err[f_start[b]:f_start[b] + F[b]]
+        out.append(TexturedMesh(*written[b], uv[b], atlas[b], atlas_n[b],
                                 dict(faces=F[b], atlas=A, rows=rows, err_mean=float(e.mean()), err_max=float(e.max()))))
     return out
 
@@ -370,18 +366,16 @@ def mesh_render(opt, level_vox, textured, pose, intr, H, W, large_pixels=None):
     lo, hi = opt.eval.range
     B, S = level_vox.shape[0], level_vox.shape[1]
     dev = level_vox.device
-    verts, faces, v_count, f_count = ops.isosurface_mesh(level_vox)
-    world = (lo + verts * ((hi - lo) / (S - 1))).contiguous()              # mesh_attributes' expression
-    v_end, f_end = torch.cumsum(v_count, 0).tolist(), torch.cumsum(f_count, 0).tolist()
-    v_start, f_start = [0] + v_end[:-1], [0] + f_end[:-1]
-    F = f_count.tolist()
+    mesh = ops.isosurface_mesh(level_vox)
+    world = sampled_position(mesh.verts, lo, hi, S).contiguous()           # mesh_attributes' positions
+    v_start, f_start, F = mesh.starts()
     pose = pose.float()
     pose = (pose[:, None] if pose.dim() == 3 else pose).contiguous()
     intr = intr.float()
     if (int(H), int(W)) != (int(opt.H), int(opt.W)):
         intr = intr * torch.tensor([W / opt.W, H / opt.H, 1.0], device=intr.device).view(1, 3, 1)
     kw = {} if large_pixels is None else dict(large_pixels=large_pixels)
-    r = ops.mesh_raster(world, faces, v_start, f_start, F, pose, intr.contiguous(), int(H), int(W), MESH_RENDER_NEAR, **kw)
+    r = ops.mesh_raster(world, mesh.faces, v_start, f_start, F, pose, intr.contiguous(), int(H), int(W), MESH_RENDER_NEAR, **kw)
     V = pose.shape[1]
     mask = r.face >= 0
     bg, grey = float(opt.data.bgcolor), 0.5
@@ -460,14 +454,12 @@ def meshes_dual(opt, sdf_network, proj_latent_sdf, level_vox, reg, keep=None):
     padded one-launch layout (one ops.sdf_forward with d sdf/dx; sdf_network.eager: stock operators, model/eager_path.py).  The written
     vertices take meshes_device's v / S (hi - lo) + lo, so the mesh overlays {idx}_mesh.ply.  The crossing vertices are extracted twice,
     here for the queries and again inside dual_contour_mesh, whose public form takes the grid and the normals.  keep (the batch's var):
-    keep.mesh_dual_packed = [verts, faces, v_count, f_count] as ops.dual_contour_mesh returned them, when there is a mesh."""
+    keep.mesh_dual_packed = the PackedMesh as ops.dual_contour_mesh returned it (a list of its four fields), when there is a mesh."""
     lo, hi = opt.eval.range
     B, S = level_vox.shape[0], level_vox.shape[1]
     dev = level_vox.device
-    verts, _, v_count, _ = ops.isosurface_mesh(level_vox)
-    v_end = torch.cumsum(v_count, 0).tolist()
-    v_start = [0] + v_end[:-1]
-    P, query = _padded_vertex_queries(verts, v_count, v_start, lo, hi, S)
+    mesh = ops.isosurface_mesh(level_vox)
+    P, query = _padded_vertex_queries(mesh, lo, hi, S)
     if P == 0:
         return [(torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.int32, device=dev))] * B
     if sdf_network.eager:
@@ -477,14 +469,11 @@ def meshes_dual(opt, sdf_network, proj_latent_sdf, level_vox, reg, keep=None):
         w_pack, cbias = sdf_network.packed(proj_latent_sdf)
         _, grad, _ = ops.sdf_forward(query, w_pack, cbias, P, symmetric=bool(sdf_network.force_symmetry), want_grad=True, want_feat=False)
     normal = torch.nn.functional.normalize(grad.detach(), dim=1, eps=1e-12)
-    normals = torch.cat([normal[b * P:b * P + n] for b, n in enumerate(v_count.tolist())])
-    dverts, dfaces, dv_count, df_count = ops.dual_contour_mesh(level_vox, normals, 0.0, reg)
+    normals = torch.cat([normal[b * P:b * P + n] for b, n in enumerate(mesh.v_count.tolist())])
+    dual = ops.dual_contour_mesh(level_vox, normals, 0.0, reg)
     if keep is not None:                    # the packed mesh in grid-index units, for mesh_stats
-        keep.mesh_dual_packed = [dverts, dfaces, dv_count, df_count]
-    dverts = dverts / S * (hi - lo) + lo
-    dv_end, df_end = torch.cumsum(dv_count, 0).tolist(), torch.cumsum(df_count, 0).tolist()
-    dv_start, df_start = [0] + dv_end[:-1], [0] + df_end[:-1]
-    return [(dverts[dv_start[b]:dv_end[b]], dfaces[df_start[b]:df_end[b]]) for b in range(B)]
+        keep.mesh_dual_packed = list(dual)
+    return dual.split(written_position(dual.verts, lo, hi, S))
 
 
 def convert_to_explicit_worker(opt, i, level_vox_i, isoval, meshes, pointclouds=None):
@@ -493,7 +482,7 @@ def convert_to_explicit_worker(opt, i, level_vox_i, isoval, meshes, pointclouds=
     assert level_vox_i.shape[0] == level_vox_i.shape[1] == level_vox_i.shape[2]
     if HAVE_MESHING:
         vertices, faces = mcubes.marching_cubes(level_vox_i, isovalue=isoval)
-        mesh = trimesh.Trimesh(vertices / S * (hi - lo) + lo, faces)
+        mesh = trimesh.Trimesh(written_position(vertices, lo, hi, S), faces)
         meshes[i] = mesh
         if pointclouds is not None:
             pointclouds[i] = mesh.sample(opt.eval.num_points) if len(mesh.triangles) != 0 else np.zeros([opt.eval.num_points, 3])
@@ -614,17 +603,16 @@ def normal_metrics(opt, var, sdf_network, points_object, idx1, idx2, k, icp=None
 
 
 def _pack_meshes(meshes, anchors):
-    """[(verts [V,3], faces [F,3] int32)] per image -> (verts [Vtot,3], faces [Ftot,3], v_count [B], f_count [B]) in the packed form of
-    ops.point_mesh_distance.  An image with an empty mesh is given ONE degenerate triangle, three times anchors[b] (anchors [B,3]: a
-    point per image)."""
+    """[(verts [V,3], faces [F,3] int32)] per image -> their ops.PackedMesh (host counts).  An image with an empty mesh is given ONE
+    degenerate triangle, three times anchors[b] (anchors [B,3]: a point per image)."""
     dev = anchors.device
     verts, faces, nv, nf = [], [], [], []
     for b, (v, f) in enumerate(meshes):
         if f.shape[0] == 0 or v.shape[0] == 0:
             v, f = anchors[b:b + 1].float().expand(3, 3), torch.tensor([[0, 1, 2]], dtype=torch.int32, device=dev)
         verts.append(v.float()); faces.append(f.to(torch.int32)); nv.append(v.shape[0]); nf.append(f.shape[0])
-    i32 = dict(dtype=torch.int32, device=dev)
-    return torch.cat(verts).contiguous(), torch.cat(faces).contiguous(), torch.tensor(nv, **i32), torch.tensor(nf, **i32)
+    return ops.PackedMesh(torch.cat(verts).contiguous(), torch.cat(faces).contiguous(), torch.tensor(nv, dtype=torch.int64),
+                          torch.tensor(nf, dtype=torch.int64))
 
 
 @torch.no_grad()
@@ -744,6 +732,14 @@ def voxel_centres(bits, origin, pitch):
     return ((index + 0.5) * pitch.float() + origin.float()).cpu()
 
 
+def _mesh_packed(var):
+    """ops.isosurface_mesh(var.level_vox), built once and kept in var.mesh_packed.  var turns a tuple into a plain list, so the packed
+    meshes it keeps (this one and var.mesh_dual_packed) are lists of the four fields and are read back as ops.PackedMesh(*list)."""
+    if "mesh_packed" not in var:
+        var.mesh_packed = list(ops.isosurface_mesh(var.level_vox))
+    return ops.PackedMesh(*var.mesh_packed)
+
+
 @torch.no_grad()
 def mesh_stats(opt, var, sdf_network=None):
     """`--eval.mesh_stats`: is the mesh that is written a valid surface?  ops.mesh_topology (csrc/mesh_topology.hip) on the mesh of
@@ -752,7 +748,7 @@ def mesh_stats(opt, var, sdf_network=None):
     var.mesh_stats: ops.MeshTopology as a dict (var keeps dicts with attribute access; a tuple would become a plain list) -- per image
     vertices, faces, edges, boundary / non-manifold / inconsistent edges, non-manifold vertices, degenerate faces, unreferenced
     vertices, components, largest_component_faces, euler, genus, the flags watertight, oriented, manifold, area, volume -- and
-    face_component [F].  The packed mesh stays in var.mesh_packed = [verts (grid-index units), faces, v_count, f_count] and is taken
+    face_component [F].  The packed mesh stays in var.mesh_packed (ops.PackedMesh's four fields, verts in grid-index units) and is taken
     from there when it is already present.  With `--eval.dual_mesh`: the same for the dual-contouring mesh in var.mesh_stats_dual,
     from var.mesh_dual_packed when --eval.mesh_dist left it there, else built here with sdf_network (var.mesh_dual then serves the
     dump); without a network and without that mesh the dual statistics are left out.  Nothing is repaired, nothing enters a loss."""
@@ -760,14 +756,10 @@ def mesh_stats(opt, var, sdf_network=None):
     S = var.level_vox.shape[1]
     B = var.level_vox.shape[0]
 
-    def measure(packed):
-        verts, faces, v_count, f_count = packed
-        stats = ops.mesh_topology((lo + verts * ((hi - lo) / (S - 1))).contiguous(), faces, v_count, f_count)
-        return stats._asdict()
+    def measure(mesh):
+        return ops.mesh_topology(*mesh._replace(verts=sampled_position(mesh.verts, lo, hi, S).contiguous()))._asdict()
 
-    if "mesh_packed" not in var:
-        var.mesh_packed = list(ops.isosurface_mesh(var.level_vox))
-    var.mesh_stats = measure(var.mesh_packed)
+    var.mesh_stats = measure(_mesh_packed(var))
     reg = options.dual_mesh_reg(opt)
     if reg is None:
         return
@@ -776,11 +768,9 @@ def mesh_stats(opt, var, sdf_network=None):
         if "mesh_dual" not in var:
             var.mesh_dual = dual
         if "mesh_dual_packed" not in var:       # no crossing vertex in the whole batch
-            dev = var.level_vox.device
-            var.mesh_dual_packed = [torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.int32, device=dev),
-                                    torch.zeros(B, dtype=torch.int64), torch.zeros(B, dtype=torch.int64)]
+            var.mesh_dual_packed = list(ops.PackedMesh.empty(B, var.level_vox.device))
     if "mesh_dual_packed" in var:
-        var.mesh_stats_dual = measure(var.mesh_dual_packed)
+        var.mesh_stats_dual = measure(ops.PackedMesh(*var.mesh_dual_packed))
 
 
 @torch.no_grad()
@@ -803,33 +793,24 @@ def meshes_simplified(opt, var):
     if G > ops.MESH_SIMPLIFY_MAX_CELLS:
         raise ValueError("eval.simplify = %d gives %d cells per axis at a level grid of %d points; at most %d (choose eval.simplify >= %d)"
                          % (k, G, S, ops.MESH_SIMPLIFY_MAX_CELLS, -(-(S - 1) // ops.MESH_SIMPLIFY_MAX_CELLS)))
-    if "mesh_packed" not in var:
-        var.mesh_packed = list(ops.isosurface_mesh(var.level_vox))
-    verts, faces, v_count, f_count = var.mesh_packed
-    res = ops.mesh_cluster_simplify(verts, faces, v_count, f_count, (0.0, 0.0, 0.0), float(k), G, reg)
-    to_object = lambda v: (lo + v * ((hi - lo) / (S - 1))).contiguous()
-    v_in, v_out, f_out = v_count.tolist(), res.v_count.tolist(), res.f_count.tolist()
+    mesh = _mesh_packed(var)
+    res = ops.mesh_cluster_simplify(*mesh, (0.0, 0.0, 0.0), float(k), G, reg)
+    to_object = lambda v: sampled_position(v, lo, hi, S).contiguous()
+    v_in, f_out = mesh.v_count.tolist(), res.f_count.tolist()
     dist_mean = torch.full((B,), float("nan"), device=dev)
     dist_max = torch.full((B,), float("nan"), device=dev)
-    N = max(v_in, default=0)
-    if N > 0 and res.faces.shape[0] > 0:
-        start = (torch.cumsum(v_count, 0) - v_count).to(dev).clamp_max(verts.shape[0] - 1)
-        j = torch.arange(N, device=dev)
-        real = j[None] < v_count.to(dev)[:, None]                       # padding rows repeat the image's first vertex
-        rows = torch.where(real, start[:, None] + j[None], start[:, None])
-        i32 = dict(dtype=torch.int32, device=dev)
-        dist = ops.point_mesh_distance(to_object(verts)[rows].contiguous(), to_object(res.verts), res.faces.contiguous(),
-                                       torch.tensor(v_out, **i32), torch.tensor(f_out, **i32), search="grid").dist2.sqrt()
+    if max(v_in, default=0) > 0 and res.faces.shape[0] > 0:
+        _, rows = mesh.padded_rows()                                    # padding rows repeat the image's first vertex
+        dist = ops.point_mesh_distance(to_object(mesh.verts)[rows].contiguous(), to_object(res.verts), res.faces.contiguous(),
+                                       res.v_count, res.f_count, search="grid").dist2.sqrt()
         for b in range(B):
             if v_in[b] > 0 and f_out[b] > 0:
                 dist_mean[b], dist_max[b] = dist[b, :v_in[b]].mean(), dist[b, :v_in[b]].max()
-    var.mesh_simplified = dict(res._asdict(), cell=k, vertices_in=v_count.clone(), faces_in=f_count.clone(), dist_mean=dist_mean,
+    var.mesh_simplified = dict(res._asdict(), cell=k, vertices_in=mesh.v_count.clone(), faces_in=mesh.f_count.clone(), dist_mean=dist_mean,
                                dist_max=dist_max)
     if options.mesh_stats_settings(opt):
-        var.mesh_stats_simplified = ops.mesh_topology(to_object(res.verts), res.faces, res.v_count, res.f_count)._asdict()
-    world = res.verts / S * (hi - lo) + lo
-    v_end, f_end = torch.cumsum(res.v_count, 0).tolist(), torch.cumsum(res.f_count, 0).tolist()
-    var.mesh_simplified_world = [(world[e - n:e], res.faces[fe - fn:fe]) for e, n, fe, fn in zip(v_end, v_out, f_end, f_out)]
+        var.mesh_stats_simplified = ops.mesh_topology(*res.packed._replace(verts=to_object(res.verts)))._asdict()
+    var.mesh_simplified_world = res.packed.split(written_position(res.verts, lo, hi, S))
     return var.mesh_simplified_world
 
 
