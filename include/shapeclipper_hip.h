@@ -1525,6 +1525,22 @@ int sc_grid_cus(void);
  * of a shape outside a stream capture (stream-ordered copy on the launch stream).  This frees them all (rebuilt on demand); call
  * with no convolution in flight.                                                                                               */
 int sc_conv3x3_release_tables(void);
+/* The work partition a 3x3 convolution launch follows (conv_plan / conv_span_cut in csrc/conv3x3.hip, which the launches themselves
+ * read): host only, launches nothing.  family 0: sc_conv3x3_forward, 1: sc_conv3x3_forward_split, 2: sc_conv3x3s2_forward,
+ * 3: sc_conv3x3s2_backward_data; hw, batch, cin, cout as that entry point takes them (family 2 / 3: hw = side of the forward INPUT
+ * map, cin / cout of the forward convolution).  cus: compute units of the persistent grid, cus <= 0 asks sc_grid_cus() (the only
+ * device call); equal_spans != 0: the cut a launch uses when it has no span table (first launch of a shape under a stream capture).
+ * The rule: a tile is CT output channels x PT consecutive flat output pixels (x 4 parity phases, family 3), its reduction nk K-steps
+ * of 8 channels (family 1: rounded up to even).  G = workgroups.  Workgroup g computes the tiles r G + perm(g), r < rounds = tiles / G,
+ * whole, with perm(g) = (x < G % 8 ? x (G / 8 + 1) : (G % 8) (G / 8 + 1) + (x - G % 8) (G / 8)) + g / 8, x = g % 8 (one contiguous
+ * range of a round per XCD).  The K-steps of the other tail_tiles = tiles % G tiles, in tile-major order, are cut into G spans
+ * [spans[g], spans[g + 1]) of at most nk steps -- greedy at the smallest bound on 2 steps + ov2 tiles touched that G spans cover, or
+ * equal spans of per_wg = ceil(tail_tiles nk / G) -- and the fix-up launch adds the partial tiles of a shared tile in K order; a tail
+ * tile that one span covers exactly is stored by its workgroup and skipped by the fix-up.
+ * plan[10] (host memory) = { tiles, nk, rounds, tail_tiles, per_wg, PT, CT, ov2, G, 1 if the spans are the table's else 0 };
+ * spans[G + 1] (host memory, may be NULL; size it with a first call) = the span starts, spans[G] = tail_tiles nk.
+ * Refuses what the launch refuses (hipErrorInvalidValue; -1 for a map side the family does not have), and a NULL plan.          */
+int sc_conv3x3_plan(int family, int hw, int batch, int cin, int cout, int cus, int equal_spans, int* plan, int* spans);
 
 #ifdef __cplusplus
 }

@@ -57,7 +57,7 @@ _lib: Optional[ctypes.CDLL] = None
 # Optional per-entry-point GPU timing (bench.py): when TIMING is a dict every C-ABI call is bracketed by
 # two events on torch's current stream (the stream the kernels are enqueued on).
 TIMING = None
-TIMING_SKIP = ("sc_sdf_stream_pack", "sc_sdf_stream_pack_bytes", "sc_rgb_composite_backward_fused_parts", "sc_rgb_composite_backward_fused_partial_floats", "sc_latent_bias_forward", "sc_latent_bias_backward", "sc_set_reserved_cus", "sc_grid_cus", "sc_chamfer3d_backward_ordered_chunk","sc_conv3x3_release_tables", "sc_linear_bn_supported", "sc_linear_bn_forward", "sc_linear_bn_backward", "sc_linear_backward_data", "sc_bn_splits", "sc_isosurface_blocks_per_image", "sc_marching_cubes_mesh_vertex_blocks_per_image", "sc_bn_act_forward", "sc_bn_act_backward", "sc_bn_relu_pool_forward", "sc_bn_relu_pool_backward", "sc_gemm_plan",
+TIMING_SKIP = ("sc_sdf_stream_pack", "sc_sdf_stream_pack_bytes", "sc_rgb_composite_backward_fused_parts", "sc_rgb_composite_backward_fused_partial_floats", "sc_latent_bias_forward", "sc_latent_bias_backward", "sc_set_reserved_cus", "sc_grid_cus", "sc_chamfer3d_backward_ordered_chunk","sc_conv3x3_release_tables", "sc_conv3x3_plan","sc_linear_bn_supported", "sc_linear_bn_forward", "sc_linear_bn_backward", "sc_linear_backward_data", "sc_bn_splits", "sc_isosurface_blocks_per_image", "sc_marching_cubes_mesh_vertex_blocks_per_image", "sc_bn_act_forward", "sc_bn_act_backward", "sc_bn_relu_pool_forward", "sc_bn_relu_pool_backward", "sc_gemm_plan",
                # the trunks' convolutions: ~250 calls per step -- two events each cost the step ~1 ms (rocprofv3 covers them: profiles/)
                "sc_conv3x3_forward", "sc_conv3x3_forward_split", "sc_conv3x3_forward_add", "sc_conv3x3_wgrad", "sc_conv3x3_wgrad_split", "sc_conv3x3_pack", "sc_conv3x3_pack_multi", "sc_conv3x3_pack_multi_units",
                "sc_conv_stem_forward", "sc_conv_stem_wgrad", "sc_conv1x1s2_forward", "sc_conv1x1s2_backward_data", "sc_conv1x1s2_wgrad",

@@ -806,21 +806,11 @@ struct SpanTable {
 static std::mutex span_mu;
 static std::map<std::tuple<int, int, int, int, int>, SpanTable> span_cache;
 
-static const int* conv_spans(int tail_tiles, int nk, int G, int ov2, hipStream_t st) {
-    std::map<std::tuple<int, int, int, int, int>, SpanTable>& cache = span_cache;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lock(span_mu);
-    const auto key = std::make_tuple(dev, tail_tiles, nk, G, ov2);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second.dev;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
-        (void)hipGetLastError();
-        return nullptr;                                               // not cached: built by the first launch outside a capture
-    }
+// The cut itself, a pure function of (tail tiles, K-steps, grid, ov2): G + 1 span starts, U[G] = tail_tiles * nk.  Host arithmetic only
+// (sc_conv3x3_plan reports it without a device).
+static std::vector<int> conv_span_cut(int tail_tiles, int nk, int G, int ov2) {
     const int total = tail_tiles * nk;
-    std::vector<int> U(G + 1), best;
+    std::vector<int> U(G + 1);
     auto build = [&](int bound) {
         int pos = 0;
         for (int g = 0; g < G; ++g) {
@@ -843,8 +833,25 @@ static const int* conv_spans(int tail_tiles, int nk, int G, int ov2, hipStream_t
         if (build(mid)) hi = mid; else lo = mid + 1;
     }
     (void)build(hi);
+    return U;
+}
+
+// The device copy of the cut, cached per (device, tail tiles, K-steps, grid, ov2); null under a stream capture of an unseen key
+static const int* conv_spans(int tail_tiles, int nk, int G, int ov2, hipStream_t st) {
+    std::map<std::tuple<int, int, int, int, int>, SpanTable>& cache = span_cache;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(span_mu);
+    const auto key = std::make_tuple(dev, tail_tiles, nk, G, ov2);
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second.dev;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return nullptr;                                               // not cached: built by the first launch outside a capture
+    }
     SpanTable& t = cache[key];
-    t.host = U;                                                       // the source of the asynchronous copy outlives it
+    t.host = conv_span_cut(tail_tiles, nk, G, ov2);                   // the source of the asynchronous copy outlives it
     if (hipMalloc(&t.dev, (size_t)(G + 1) * sizeof(int)) != hipSuccess ||
         hipMemcpyAsync(t.dev, t.host.data(), (size_t)(G + 1) * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
         // the table is cached and handed to launches on ANY stream (the two trunks run on two streams with equal shapes): the one-time
@@ -857,23 +864,60 @@ static const int* conv_spans(int tail_tiles, int nk, int G, int ov2, hipStream_t
     return t.dev;
 }
 
+// The work partition of one launch on a grid of G workgroups: what launch_conv launches from and sc_conv3x3_plan reports.
+struct ConvPlan {
+    int tiles, nk, G, ov2;
+    ConvSplit sp;
+    bool table;          // the shared tiles are cut by the span table (conv_span_cut); false: equal spans of per_wg units, or no shared tile
+};
+template <class C>
+static ConvPlan conv_plan(int batch, int cin, int cout, int G) {
+    ConvPlan p;
+    p.tiles = ((batch * C::HWO + C::PT - 1) / C::PT) * ((cout + C::CT - 1) / C::CT) * (C::BD2 ? 4 : 1);
+    p.nk = conv_nk<C>(cin);
+    p.G = G;
+    // overhead of a touched tile in half K-steps: a K-step of the 512-pixel tiles takes ~5.3 us, of the 256-pixel tiles ~3.2
+    p.ov2 = C::PT >= 512 ? 2 : 3;
+    p.sp = conv_split(p.tiles, p.nk, G);
+    p.table = SC_CONV_SPANS && p.sp.tail_tiles > 0 && p.sp.per_wg <= p.nk;
+    return p;
+}
+
 template <class C>
 static int launch_conv(const float* x, const float* wpack, float* out, float* workspace, int batch, int cin, int cout, hipStream_t st,
                        const float* addend = nullptr) {
     if (cin % C::CB || batch <= 0) return (int)hipErrorInvalidValue;
-    const int tiles = ((batch * C::HWO + C::PT - 1) / C::PT) * ((cout + C::CT - 1) / C::CT) * (C::BD2 ? 4 : 1), nk = conv_nk<C>(cin);
-    const int G = conv_grid() * C::WGS_PER_CU;
+    const ConvPlan p = conv_plan<C>(batch, cin, cout, conv_grid() * C::WGS_PER_CU);
     // SPLIT instances read x through a buffer resource whose byte range is a 31-bit count: a larger input must be refused, not silently
     // read as zeros past the clamp; 2 GiB of fp32 is 2,674 images of 64 x 56 x 56 -- far outside any batch of this path
     if (C::SPLIT && (long long)batch * cin * C::HW * 4 > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     (void)hipFuncSetAttribute((const void*)conv3x3_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    const ConvSplit sp = conv_split(tiles, nk, G);
-    // overhead of a touched tile in half K-steps: a K-step of the 512-pixel tiles takes ~5.3 us, of the 256-pixel tiles ~3.2
-    const int* spans = (SC_CONV_SPANS && sp.tail_tiles > 0 && sp.per_wg <= nk) ? conv_spans(sp.tail_tiles, nk, G, C::PT >= 512 ? 2 : 3, st) : nullptr;
-    hipLaunchKernelGGL((conv3x3_kernel<C>), dim3(G), dim3(C::NT), C::LDS_BYTES, st, x, wpack, out, workspace, batch, cin, cout, spans, addend);
-    if (sp.tail_tiles > 0)
-        hipLaunchKernelGGL((conv3x3_fixup_kernel<C>), dim3(sp.tail_tiles, 4), dim3(C::NT), 0, st, workspace, out, batch, cin, cout, G, spans, addend);
+    const int* spans = p.table ? conv_spans(p.sp.tail_tiles, p.nk, p.G, p.ov2, st) : nullptr;
+    hipLaunchKernelGGL((conv3x3_kernel<C>), dim3(p.G), dim3(C::NT), C::LDS_BYTES, st, x, wpack, out, workspace, batch, cin, cout, spans, addend);
+    if (p.sp.tail_tiles > 0)
+        hipLaunchKernelGGL((conv3x3_fixup_kernel<C>), dim3(p.sp.tail_tiles, 4), dim3(C::NT), 0, st, workspace, out, batch, cin, cout, p.G, spans, addend);
     return (int)hipGetLastError();
+}
+
+// sc_conv3x3_plan for one instance: `cus` compute units (<= 0: the device's persistent grid), equal != 0: the equal-span fallback
+template <class C>
+static int report_plan(int batch, int cin, int cout, int cus, int equal, int* plan, int* spans) {
+    if (cin <= 0 || cout <= 0 || cin % C::CB || batch <= 0 || !plan) return (int)hipErrorInvalidValue;
+    if (C::SPLIT && (long long)batch * cin * C::HW * 4 > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    const ConvPlan p = conv_plan<C>(batch, cin, cout, (cus > 0 ? cus : conv_grid()) * C::WGS_PER_CU);
+    const bool table = p.table && !equal;
+    const int v[10] = {p.tiles, p.nk, p.sp.rounds, p.sp.tail_tiles, p.sp.per_wg, C::PT, C::CT, p.ov2, p.G, table ? 1 : 0};
+    for (int i = 0; i < 10; ++i) plan[i] = v[i];
+    if (spans) {
+        if (table) {
+            const std::vector<int> U = conv_span_cut(p.sp.tail_tiles, p.nk, p.G, p.ov2);
+            for (int g = 0; g <= p.G; ++g) spans[g] = U[g];
+        } else {                                                          // conv_span_at without a table
+            const long long total = (long long)p.sp.tail_tiles * p.nk;
+            for (int g = 0; g <= p.G; ++g) spans[g] = (int)((long long)g * p.sp.per_wg < total ? (long long)g * p.sp.per_wg : total);
+        }
+    }
+    return 0;
 }
 
 }  // namespace sc
@@ -1068,6 +1112,30 @@ extern "C" int sc_conv3x3_forward_add(const float* x, const float* w_pack, const
 #define CALL(C) sc::launch_conv<C>(x, w_pack, out, workspace, batch, cin, cout, (hipStream_t)stream, addend)
     SC_CONV_DISPATCH(hw, CALL)
 #undef CALL
+}
+
+// The work partition the launches above follow (launch_conv and this report both read conv_plan / conv_span_cut); host only.
+// cin / cout: the FORWARD convolution's for every family (family 3 reduces over cout, as sc_conv3x3s2_backward_data does).
+extern "C" int sc_conv3x3_plan(int family, int hw, int batch, int cin, int cout, int cus, int equal_spans, int* plan, int* spans) {
+    switch (family) {
+        case 0: {
+#define CALL(C) sc::report_plan<C>(batch, cin, cout, cus, equal_spans, plan, spans)
+            SC_CONV_DISPATCH(hw, CALL)
+        }
+        case 1: {
+            SC_CONV_DISPATCH_SPLIT(hw, CALL)
+        }
+        case 2: {
+            SC_CONV_DISPATCH_S2(hw, CALL)
+#undef CALL
+        }
+        case 3: {
+#define CALL(C) sc::report_plan<C>(batch, cout, cin, cus, equal_spans, plan, spans)
+            SC_CONV_DISPATCH_BD(hw, CALL)
+#undef CALL
+        }
+        default: return -1;
+    }
 }
 
 extern "C" int sc_conv3x3_forward(const float* x, const float* w_pack, float* out, float* workspace, int batch, int cin, int cout, int hw,
