@@ -1267,6 +1267,9 @@ int sc_basic_block_backward(const sc_block_args* args, void* stream);
  * rows with their own statistics (save_mean / save_rstd [groups][Cout]); running statistics (may be NULL when training) are updated
  * once per group in order, *n_tracked += groups.  Limits: N <= 128, groups <= 4, Cin % 64 == 0, Cout % 16 == 0
  * (sc_linear_bn_supported says whether a shape is taken).  Fixed summation orders: bit-reproducible.
+ * The reduction length of each of the three products is split over four waves in steps of 16, so it must be a multiple of 64: Cin in the
+ * forward pass (above); Cnext in sc_linear_bn_backward when g_out is NULL; Cout in sc_linear_backward_data (whose Cin, the columns of
+ * dx, need only Cin % 16 == 0, and N <= 128).  Anything else is refused with hipErrorInvalidValue before a launch.
  *   forward:   y = x w^T;  out = [relu]( gamma (y - mean) rstd + beta [+ res] )
  *   backward:  g = (g_out, or gy_next [N][Cnext] x w_next [Cnext][Cout] when g_out is NULL) [+ g_add]; ReLU mask from `out`;
  *              g_res (may be NULL) receives the masked gradient (= gradient of `res`); BatchNorm backward -> gy [N][Cout];

@@ -382,7 +382,8 @@ extern "C" int sc_linear_bn_backward(const float* g_out, const float* gy_next, c
                                      const float* y, const float* save_mean, const float* save_rstd, const float* gamma, const float* x, float* gy,
                                      float* g_res, float* dw, float* dgamma, float* dbeta, int N, int Cin, int Cout, int groups, int training, int relu,
                                      void* stream) {
-    if (!sc::bl::ok(N, Cin, Cout, groups) || (!g_out && (!gy_next || !w_next || Cnext <= 0 || Cnext % 16))) return (int)hipErrorInvalidValue;
+    // Cnext is the K of gemm_rows when the gradient is formed here: the four waves take a quarter each, in steps of 16
+    if (!sc::bl::ok(N, Cin, Cout, groups) || (!g_out && (!gy_next || !w_next || Cnext <= 0 || Cnext % 64))) return (int)hipErrorInvalidValue;
     sc::bl::BwdArgs a{g_out, gy_next, w_next, g_add, Cnext, out, y, save_mean, save_rstd, gamma, x, gy, g_res, dw, dgamma, dbeta, N, Cin, Cout, groups,
                       training, relu};
     hipLaunchKernelGGL(sc::bl::linear_bn_bwd_kernel, dim3(Cout / 16), dim3(64 * sc::bl::WAVES), 0, (hipStream_t)stream, a);
@@ -390,7 +391,8 @@ extern "C" int sc_linear_bn_backward(const float* g_out, const float* gy_next, c
 }
 
 extern "C" int sc_linear_backward_data(const float* gy, const float* w, const float* g_add, float* dx, int N, int Cin, int Cout, void* stream) {
-    if (N <= 0 || N > 16 * sc::bl::MAXT || Cin % 16 || Cout % 16 || Cin <= 0 || Cout <= 0) return (int)hipErrorInvalidValue;
+    // Cout is the K of gemm_rows (K % 64 == 0); Cin only counts workgroups of 16 columns
+    if (N <= 0 || N > 16 * sc::bl::MAXT || Cin % 16 || Cout % 64 || Cin <= 0 || Cout <= 0) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(sc::bl::linear_bwd_data_kernel, dim3(Cin / 16), dim3(64 * sc::bl::WAVES), 0, (hipStream_t)stream, gy, w, g_add, dx, N, Cin, Cout);
     return (int)hipGetLastError();
 }

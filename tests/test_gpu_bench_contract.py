@@ -141,8 +141,10 @@ def torch_cus():
 
 
 def test_reserved_cus_same_results():
-    """`--hip.reserve_cus`: the stream-K convolution, its weight gradient and the stride-2 / stem gradients on a (CUs - 32) grid give the
-    values of the full grid up to the summation order of the shared tiles (fp32 rounding), and the setting is undone by 0."""
+    """`--hip.reserve_cus`: the stream-K 3x3 convolution (split arithmetic) and its weight gradient on a (CUs - 32) grid give the values of
+    the full grid up to the summation order of the shared tiles (fp32 rounding), and the setting is undone by 0.  The 3x3 kernels only:
+    the stem and the 1x1 / stride 2 shortcut run on reduced grids in tests/test_gpu_gemm_partition_exact.py, the stride-2 3x3 kernels in
+    tests/test_gpu_conv_plan.py."""
     import torch
     from shapeclipper_amd import ops
     torch.manual_seed(0)

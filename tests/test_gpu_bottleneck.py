@@ -38,7 +38,9 @@ def _pair(C, seed):
 
 
 @pytest.mark.parametrize("N,C,groups,training", [(32, 512, 1, True), (96, 512, 3, True), (64, 512, 2, True), (48, 128, 3, True), (20, 64, 1, True),
-                                                  (96, 512, 3, False), (128, 256, 4, True)])
+                                                  (96, 512, 3, False), (128, 256, 4, True),
+                                                  # group boundaries inside a lane's four rows (10, 2 and 25 rows per group), ragged row tiles
+                                                  (20, 64, 2, True), (6, 64, 3, True), (100, 128, 4, True)])
 def test_block_matches_the_stock_modules(N, C, groups, training):
     ref, mine = _pair(C, seed=N + C)
     ref.train(training); mine.train(training)
