@@ -1069,6 +1069,60 @@ int sc_mesh_cluster_simplify(const float* verts, const int32_t* faces, const int
                              float* verts_out, int32_t* faces_out, int64_t* counts, int32_t* vertex_cluster, int32_t* face_source,
                              int32_t* bad_vertex, int32_t* bad_index, void* stream);
 
+/* ---- post-processing: Taubin lambda|mu smoothing by the umbrella operator (csrc/mesh_smooth.hip) --------------------------------------
+ * What ops.mesh_smooth runs and {idx}_mesh_smooth.ply holds (`--mesh.smooth`).  A batch of packed meshes in the form of sc_mesh_topology
+ * above (verts, faces with image-local indices, v_off / f_off); everything below is per image.  The faces are not changed, so neither is
+ * the topology.  tests/mesh_smooth_ref.py restates every rule in numpy.  All arithmetic is float64, every operation rounded once (the
+ * file is built without contraction; sqrt and the divisions are the correctly rounded ones).
+ *
+ * Faces.  A face with an index outside [0, v_off[b+1] - v_off[b]) sets *bad_index to 1, is never dereferenced and takes part in nothing
+ *   (the caller raises; the other outputs of the call are then unspecified).  Every other face, degenerate or not, takes part with its
+ *   DISTINCT undirected edges: {a, b} of consecutive corners (i0,i1), (i1,i2), (i2,i0) with a != b, each once per face -- (a, a, b) has
+ *   the one edge {a, b}, (a, a, a) none.
+ * Edges.  count = the faces that have the edge (two faces with the same three indices are two faces).
+ * Neighbours.  N(i) = the distinct vertices j != i that share an edge with i, whatever its count;  |N(i)| is the DEGREE of i.
+ * Vertices.  A vertex with a component that is not finite sets *bad_vertex to 1 (the caller raises).  i is FIXED_BOUNDARY if it lies on
+ *   an edge of count 1 (the open rim that the grid boundary cuts: it must not creep inward), ISOLATED if N(i) is empty (no face, or only
+ *   faces like (i, i, i), names it), FREE otherwise; an edge of count >= 3 is an ordinary edge.  Only free vertices move.
+ * State.  x_i = the vertex widened exactly to float64.  A HALF-STEP with factor f maps every free i, per component, to
+ *       s = +0.0;  s = s + x_j for j in N(i) in ASCENDING j;   m = s / (double)|N(i)|;   d = m - x_i;   t = f d;   x_i' = x_i + t
+ *   reading only the state at its start (Jacobi); the others keep their bits.  One ITERATION is a half-step with lam, then, if mu != 0, a
+ *   half-step with mu (Taubin: 0 < lam <= 1, -1 <= mu <= 0; mu = 0 is plain Laplacian smoothing).  `iters` iterations run (0 <= iters <=
+ *   SC_MESH_SMOOTH_MAX_ITERS = 1000; 0 returns the input bits).
+ * verts_out [n_verts][3] fp32 = the final state rounded to fp32 once (to nearest, ties to even); the input bits for a vertex that is not
+ *   free.
+ * counts [SC_MESH_SMOOTH_FIELDS][n_images] int64, row by row: 0 free, 1 fixed_boundary, 2 isolated (the three sum to the image's
+ *   vertices), 3 degree_max (over all its vertices; 0 without one).
+ * measures [SC_MESH_SMOOTH_MEASURES][n_images] float64, row by row, with |v| = sqrt((v_x v_x + v_y v_y) + v_z v_z) and m_i as above:
+ *    0 rough_before  the mean over the free vertices of |m_i - x_i| on the start state     1 rough_after  the same on the final state
+ *    2 disp_mean     the mean over the free vertices of |x_i(final) - x_i(start)|           3 disp_max     the largest of them
+ *   (the final state is the float64 one, before the rounding to fp32).  Order of the sums: an image's vertices are cut into chunks of
+ *   SC_MESH_SMOOTH_CHUNK = 256 consecutive vertices from its first vertex; a vertex that is not free has the terms +0.0; a chunk's
+ *   partial is 0.0 plus its terms in ascending vertex number, one addition at a time; the image's sum is 0.0 plus the chunk partials in
+ *   ascending chunk number; a mean is that sum / (double)free.  disp_max folds the same way with  acc = term > acc ? term : acc  from
+ *   0.0.  All four are 0.0 for an image without a free vertex.  Partials are plain stores read by a later launch: no float atomics.
+ * Edge table.  Open addressing in scratch, table_slots slots: a power of two, > 3 n_faces (so every linear probe meets an empty or
+ *   matching slot) and <= 2^30.  The key (global lo << 32) | global hi over image-offset vertex numbers is claimed by a 64-bit
+ *   compare-and-swap on the empty key; the thread that claims a slot adds one to the degree of both ends, every face adds one to the
+ *   slot's count (integer adds).  The rows of a CSR adjacency (offsets: an integer block scan of the degrees) are filled at an integer
+ *   atomic cursor and then put into ascending order by rank, so the arrival order leaves no trace; there is no cap on the degree.
+ *   Only integer atomics decide anything: every output has the same bits from run to run, for any batch, stream, face order and
+ *   table_slots.
+ * 7 + (mu != 0 ? 2 : 1) iters launches on `stream`, one per half-step, two fewer when n_faces == 0; no wait on another workgroup, no
+ * host synchronisation.  scratch: sc_mesh_smooth_scratch_bytes(n_images, n_verts, n_faces, table_slots) bytes of device memory, 16-byte
+ * aligned, contents irrelevant on entry (the query gives 0 for sizes the entry point refuses).  n_images <= 0 returns 0 and launches
+ * nothing; hipErrorInvalidValue for n_images > 65535, n_faces > 2^26, n_verts > 2^30, a negative count, a table_slots that is not such a
+ * power of two, iters outside 0..1000, lam outside (0, 1], mu outside [-1, 0], a NULL pointer or a misaligned scratch (verts and
+ * verts_out may be NULL when n_verts == 0, faces when n_faces == 0).                                                                    */
+#define SC_MESH_SMOOTH_CHUNK 256
+#define SC_MESH_SMOOTH_FIELDS 4
+#define SC_MESH_SMOOTH_MEASURES 4
+#define SC_MESH_SMOOTH_MAX_ITERS 1000
+long long sc_mesh_smooth_scratch_bytes(int n_images, int n_verts, int n_faces, int table_slots);
+int sc_mesh_smooth(const float* verts, const int32_t* faces, const int64_t* v_off, const int64_t* f_off, int n_images, int n_verts,
+                   int n_faces, int table_slots, int iters, double lam, double mu, void* scratch, float* verts_out, int64_t* counts,
+                   double* measures, int32_t* bad_vertex, int32_t* bad_index, void* stream);
+
 /* ---- camera algebra of a render -------------------------------------------------------------------
  * sc_camera_rays_*: utils/camera.py:157-196 (get_center_and_ray on the rendered pixels only) + the normalisation of
  * model/renderer.py:69-76.  pose [n_images][3][4] = [R|t] world->camera, intr [n_images][3][3], ray_idx

@@ -707,6 +707,9 @@ class Runner:
         --eval.dual_mesh also {idx}_mesh_dual.ply (eval_3D.meshes_dual: the dual-contouring mesh of the same grid, positions and faces);
         with --eval.simplify also {idx}_mesh_simplified.ply (eval_3D.meshes_simplified: the mesh of {idx}_mesh.ply decimated by vertex
         clustering, positions and faces);
+        with --mesh.smooth also {idx}_mesh_smooth.ply (eval_3D.meshes_smoothed: the mesh of {idx}_mesh.ply after Taubin smoothing, positions
+        and the same faces) and {idx}_mesh_smooth.txt (one line: idx iters lambda mu vertices free fixed_boundary isolated degree_max
+        disp_mean disp_max rough_before rough_after area_before area_after volume_before volume_after, lengths in object units);
         with --eval.icp also {idx}_pointclouds_comp_icp.ply (the ICP-aligned prediction of eval_3D.icp_metrics red, ground truth green);
         with --eval.normals also {idx}_pointclouds_normals.ply (pointclouds_comp's vertices as x y z nx ny nz red green blue: the SDF's
         normals on the prediction, the estimated PCA normals on the ground truth); with --eval.emd also {idx}_pointclouds_emd.ply (the
@@ -739,6 +742,11 @@ class Runner:
             # (eval_metrics decimated the mesh already and left it in var)
             simple = var.mesh_simplified_world if "mesh_simplified_world" in var else eval_3D.meshes_simplified(opt, var)
             util_vis.dump_meshes(opt, var.idx, "mesh_simplified", simple, folder=folder)
+        if options.smooth_settings(opt) is not None:
+            # (eval_metrics smoothed the mesh already and left it in var)
+            smooth = var.mesh_smoothed_world if "mesh_smoothed_world" in var else eval_3D.meshes_smoothed(opt, var)
+            util_vis.dump_meshes(opt, var.idx, "mesh_smooth", smooth, folder=folder)
+            util_vis.dump_lines(opt, var.idx, "mesh_smooth", eval_3D.smoothed_lines(var), folder=folder)
         if options.texture_texels(opt) is not None:
             net = self.graph.module
             var.texture = eval_3D.mesh_texture(opt, net.sdf_network, net.rgb_network, var.proj_latent_sdf, var.proj_latent_rgb, var.level_vox)

@@ -2454,3 +2454,77 @@ def mesh_cluster_simplify(verts, faces, v_count, f_count, origin, pitch, cells, 
         raise ValueError("%s: a face index lies outside its image's vertex range [0, v_count[b])" % who)
     return SimplifiedMesh(verts_out[:int(sizes[0].sum())], faces_out[:int(sizes[1].sum())], sizes[0], sizes[1], vertex_cluster,
                           face_source[:int(sizes[1].sum())], counts[2], counts[3])
+
+
+# ---- post-processing: Taubin smoothing of indexed triangle meshes by the umbrella operator (csrc/mesh_smooth.hip) -----------------------
+MESH_SMOOTH_MAX_ITERS = 1000                # SC_MESH_SMOOTH_MAX_ITERS
+MESH_SMOOTH_MAX_VERTS = 1 << 30
+MESH_SMOOTH_MU = 1.0 / (0.1 - 1.0 / 0.5)    # Taubin's mu for the pass-band 0.1 at lam = 0.5: -0.5263157894736842
+MESH_SMOOTH_COUNTS = ("free", "fixed_boundary", "isolated", "degree_max")           # rows of sc_mesh_smooth's counts
+MESH_SMOOTH_MEASURES = ("disp_mean", "disp_max", "rough_before", "rough_after")     # SmoothedMesh's order; the rows are 2, 3, 0, 1
+
+
+class SmoothedMesh(collections.namedtuple("SmoothedMesh", ("verts", "faces", "v_count", "f_count") + MESH_SMOOTH_COUNTS + MESH_SMOOTH_MEASURES)):
+    __slots__ = ()
+    packed = property(lambda self: PackedMesh(*self[:4]), doc="the smoothed meshes alone, as a PackedMesh")
+
+
+def mesh_smooth(verts, faces, v_count, f_count, iters, lam=0.5, mu=MESH_SMOOTH_MU, table_slots=None):
+    """Smooths a PackedMesh (mesh_pack.py) of B images, passed as `*mesh` -- verts and faces on the device, v_count / f_count [B] int64 or
+    int32 (host or device) -- by Taubin's lambda|mu scheme on the umbrella operator: `iters` (0..1000) iterations, each a Jacobi half-step
+    x_i += lam (m_i - x_i) and, unless mu == 0 (plain Laplacian smoothing), a half-step with `mu` in [-1, 0]; m_i is the mean of the
+    vertices that share an edge with i.  Vertices on an edge that one face only uses (the open rim) and vertices without a neighbour keep
+    their bits; the faces are not changed.  The state is float64, every operation rounded once, the sums in ascending neighbour number;
+    the output is rounded to fp32 once.  include/shapeclipper_hip.h states every rule (sc_mesh_smooth); tests/mesh_smooth_ref.py restates
+    them in numpy.  The default mu is Taubin's for a pass-band of 0.1 at lam = 0.5.
+
+    -> SmoothedMesh(verts [V,3] fp32, faces, v_count, f_count as given -- `.packed` is these four as a PackedMesh --, free,
+    fixed_boundary, isolated, degree_max [B] int64 and disp_mean, disp_max (how far the free vertices moved), rough_before, rough_after
+    (their mean |m_i - x_i| on the start and on the final state) [B] float64, all on the device, the measures fixed-order sums in the
+    units of verts).  An image without faces returns its vertices unchanged.  Only integer atomics decide anything: the same bits from
+    run to run, for any batch, stream, face order and table_slots (the edge table's size as in mesh_topology).  Scratch comes from the
+    scratch cache ("mesh smooth").
+
+    ValueError for wrong dtypes, shapes or devices, counts that are negative or do not sum to the packed lengths, a bad iters, lam, mu or
+    table_slots -- all before any launch -- and, checked on the device and raised after the launches, for a vertex that is not finite and
+    for a face index outside its image's vertex range (never dereferenced).
+
+    Host synchronisation: one read of the two flags after the launches.  Runs on the current stream."""
+    who = "shapeclipper_amd: mesh_smooth"
+    B, V, F, _, offsets = check_packed(who, verts, faces, v_count, f_count, max_images=MESH_TOPOLOGY_MAX_IMAGES,
+                                       max_faces=MESH_TOPOLOGY_MAX_FACES)
+    dev = verts.device
+    if V > MESH_SMOOTH_MAX_VERTS:
+        raise ValueError("%s: verts: at most 2^30 vertices per call, got %d" % (who, V))
+    number = lambda x: isinstance(x, (int, float)) and not isinstance(x, bool) and x == x and abs(x) != float("inf")
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= MESH_SMOOTH_MAX_ITERS:
+        raise ValueError("%s: iters must be an integer in 0..%d, got %r" % (who, MESH_SMOOTH_MAX_ITERS, iters))
+    if not number(lam) or not 0 < lam <= 1:
+        raise ValueError("%s: lam must be a finite number in (0, 1], got %r" % (who, lam))
+    if not number(mu) or not -1 <= mu <= 0:
+        raise ValueError("%s: mu must be a finite number in [-1, 0], got %r" % (who, mu))
+    if table_slots is None:
+        table_slots = mesh_topology_slots(F)
+    if (isinstance(table_slots, bool) or not isinstance(table_slots, int) or table_slots < 1 or table_slots & (table_slots - 1)
+            or table_slots <= 3 * F or table_slots > MESH_TOPOLOGY_MAX_SLOTS):
+        raise ValueError("%s: table_slots must be a power of two greater than 3 F = %d (and at most 2^30), got %r" % (who, 3 * F, table_slots))
+    verts_out = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    counts = torch.zeros(len(MESH_SMOOTH_COUNTS), B, device=dev, dtype=torch.int64)
+    measures = torch.zeros(len(MESH_SMOOTH_MEASURES), B, device=dev, dtype=torch.float64)
+    if B > 0:
+        offsets = offsets.to(dev)
+        bad = torch.empty(2, device=dev, dtype=torch.int32)             # bad_vertex, bad_index
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            ws = _scratch("mesh smooth", dev, (lib.sc_mesh_smooth_scratch_bytes(B, V, F, table_slots) + 3) // 4)
+            code = lib.sc_mesh_smooth(_lib.ptr(verts.contiguous()) if V else None, _lib.ptr(faces.contiguous()) if F else None,
+                                      _lib.ptr(offsets[0]), _lib.ptr(offsets[1]), B, V, F, table_slots, iters, float(lam), float(mu),
+                                      _lib.ptr(ws), _lib.ptr(verts_out) if V else None, _lib.ptr(counts), _lib.ptr(measures),
+                                      _lib.ptr(bad[:1]), _lib.ptr(bad[1:]), _lib.stream())
+        _lib.check(code, "sc_mesh_smooth")
+        flags = bad.tolist()
+        if flags[0]:
+            raise ValueError("%s: a vertex is not finite" % who)
+        if flags[1]:
+            raise ValueError("%s: a face index lies outside its image's vertex range [0, v_count[b])" % who)
+    return SmoothedMesh(verts_out, faces, v_count, f_count, *counts.unbind(0), measures[2], measures[3], measures[0], measures[1])

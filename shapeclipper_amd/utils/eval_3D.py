@@ -29,6 +29,8 @@ Call surface of the reference's utils/eval_3D.py.
     (csrc/dual_contour.hip), which keeps corners and creases that marching cubes chamfers at the grid pitch.
   * meshes_simplified (`--eval.simplify=k`): the marching-cubes mesh decimated by vertex clustering in cells of k grid pitches with
     quadric placement (ops.mesh_cluster_simplify, csrc/mesh_simplify.hip), and what the smaller file costs in distance.
+  * meshes_smoothed (`--mesh.smooth=n`): the marching-cubes mesh after n Taubin lambda|mu iterations of the umbrella operator
+    (ops.mesh_smooth, csrc/mesh_smooth.hip): the same faces, the grid's staircase gone, the volume within about a per cent.
 """
 from __future__ import annotations
 
@@ -814,6 +816,46 @@ def meshes_simplified(opt, var):
     return var.mesh_simplified_world
 
 
+@torch.no_grad()
+def meshes_smoothed(opt, var):
+    """`--mesh.smooth=n`: the mesh that is written, smoothed.  ops.mesh_smooth (csrc/mesh_smooth.hip) -- n Taubin iterations with
+    mesh.smooth_lambda and the mu of mesh.smooth_band -- on the packed mesh of ops.isosurface_mesh(var.level_vox) -- var.mesh_packed,
+    built here as mesh_stats does when it is absent -- in grid-index units, where every grid pitch is 1 on all three axes.
+    Sets var.mesh_smoothed, a dict (var keeps dicts with attribute access): the fields of ops.SmoothedMesh (verts in grid-index units),
+    iters, lam, mu, and area_before, area_after, volume_before, volume_after [B] float64 -- ops.mesh_topology's of the original and of
+    the smoothed vertices at the positions the level grid was sampled at, lo + v (hi - lo) / (S - 1), in object units (the "before" pair
+    is taken from var.mesh_stats when `--eval.mesh_stats` left it there); disp_* and rough_* are scaled to object units by (hi - lo) /
+    (S - 1) on the host.  Returns, and keeps in var.mesh_smoothed_world for the dump, the per-image list of (vertices, faces) with
+    meshes_device's v / S rescale, which overlays {idx}_mesh.ply.  The metrics keep sampling the unsmoothed surface; nothing enters a
+    loss."""
+    iters, lam, mu = options.smooth_settings(opt)
+    lo, hi = opt.eval.range
+    S = var.level_vox.shape[1]
+    mesh = _mesh_packed(var)
+    res = ops.mesh_smooth(*mesh, iters, lam, mu)
+    to_object = lambda v: sampled_position(v, lo, hi, S).contiguous()
+    after = ops.mesh_topology(*res.packed._replace(verts=to_object(res.verts)))
+    before = var.mesh_stats if "mesh_stats" in var else ops.mesh_topology(*mesh._replace(verts=to_object(mesh.verts)))._asdict()
+    pitch = (hi - lo) / (S - 1)
+    scaled = {k: getattr(res, k) * pitch for k in ops.MESH_SMOOTH_MEASURES}
+    var.mesh_smoothed = dict(res._asdict(), **scaled, iters=iters, lam=lam, mu=mu, area_before=before["area"], area_after=after.area,
+                             volume_before=before["volume"], volume_after=after.volume)
+    var.mesh_smoothed_world = res.packed.split(written_position(res.verts, lo, hi, S))
+    return var.mesh_smoothed_world
+
+
+def smoothed_lines(var):
+    """One line per sample for {idx}_mesh_smooth.txt: idx iters lambda mu vertices free fixed_boundary isolated degree_max disp_mean
+    disp_max rough_before rough_after area_before area_after volume_before volume_after (17 fields; one host read per field)."""
+    r = var.mesh_smoothed
+    ints = [torch.as_tensor(r[k]).cpu().tolist() for k in ("v_count",) + ops.MESH_SMOOTH_COUNTS]
+    reals = [torch.as_tensor(r[k]).cpu().tolist() for k in ops.MESH_SMOOTH_MEASURES + ("area_before", "area_after", "volume_before",
+                                                                                      "volume_after")]
+    head = "%d %.17g %.17g" % (r["iters"], r["lam"], r["mu"])
+    return ["%d %s %s %s" % (int(i), head, " ".join("%d" % col[b] for col in ints), " ".join("%.9g" % col[b] for col in reals))
+            for b, i in enumerate(var.idx.cpu().tolist())]
+
+
 _FLIP_PRED = [[1, 0, 0], [0, -1, 0], [0, 0, -1]]
 _FLIP_GT = [[-1, 0, 0], [0, 1, 0], [0, 0, 1]]
 
@@ -824,6 +866,7 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     icp, normals_k, emd, iou = (f(opt) for f in (options.icp_settings, options.normal_settings, options.emd_settings, options.iou_settings))
     mesh_dist = None if vis_only else options.mesh_dist_settings(opt)
     want_stats, simplify = options.mesh_stats_settings(opt), options.simplify_settings(opt)
+    smooth = options.smooth_settings(opt)
     points_3D = get_dense_3D_grid(opt, var)
     B = points_3D.shape[0]
     level_vox = compute_level_grid(opt, sdf_network, var.proj_latent_sdf, points_3D)
@@ -863,6 +906,8 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
             mesh_stats(opt, var, sdf_network)
         if simplify is not None:                # vis_{ep}/{idx}_mesh_simplified.ply
             meshes_simplified(opt, var)
+        if smooth is not None:                  # vis_{ep}/{idx}_mesh_smooth.ply and .txt
+            meshes_smoothed(opt, var)
         return
     dist_acc, dist_comp, idx1, idx2 = chamfer_distance(opt, X1=var.dpc_pred, X2=var.dpc.points)
     var.f_score = compute_fscore(dist_acc, dist_comp, opt.eval.f_thresholds)
@@ -885,4 +930,6 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
         mesh_stats(opt, var, sdf_network)
     if simplify is not None:                # likewise
         meshes_simplified(opt, var)
+    if smooth is not None:                  # post-processing of the written mesh: no metric reads it
+        meshes_smoothed(opt, var)
     return dist_acc.mean(), dist_comp.mean()

@@ -120,20 +120,20 @@ EVAL_TABLE = tuple(Setting(*row) for row in (
 EVAL = {row.key: row for row in EVAL_TABLE}
 
 
-def eval_setting(opt, key):
-    """opt.eval[key] checked against its row of EVAL_TABLE, the row's default where the option tree has no such key."""
-    row = EVAL[key]
-    v = (opt.get("eval", None) or {}).get(key, row.default)
+def _checked(group, row, v):
+    """v checked against a Setting row of the table of `group` ("eval", "mesh"): the value, as the row's kind; a ValueError that names
+    group.key otherwise."""
+    key = row.key
     if row.kind is bool:
         if not isinstance(v, bool):
-            raise ValueError("eval.%s must be a bool, got %r" % (key, v))
+            raise ValueError("%s.%s must be a bool, got %r" % (group, key, v))
         return v
     if v is None and row.flag == "absent":
         return None
     lo, hi = row.kind
     if isinstance(lo, int):
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
-            raise ValueError("eval.%s must be an integer in %d..%d, got %r" % (key, lo, hi, v))
+            raise ValueError("%s.%s must be an integer in %d..%d, got %r" % (group, key, lo, hi, v))
         return v
     if row.flag == "str" and isinstance(v, str):
         try:
@@ -141,8 +141,14 @@ def eval_setting(opt, key):
         except ValueError:
             pass
     if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo < v <= hi:
-        raise ValueError("eval.%s must be a float in (%g, %g], got %r" % (key, lo, hi, v))
+        raise ValueError("%s.%s must be a float in (%g, %g], got %r" % (group, key, lo, hi, v))
     return float(v)
+
+
+def eval_setting(opt, key):
+    """opt.eval[key] checked against its row of EVAL_TABLE, the row's default where the option tree has no such key."""
+    row = EVAL[key]
+    return _checked("eval", row, (opt.get("eval", None) or {}).get(key, row.default))
 
 
 def dual_mesh_reg(opt):
@@ -201,6 +207,35 @@ def simplify_settings(opt):
     """None unless `--eval.simplify=k` is given, else (k, reg), the arguments of eval_3D.meshes_simplified."""
     k, reg = eval_setting(opt, "simplify"), eval_setting(opt, "simplify_reg")
     return None if k is None else (k, reg)
+
+
+# The `mesh.*` settings: post-processing of the mesh that is written, one Setting row each as in EVAL_TABLE.  They are not eval.* settings:
+# nothing here is measured against the ground truth and no report file or gather belongs to them -- a post-processed mesh is another file
+# in the dump and a one-line sidecar beside it.  An absent key, or an absent `mesh` group, means the default, so a reference YAML loads
+# unchanged and nothing is written into the option tree.
+MESH_TABLE = tuple(Setting(*row) for row in (
+    ("smooth", None, (1, 100), "Taubin-smoothed mesh {idx}_mesh_smooth.ply / .txt: the iterations (ops.mesh_smooth)", "absent"),
+    ("smooth_lambda", 0.5, (0.0, 1.0), "... the positive step lambda", "str"),
+    ("smooth_band", 0.1, (0.0, 0.5), "... Taubin's pass-band k_PB: the negative step is mu = 1 / (smooth_band - 1 / smooth_lambda)", "str"),
+))
+MESH = {row.key: row for row in MESH_TABLE}
+
+
+def mesh_setting(opt, key):
+    """opt.mesh[key] checked against its row of MESH_TABLE, the row's default where the option tree has no such key or no `mesh` group."""
+    row = MESH[key]
+    return _checked("mesh", row, (opt.get("mesh", None) or {}).get(key, row.default))
+
+
+def smooth_settings(opt):
+    """None unless `--mesh.smooth=n` is given, else (n, lam, mu), the arguments of ops.mesh_smooth.  A pair with mu <= -1 is refused,
+    switch on or off: the negative step would amplify the highest frequency of the umbrella operator."""
+    iters, lam, band = (mesh_setting(opt, k) for k in ("smooth", "smooth_lambda", "smooth_band"))
+    mu = 1.0 / (band - 1.0 / lam)
+    if mu <= -1.0:
+        raise ValueError("mesh.smooth_lambda = %r and mesh.smooth_band = %r give mu = %.6g <= -1: choose mesh.smooth_lambda < "
+                         "1 / (1 + mesh.smooth_band) = %.6g" % (lam, band, mu, 1.0 / (1.0 + band)))
+    return None if iters is None else (iters, lam, mu)
 
 
 def parse_arguments(args):
@@ -293,7 +328,8 @@ def process_options(opt):
             if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
                 raise ValueError("hip.%s must be an integer in %d..%d, got %r" % (row.key, lo, hi, v))
     for check in (dual_mesh_reg, texture_texels, mesh_render, icp_settings, normal_settings, mesh_dist_settings, emd_settings, iou_settings,
-                  mesh_stats_settings, simplify_settings):      # every eval.* value is checked here, whether or not its switch is on
+                  mesh_stats_settings, simplify_settings,       # every eval.* value is checked here, whether or not its switch is on
+                  smooth_settings):                             # and every mesh.* value
         check(opt)
     torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
     for row in HIP_TABLE:

@@ -41,6 +41,13 @@ def dump_arrays(opt, idx, name, arrays, folder="dump"):
         np.save("{}/{}/{}_{}.npy".format(opt.output_path, folder, int(i), name), a)
 
 
+def dump_lines(opt, idx, name, lines, folder="dump"):
+    """{idx}_{name}.txt per sample: one line of text each (a sidecar of a per-sample file, written by the rank that has the sample)."""
+    for i, line in zip(idx, lines):
+        with open("{}/{}/{}_{}.txt".format(opt.output_path, folder, int(i), name), "w") as f:
+            f.write(line + "\n")
+
+
 def draw_pose(image, rot, size=15, width=1):
     """The reference's draw_pose on an 8-bit PIL image: the first two coordinates of each column of rot [3,3] (the rotated x, y, z axes) as
     red, green and blue lines from (size, size), drawn on a transparent layer and alpha-composited.  -> RGBA image.  (The reference goes
