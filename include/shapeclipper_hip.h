@@ -1123,6 +1123,72 @@ int sc_mesh_smooth(const float* verts, const int32_t* faces, const int64_t* v_of
                    int n_faces, int table_slots, int iters, double lam, double mu, void* scratch, float* verts_out, int64_t* counts,
                    double* measures, int32_t* bad_vertex, int32_t* bad_index, void* stream);
 
+/* ---- post-processing: one Loop subdivision step and one Newton step onto the SDF's zero set (csrc/mesh_subdivide.hip) -----------------
+ * What ops.mesh_subdivide and ops.mesh_project_step run and {idx}_mesh_subdiv.ply holds (`--mesh.subdivide`).  A batch of packed meshes
+ * in the form of sc_mesh_topology above (verts, faces with image-local indices, v_off / f_off); everything below is per image.
+ * sc_mesh_subdivide does ONE level: every face becomes four.  tests/mesh_subdivide_ref.py restates every rule in numpy.  The
+ * subdivision arithmetic is float64, every operation rounded once (the file is built without contraction).
+ *
+ * Faces.  A face with an index outside [0, v_off[b+1] - v_off[b]) sets *bad_index to 1 and is never dereferenced; a face in range that
+ *   repeats an index sets *bad_face to 1; neither takes part in anything.  A vertex with a component that is not finite sets *bad_vertex
+ *   to 1.  The caller raises for each of the three; the other outputs of the call are then unspecified.  No producer of the library
+ *   emits a face that repeats an index, and such a face is not repaired here.
+ * Half-edges.  Corner c of face f (f counted over the packed faces) is half-edge 3 f + c; its edge runs from i_c to i_{(c+1) % 3}, the
+ *   vertex i_{(c+2) % 3} lies opposite.
+ * Edges.  The undirected edge {lo, hi} keeps  count = its half-edges (the faces that have it),  owner = the lowest of their numbers,
+ *   omin / omax = the lowest / highest opposite vertex number.  An edge is INTERIOR if count == 2 -- omin and omax are then its two
+ *   opposite vertices, whatever the winding (the same vertex twice for a doubled face) -- and SHARP otherwise: 1 is the rim that the grid
+ *   face cuts, 3 or more is non-manifold.
+ * Vertices.  N(i) = the distinct vertices that share an edge with i, n = |N(i)| its DEGREE.  i is FIXED if it lies on a sharp edge,
+ *   ISOLATED if it lies on no edge, INTERIOR otherwise.
+ * State.  x_i = the input vertex widened exactly to float64; both rules read it and nothing else.
+ * Even (old) vertices keep their number.  FIXED and ISOLATED ones keep their bits.  An INTERIOR one becomes, per component,
+ *       s = +0.0;  s = s + x_j for j in N(i) in ASCENDING j;   beta = (n == 3) ? 0.1875 : 0.375 / (double)n;
+ *       w = (n == 3) ? 0.4375 : 0.625;   a = w x_i;   r = beta s;   x' = a + r          (Loop's scheme with Warren's weights)
+ * Odd (new) vertices, one per edge:  e = x_lo + x_hi;  interior:  o = x_omin + x_omax;  a = 0.375 e;  r = 0.125 o;  p = a + r;
+ *   sharp:  p = 0.5 e, and the new vertex is FIXED.
+ * Numbering.  An edge's vertex is V_b + r, r the rank of the edge among the image's edges in ascending owner (an integer block scan over
+ *   the image's 3 F_b flags "this half-edge is its edge's owner"), so the numbering follows the input face order.  Image b's output
+ *   vertices are [V_b old | E_b new]; the images' blocks are packed in image order, the offsets taken on the device from the edge counts.
+ * verts_out [n_verts + 3 n_faces][3] fp32 (the bound; the first sum of vertices_out rows are used): x' and p rounded to fp32 once (to
+ *   nearest, ties to even), the input bits for a vertex that keeps them.  fixed_out [n_verts + 3 n_faces] bytes: 1 for a FIXED vertex,
+ *   old or new, else 0.
+ * faces_out [4 n_faces][3] image-local: with m_c the vertex of corner c's edge, face f becomes
+ *       4 f: (i0, m0, m2)    4 f + 1: (i1, m1, m0)    4 f + 2: (i2, m2, m1)    4 f + 3: (m0, m1, m2)
+ *   The winding is kept, so orientation, genus, watertightness and the number of components are kept by construction.
+ * counts [SC_MESH_SUBDIVIDE_FIELDS][n_images] int64, row by row: 0 vertices_out = V_b + E_b, 1 edges, 2 sharp_edges, 3 fixed_vertices
+ *   (old and new: the fixed old ones plus sharp_edges), 4 isolated, 5 degree_max (over all its vertices; 0 without one).
+ * Edge table.  Open addressing in scratch, table_slots slots: a power of two, > 3 n_faces (so every linear probe meets an empty or
+ *   matching slot) and <= 2^30.  The key (global lo << 32) | global hi over image-offset vertex numbers is claimed by a 64-bit
+ *   compare-and-swap on the empty key; the thread that claims a slot adds one to the degree of both ends; count by an integer add, owner
+ *   and omin by atomicMin, omax by atomicMax.  The rows of a CSR adjacency (offsets: an integer block scan of the degrees) are filled at
+ *   an integer atomic cursor and then put into ascending order by rank, a wave for a row of more than 32 entries; there is no cap on the
+ *   degree.  Only integer atomics decide anything: every output has the same bits from run to run, for any batch, stream and
+ *   table_slots; permuting the input faces permutes the output and changes no position's bits.
+ * 8 launches on `stream` (5 when n_faces == 0); no wait on another workgroup, no float atomic, no host synchronisation.  scratch:
+ * sc_mesh_subdivide_scratch_bytes(n_images, n_verts, n_faces, table_slots) bytes of device memory, 16-byte aligned, contents irrelevant
+ * on entry (the query gives 0 for sizes the entry point refuses).  n_images <= 0 returns 0 and launches nothing; hipErrorInvalidValue
+ * for n_images > 65535, n_faces > 2^24 (4 n_faces <= 2^26: the output is an input of the next level), n_verts > 2^30, a negative count,
+ * a table_slots that is not such a power of two, a NULL pointer or a misaligned scratch (verts may be NULL when n_verts == 0, faces and
+ * faces_out when n_faces == 0, verts_out and fixed_out when both are).
+ *
+ * sc_mesh_project_step: one clamped Newton step of every vertex onto {sdf = 0}; elementwise, fp32, every operation rounded once (the
+ * division and the square root are the correctly rounded ones), a thread per vertex.  With f = sdf[i], g = grad[i] (d sdf / d position in
+ * the SDF's own units) and v = verts[i]:
+ *       g2 = (gx gx + gy gy) + gz gz
+ *   v keeps its bits if fixed[i] != 0, if f or g2 is not finite, or if g2 < 1e-12f.  Otherwise
+ *       t = f / g2;   d_c = (t g_c) scale;   l = sqrtf((dx dx + dy dy) + dz dz)
+ *   v keeps its bits if l is not finite;  if l > max_step:  r = max_step / l;  d_c = d_c r;   then v'_c = v_c - d_c.
+ * `scale` turns the SDF's units into those of verts.  n_verts == 0 returns 0 and launches nothing; hipErrorInvalidValue for a negative
+ * n_verts, more than 2^30 or a NULL pointer.                                                                                             */
+#define SC_MESH_SUBDIVIDE_FIELDS 6
+long long sc_mesh_subdivide_scratch_bytes(int n_images, int n_verts, int n_faces, int table_slots);
+int sc_mesh_subdivide(const float* verts, const int32_t* faces, const int64_t* v_off, const int64_t* f_off, int n_images, int n_verts,
+                      int n_faces, int table_slots, void* scratch, float* verts_out, int32_t* faces_out, uint8_t* fixed_out, int64_t* counts,
+                      int32_t* bad_vertex, int32_t* bad_index, int32_t* bad_face, void* stream);
+int sc_mesh_project_step(const float* verts, const float* sdf, const float* grad, const uint8_t* fixed, int n_verts, float scale,
+                         float max_step, float* verts_out, void* stream);
+
 /* ---- camera algebra of a render -------------------------------------------------------------------
  * sc_camera_rays_*: utils/camera.py:157-196 (get_center_and_ray on the rendered pixels only) + the normalisation of
  * model/renderer.py:69-76.  pose [n_images][3][4] = [R|t] world->camera, intr [n_images][3][3], ray_idx

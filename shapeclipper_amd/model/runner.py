@@ -710,6 +710,10 @@ class Runner:
         with --mesh.smooth also {idx}_mesh_smooth.ply (eval_3D.meshes_smoothed: the mesh of {idx}_mesh.ply after Taubin smoothing, positions
         and the same faces) and {idx}_mesh_smooth.txt (one line: idx iters lambda mu vertices free fixed_boundary isolated degree_max
         disp_mean disp_max rough_before rough_after area_before area_after volume_before volume_after, lengths in object units);
+        with --mesh.subdivide also {idx}_mesh_subdiv.ply (eval_3D.meshes_subdivided: the mesh of {idx}_mesh.ply after Loop subdivision and the
+        Newton steps onto the SDF's zero set, positions and faces) and {idx}_mesh_subdiv.txt (one line: idx levels project vertices_in
+        vertices_out faces_in faces_out edges sharp_edges fixed resid_before resid_after disp_mean disp_max area_before area_after
+        volume_before volume_after, lengths in object units);
         with --eval.icp also {idx}_pointclouds_comp_icp.ply (the ICP-aligned prediction of eval_3D.icp_metrics red, ground truth green);
         with --eval.normals also {idx}_pointclouds_normals.ply (pointclouds_comp's vertices as x y z nx ny nz red green blue: the SDF's
         normals on the prediction, the estimated PCA normals on the ground truth); with --eval.emd also {idx}_pointclouds_emd.ply (the
@@ -747,6 +751,12 @@ class Runner:
             smooth = var.mesh_smoothed_world if "mesh_smoothed_world" in var else eval_3D.meshes_smoothed(opt, var)
             util_vis.dump_meshes(opt, var.idx, "mesh_smooth", smooth, folder=folder)
             util_vis.dump_lines(opt, var.idx, "mesh_smooth", eval_3D.smoothed_lines(var), folder=folder)
+        if options.subdivide_settings(opt) is not None:
+            # (eval_metrics refined the mesh already and left it in var)
+            fine = (var.mesh_subdivided_world if "mesh_subdivided_world" in var
+                    else eval_3D.meshes_subdivided(opt, var, self.graph.module.sdf_network))
+            util_vis.dump_meshes(opt, var.idx, "mesh_subdiv", fine, folder=folder)
+            util_vis.dump_lines(opt, var.idx, "mesh_subdiv", eval_3D.subdivided_lines(var), folder=folder)
         if options.texture_texels(opt) is not None:
             net = self.graph.module
             var.texture = eval_3D.mesh_texture(opt, net.sdf_network, net.rgb_network, var.proj_latent_sdf, var.proj_latent_rgb, var.level_vox)

@@ -2528,3 +2528,124 @@ def mesh_smooth(verts, faces, v_count, f_count, iters, lam=0.5, mu=MESH_SMOOTH_M
         if flags[1]:
             raise ValueError("%s: a face index lies outside its image's vertex range [0, v_count[b])" % who)
     return SmoothedMesh(verts_out, faces, v_count, f_count, *counts.unbind(0), measures[2], measures[3], measures[0], measures[1])
+
+
+# ---- post-processing: Loop subdivision of indexed triangle meshes and a Newton step onto the SDF's zero set (csrc/mesh_subdivide.hip) ----
+MESH_SUBDIVIDE_MAX_LEVELS = 3
+MESH_SUBDIVIDE_MAX_FACES = 1 << 24          # 4 F <= 2^26 per level
+MESH_SUBDIVIDE_COUNTS = ("vertices_out", "edges", "sharp_edges", "fixed_vertices", "isolated", "degree_max")    # rows of sc_mesh_subdivide's counts
+
+
+class SubdividedMesh(collections.namedtuple("SubdividedMesh", ("verts", "faces", "v_count", "f_count", "fixed", "edges", "sharp_edges",
+                                                               "fixed_vertices"))):
+    __slots__ = ()
+    packed = property(lambda self: PackedMesh(*self[:4]), doc="the subdivided meshes alone, as a PackedMesh")
+
+
+def mesh_subdivide(verts, faces, v_count, f_count, levels=1, table_slots=None):
+    """Refines a PackedMesh (mesh_pack.py) of B images, passed as `*mesh` -- verts and faces on the device, v_count / f_count [B] int64 or
+    int32 (host or device) -- by `levels` (1..3) steps of Loop subdivision with Warren's weights: every face becomes four, every edge gets
+    a vertex, an old vertex keeps its number and moves to 0.625 x_i + (0.375 / n) sum of its n neighbours (0.4375 and 0.1875 at n = 3), the
+    vertex of an edge with two faces is 3/8 of its ends plus 1/8 of the two opposite vertices.  An edge with one face (the open rim) or with
+    three or more is sharp: its ends keep their bits, its new vertex is the midpoint, and all three are `fixed`; a vertex on no edge keeps
+    its bits.  Float64 from the exactly widened input, every operation rounded once, the sums in ascending neighbour number; each level's
+    output is rounded to fp32 once and is the next level's input.  include/shapeclipper_hip.h states every rule (sc_mesh_subdivide);
+    tests/mesh_subdivide_ref.py restates them in numpy.
+
+    -> SubdividedMesh(verts [V',3] fp32, faces [4^levels F,3] int32 image-local, v_count, f_count [B] int64 on the host -- `.packed` is
+    these four as a PackedMesh again --, fixed [V'] bool on the device, edges, sharp_edges, fixed_vertices [B] int64 on the device, of the
+    last level's input).  Image b's vertices are [old | new], a new vertex numbered by its edge's first half-edge in face order; face f
+    becomes faces 4 f .. 4 f + 3 with the winding kept.  Only integer atomics decide anything: the same bits from run to run, for any
+    batch, stream and table_slots (the edge table's size as in mesh_topology; it is used for a level whose 3 F it exceeds, else the
+    default).  Scratch comes from the scratch cache ("mesh subdivide").
+
+    ValueError for wrong dtypes, shapes or devices, counts that are negative or do not sum to the packed lengths, a bad levels or
+    table_slots, more than 2^24 faces going into a level -- all before any launch -- and, checked on the device and raised after a level's
+    launches, for a vertex that is not finite, a face index outside its image's vertex range (never dereferenced) and a face that repeats
+    an index.
+
+    Host synchronisation: one read per level, of the per-image counts that size the outputs and of the three flags.  Runs on the current
+    stream."""
+    who = "shapeclipper_amd: mesh_subdivide"
+    B, V, F, counts_host, offsets = check_packed(who, verts, faces, v_count, f_count, max_images=MESH_TOPOLOGY_MAX_IMAGES,
+                                                 max_faces=MESH_TOPOLOGY_MAX_FACES)
+    dev = verts.device
+    if V > MESH_SMOOTH_MAX_VERTS:
+        raise ValueError("%s: verts: at most 2^30 vertices per call, got %d" % (who, V))
+    if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= MESH_SUBDIVIDE_MAX_LEVELS:
+        raise ValueError("%s: levels must be an integer in 1..%d, got %r" % (who, MESH_SUBDIVIDE_MAX_LEVELS, levels))
+    if F * 4 ** (levels - 1) > MESH_SUBDIVIDE_MAX_FACES:
+        raise ValueError("%s: faces: at most 2^24 faces may go into a level (4 F <= 2^26), got %d into level %d" % (who, F * 4 ** (levels - 1), levels))
+    if table_slots is not None and (isinstance(table_slots, bool) or not isinstance(table_slots, int) or table_slots < 1
+                                    or table_slots & (table_slots - 1) or table_slots <= 3 * F or table_slots > MESH_TOPOLOGY_MAX_SLOTS):
+        raise ValueError("%s: table_slots must be a power of two greater than 3 F = %d (and at most 2^30), got %r" % (who, 3 * F, table_slots))
+    fixed = torch.zeros(V, device=dev, dtype=torch.bool)
+    n_fields = len(MESH_SUBDIVIDE_COUNTS)
+    counts = torch.zeros(n_fields, B, device=dev, dtype=torch.int64)
+    if B == 0:
+        return SubdividedMesh(verts, faces, counts_host[0], counts_host[1], fixed, counts[1], counts[2], counts[3])
+    lib = _lib.load()
+    verts, faces = verts.contiguous(), faces.contiguous()
+    for level in range(levels):
+        slots = table_slots if table_slots is not None and table_slots > 3 * F else mesh_topology_slots(F)
+        verts_out = torch.empty(V + 3 * F, 3, device=dev, dtype=torch.float32)
+        faces_out = torch.empty(4 * F, 3, device=dev, dtype=torch.int32)
+        fixed = torch.empty(V + 3 * F, device=dev, dtype=torch.bool)
+        back = torch.zeros(n_fields * B + 2, device=dev, dtype=torch.int64)         # what the host reads: the counts, then the three flags
+        counts, bad = back[:n_fields * B].view(n_fields, B), back[n_fields * B:].view(torch.int32)     # bad_vertex, bad_index, bad_face
+        offsets = offsets.to(dev)
+        with torch.cuda.device(dev):
+            ws = _scratch("mesh subdivide", dev, (lib.sc_mesh_subdivide_scratch_bytes(B, V, F, slots) + 3) // 4)
+            code = lib.sc_mesh_subdivide(_lib.ptr(verts) if V else None, _lib.ptr(faces) if F else None, _lib.ptr(offsets[0]),
+                                         _lib.ptr(offsets[1]), B, V, F, slots, _lib.ptr(ws), _lib.ptr(verts_out) if V + F else None,
+                                         _lib.ptr(faces_out) if F else None, _lib.ptr(fixed) if V + F else None, _lib.ptr(counts),
+                                         _lib.ptr(bad[:1]), _lib.ptr(bad[1:2]), _lib.ptr(bad[2:3]), _lib.stream())
+        _lib.check(code, "sc_mesh_subdivide")
+        host = back.cpu()
+        flags = host[n_fields * B:].view(torch.int32).tolist()
+        if flags[0]:
+            raise ValueError("%s: a vertex is not finite" % who)
+        if flags[1]:
+            raise ValueError("%s: a face index lies outside its image's vertex range [0, v_count[b])" % who)
+        if flags[2]:
+            raise ValueError("%s: a face repeats a vertex index" % who)
+        counts_host = torch.stack([host[:B], 4 * counts_host[1]])
+        V, F = int(counts_host[0].sum()), 4 * F
+        verts, faces, fixed = verts_out[:V], faces_out, fixed[:V]
+        offsets = PackedMesh(verts, faces, counts_host[0], counts_host[1]).offsets()
+    return SubdividedMesh(verts, faces, counts_host[0], counts_host[1], fixed, counts[1], counts[2], counts[3])
+
+
+def mesh_project_step(verts, sdf, grad, fixed, scale, max_step):
+    """One clamped Newton step of vertices onto the zero set of an SDF: verts [V,3] fp32, sdf [V] and grad [V,3] fp32 (the value and d sdf /
+    d position at the vertices, in the SDF's own units), fixed [V] bool, all on one device -> verts' [V,3] fp32,
+    v' = v - d, d = scale sdf grad / |grad|^2, shortened to `max_step` where it is longer.  `scale` (> 0) turns the SDF's units into those
+    of verts, `max_step` (>= 0) is in the units of verts.  A vertex keeps its bits if it is fixed, if sdf or |grad|^2 is not finite or
+    |grad|^2 < 1e-12, or if the step's length is not finite.  Elementwise fp32, every operation rounded once (sc_mesh_project_step in
+    include/shapeclipper_hip.h; tests/mesh_subdivide_ref.py restates it in numpy).  ValueError for wrong dtypes, shapes, devices or
+    numbers, before any launch.  No host synchronisation; runs on the current stream."""
+    who = "mesh_project_step"
+    verts = device_tensor(who, "verts", verts, (torch.float32,))
+    dev = verts.device
+    sdf = device_tensor(who, "sdf", sdf, (torch.float32,), dev)
+    grad = device_tensor(who, "grad", grad, (torch.float32,), dev)
+    fixed = device_tensor(who, "fixed", fixed, (torch.bool,), dev)
+    V = verts.shape[0]
+    if verts.dim() != 2 or verts.shape[1] != 3 or grad.shape != verts.shape or sdf.shape != (V,) or fixed.shape != (V,):
+        raise ValueError("shapeclipper_amd: %s takes verts [V,3], sdf [V], grad [V,3] and fixed [V], got %s, %s, %s and %s"
+                         % (who, tuple(verts.shape), tuple(sdf.shape), tuple(grad.shape), tuple(fixed.shape)))
+    if V > MESH_SMOOTH_MAX_VERTS:
+        raise ValueError("shapeclipper_amd: %s: verts: at most 2^30 vertices per call, got %d" % (who, V))
+    number = lambda x: isinstance(x, (int, float)) and not isinstance(x, bool) and x == x and abs(x) != float("inf")
+    if not number(scale) or not scale > 0:
+        raise ValueError("shapeclipper_amd: %s: scale must be a finite number > 0, got %r" % (who, scale))
+    if not number(max_step) or not max_step >= 0:
+        raise ValueError("shapeclipper_amd: %s: max_step must be a finite number >= 0, got %r" % (who, max_step))
+    out = torch.empty_like(verts)
+    if V:
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            code = lib.sc_mesh_project_step(_lib.ptr(verts), _lib.ptr(sdf), _lib.ptr(grad), _lib.ptr(fixed), V, float(scale), float(max_step),
+                                            _lib.ptr(out), _lib.stream())
+        _lib.check(code, "sc_mesh_project_step")
+    return out

@@ -31,6 +31,9 @@ Call surface of the reference's utils/eval_3D.py.
     quadric placement (ops.mesh_cluster_simplify, csrc/mesh_simplify.hip), and what the smaller file costs in distance.
   * meshes_smoothed (`--mesh.smooth=n`): the marching-cubes mesh after n Taubin lambda|mu iterations of the umbrella operator
     (ops.mesh_smooth, csrc/mesh_smooth.hip): the same faces, the grid's staircase gone, the volume within about a per cent.
+  * meshes_subdivided (`--mesh.subdivide=n`): the marching-cubes mesh after n levels of Loop subdivision (ops.mesh_subdivide,
+    csrc/mesh_subdivide.hip), its new vertices put back on the network's zero set by mesh.subdivide_project clamped Newton steps
+    (ops.mesh_project_step): four times the faces per level for about 1.5 network evaluations per input face and step.
 """
 from __future__ import annotations
 
@@ -856,6 +859,121 @@ def smoothed_lines(var):
             for b, i in enumerate(var.idx.cpu().tolist())]
 
 
+SUBDIVIDE_MAX_STEP = 0.5    # the longest Newton step of meshes_subdivided, in grid pitches
+
+
+def _ordered_sums(terms):
+    """terms [..., n] float64, non-negative -> [...]: the sum over the last axis in a fixed order that depends on a term's position
+    alone -- chunks of 16 consecutive terms added one at a time in ascending position, the chunk partials folded the same way, until one
+    is left (15 elementwise additions a level, four levels for 65,536 terms).  Zeros appended to a row change no bit, so a row padded to
+    another batch's width sums to the same bits."""
+    x = terms
+    while x.shape[-1] > 1:
+        n = x.shape[-1]
+        chunks = (n + 15) // 16
+        x = torch.nn.functional.pad(x, (0, chunks * 16 - n)).view(*x.shape[:-1], chunks, 16)
+        acc = x[..., 0]
+        for t in range(1, 16):
+            acc = acc + x[..., t]
+        x = acc
+    return x[..., 0] if x.shape[-1] else x.sum(-1)
+
+
+def _sdf_at(sdf_network, proj_latent_sdf):
+    """-> ask(query, B, P, want_grad): query [B P, 3] in the padded one-launch layout (P a multiple of 16 rows per image) -> (sdf [B P]
+    fp32, d sdf / d position [B P, 3] fp32 or None), by one ops.sdf_forward on weight images packed once here; architectures outside the
+    compiled family (sdf_network.eager) run the same step on stock operators (model/eager_path.py)."""
+    if getattr(sdf_network, "eager", False):
+        from ..model import eager_path
+
+        def ask(query, B, P, want_grad):
+            sdf, _, grad = eager_path.sdf_conditional_output(sdf_network, B, query, proj_latent_sdf, compute_grad=want_grad)
+            return sdf.detach().reshape(-1).float(), grad.detach().float().contiguous() if want_grad else None
+        return ask
+    w_pack, cbias = sdf_network.packed(proj_latent_sdf)
+
+    def ask(query, B, P, want_grad):
+        sdf, grad, _ = ops.sdf_forward(query, w_pack, cbias, P, symmetric=bool(sdf_network.force_symmetry), want_grad=want_grad, want_feat=False)
+        return sdf.reshape(-1).float(), grad.float() if want_grad else None
+    return ask
+
+
+@torch.no_grad()
+def meshes_subdivided(opt, var, sdf_network):
+    """`--mesh.subdivide=n`: the mesh that is written, refined and put back on the network's zero set.  ops.mesh_subdivide
+    (csrc/mesh_subdivide.hip) -- n levels of Loop subdivision -- on the packed mesh of ops.isosurface_mesh(var.level_vox) --
+    var.mesh_packed, built here as mesh_stats does when it is absent -- in grid-index units, where every grid pitch is 1 on all three
+    axes.  Then k = mesh.subdivide_project rounds of: one SDF evaluation with gradient at sampled_position(v), in mesh_attributes' padded
+    one-launch layout (sdf_network.eager: stock operators), and one ops.mesh_project_step with scale = (S - 1) / (hi - lo), which turns
+    the Newton step from object units into grid pitches, and max_step = 0.5 pitches; fixed vertices (the open rim and its midpoints,
+    non-manifold edges) keep their bits.  After the last round one value-only evaluation.  k = 0 asks the network nothing.
+    Sets var.mesh_subdivided, a dict (var keeps dicts with attribute access): the fields of ops.SubdividedMesh (verts in grid-index
+    units, after the projection), levels, project, vertices_in, faces_in [B] int64 and, [B] float64 on the device: resid_before /
+    resid_after, the mean |sdf| over the vertices that are not fixed before the first step and after the last (nan for k = 0; 0 for
+    an image without such a vertex); disp_mean / disp_max, how far the projection moved them, in object units; area_before, area_after,
+    volume_before, volume_after, ops.mesh_topology's of the original and of the refined mesh at the positions the level grid was
+    sampled at, in object units (the "before" pair is taken from var.mesh_stats when `--eval.mesh_stats` left it there).  The means
+    are float64 sums in a fixed order (_ordered_sums): the same bits whatever batch the sample is in.  Returns, and keeps in
+    var.mesh_subdivided_world for the dump, the per-image list of (vertices, faces) with meshes_device's v / S rescale, which overlays
+    {idx}_mesh.ply.  The metrics keep sampling the marching-cubes surface; nothing enters a loss."""
+    levels, project = options.subdivide_settings(opt)
+    lo, hi = opt.eval.range
+    S = var.level_vox.shape[1]
+    mesh = _mesh_packed(var)
+    B = mesh.v_count.shape[0]
+    res = ops.mesh_subdivide(*mesh, levels)
+    sub = res.packed
+    dev = sub.verts.device
+    pitch = (hi - lo) / (S - 1)
+    start = verts = sub.verts
+    nan = torch.full((B,), float("nan"), dtype=torch.float64, device=dev)
+    measures = dict(resid_before=nan, resid_after=nan, disp_mean=torch.zeros_like(nan), disp_max=torch.zeros_like(nan))
+    P, rows = sub.padded_rows(16)
+    if project > 0 and P > 0:
+        ask = _sdf_at(sdf_network, var.proj_latent_sdf)
+        real = torch.arange(P, device=dev)[None] < sub.v_count.to(dev)[:, None]         # [B, P]: the rows that are a vertex, in packed order
+        flat, real_flat = rows.reshape(-1), real.reshape(-1)
+        query = lambda v: sampled_position(v[flat], lo, hi, S).contiguous()
+        first = None
+        for _ in range(project):
+            sdf, grad = ask(query(verts), B, P, True)
+            first = sdf if first is None else first
+            verts = ops.mesh_project_step(verts, sdf[real_flat].contiguous(), grad[real_flat].contiguous(), res.fixed, 1.0 / pitch,
+                                          SUBDIVIDE_MAX_STEP)
+        last, _ = ask(query(verts), B, P, False)
+        free = real & ~res.fixed[flat].view(B, P)
+        d = verts.double() - start.double()
+        moved = (torch.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]) * pitch)[flat].view(B, P)
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        terms = torch.stack([torch.where(free, t, zero) for t in (first.view(B, P).double().abs(), last.view(B, P).double().abs(), moved)])
+        n_free = free.sum(1)
+        mean = torch.where(n_free > 0, _ordered_sums(terms) / n_free.double().clamp_min(1.0), zero)
+        measures = dict(resid_before=mean[0], resid_after=mean[1], disp_mean=mean[2], disp_max=terms[2].amax(1))
+    elif project > 0:
+        measures.update(resid_before=torch.zeros_like(nan), resid_after=torch.zeros_like(nan))
+    to_object = lambda v: sampled_position(v, lo, hi, S).contiguous()
+    after = ops.mesh_topology(*sub._replace(verts=to_object(verts)))
+    before = var.mesh_stats if "mesh_stats" in var else ops.mesh_topology(*mesh._replace(verts=to_object(mesh.verts)))._asdict()
+    var.mesh_subdivided = dict(res._replace(verts=verts)._asdict(), **measures, levels=levels, project=project,
+                               vertices_in=mesh.v_count.long(), faces_in=mesh.f_count.long(), area_before=before["area"],
+                               area_after=after.area, volume_before=before["volume"], volume_after=after.volume)
+    var.mesh_subdivided_world = sub.split(written_position(verts, lo, hi, S))
+    return var.mesh_subdivided_world
+
+
+def subdivided_lines(var):
+    """One line per sample for {idx}_mesh_subdiv.txt: idx levels project vertices_in vertices_out faces_in faces_out edges sharp_edges
+    fixed resid_before resid_after disp_mean disp_max area_before area_after volume_before volume_after (18 fields; one host read per
+    field)."""
+    r = var.mesh_subdivided
+    ints = [torch.as_tensor(r[k]).cpu().tolist() for k in ("vertices_in", "v_count", "faces_in", "f_count", "edges", "sharp_edges",
+                                                           "fixed_vertices")]
+    reals = [torch.as_tensor(r[k]).cpu().tolist() for k in ("resid_before", "resid_after", "disp_mean", "disp_max", "area_before",
+                                                            "area_after", "volume_before", "volume_after")]
+    return ["%d %d %d %s %s" % (int(i), r["levels"], r["project"], " ".join("%d" % col[b] for col in ints),
+                                " ".join("%.9g" % col[b] for col in reals)) for b, i in enumerate(var.idx.cpu().tolist())]
+
+
 _FLIP_PRED = [[1, 0, 0], [0, -1, 0], [0, 0, -1]]
 _FLIP_GT = [[-1, 0, 0], [0, 1, 0], [0, 0, 1]]
 
@@ -866,7 +984,7 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     icp, normals_k, emd, iou = (f(opt) for f in (options.icp_settings, options.normal_settings, options.emd_settings, options.iou_settings))
     mesh_dist = None if vis_only else options.mesh_dist_settings(opt)
     want_stats, simplify = options.mesh_stats_settings(opt), options.simplify_settings(opt)
-    smooth = options.smooth_settings(opt)
+    smooth, subdivide = options.smooth_settings(opt), options.subdivide_settings(opt)
     points_3D = get_dense_3D_grid(opt, var)
     B = points_3D.shape[0]
     level_vox = compute_level_grid(opt, sdf_network, var.proj_latent_sdf, points_3D)
@@ -908,6 +1026,8 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
             meshes_simplified(opt, var)
         if smooth is not None:                  # vis_{ep}/{idx}_mesh_smooth.ply and .txt
             meshes_smoothed(opt, var)
+        if subdivide is not None:               # vis_{ep}/{idx}_mesh_subdiv.ply and .txt
+            meshes_subdivided(opt, var, sdf_network)
         return
     dist_acc, dist_comp, idx1, idx2 = chamfer_distance(opt, X1=var.dpc_pred, X2=var.dpc.points)
     var.f_score = compute_fscore(dist_acc, dist_comp, opt.eval.f_thresholds)
@@ -932,4 +1052,6 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
         meshes_simplified(opt, var)
     if smooth is not None:                  # post-processing of the written mesh: no metric reads it
         meshes_smoothed(opt, var)
+    if subdivide is not None:               # likewise
+        meshes_subdivided(opt, var, sdf_network)
     return dist_acc.mean(), dist_comp.mean()

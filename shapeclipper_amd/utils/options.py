@@ -218,11 +218,17 @@ MESH_TABLE = tuple(Setting(*row) for row in (
     ("smooth_lambda", 0.5, (0.0, 1.0), "... the positive step lambda", "str"),
     ("smooth_band", 0.1, (0.0, 0.5), "... Taubin's pass-band k_PB: the negative step is mu = 1 / (smooth_band - 1 / smooth_lambda)", "str"),
 ))
-MESH = {row.key: row for row in MESH_TABLE}
+# The refinement of the written mesh, in a table of its own with the same rows: MESH_TABLE stays the smoothing's three.
+MESH_SUBDIVIDE_TABLE = tuple(Setting(*row) for row in (
+    ("subdivide", None, (1, 3), "Loop-subdivided mesh {idx}_mesh_subdiv.ply / .txt projected onto the SDF: the levels (ops.mesh_subdivide)", "absent"),
+    ("subdivide_project", 2, (0, 8), "... the Newton steps onto the network's zero set after the subdivision (ops.mesh_project_step); 0 = none"),
+))
+MESH = {row.key: row for row in MESH_TABLE + MESH_SUBDIVIDE_TABLE}
 
 
 def mesh_setting(opt, key):
-    """opt.mesh[key] checked against its row of MESH_TABLE, the row's default where the option tree has no such key or no `mesh` group."""
+    """opt.mesh[key] checked against its row of MESH_TABLE or MESH_SUBDIVIDE_TABLE, the row's default where the option tree has no such
+    key or no `mesh` group."""
     row = MESH[key]
     return _checked("mesh", row, (opt.get("mesh", None) or {}).get(key, row.default))
 
@@ -236,6 +242,13 @@ def smooth_settings(opt):
         raise ValueError("mesh.smooth_lambda = %r and mesh.smooth_band = %r give mu = %.6g <= -1: choose mesh.smooth_lambda < "
                          "1 / (1 + mesh.smooth_band) = %.6g" % (lam, band, mu, 1.0 / (1.0 + band)))
     return None if iters is None else (iters, lam, mu)
+
+
+def subdivide_settings(opt):
+    """None unless `--mesh.subdivide=n` is given, else (levels, project): the levels of ops.mesh_subdivide and the Newton steps of
+    eval_3D.meshes_subdivided.  Both values are checked, switch on or off."""
+    levels, project = (mesh_setting(opt, k) for k in ("subdivide", "subdivide_project"))
+    return None if levels is None else (levels, project)
 
 
 def parse_arguments(args):
@@ -329,7 +342,7 @@ def process_options(opt):
                 raise ValueError("hip.%s must be an integer in %d..%d, got %r" % (row.key, lo, hi, v))
     for check in (dual_mesh_reg, texture_texels, mesh_render, icp_settings, normal_settings, mesh_dist_settings, emd_settings, iou_settings,
                   mesh_stats_settings, simplify_settings,       # every eval.* value is checked here, whether or not its switch is on
-                  smooth_settings):                             # and every mesh.* value
+                  smooth_settings, subdivide_settings):         # and every mesh.* value
         check(opt)
     torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
     for row in HIP_TABLE:
