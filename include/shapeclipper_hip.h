@@ -1189,6 +1189,58 @@ int sc_mesh_subdivide(const float* verts, const int32_t* faces, const int64_t* v
 int sc_mesh_project_step(const float* verts, const float* sdf, const float* grad, const uint8_t* fixed, int n_verts, float scale,
                          float max_step, float* verts_out, void* stream);
 
+/* ---- validity: pairs of faces of a mesh that properly cross (csrc/mesh_intersect.hip) -------------------------------------------------
+ * What ops.mesh_self_intersections runs and {idx}_mesh_selfx.txt reports (`--mesh.self_intersect`).  A batch of packed meshes: verts
+ * [n_verts][3] fp32, faces [n_faces][3] with image-local indices, v_count / f_count [n_images] int32 on the device, non-negative, summing
+ * to n_verts / n_faces (the form of sc_point_mesh_distance above).  Everything below is per image; faces are numbered image-locally.
+ * tests/mesh_intersect_ref.py restates every rule in numpy.  The file is built without contraction: every operation is rounded once.
+ *
+ * Sign of a point against a plane, sign3(a, b, c, d) in {-1, 0, +1}.  The fp32 coordinates are widened to float64, then
+ *       ad = a - d;  bd = b - d;  cd = c - d                                   (per component)
+ *       m1 = bd.x cd.y;  m2 = bd.y cd.x;  m3 = cd.x ad.y;  m4 = cd.y ad.x;  m5 = ad.x bd.y;  m6 = ad.y bd.x
+ *       det  = (ad.z (m1 - m2) + bd.z (m3 - m4)) + cd.z (m5 - m6)
+ *       perm = ((|m1| + |m2|) |ad.z| + (|m3| + |m4|) |bd.z|) + (|m5| + |m6|) |cd.z|
+ *   sign3 = 0 if |det| <= 2^-49 perm, else the sign of det.  2^-49 = 16 eps covers Shewchuk's static bound for this expansion (about
+ *   7 eps times the permanent) and the three roundings of differences that are not exact in float64: a NON-ZERO sign3 is the sign of the
+ *   exact determinant of the fp32 coordinates.  That is the property the whole check rests on.
+ * Segment against triangle.  pierces(p, q; a, b, c) holds when  sign3(a,b,c,p) sign3(a,b,c,q) == -1  and  sign3(p,q,a,b), sign3(p,q,b,c),
+ *   sign3(p,q,c,a) are equal and not zero: the ends lie strictly on both sides of the plane and the segment passes strictly inside.
+ * Edges.  The face (i0, i1, i2) has the edges (v0,v1), (v1,v2), (v2,v0), in this orientation; the edge OPPOSITE corner s is
+ *   (v_{(s+1)%3}, v_{(s+2)%3}).  A triangle enters sign3 and pierces in its own corner order.
+ * A pair of faces, A the lower-numbered and B the higher, by the vertex indices they share:
+ *       two or three:  never a hit (neighbours across an edge, duplicates) and not a pair at all;
+ *       one, corner sa of A and sb of B:  a hit iff A's edge opposite sa pierces B or B's edge opposite sb pierces A;
+ *       none:  a hit iff one of A's three edges pierces B or one of B's three edges pierces A.
+ *   A face that repeats an index takes no part in any pair and is counted as degenerate.  Early exits are taken where signs settle the
+ *   outcome (all of A strictly on one side of B's plane); the result is the plain definition's.
+ * The rule is STRICT: it counts proper crossings only.  Contacts with a zero sign -- a vertex on a face, an edge through an edge,
+ *   coplanar overlap, a crossing too close to call at 2^-49 -- are not hits.  Every counted pair truly intersects; the count is a lower
+ *   bound on the pairs that touch.
+ * counts [3][n_images] int64, row by row: 0 pairs = the hits, 1 pairs_vertex = those that share one vertex, 2 box_pairs = the unordered
+ *   pairs of faces that take part, share at most one index and whose closed fp32 bounding boxes overlap (raw coordinates, no slack): a
+ *   function of the mesh alone, there so that a broad phase that drops or repeats a pair shows.  A hit implies such an overlap.
+ * face_counts [2][n_images] int32: 0 faces_hit = faces in at least one hit, 1 degenerate = faces in range that repeat an index.
+ * hits [n_faces] int32: per packed face, the hits it is part of (their sum is 2 pairs).  partner [n_faces] int32: the lowest face it
+ *   crosses, -1 without one.
+ * flags [2] int32: 0 is set to 1 when a vertex of the batch has a component that is not finite or of magnitude >= 1e15, 1 when a face
+ *   has an index outside [0, v_count[b]); such a face is never dereferenced and takes no part.  The caller raises for both; the other
+ *   outputs are then unspecified.
+ * brute != 0: all pairs, a thread per face, 256 higher-numbered faces at a time staged in LDS.  brute == 0: the triangle grid of
+ *   sc_point_mesh_distance (csrc/triangle_grid.hpp); a pair whose boxes overlap is tested once, by the thread of its lower-numbered face
+ *   in the cell that holds the component-wise maximum of the two box minima; a face on its image's large list is walked by a wave against
+ *   every higher-numbered face of its image, and every other face also walks the higher-numbered faces of that list; an image whose grid
+ *   is invalid (zero extent) takes the all-pairs path.  Both give the same integers in every output.
+ * Integer atomics only (add on hits and the counters, min on partner): the same bits from run to run, for any batch, stream and face
+ *   order; the integers permute with the faces.  One stream, no wait on another workgroup, no host synchronisation.  scratch:
+ * sc_mesh_self_intersections_scratch_bytes(n_images, n_verts, n_faces) bytes of device memory, 16-byte aligned, contents irrelevant on
+ * entry (-1 for sizes the entry point refuses).  n_images <= 0 returns 0 and launches nothing; hipErrorInvalidValue for n_images > 65535,
+ * n_faces > 2^26, a negative count, a NULL pointer or a misaligned scratch (verts may be NULL when n_verts == 0; faces, hits and partner
+ * when n_faces == 0).                                                                                                                     */
+long long sc_mesh_self_intersections_scratch_bytes(int n_images, int n_verts, int n_faces);
+int sc_mesh_self_intersections(const float* verts, const int32_t* faces, const int32_t* v_count, const int32_t* f_count, int n_images,
+                               int n_verts, int n_faces, int brute, void* scratch, long long* counts, int32_t* face_counts, int32_t* hits,
+                               int32_t* partner, int32_t* flags, void* stream);
+
 /* ---- camera algebra of a render -------------------------------------------------------------------
  * sc_camera_rays_*: utils/camera.py:157-196 (get_center_and_ray on the rendered pixels only) + the normalisation of
  * model/renderer.py:69-76.  pose [n_images][3][4] = [R|t] world->camera, intr [n_images][3][3], ray_idx

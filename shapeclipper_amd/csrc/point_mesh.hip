@@ -8,8 +8,8 @@
 //   * sc_point_mesh_distance_brute: all pairs.  A workgroup stages 256 triangles at a time in LDS (gathered through the face indices,
 //     out-of-range faces flagged), every thread keeps its query and its best candidate in registers and reads the staged triangles at
 //     wave-uniform addresses (LDS broadcasts).
-//   * sc_point_mesh_distance: the triangle counterpart of chamfer_grid.hip.  A uniform grid over the bounding box of the image's valid
-//     triangles; a triangle is referenced from every cell its AABB (padded by `slack`) overlaps: count pass, exclusive scan, fill pass
+//   * sc_point_mesh_distance: the triangle counterpart of chamfer_grid.hip.  The grid is built by triangle_grid.hpp (steps 0 to 5, shared
+//     with mesh_intersect.hip): a uniform grid over the bounding box of the image's valid triangles; a triangle is referenced from every cell its AABB (padded by `slack`) overlaps: count pass, exclusive scan, fill pass
 //     (integer atomics; the order inside a cell is arbitrary).  The cell side is max(2 x mean AABB extent, cbrt(volume / F)), grown
 //     until the grid has at most 2 F + 64 cells, so a typical triangle overlaps at most 2 x 2 x 2 cells.  A triangle that overlaps more
 //     than PM_CELL_CAP cells (one huge triangle across the box) goes on the image's "large" list instead, which every query of the image
@@ -35,31 +35,23 @@
 #include <limits.h>
 #include <stdint.h>
 
-#include "block_scan.hpp"
 #include "shapeclipper_hip.h"
-#include "uniform_grid.hpp"
+#include "triangle_grid.hpp"
 
 #pragma clang fp contract(off)
 
 namespace sc_pm {
 
-constexpr int THREADS = 256;
-constexpr int PM_GMAX = 128;          // cells per axis
-constexpr int PM_CELL_CAP = 16;       // cells a triangle may be referenced from; more: the image's large list
+using namespace sc_tgrid;             // steps 0 to 5: the offsets, the box, the geometry, the references and the large lists (triangle_grid.hpp)
+constexpr int PM_CELL_CAP = CELL_CAP; // cells a triangle may be referenced from; more: the image's large list
 constexpr int PM_RMAX = 6;            // rings before a query is handed to the all-pairs scan
 constexpr int PM_BUDGET = 4096;       // candidates before a query is handed to the scan
 constexpr int PM_REMPTY = 2;          // cells outside the box / rings without a candidate before a query is handed to the scan
 constexpr int PM_SLICES = 16;         // slices of the faces the scan of the listed queries is split over
-constexpr int MAX_IMAGES = 65535;
-constexpr int MAX_FACES = 1 << 26;    // PM_CELL_CAP * f_total stays below 2^31
 constexpr long long MAX_QUERIES = 1ll << 30;
 constexpr float PM_FLAT = 1.0e-5f;   // den = |ab|^2 |ac|^2 sin^2: below this sin^2 the interior weights are rounding noise, the triangle counts as its edges
-constexpr float PM_HUGE = 1.0e15f;    // magnitudes the padding / slack arithmetic is not made for
+constexpr float PM_HUGE = HUGE_COORD; // magnitudes the padding / slack arithmetic is not made for
 constexpr unsigned long long EMPTY = ~0ull;
-
-struct Meta : sc_grid::Geometry {     // one per image; valid: finite vertices of sensible magnitude, a box of positive extent
-    int cbase;                        // first cell of the image in the packed cell arrays
-};
 
 // ---- one (point, triangle) pair: include/shapeclipper_hip.h, "Arithmetic of one pair" ---------------------------------------------------
 __device__ __forceinline__ float pm_dot(float x0, float x1, float x2, float y0, float y1, float y2) { return (x0 * y0 + x1 * y1) + x2 * y2; }
@@ -153,218 +145,6 @@ __device__ __forceinline__ void pm_write(const Best& s, bool finite_query, size_
         dist2[at] = s.d; face[at] = s.f;
         closest[at * 3 + 0] = s.q[0]; closest[at * 3 + 1] = s.q[1]; closest[at * 3 + 2] = s.q[2];
     }
-}
-
-// ---- 0. the images' slices of the packed arrays: starts[0..B] of the vertices and of the faces, never past the packed lengths ----------
-__global__ void pm_offsets_kernel(int n_images, const int32_t* __restrict__ v_count, const int32_t* __restrict__ f_count, int v_total,
-                                  int f_total, int* __restrict__ v_start, int* __restrict__ f_start) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    long long v = 0, f = 0;
-    for (int b = 0; b < n_images; ++b) {
-        v_start[b] = (int)v; f_start[b] = (int)f;
-        const int vc = v_count[b], fc = f_count[b];
-        v += vc > 0 ? vc : 0; f += fc > 0 ? fc : 0;
-        v = v < v_total ? v : v_total; f = f < f_total ? f : f_total;
-    }
-    v_start[n_images] = (int)v; f_start[n_images] = (int)f;
-}
-
-// image of packed face k: the last b with f_start[b] <= k (k < f_start[n_images])
-__device__ __forceinline__ int pm_image_of(int k, const int* __restrict__ f_start, int n_images) {
-    int lo = 0, hi = n_images;                          // invariant: f_start[lo] <= k < f_start[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (f_start[mid] <= k) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// the vertices of packed face k of image b, or false when an index is outside [0, v_count[b])
-__device__ __forceinline__ bool pm_load(int k, int b, const float* __restrict__ verts, const int32_t* __restrict__ faces,
-                                        const int* __restrict__ v_start, float a[3], float bb[3], float c[3]) {
-    const int v0 = v_start[b], nv = v_start[b + 1] - v0;
-    const int i0 = faces[(size_t)k * 3 + 0], i1 = faces[(size_t)k * 3 + 1], i2 = faces[(size_t)k * 3 + 2];
-    if (i0 < 0 || i0 >= nv || i1 < 0 || i1 >= nv || i2 < 0 || i2 >= nv) return false;
-    for (int i = 0; i < 3; ++i) {
-        a[i] = verts[(size_t)(v0 + i0) * 3 + i]; bb[i] = verts[(size_t)(v0 + i1) * 3 + i]; c[i] = verts[(size_t)(v0 + i2) * 3 + i];
-    }
-    return true;
-}
-
-// the lanes of a wave whose `ok` is set: all of one image -> the first such lane (it issues the wave's atomics after a reduction);
-// of several images -> -1 (every lane issues its own); none -> -2.  Every lane of the wave calls it.
-__device__ __forceinline__ int pm_wave_leader(bool ok, int b) {
-    const unsigned long long m = __ballot(ok);
-    if (!m) return -2;
-    const int first = __builtin_ctzll(m);
-    const int b0 = __shfl(b, first);
-    return __all(!ok || b == b0) ? first : -1;
-}
-
-// ---- 1. bounding box of the valid triangles (the box of uniform_grid.hpp; its free word counts the valid faces) ------------------------------
-__global__ __launch_bounds__(THREADS) void pm_bbox_kernel(int n_images, int f_total, const float* __restrict__ verts,
-                                                          const int32_t* __restrict__ faces, const int* __restrict__ v_start,
-                                                          const int* __restrict__ f_start, unsigned* __restrict__ box_all,
-                                                          float4* __restrict__ tris) {
-    const int k = blockIdx.x * THREADS + threadIdx.x, lane = threadIdx.x & 63;
-    const bool in = k < f_total && k < f_start[n_images];
-    const int b = in ? pm_image_of(k, f_start, n_images) : 0;
-    float a[3] = {0.f, 0.f, 0.f}, bb[3] = {0.f, 0.f, 0.f}, c[3] = {0.f, 0.f, 0.f};
-    const bool ok = in && pm_load(k, b, verts, faces, v_start, a, bb, c);
-    if (in) {       // the gathered triangle, for the walk: w of the first vertex says whether the face is valid
-        tris[(size_t)k * 3 + 0] = ok ? make_float4(a[0], a[1], a[2], 1.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-        tris[(size_t)k * 3 + 1] = ok ? make_float4(bb[0], bb[1], bb[2], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-        tris[(size_t)k * 3 + 2] = ok ? make_float4(c[0], c[1], c[2], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    float mn[3], mx[3];
-    int bad = 0;
-    for (int i = 0; i < 3; ++i) {
-        bad |= ok && (!(fabsf(a[i]) < PM_HUGE) || !(fabsf(bb[i]) < PM_HUGE) || !(fabsf(c[i]) < PM_HUGE));
-        mn[i] = ok ? fminf(a[i], fminf(bb[i], c[i])) : __builtin_inff();
-        mx[i] = ok ? fmaxf(a[i], fmaxf(bb[i], c[i])) : -__builtin_inff();
-    }
-    const int leader = pm_wave_leader(ok, b);
-    unsigned count = ok ? 1u : 0u;
-    if (leader >= 0) {
-        sc_grid::wave_minmax(mn, mx);
-        bad = __any(bad);
-        count = (unsigned)__builtin_popcountll(__ballot(ok));
-    }
-    if (ok && (leader == -1 || lane == leader)) {
-        unsigned* box = box_all + (size_t)b * sc_grid::BOX_WORDS;
-        sc_grid::box_merge(box, mn, mx, bad);
-        atomicAdd(&box[sc_grid::BOX_USER], count);
-    }
-}
-
-// ---- 2. sum of the triangles' largest AABB extents, in units of (largest box extent) / 65536, as a 64-bit integer ------------------------
-__global__ __launch_bounds__(THREADS) void pm_extent_kernel(int n_images, int f_total, const int* __restrict__ f_start,
-                                                            const unsigned* __restrict__ box_all, const float4* __restrict__ tris,
-                                                            unsigned long long* __restrict__ ext_sum) {
-    const int k = blockIdx.x * THREADS + threadIdx.x, lane = threadIdx.x & 63;
-    const bool in = k < f_total && k < f_start[n_images];
-    const float4 a = in ? tris[(size_t)k * 3 + 0] : make_float4(0.f, 0.f, 0.f, 0.f);
-    bool ok = in && a.w != 0.f;
-    const int b = ok ? pm_image_of(k, f_start, n_images) : 0;
-    unsigned q = 0;
-    if (ok) {
-        float lo[3], hi[3], emax = 0.f;
-        const bool bad = sc_grid::box_read(box_all + (size_t)b * sc_grid::BOX_WORDS, lo, hi);
-        for (int i = 0; i < 3; ++i) emax = fmaxf(emax, hi[i] - lo[i]);
-        ok = !bad && emax > 0.f;
-        if (ok) {
-            const float4 bb = tris[(size_t)k * 3 + 1], c = tris[(size_t)k * 3 + 2];
-            const float ex = fmaxf(a.x, fmaxf(bb.x, c.x)) - fminf(a.x, fminf(bb.x, c.x));
-            const float ey = fmaxf(a.y, fmaxf(bb.y, c.y)) - fminf(a.y, fminf(bb.y, c.y));
-            const float ez = fmaxf(a.z, fmaxf(bb.z, c.z)) - fminf(a.z, fminf(bb.z, c.z));
-            const float e = fminf(fmaxf(ex, fmaxf(ey, ez)) / emax * 65536.f, 65536.f);
-            q = (unsigned)(e >= 0.f ? e : 0.f);
-        }
-    }
-    const int leader = pm_wave_leader(ok, b);
-    if (leader >= 0)
-        for (int d = 32; d >= 1; d >>= 1) q += __shfl_xor(q, d);
-    if (ok && (leader == -1 || lane == leader)) atomicAdd(&ext_sum[b], (unsigned long long)q);
-}
-
-// ---- 3. grid geometry of every image, then the images' first cells -----------------------------------------------------------------------
-__global__ __launch_bounds__(THREADS) void pm_meta_kernel(int n_images, const unsigned* __restrict__ box_all,
-                                                          const unsigned long long* __restrict__ ext_sum, Meta* __restrict__ meta) {
-    for (int b = threadIdx.x; b < n_images; b += THREADS) {
-        const unsigned* box = box_all + (size_t)b * sc_grid::BOX_WORDS;
-        const int nf = (int)box[sc_grid::BOX_USER];
-        const float count = (float)(nf > 0 ? nf : 1), ext_units = (float)ext_sum[b];
-        Meta g;
-        // (24 growth rounds where the two point grids take 8: possibly drift between the copies; kept, the geometry is not to change)
-        const float h = sc_grid::geometry_from_box(box, 2ll * nf + 64, PM_GMAX, 24, [=](float vol, float emax) {
-            const float mean_ext = emax * (ext_units / (65536.f * count));
-            return fmaxf(2.f * mean_ext, cbrtf(vol / count));
-        }, g);
-        g.valid = (g.valid && nf > 0 && h > 0.f) ? 1 : 0;
-        if (!g.valid) g.g[0] = g.g[1] = g.g[2] = 1;
-        g.cbase = 0;
-        meta[b] = g;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int base = 0;                                   // at most 2 F_b + 64 cells each: the sum fits the packed arrays (and an int)
-        for (int b = 0; b < n_images; ++b) { meta[b].cbase = base; base += meta[b].g[0] * meta[b].g[1] * meta[b].g[2]; }
-    }
-}
-
-// ---- 4. references: count pass (FILL = false; also builds the large lists) and fill pass (FILL = true) -----------------------------------
-template <bool FILL>
-__global__ __launch_bounds__(THREADS) void pm_bin_kernel(int n_images, int f_total, const int* __restrict__ f_start,
-                                                         const Meta* __restrict__ meta, const float4* __restrict__ tris,
-                                                         int* __restrict__ counts, int* __restrict__ cursor, int* __restrict__ refs,
-                                                         int* __restrict__ large, int* __restrict__ large_count) {
-    const int k = blockIdx.x * THREADS + threadIdx.x;
-    if (k >= f_total || k >= f_start[n_images]) return;
-    const float4 a = tris[(size_t)k * 3 + 0];
-    if (a.w == 0.f) return;
-    const int b = pm_image_of(k, f_start, n_images);
-    const Meta& g = meta[b];
-    if (!g.valid) return;
-    const float4 bb = tris[(size_t)k * 3 + 1], c = tris[(size_t)k * 3 + 2];
-    const float mn[3] = {fminf(a.x, fminf(bb.x, c.x)), fminf(a.y, fminf(bb.y, c.y)), fminf(a.z, fminf(bb.z, c.z))};
-    const float mx[3] = {fmaxf(a.x, fmaxf(bb.x, c.x)), fmaxf(a.y, fmaxf(bb.y, c.y)), fmaxf(a.z, fmaxf(bb.z, c.z))};
-    int c0[3], c1[3];
-    long long ncells = 1;
-    for (int i = 0; i < 3; ++i) {
-        c0[i] = sc_grid::axis_cell_far(mn[i] - g.slack, g.lo[i], g.inv_h[i], g.g[i]);
-        c1[i] = sc_grid::axis_cell_far(mx[i] + g.slack, g.lo[i], g.inv_h[i], g.g[i]);
-        ncells *= (c1[i] - c0[i] + 1);
-    }
-    const int local = k - f_start[b];
-    if (ncells > PM_CELL_CAP) {
-        if (!FILL) large[f_start[b] + atomicAdd(&large_count[b], 1)] = local;      // at most F_b entries: the image's own slice
-        return;
-    }
-    for (int z = c0[2]; z <= c1[2]; ++z)
-        for (int y = c0[1]; y <= c1[1]; ++y)
-            for (int x = c0[0]; x <= c1[0]; ++x) {
-                const int cell = g.cbase + (z * g.g[1] + y) * g.g[0] + x;
-                if (FILL) refs[counts[cell] + atomicAdd(&cursor[cell], 1)] = local;
-                else atomicAdd(&counts[cell], 1);
-            }
-}
-
-// ---- 5. exclusive scan of the packed histogram, in place, over [0, n): entry `cells` of the last image ends up holding the total ---------
-__global__ __launch_bounds__(1024) void pm_scan_local_kernel(int n, int* __restrict__ counts, int* __restrict__ block_tot) {
-    __shared__ int wtot[16];
-    const int tid = threadIdx.x;
-    const int i = blockIdx.x * 1024 + tid;
-    const int v = i < n ? counts[i] : 0;
-    int total;
-    const int before = sc_scan::block_exclusive<16>(v, wtot, total);
-    if (i < n) counts[i] = before;
-    if (tid == 0) block_tot[blockIdx.x] = total;
-}
-
-// exclusive scan of the block totals, in place: one workgroup, 1,024 totals per round with a running carry
-__global__ __launch_bounds__(1024) void pm_scan_totals_kernel(int nblk, int* __restrict__ block_tot) {
-    __shared__ int wtot[16];
-    __shared__ int carry_s;
-    const int tid = threadIdx.x;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (int base = 0; base < nblk; base += 1024) {
-        const int i = base + tid;
-        const int v = i < nblk ? block_tot[i] : 0;
-        int total;
-        const int before = sc_scan::block_exclusive<16>(v, wtot, total);      // the round's two barriers below free wtot for the next
-        const int carry = carry_s;
-        if (i < nblk) block_tot[i] = carry + before;
-        __syncthreads();
-        if (tid == 0) carry_s = carry + total;
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(1024) void pm_scan_add_kernel(int n, int* __restrict__ counts, const int* __restrict__ block_tot) {
-    const int i = blockIdx.x * 1024 + threadIdx.x;
-    const int off = block_tot[blockIdx.x];
-    if (i < n && off) counts[i] += off;
 }
 
 // ---- 6. the ring walk, one thread per query -----------------------------------------------------------------------------------------------
@@ -486,7 +266,7 @@ __global__ __launch_bounds__(THREADS) void pm_brute_kernel(int n, const float* _
         __syncthreads();
         if (tid < chunk) {
             float a[3], bb[3], c[3];
-            const bool ok = pm_load(f0 + k0 + tid, b, verts, faces, v_start, a, bb, c);
+            const bool ok = load_face(f0 + k0 + tid, b, verts, faces, v_start, a, bb, c);
             tri_ok[tid] = ok ? 1 : 0;
             if (ok)
                 for (int i = 0; i < 3; ++i) { tri[tid][i] = a[i]; tri[tid][3 + i] = bb[i]; tri[tid][6 + i] = c[i]; }
@@ -526,38 +306,25 @@ __global__ __launch_bounds__(THREADS) void pm_unpack_kernel(int n, const float* 
     if (key != EMPTY) {                                             // the winner's closest point: the same pair, the same bits
         const int f = (int)(unsigned int)(key & 0xFFFFFFFFull);
         float a[3], bb[3], c[3];
-        if (pm_load(f_start[b] + f, b, verts, faces, v_start, a, bb, c)) pm_test(s, q, a, bb, c, f);
+        if (load_face(f_start[b] + f, b, verts, faces, v_start, a, bb, c)) pm_test(s, q, a, bb, c, f);
     }
     pm_write(s, true, at, dist2, face, closest);                    // non-finite queries never reach the list
 }
 
-// workspace, in 4-byte words
-struct Carve {
-    size_t box, ext_sum, large_count, todo_count, counts, cursor, cleared;      // cleared by one memset: first and adjacent
-    size_t v_start, f_start, meta, block_tot, large, todo, keys, tris, refs, total;
-    size_t n_cells, nblk;
+// workspace, in 4-byte words: the grid's regions (triangle_grid.hpp) and the scan's list
+struct Workspace : sc_tgrid::Carve {
+    size_t todo_count, cleared;         // cleared by one memset: todo_count and the grid's cleared regions, first and adjacent
+    size_t todo, keys, total;
 };
-inline Carve carve(int b, int n, int f_total) {
-    Carve c;
+inline Workspace carve(int b, int n, int f_total) {
+    Workspace c;
     sc_grid::WordCarver w;
-    c.n_cells = 2 * (size_t)f_total + 64 * (size_t)b + 1;           // sum of the images' cell budgets, and the entry behind the last cell
-    c.nblk = (c.n_cells + 1023) / 1024;
-    c.box = w.take((size_t)b * sc_grid::BOX_WORDS);
-    c.ext_sum = w.take((size_t)b * 2);
-    c.large_count = w.take((size_t)b);
     c.todo_count = w.take((size_t)b);
-    c.counts = w.take(c.n_cells);
-    c.cursor = w.take(c.n_cells);
+    carve_cleared(w, b, f_total, c);
     c.cleared = w.words;
-    c.v_start = w.take((size_t)b + 1);
-    c.f_start = w.take((size_t)b + 1);
-    c.meta = w.take((size_t)b * (sizeof(Meta) / 4));
-    c.block_tot = w.take(c.nblk);
-    c.large = w.take((size_t)f_total);
+    carve_rest(w, b, f_total, c);
     c.todo = w.take((size_t)b * n);
     c.keys = w.take((size_t)b * n * 2);                               // 64-bit: offsets are multiples of 4 words
-    c.tris = w.take((size_t)f_total * 12);
-    c.refs = w.take((size_t)f_total * PM_CELL_CAP);
     c.total = w.words;
     return c;
 }
@@ -586,9 +353,9 @@ int sc_point_mesh_distance_brute(const float* points, const float* verts, const 
     if (refused(n_images, n_points, v_total, f_total) || !points || !v_count || !f_count || !workspace || !dist2 || !face || !closest ||
         (v_total > 0 && !verts) || (f_total > 0 && !faces) || ((uintptr_t)workspace & 15))
         return (int)hipErrorInvalidValue;
-    const Carve c = carve(n_images, n_points, f_total);
+    const Workspace c = carve(n_images, n_points, f_total);
     int* ws = (int*)workspace;
-    hipLaunchKernelGGL(pm_offsets_kernel, dim3(1), dim3(64), 0, stream, n_images, v_count, f_count, v_total, f_total, ws + c.v_start,
+    hipLaunchKernelGGL(offsets_kernel, dim3(1), dim3(64), 0, stream, n_images, v_count, f_count, v_total, f_total, ws + c.v_start,
                        ws + c.f_start);
     hipLaunchKernelGGL(pm_brute_kernel<false>, dim3((n_points + THREADS - 1) / THREADS, n_images), dim3(THREADS), 0, stream, n_points, points,
                        verts, faces, ws + c.v_start, ws + c.f_start, (const int*)nullptr, (const int*)nullptr,
@@ -606,28 +373,15 @@ int sc_point_mesh_distance(const float* points, const float* verts, const int32_
         !dist2 || !face || !closest || ((uintptr_t)workspace & 15))           // no face at all: the twin writes the empty result
         return sc_point_mesh_distance_brute(points, verts, faces, v_count, f_count, n_images, n_points, v_total, f_total, workspace, dist2,
                                             face, closest, stream_);
-    const Carve c = carve(n_images, n_points, f_total);
+    const Workspace c = carve(n_images, n_points, f_total);
     int* ws = (int*)workspace;
     int *v_start = ws + c.v_start, *f_start = ws + c.f_start;
-    unsigned* box = (unsigned*)(ws + c.box);
-    unsigned long long* ext_sum = (unsigned long long*)(ws + c.ext_sum);
     unsigned long long* keys = (unsigned long long*)(ws + c.keys);
     Meta* meta = (Meta*)(ws + c.meta);
     float4* tris = (float4*)(ws + c.tris);
-    const int face_blocks = (f_total + THREADS - 1) / THREADS, query_blocks = (n_points + THREADS - 1) / THREADS;
-    const int n_cells = (int)c.n_cells, nblk = (int)c.nblk;
+    const int query_blocks = (n_points + THREADS - 1) / THREADS;
     (void)hipMemsetAsync(ws, 0, c.cleared * sizeof(int), stream);
-    hipLaunchKernelGGL(pm_offsets_kernel, dim3(1), dim3(64), 0, stream, n_images, v_count, f_count, v_total, f_total, v_start, f_start);
-    hipLaunchKernelGGL(pm_bbox_kernel, dim3(face_blocks), dim3(THREADS), 0, stream, n_images, f_total, verts, faces, v_start, f_start, box, tris);
-    hipLaunchKernelGGL(pm_extent_kernel, dim3(face_blocks), dim3(THREADS), 0, stream, n_images, f_total, f_start, box, tris, ext_sum);
-    hipLaunchKernelGGL(pm_meta_kernel, dim3(1), dim3(THREADS), 0, stream, n_images, box, ext_sum, meta);
-    hipLaunchKernelGGL(pm_bin_kernel<false>, dim3(face_blocks), dim3(THREADS), 0, stream, n_images, f_total, f_start, meta, tris,
-                       ws + c.counts, ws + c.cursor, ws + c.refs, ws + c.large, ws + c.large_count);
-    hipLaunchKernelGGL(pm_scan_local_kernel, dim3(nblk), dim3(1024), 0, stream, n_cells, ws + c.counts, ws + c.block_tot);
-    hipLaunchKernelGGL(pm_scan_totals_kernel, dim3(1), dim3(1024), 0, stream, nblk, ws + c.block_tot);
-    hipLaunchKernelGGL(pm_scan_add_kernel, dim3(nblk), dim3(1024), 0, stream, n_cells, ws + c.counts, ws + c.block_tot);
-    hipLaunchKernelGGL(pm_bin_kernel<true>, dim3(face_blocks), dim3(THREADS), 0, stream, n_images, f_total, f_start, meta, tris,
-                       ws + c.counts, ws + c.cursor, ws + c.refs, ws + c.large, ws + c.large_count);
+    build(ws, c, verts, faces, v_count, f_count, n_images, v_total, f_total, stream);
     hipLaunchKernelGGL(pm_query_kernel, dim3(query_blocks, n_images), dim3(THREADS), 0, stream, n_points, points, meta, f_start,
                        ws + c.counts, ws + c.refs, tris, ws + c.large, ws + c.large_count, dist2, face, closest, ws + c.todo,
                        ws + c.todo_count, keys);

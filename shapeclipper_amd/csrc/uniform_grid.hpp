@@ -1,5 +1,6 @@
 // uniform_grid.hpp -- the uniform grid the exact searches bin their data into before they walk it (chamfer_grid.hip: the target cloud
-// and, for the wave walk, the query cloud; point_normals.hip: the cloud itself; point_mesh.hip: triangles by their boxes).
+// and, for the wave walk, the query cloud; point_normals.hip: the cloud itself; triangle_grid.hpp, for point_mesh.hip and
+// mesh_intersect.hip: triangles by their boxes).
 //
 // The correctness argument of every walk leans on these pieces and on nothing else of the build:
 //   * the box is exact: minima and maxima travel as order-preserving integer keys through atomicMax, so lo / hi are coordinates of the

@@ -714,6 +714,9 @@ class Runner:
         Newton steps onto the SDF's zero set, positions and faces) and {idx}_mesh_subdiv.txt (one line: idx levels project vertices_in
         vertices_out faces_in faces_out edges sharp_edges fixed resid_before resid_after disp_mean disp_max area_before area_after
         volume_before volume_after, lengths in object units);
+        with --mesh.self_intersect also {idx}_mesh_selfx.txt (eval_3D.mesh_intersections: one line per mesh variant written above, in the
+        order mc dual simplified smooth subdiv: idx variant faces degenerate box_pairs pairs pairs_vertex faces_hit first_face
+        first_partner) and, for a variant with a face in a crossing pair only, {idx}_mesh_selfx_{variant}.ply (those faces alone);
         with --eval.icp also {idx}_pointclouds_comp_icp.ply (the ICP-aligned prediction of eval_3D.icp_metrics red, ground truth green);
         with --eval.normals also {idx}_pointclouds_normals.ply (pointclouds_comp's vertices as x y z nx ny nz red green blue: the SDF's
         normals on the prediction, the estimated PCA normals on the ground truth); with --eval.emd also {idx}_pointclouds_emd.ply (the
@@ -757,6 +760,14 @@ class Runner:
                     else eval_3D.meshes_subdivided(opt, var, self.graph.module.sdf_network))
             util_vis.dump_meshes(opt, var.idx, "mesh_subdiv", fine, folder=folder)
             util_vis.dump_lines(opt, var.idx, "mesh_subdiv", eval_3D.subdivided_lines(var), folder=folder)
+        if options.self_intersect_settings(opt):
+            # (eval_metrics tested the meshes already and left the counts in var)
+            if "mesh_intersections" not in var:
+                eval_3D.mesh_intersections(opt, var, self.graph.module.sdf_network)
+            util_vis.dump_lines(opt, var.idx, "mesh_selfx", eval_3D.intersection_lines(var), folder=folder)
+            for variant in var.mesh_intersections:
+                rows, hit = eval_3D.intersection_hit_meshes(opt, var, variant)
+                util_vis.dump_meshes(opt, [var.idx[b] for b in rows], "mesh_selfx_" + variant, hit, folder=folder)
         if options.texture_texels(opt) is not None:
             net = self.graph.module
             var.texture = eval_3D.mesh_texture(opt, net.sdf_network, net.rgb_network, var.proj_latent_sdf, var.proj_latent_rgb, var.level_vox)

@@ -2380,6 +2380,62 @@ def mesh_topology(verts, faces, v_count, f_count, table_slots=None):
                         face_component)
 
 
+# ---- validity: pairs of faces that properly cross (csrc/mesh_intersect.hip) --------------------------------------------------------------
+MESH_INTERSECT_MAX_IMAGES = 65535
+MESH_INTERSECT_MAX_FACES = 1 << 26
+MeshIntersections = collections.namedtuple("MeshIntersections", ["pairs", "pairs_vertex", "box_pairs", "faces_hit", "degenerate", "hits",
+                                                                 "partner"])
+
+
+def mesh_self_intersections(verts, faces, v_count, f_count, search="grid"):
+    """A PackedMesh (mesh_pack.py) of B images, passed as `*mesh` -- verts and faces on the device, v_count / f_count [B] int64 or int32,
+    on the host (as every producer returns them) or on the device -> MeshIntersections, all on the device: pairs [B] int64, the pairs of
+    faces of an image that properly cross; pairs_vertex [B] int64, those of them that share one vertex; box_pairs [B] int64, the pairs
+    that share at most one index and whose closed fp32 boxes overlap (the candidates: a function of the mesh alone, whatever the
+    search); faces_hit [B] int32, the faces in at least one such pair; degenerate [B] int32, the faces that repeat an index (they take
+    part in nothing); hits [F] int32, per packed face how many faces it crosses; partner [F] int32, the lowest image-local face it
+    crosses, or -1.  include/shapeclipper_hip.h states the rule (sc_mesh_self_intersections); tests/mesh_intersect_ref.py restates it in
+    numpy.  The rule is STRICT: a filtered float64 orientation sign that is either zero or the sign of the exact determinant, so every
+    counted pair truly intersects, and contacts with a zero sign -- a vertex on a face, an edge through an edge, coplanar overlap -- are
+    not counted: the count is a lower bound.  Faces that share two or three indices are never a pair.
+    search="grid": the triangle grid of point_mesh_distance (csrc/triangle_grid.hpp), every candidate pair tested once; search="brute":
+    all pairs, the same integers.  Integer atomics only: the same bits from run to run, for any batch, stream and face order.
+
+    ValueError for wrong dtypes, shapes or devices, counts that are negative or do not sum to the packed lengths, a bad search -- all
+    before any launch -- and for a vertex that is not finite or of magnitude 1e15 or more and for a face index outside its image's vertex
+    range: both are flagged on the device (such a face is never dereferenced) and raised after the launches.
+
+    Host synchronisation: one read of the two 4-byte flags after the launches.  Runs on the current stream; the workspace has a fixed
+    capacity (the `_scratch` cache, tag "mesh intersect")."""
+    who = "shapeclipper_amd: mesh_self_intersections"
+    if search not in ("grid", "brute"):
+        raise ValueError("%s: search must be 'grid' or 'brute', got %r" % (who, search))
+    B, V, F, counts_host, _ = check_packed(who, verts, faces, v_count, f_count, max_images=MESH_INTERSECT_MAX_IMAGES,
+                                           max_faces=MESH_INTERSECT_MAX_FACES)
+    dev = verts.device
+    counts = torch.zeros(3, B, device=dev, dtype=torch.int64)
+    face_counts = torch.zeros(2, B, device=dev, dtype=torch.int32)
+    hits = torch.empty(F, device=dev, dtype=torch.int32)
+    partner = torch.empty(F, device=dev, dtype=torch.int32)
+    if B > 0:
+        counts32 = counts_host.int().to(dev)                            # the C entry point takes int32 device counts
+        flags = torch.empty(2, device=dev, dtype=torch.int32)
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            ws = _scratch("mesh intersect", dev, (lib.sc_mesh_self_intersections_scratch_bytes(B, V, F) + 3) // 4)
+            code = lib.sc_mesh_self_intersections(_lib.ptr(verts.contiguous()) if V else None, _lib.ptr(faces.contiguous()) if F else None,
+                                                  _lib.ptr(counts32[0]), _lib.ptr(counts32[1]), B, V, F, 1 if search == "brute" else 0,
+                                                  _lib.ptr(ws), _lib.ptr(counts), _lib.ptr(face_counts), _lib.ptr(hits) if F else None,
+                                                  _lib.ptr(partner) if F else None, _lib.ptr(flags), _lib.stream())
+        _lib.check(code, "sc_mesh_self_intersections")
+        bad_vertex, bad_index = flags.tolist()
+        if bad_vertex:
+            raise ValueError("%s: a vertex is not finite or has a magnitude of 1e15 or more" % who)
+        if bad_index:
+            raise ValueError("%s: a face index lies outside its image's vertex range [0, v_count[b])" % who)
+    return MeshIntersections(counts[0], counts[1], counts[2], face_counts[0], face_counts[1], hits, partner)
+
+
 # ---- evaluation: decimation by vertex clustering with quadric placement (csrc/mesh_simplify.hip) ----------------------------------------
 MESH_SIMPLIFY_MAX_CELLS = 128               # SC_MESH_SIMPLIFY_MAX_CELLS
 MESH_SIMPLIFY_MAX_WORDS = 1 << 28           # mask words of a whole batch: B ceil(G^3 / 64)

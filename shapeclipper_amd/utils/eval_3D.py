@@ -34,6 +34,8 @@ Call surface of the reference's utils/eval_3D.py.
   * meshes_subdivided (`--mesh.subdivide=n`): the marching-cubes mesh after n levels of Loop subdivision (ops.mesh_subdivide,
     csrc/mesh_subdivide.hip), its new vertices put back on the network's zero set by mesh.subdivide_project clamped Newton steps
     (ops.mesh_project_step): four times the faces per level for about 1.5 network evaluations per input face and step.
+  * mesh_intersections (`--mesh.self_intersect`): does a written mesh pass through itself?  The pairs of faces that properly cross
+    (ops.mesh_self_intersections, csrc/mesh_intersect.hip), for every mesh variant the run writes.
 """
 from __future__ import annotations
 
@@ -974,6 +976,99 @@ def subdivided_lines(var):
                                 " ".join("%.9g" % col[b] for col in reals)) for b, i in enumerate(var.idx.cpu().tolist())]
 
 
+INTERSECT_VARIANTS = ("mc", "dual", "simplified", "smooth", "subdiv")      # the order of {idx}_mesh_selfx.txt's lines
+
+
+@torch.no_grad()
+def mesh_intersections(opt, var, sdf_network=None):
+    """`--mesh.self_intersect`: does a written mesh pass through itself?  ops.mesh_self_intersections (csrc/mesh_intersect.hip) on every
+    mesh variant this run writes, in the order of INTERSECT_VARIANTS: "mc", the marching-cubes mesh (var.mesh_packed, built here as
+    mesh_stats does when it is absent); "dual" with `--eval.dual_mesh` (var.mesh_dual_packed, built here with sdf_network when no earlier
+    step left it there; without a network and without that mesh the variant is left out); "simplified", "smooth" and "subdiv" with
+    `--eval.simplify`, `--mesh.smooth` and `--mesh.subdivide`, the meshes eval_metrics' meshers left in var.  Each is tested as it is held:
+    packed, in grid-index units.  The rule is strict (proper crossings only; see the op), so every counted pair truly intersects and the
+    count is a lower bound.  Sets var.mesh_intersections, a dict per variant (var keeps dicts with attribute access) of the fields of
+    ops.MeshIntersections and v_count, f_count [B] int64 on the host.  Runs after the meshers; nothing is repaired, nothing enters a loss."""
+    B = var.level_vox.shape[0]
+    found = {"mc": _mesh_packed(var)}
+    reg = options.dual_mesh_reg(opt)
+    if reg is not None:
+        if "mesh_dual_packed" not in var and sdf_network is not None:
+            dual = meshes_dual(opt, sdf_network, var.proj_latent_sdf, var.level_vox, reg, keep=var)
+            if "mesh_dual" not in var:
+                var.mesh_dual = dual                # serves the dump
+            if "mesh_dual_packed" not in var:       # no crossing vertex in the whole batch
+                var.mesh_dual_packed = list(ops.PackedMesh.empty(B, var.level_vox.device))
+        if "mesh_dual_packed" in var:
+            found["dual"] = ops.PackedMesh(*var.mesh_dual_packed)
+    for variant, key in (("simplified", "mesh_simplified"), ("smooth", "mesh_smoothed"), ("subdiv", "mesh_subdivided")):
+        if key in var:
+            found[variant] = ops.PackedMesh(*(var[key][k] for k in ("verts", "faces", "v_count", "f_count")))
+    out = {}
+    for variant in INTERSECT_VARIANTS:
+        if variant in found:
+            mesh = found[variant]
+            res = ops.mesh_self_intersections(mesh.verts.contiguous(), mesh.faces.contiguous(), mesh.v_count, mesh.f_count)
+            out[variant] = dict(res._asdict(), v_count=mesh.v_count.long().cpu(), f_count=mesh.f_count.long().cpu())
+    var.mesh_intersections = out
+    return out
+
+
+def _intersection_meshes(var, variant):
+    """The packed mesh (grid-index units) a variant of var.mesh_intersections was measured on."""
+    if variant == "mc":
+        return _mesh_packed(var)
+    if variant == "dual":
+        return ops.PackedMesh(*var.mesh_dual_packed)
+    held = var[{"simplified": "mesh_simplified", "smooth": "mesh_smoothed", "subdiv": "mesh_subdivided"}[variant]]
+    return ops.PackedMesh(*(held[k] for k in ("verts", "faces", "v_count", "f_count")))
+
+
+def intersection_lines(var):
+    """Per sample the text of {idx}_mesh_selfx.txt: one line per variant of var.mesh_intersections, in INTERSECT_VARIANTS' order --
+    idx variant faces degenerate box_pairs pairs pairs_vertex faces_hit first_face first_partner (10 fields): first_face is the lowest
+    face of the variant's mesh that crosses another, first_partner the lowest face it crosses; both -1 without a hit.  The lines of a
+    sample are joined by newlines (util_vis.dump_lines writes one text per sample); one host read per field."""
+    idx = var.idx.cpu().tolist()
+    text = [[] for _ in idx]
+    for variant in INTERSECT_VARIANTS:
+        r = var.mesh_intersections.get(variant)
+        if r is None:
+            continue
+        cols = [torch.as_tensor(r[k]).cpu().tolist() for k in ("f_count", "degenerate", "box_pairs", "pairs", "pairs_vertex", "faces_hit")]
+        hits, partner = r["hits"].cpu(), r["partner"].cpu()
+        start = 0
+        for b, i in enumerate(idx):
+            nf = cols[0][b]
+            hit = (hits[start:start + nf] > 0).nonzero()
+            first = int(hit[0]) if len(hit) else -1
+            other = int(partner[start + first]) if first >= 0 else -1
+            text[b].append("%d %s %s %d %d" % (int(i), variant, " ".join("%d" % c[b] for c in cols), first, other))
+            start += nf
+    return ["\n".join(lines) for lines in text]
+
+
+def intersection_hit_meshes(opt, var, variant):
+    """-> (rows, meshes): the samples (positions in the batch) whose `variant` mesh has a face in a hit pair and, for each, (vertices,
+    faces) of the HIT faces alone -- their vertices renumbered in ascending order -- with meshes_device's v / S rescale, which overlays
+    {idx}_mesh.ply: what {idx}_mesh_selfx_{variant}.ply holds."""
+    lo, hi = opt.eval.range
+    S = var.level_vox.shape[1]
+    r = var.mesh_intersections[variant]
+    mesh = _intersection_meshes(var, variant)
+    world = mesh.split(written_position(mesh.verts, lo, hi, S))
+    f_off = mesh.offsets()[1].tolist()
+    faces_hit = torch.as_tensor(r["faces_hit"]).cpu().tolist()
+    rows, meshes = [], []
+    for b, (v, f) in enumerate(world):
+        if faces_hit[b] > 0:
+            keep = f[r["hits"][f_off[b]:f_off[b + 1]] > 0].long()
+            used, renumbered = torch.unique(keep, return_inverse=True)
+            rows.append(b)
+            meshes.append((v[used].contiguous(), renumbered.int().contiguous()))
+    return rows, meshes
+
+
 _FLIP_PRED = [[1, 0, 0], [0, -1, 0], [0, 0, -1]]
 _FLIP_GT = [[-1, 0, 0], [0, 1, 0], [0, 0, 1]]
 
@@ -985,6 +1080,7 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     mesh_dist = None if vis_only else options.mesh_dist_settings(opt)
     want_stats, simplify = options.mesh_stats_settings(opt), options.simplify_settings(opt)
     smooth, subdivide = options.smooth_settings(opt), options.subdivide_settings(opt)
+    self_intersect = options.self_intersect_settings(opt)
     points_3D = get_dense_3D_grid(opt, var)
     B = points_3D.shape[0]
     level_vox = compute_level_grid(opt, sdf_network, var.proj_latent_sdf, points_3D)
@@ -1028,6 +1124,8 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
             meshes_smoothed(opt, var)
         if subdivide is not None:               # vis_{ep}/{idx}_mesh_subdiv.ply and .txt
             meshes_subdivided(opt, var, sdf_network)
+        if self_intersect:                      # vis_{ep}/{idx}_mesh_selfx.txt: after the meshers, on what they left in var
+            mesh_intersections(opt, var, sdf_network)
         return
     dist_acc, dist_comp, idx1, idx2 = chamfer_distance(opt, X1=var.dpc_pred, X2=var.dpc.points)
     var.f_score = compute_fscore(dist_acc, dist_comp, opt.eval.f_thresholds)
@@ -1054,4 +1152,6 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
         meshes_smoothed(opt, var)
     if subdivide is not None:               # likewise
         meshes_subdivided(opt, var, sdf_network)
+    if self_intersect:                      # a check of what is written, after the meshers: no metric reads it
+        mesh_intersections(opt, var, sdf_network)
     return dist_acc.mean(), dist_comp.mean()

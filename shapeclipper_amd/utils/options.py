@@ -251,6 +251,21 @@ def subdivide_settings(opt):
     return None if levels is None else (levels, project)
 
 
+# The checks of the written meshes, in a table and a dict of their own (MESH stays the post-processing steps' five rows): a check
+# changes no mesh and writes no mesh of its own, only a sidecar that says what it found.
+MESH_CHECK_TABLE = tuple(Setting(*row) for row in (
+    ("self_intersect", False, bool, "pairs of faces that properly cross, per written mesh: {idx}_mesh_selfx.txt and the hit faces "
+                                    "{idx}_mesh_selfx_{variant}.ply (ops.mesh_self_intersections)"),
+))
+MESH_CHECK = {row.key: row for row in MESH_CHECK_TABLE}
+
+
+def self_intersect_settings(opt):
+    """`--mesh.self_intersect`, a bool; absent (the key or the whole `mesh` group) means off."""
+    row = MESH_CHECK["self_intersect"]
+    return _checked("mesh", row, (opt.get("mesh", None) or {}).get(row.key, row.default))
+
+
 def parse_arguments(args):
     """--key1.key2=value ; --flag (true) ; --flag! (false)"""
     opt_cmd = {}
@@ -342,7 +357,7 @@ def process_options(opt):
                 raise ValueError("hip.%s must be an integer in %d..%d, got %r" % (row.key, lo, hi, v))
     for check in (dual_mesh_reg, texture_texels, mesh_render, icp_settings, normal_settings, mesh_dist_settings, emd_settings, iou_settings,
                   mesh_stats_settings, simplify_settings,       # every eval.* value is checked here, whether or not its switch is on
-                  smooth_settings, subdivide_settings):         # and every mesh.* value
+                  smooth_settings, subdivide_settings, self_intersect_settings):        # and every mesh.* value
         check(opt)
     torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
     for row in HIP_TABLE:
