@@ -6,7 +6,7 @@
 //                          neighbours; every voxel gets the image-linear index of its tile-local root (-1 outside), every tile-local
 //                          root the voxel count of its piece (0 elsewhere).  Tiles that S does not fill mask their missing voxels.
 //   2. lc_merge_kernel     every inside voxel on a low tile face unites with the inside voxel across the face: integer atomicMin on
-//                          the global label array.
+//                          the global label array (find / unite of mesh_edges.hpp, shared with mesh_topology.hip).
 //   3. lc_flatten_kernel   label[v] = root(v); a tile-local root that is not the global root adds its piece's count to the root's.
 //   4. lc_select_kernel    per image: number of roots, sum of their counts, max of (count << 32 | ~label) -- the largest component,
 //                          the smaller label on a tie -- reduced per workgroup, then one integer atomic each.
@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "shapeclipper_hip.h"
+#include "mesh_edges.hpp"
 
 namespace sc {
 namespace lc {
@@ -49,25 +50,7 @@ __device__ __forceinline__ void unite_lds(int* lab, int a, int b) {
     }
 }
 
-// ---- the same on the global label array of one image; loads go past this CU's L1 (relaxed, agent scope) ----
-__device__ __forceinline__ int find_global(const int* L, int x) {
-    for (;;) {
-        const int p = __hip_atomic_load(L + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p >= x || p < 0) return x;
-        x = p;
-    }
-}
-__device__ __forceinline__ void unite_global(int* L, int a, int b) {
-    for (;;) {
-        a = find_global(L, a);
-        b = find_global(L, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(L + a, b);
-        if (old == a) return;
-        a = old;
-    }
-}
+// ---- the same on the global label array of one image: sc_mesh::find / sc_mesh::unite (mesh_edges.hpp) ----
 
 // grid (T^3, n_images), T = ceil(S / 8)
 __global__ __launch_bounds__(TILE_VOX) void lc_tile_kernel(const float* __restrict__ level, int S, int T, float iso, int* __restrict__ label,
@@ -112,9 +95,9 @@ __global__ __launch_bounds__(256) void lc_merge_kernel(int* label, int S, int pe
     for (int v = blockIdx.x * 256 + threadIdx.x; v < per; v += gridDim.x * 256) {
         if (L[v] < 0) continue;                             // the sign of a label never changes
         const int q = v / S, z = v - q * S, x = q / S, y = q - x * S;
-        if ((x & 7) == 0 && x > 0 && L[v - SS] >= 0) unite_global(L, v, v - SS);
-        if ((y & 7) == 0 && y > 0 && L[v - S] >= 0) unite_global(L, v, v - S);
-        if ((z & 7) == 0 && z > 0 && L[v - 1] >= 0) unite_global(L, v, v - 1);
+        if ((x & 7) == 0 && x > 0 && L[v - SS] >= 0) sc_mesh::unite(L, v, v - SS);
+        if ((y & 7) == 0 && y > 0 && L[v - S] >= 0) sc_mesh::unite(L, v, v - S);
+        if ((z & 7) == 0 && z > 0 && L[v - 1] >= 0) sc_mesh::unite(L, v, v - 1);
     }
 }
 
@@ -124,7 +107,7 @@ __global__ __launch_bounds__(256) void lc_flatten_kernel(int* label, int* count,
     int* C = count + (size_t)blockIdx.y * per;
     for (int v = blockIdx.x * 256 + threadIdx.x; v < per; v += gridDim.x * 256) {
         if (L[v] < 0) continue;
-        const int r = find_global(L, v);
+        const int r = sc_mesh::find(L, v);
         if (r == v) continue;
         L[v] = r;                                           // a reader sees the old parent or the root: both are ancestors
         const int c = C[v];
@@ -192,7 +175,7 @@ __global__ __launch_bounds__(256) void lc_mask_kernel(const float* level, const 
     }
 }
 
-static inline long long align16(long long n) { return (n + 15) / 16 * 16; }
+using sc_mesh::align16;
 
 }  // namespace lc
 }  // namespace sc

@@ -19,13 +19,14 @@
 //  10. ms_emit_kernel      a workgroup per 256 faces: block-scan compaction -> faces_out and face_source in ascending source face number.
 // Every probe ends: an image's region has more slots than it has faces.  Only integer atomics decide anything, so no output depends on
 // the arrival order: the same bits run to run, for any batch, stream and face order (the face LIST follows the source order).
+// image_of, image_add and the scratch carver are those of mesh_edges.hpp; the face table (cluster triples, a region per image) is this file's.
 // Bound: latency of scattered 8-byte atomics (thirteen accumulators per cluster, up to 27 adds per face); not privatised in LDS --
 // docs/LAB_NOTEBOOK.md holds the measured times; not a hot path of training.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <limits.h>
 #include "shapeclipper_hip.h"
-#include "block_scan.hpp"
+#include "mesh_edges.hpp"
 
 namespace sc {
 namespace ms {
@@ -39,6 +40,7 @@ constexpr int MAX_CELLS = 128;                              // 128^3 = 2^21 cell
 constexpr long long MAX_WORDS = 1LL << 28;                  // mask words of the whole batch (2 GiB)
 constexpr int ACC = 13;                                     // n, s[3], A00 A01 A02 A11 A12 A22, b[3]
 constexpr unsigned long long EMPTY = ~0ull;                 // no key looks like this: a key is < 2^63
+using sc_mesh::image_of;
 constexpr double SCALE = 16777216.0;                        // 2^24
 constexpr double CLAMP = 4096.0;                            // 2^12
 static_assert(MAX_CELLS == SC_MESH_SIMPLIFY_MAX_CELLS && ACC == SC_MESH_SIMPLIFY_ACC, "the header states both");
@@ -66,16 +68,6 @@ struct Scratch {
     int* block_off;                 // [ceil(F / THREADS)]
 };
 
-// the image of packed item i: the largest b with off[b] <= i (empty images share their offset with the next)
-__device__ __forceinline__ int image_of(const long long* __restrict__ off, int B, long long i) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // q = (p - o) / h of packed vertex gv and its cell; false for a vertex that takes part in nothing
 __device__ __forceinline__ bool locate(const float* __restrict__ verts, long long gv, const Frame& fr, double (&q)[3], int (&c)[3]) {
     bool ok = true;
@@ -99,32 +91,6 @@ __device__ __forceinline__ void add64(long long* p, long long v) { atomicAdd((un
 __device__ __forceinline__ long long fixed(double t) {
     t = t > CLAMP ? CLAMP : (t < -CLAMP ? -CLAMP : t);
     return __double2ll_rn(t * SCALE);
-}
-
-// counts[field[k]][b] += v[k] for every lane with b >= 0.  Called by whole waves: when the lanes that have something agree on the image
-// the wave folds its values and lane 0 adds them, else every lane adds its own.  Integer sums: the order does not matter.
-template <int K>
-__device__ __forceinline__ void image_add(unsigned long long* counts, int B, int b, const int (&field)[K], int (&v)[K]) {
-    int lo = b < 0 ? INT_MAX : b, hi = b;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const int l = __shfl_xor(lo, d), h = __shfl_xor(hi, d);
-        lo = l < lo ? l : lo, hi = h > hi ? h : hi;
-    }
-    if (hi < 0) return;                                     // wave-uniform
-    if (lo == hi) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            int s = b < 0 ? 0 : v[k];
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-            if ((threadIdx.x & 63) == 0 && s != 0) atomicAdd(counts + (size_t)field[k] * B + lo, (unsigned long long)s);
-        }
-    } else if (b >= 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            if (v[k] != 0) atomicAdd(counts + (size_t)field[k] * B + b, (unsigned long long)v[k]);
-    }
 }
 
 __global__ __launch_bounds__(THREADS) void ms_init_kernel(Scratch s, long long words, long long accs, long long T, int B,
@@ -272,7 +238,7 @@ __global__ __launch_bounds__(THREADS) void ms_face_kernel(const float* __restric
             s.fcode[f] = code;
         }
         const int field[1] = {COLLAPSED};
-        image_add<1>(counts, B, b, field, v);
+        sc_mesh::image_add<1>(counts, B, b, field, v);
     }
 }
 
@@ -334,7 +300,7 @@ __global__ __launch_bounds__(THREADS) void ms_decide_kernel(const long long* __r
     sc_scan::block_exclusive<WAVES>(v[0], wave_tot, total);
     if (threadIdx.x == 0) s.block_cnt[blockIdx.x] = total;
     const int field[2] = {FACES_OUT, CANCELLED};
-    image_add<2>(counts, B, b, field, v);
+    sc_mesh::image_add<2>(counts, B, b, field, v);
 }
 
 // grid: one workgroup
@@ -371,7 +337,7 @@ __global__ __launch_bounds__(THREADS) void ms_emit_kernel(const int* __restrict_
     face_source[at] = (int)(f - f_off[b]);
 }
 
-static inline long long align16(long long n) { return (n + 15) / 16 * 16; }
+using sc_mesh::align16;
 static inline long long words_per_image(int cells) { return ((long long)cells * cells * cells + 63) / 64; }
 static inline bool sizes_ok(int n_images, long long n_verts, long long n_faces, int cells) {
     return n_images >= 1 && n_images <= MAX_IMAGES && n_verts >= 0 && n_verts <= INT_MAX && n_faces >= 0 && n_faces <= MAX_FACES &&
@@ -408,21 +374,20 @@ extern "C" int sc_mesh_cluster_simplify(const float* verts, const int32_t* faces
     const int B = n_images, V = n_verts, F = n_faces;
     const long long Wl = words_per_image(cells), words = (long long)B * Wl, T = 2LL * F + B, FB = face_blocks(F);
     const int W = (int)Wl;
-    char* ws = (char*)scratch;
-    auto take = [&](long long bytes) { char* p = ws; ws += align16(bytes); return p; };
+    sc_mesh::Carver ws{(char*)scratch};
     Scratch s;
-    s.mask = (unsigned long long*)take(8 * words);
-    s.acc = (long long*)take(8LL * ACC * V);
-    s.keys = (unsigned long long*)take(8 * T);
-    s.c_off = (long long*)take(8LL * (B + 1));
-    s.wprefix = (int*)take(4 * words);
-    s.vcell = (int*)take(4LL * V), s.ccell = (int*)take(4LL * V);
-    s.cnt = (int*)take(8 * T), s.minf = (int*)take(8 * T);
-    s.fcode = (int*)take(4LL * F);
-    s.block_cnt = (int*)take(4 * FB), s.block_off = (int*)take(4 * FB);
+    ws.take(s.mask, words);
+    ws.take(s.acc, (long long)ACC * V);
+    ws.take(s.keys, T);
+    ws.take(s.c_off, B + 1LL);
+    ws.take(s.wprefix, words);
+    ws.take(s.vcell, V), ws.take(s.ccell, V);
+    ws.take(s.cnt, 2 * T), ws.take(s.minf, 2 * T);
+    ws.take(s.fcode, F);
+    ws.take(s.block_cnt, FB), ws.take(s.block_off, FB);
     Frame fr;
     fr.o[0] = (double)origin_x, fr.o[1] = (double)origin_y, fr.o[2] = (double)origin_z, fr.h = (double)pitch, fr.G = cells;
-    auto blocks = [](long long n) { const long long g = (n + THREADS - 1) / THREADS; return (unsigned)(g < 1 ? 1 : g > MAX_BLOCKS ? MAX_BLOCKS : g); };
+    constexpr auto blocks = sc_mesh::blocks<THREADS, MAX_BLOCKS>;
     const long long *vo = (const long long*)v_off, *fo = (const long long*)f_off;
     unsigned long long* acc = (unsigned long long*)counts;
     long long widest = words > (long long)ACC * V ? words : (long long)ACC * V;

@@ -3,32 +3,30 @@
 // tests/mesh_smooth_ref.py).  Built without contraction: every float64 operation of a half-step and of the measures rounds once.
 //
 // 7 + (mu != 0 ? 2 : 1) iters launches on one stream (5 + ... when n_faces == 0), no spin barrier, no cooperative launch, no host read:
-//   1. ms_init_kernel      the edge table (keys empty, count 0), the per-vertex degree, cursor and fixed words, the two flags.
-//   2. ms_insert_kernel    a thread per face: range check, then its DISTINCT undirected edges go into the open-addressing table -- the slot
-//                          of key (global lo << 32) | global hi is claimed by a 64-bit atomicCAS on the empty key, linear probing; the
-//                          thread that claims a slot adds one to the degree of both ends; every face adds one to the slot's count.
-//   3. ms_scan_kernel      ONE workgroup: row[i] = the exclusive running sum of the degrees (block_scan.hpp, rounds with a carry).
-//   4. ms_fill_kernel      grid-stride over table slots: each end of an edge goes into the other's row at an integer atomic cursor; a
-//                          slot of count 1 stores 1 into the fixed word of both ends (every writer stores the same word).
-//   5. ms_rows_kernel      a thread per vertex: the float64 start state, the finite check, and its row put into ASCENDING order in a second
-//                          buffer by rank (the elements of a row are distinct, so ranks are unique and the arrival order leaves no
-//                          trace); rows longer than SHORT_ROW are ranked by the whole wave, one after the other.
-//   6. ms_step_kernel      one launch per half-step, a thread per vertex, from one state buffer into the other (Jacobi).
-//   7. ms_measure_kernel   a workgroup per chunk of SC_MESH_SMOOTH_CHUNK vertices of ONE image: a thread per vertex writes the output
+//   1. sm_init_kernel      the edge table (keys empty, count 0), the per-vertex degree, cursor and fixed words, the two flags.
+//   2. sm_insert_kernel    a thread per face: range check, then its DISTINCT undirected edges go into the open-addressing table of
+//                          mesh_edges.hpp; the thread that claims a slot adds one to the degree of both ends; every face adds one to
+//                          the slot's count.
+//   3. sm_scan_kernel      ONE workgroup: row[i] = the exclusive running sum of the degrees (scan_array).
+//   4. sm_fill_kernel      grid-stride over table slots: the rows in arrival order; an edge of one face fixes both its ends (fill_rows).
+//   5. sm_rows_kernel      a thread per vertex: the float64 start state, the finite check, and its row put into ASCENDING order in a second
+//                          buffer (sort_rows).
+//   6. sm_step_kernel      one launch per half-step, a thread per vertex, from one state buffer into the other (Jacobi).
+//   7. sm_measure_kernel   a workgroup per chunk of SC_MESH_SMOOTH_CHUNK vertices of ONE image: a thread per vertex writes the output
 //                          vertex and its three float64 terms to LDS, one lane per column folds it in ascending vertex number; the
 //                          integers by LDS integer atomics; plain stores of the chunk's partials.
-//   8. ms_final_kernel     a thread per image: the chunk partials in ascending chunk number, the means.
-// Every probe ends: the table has more slots than there are half-edges, so an empty slot always exists.  Only integer atomics decide
+//   8. sm_final_kernel     a thread per image: the chunk partials in ascending chunk number, the means.
+// mesh_edges.hpp states why every probe ends and why the sorted rows keep no trace of the arrival order.  Only integer atomics decide
 // anything and no float is accumulated by an atomic: the same bits run to run, for any batch, stream, face order or table size.
 // Bound: launch latency (a few thousand to a few ten thousand vertices) and the latency of the dependent row gathers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <limits.h>
 #include "shapeclipper_hip.h"
-#include "block_scan.hpp"
+#include "mesh_edges.hpp"
 
 namespace sc {
-namespace ms {
+namespace sm {
 
 constexpr int THREADS = 256;
 constexpr int CHUNK = 256;                                  // vertices per chunk of the float64 sums: one workgroup
@@ -39,45 +37,28 @@ constexpr int MAX_BLOCKS = 4096;                            // cap of the grid-s
 constexpr int MAX_IMAGES = 65535;
 constexpr int MAX_FACES = 1 << 26;                          // 6 F < 2^29: row offsets fit an int
 constexpr int MAX_VERTS = 1 << 30;                          // a grid-stride index plus one stride fits an int
-constexpr int MAX_SLOTS = 1 << 30;
-constexpr unsigned long long EMPTY = ~0ull;                 // no key looks like this: hi < 2^31
+using sc_mesh::EMPTY;
+using sc_mesh::image_of;
 static_assert(CHUNK == SC_MESH_SMOOTH_CHUNK && CHUNK == THREADS, "the header states the chunk size; one thread per vertex of a chunk");
 
 enum { FREE, FIXED_BOUNDARY, ISOLATED, DEGREE_MAX, FIELDS };             // rows of counts [FIELDS][n_images]
 enum { ROUGH_BEFORE, ROUGH_AFTER, DISP_MEAN, DISP_MAX, MEASURES };       // rows of measures [MEASURES][n_images]
 static_assert(FIELDS == SC_MESH_SMOOTH_FIELDS && MEASURES == SC_MESH_SMOOTH_MEASURES, "the header states the number of rows");
 
-// the image of packed item i: the largest b with off[b] <= i (off[0] = 0 <= i < off[B]; empty images share their offset with the next)
-__device__ __forceinline__ int image_of(const long long* __restrict__ off, int B, long long i) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-// first chunk slot of image b: chunks of different images never share a slot (ceil(n / CHUNK) <= floor(n / CHUNK) + 1)
-__device__ __forceinline__ long long chunk_start(const long long* __restrict__ v_off, int b) { return v_off[b] / CHUNK + b; }
-
-struct Scratch {
-    unsigned long long* keys;       // [T]
+struct Scratch : sc_mesh::Rings {
     double *state[2];               // [V][3] each: the half-steps go from one into the other
     double* part;                   // [chunk slots][MEASURES]
-    int* count;                     // [T] faces on the edge
-    int *deg, *cursor, *fixed;      // [V]
-    int* row;                       // [V + 1] first entry of every vertex's row
-    int *raw, *nbr;                 // [6 F] the rows in arrival order / in ascending order (batch-global vertex numbers)
     int* ipart;                     // [chunk slots][FIELDS]
 };
 
-__global__ __launch_bounds__(THREADS) void ms_init_kernel(Scratch s, int T, int V, int* bad_vertex, int* bad_index) {
+__global__ __launch_bounds__(THREADS) void sm_init_kernel(Scratch s, int T, int V, int* bad_vertex, int* bad_index) {
     const int step = gridDim.x * THREADS, t0 = blockIdx.x * THREADS + threadIdx.x;
     for (int i = t0; i < T; i += step) s.keys[i] = EMPTY, s.count[i] = 0;
     for (int i = t0; i < V; i += step) s.deg[i] = 0, s.cursor[i] = 0, s.fixed[i] = 0;
     if (t0 == 0) *bad_vertex = 0, *bad_index = 0;
 }
 
-__global__ __launch_bounds__(THREADS) void ms_insert_kernel(const int* __restrict__ faces, const long long* __restrict__ v_off,
+__global__ __launch_bounds__(THREADS) void sm_insert_kernel(const int* __restrict__ faces, const long long* __restrict__ v_off,
                                                             const long long* __restrict__ f_off, int B, int F, Scratch s, int T, int shift,
                                                             int* bad_index) {
     for (int f = blockIdx.x * THREADS + threadIdx.x; f < F; f += gridDim.x * THREADS) {
@@ -99,65 +80,23 @@ __global__ __launch_bounds__(THREADS) void ms_insert_kernel(const int* __restric
         }
         for (int e = 0; e < n; ++e) {
             const unsigned long long glo = (unsigned long long)(vs + lo[e]), ghi = (unsigned long long)(vs + hi[e]);
-            const unsigned long long key = (glo << 32) | ghi;
-            int at = (int)((key * 0x9E3779B97F4A7C15ull) >> shift);
-            unsigned long long old = EMPTY;
-            for (int p = 0; p < T; ++p) {                   // T > 3 F: an empty or matching slot comes first
-                old = atomicCAS(s.keys + at, EMPTY, key);
-                if (old == EMPTY || old == key) break;
-                at = (at + 1) & (T - 1);
-            }
-            if (old == EMPTY) atomicAdd(s.deg + glo, 1), atomicAdd(s.deg + ghi, 1);       // the one thread that claimed the slot
-            atomicAdd(s.count + at, 1);
+            const sc_mesh::EdgeSlot slot = sc_mesh::edge_slot(s.keys, T, shift, glo, ghi);
+            if (slot.claimed) atomicAdd(s.deg + glo, 1), atomicAdd(s.deg + ghi, 1);
+            atomicAdd(s.count + slot.at, 1);
         }
     }
 }
 
 // ONE workgroup: row[i] = deg[0] + ... + deg[i - 1], row[V] = the number of row entries
-__global__ __launch_bounds__(SCAN_THREADS) void ms_scan_kernel(Scratch s, int V) {
+__global__ __launch_bounds__(SCAN_THREADS) void sm_scan_kernel(Scratch s, int V) {
     __shared__ int wave_tot[SCAN_THREADS / 64];
-    int carry = 0;
-    for (long long base = 0; base < V; base += SCAN_THREADS * SCAN_ITEMS) {          // workgroup-uniform
-        const long long i0 = base + (long long)threadIdx.x * SCAN_ITEMS;
-        int d[SCAN_ITEMS], sum = 0;
-#pragma unroll
-        for (int k = 0; k < SCAN_ITEMS; ++k) d[k] = i0 + k < V ? s.deg[i0 + k] : 0, sum += d[k];
-        int total;
-        int before = carry + sc_scan::block_exclusive<SCAN_THREADS / 64>(sum, wave_tot, total);
-#pragma unroll
-        for (int k = 0; k < SCAN_ITEMS; ++k) {
-            if (i0 + k < V) s.row[i0 + k] = before;
-            before += d[k];
-        }
-        carry += total;
-        __syncthreads();                                    // the next round writes wave_tot again
-    }
-    if (threadIdx.x == 0) s.row[V] = carry;
+    sc_mesh::scan_array<SCAN_THREADS, SCAN_ITEMS>(s.deg, s.row, V, wave_tot);
 }
 
-__global__ __launch_bounds__(THREADS) void ms_fill_kernel(Scratch s, int T) {
-    for (int i = blockIdx.x * THREADS + threadIdx.x; i < T; i += gridDim.x * THREADS) {
-        const unsigned long long key = s.keys[i];
-        if (key == EMPTY) continue;
-        const int lo = (int)(key >> 32), hi = (int)(key & 0xFFFFFFFFull);
-        s.raw[s.row[lo] + atomicAdd(s.cursor + lo, 1)] = hi;
-        s.raw[s.row[hi] + atomicAdd(s.cursor + hi, 1)] = lo;
-        if (s.count[i] == 1) s.fixed[lo] = 1, s.fixed[hi] = 1;                       // every writer stores the same word
-    }
-}
+__global__ __launch_bounds__(THREADS) void sm_fill_kernel(Scratch s, int T) { sc_mesh::fill_rows<THREADS, true>(s, T); }
 
-// raw[r0 + k], k in lanes `first`, first + stride, ... of a row of d distinct elements -> nbr[r0 + rank]
-__device__ __forceinline__ void rank_row(const int* __restrict__ raw, int* __restrict__ nbr, int r0, int d, int first, int stride) {
-    for (int k = first; k < d; k += stride) {
-        const int e = raw[r0 + k];
-        int rank = 0;
-        for (int t = 0; t < d; ++t) rank += raw[r0 + t] < e;
-        nbr[r0 + rank] = e;
-    }
-}
-
-__global__ __launch_bounds__(THREADS) void ms_rows_kernel(const float* __restrict__ verts, Scratch s, int V, int* bad_vertex) {
-    for (int base = blockIdx.x * THREADS; base < V; base += gridDim.x * THREADS) {   // wave-uniform: the waves cooperate below
+__global__ __launch_bounds__(THREADS) void sm_rows_kernel(const float* __restrict__ verts, Scratch s, int V, int* bad_vertex) {
+    for (int base = blockIdx.x * THREADS; base < V; base += gridDim.x * THREADS) {   // wave-uniform: the waves cooperate in sort_rows
         const int i = base + threadIdx.x;
         int r0 = 0, d = 0;
         if (i < V) {
@@ -166,18 +105,12 @@ __global__ __launch_bounds__(THREADS) void ms_rows_kernel(const float* __restric
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float x = verts[3 * (size_t)i + c];
-                finite = finite && x - x == 0.0f;           // false for an infinity and for a NaN
+                finite = finite && sc_mesh::finite(x);
                 s.state[0][3 * (size_t)i + c] = (double)x;
             }
             if (!finite) atomicOr(bad_vertex, 1);
-            if (d <= SHORT_ROW) rank_row(s.raw, s.nbr, r0, d, 0, 1);
         }
-        unsigned long long todo = __ballot(d > SHORT_ROW);
-        while (todo) {                                      // wave-uniform
-            const int lane = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            rank_row(s.raw, s.nbr, __shfl(r0, lane), __shfl(d, lane), threadIdx.x & 63, 64);
-        }
+        sc_mesh::sort_rows<SHORT_ROW>(s, r0, d);
     }
 }
 
@@ -194,7 +127,7 @@ __device__ __forceinline__ void umbrella_mean(const X* __restrict__ x, const int
     m[0] = sx / n, m[1] = sy / n, m[2] = sz / n;
 }
 
-__global__ __launch_bounds__(THREADS) void ms_step_kernel(const double* __restrict__ src, double* __restrict__ dst, Scratch s, int V,
+__global__ __launch_bounds__(THREADS) void sm_step_kernel(const double* __restrict__ src, double* __restrict__ dst, Scratch s, int V,
                                                           double factor) {
     for (int i = blockIdx.x * THREADS + threadIdx.x; i < V; i += gridDim.x * THREADS) {
         const int r0 = s.row[i], r1 = s.row[i + 1];
@@ -217,17 +150,13 @@ __global__ __launch_bounds__(THREADS) void ms_step_kernel(const double* __restri
 __device__ __forceinline__ double norm3(double dx, double dy, double dz) { return __dsqrt_rn((dx * dx + dy * dy) + dz * dz); }
 
 // grid: one workgroup per chunk slot
-__global__ __launch_bounds__(THREADS) void ms_measure_kernel(const float* __restrict__ verts, const long long* __restrict__ v_off, int B,
+__global__ __launch_bounds__(THREADS) void sm_measure_kernel(const float* __restrict__ verts, const long long* __restrict__ v_off, int B,
                                                              Scratch s, const double* __restrict__ last, float* __restrict__ verts_out) {
     __shared__ double term[3][CHUNK];
     __shared__ int tally[FIELDS];
-    int lo = 0, hi = B;                                     // the largest b with chunk_start(b) <= blockIdx.x
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (chunk_start(v_off, mid) <= (long long)blockIdx.x) lo = mid; else hi = mid;
-    }
-    const int b = lo;
-    const long long first = v_off[b] + ((long long)blockIdx.x - chunk_start(v_off, b)) * CHUNK, end = v_off[b + 1];
+    long long first;
+    const int b = sc_mesh::chunk_image<CHUNK>(v_off, B, first);
+    const long long end = v_off[b + 1];
     if (first >= end) return;                               // a slot no image uses (workgroup-uniform)
     if (threadIdx.x < FIELDS) tally[threadIdx.x] = 0;
     __syncthreads();
@@ -267,11 +196,11 @@ __global__ __launch_bounds__(THREADS) void ms_measure_kernel(const float* __rest
     if (threadIdx.x < FIELDS) s.ipart[FIELDS * (size_t)blockIdx.x + threadIdx.x] = tally[threadIdx.x];
 }
 
-__global__ __launch_bounds__(THREADS) void ms_final_kernel(const long long* __restrict__ v_off, int B, Scratch s, long long* __restrict__ counts,
+__global__ __launch_bounds__(THREADS) void sm_final_kernel(const long long* __restrict__ v_off, int B, Scratch s, long long* __restrict__ counts,
                                                            double* __restrict__ measures) {
     const int b = blockIdx.x * THREADS + threadIdx.x;
     if (b >= B) return;
-    const long long chunks = (v_off[b + 1] - v_off[b] + CHUNK - 1) / CHUNK, start = chunk_start(v_off, b);
+    const long long chunks = (v_off[b + 1] - v_off[b] + CHUNK - 1) / CHUNK, start = sc_mesh::chunk_start<CHUNK>(v_off, b);
     double sum[3] = {0.0, 0.0, 0.0}, top = 0.0;
     long long n[FIELDS] = {0, 0, 0, 0};
     for (long long c = 0; c < chunks; ++c) {
@@ -293,20 +222,21 @@ __global__ __launch_bounds__(THREADS) void ms_final_kernel(const long long* __re
     measures[(size_t)DISP_MAX * B + b] = any ? top : 0.0;
 }
 
-static inline long long align16(long long n) { return (n + 15) / 16 * 16; }
+using sc_mesh::align16;
 static inline bool sizes_ok(int n_images, long long n_verts, long long n_faces, long long table_slots) {
     return n_images >= 1 && n_images <= MAX_IMAGES && n_verts >= 0 && n_verts <= MAX_VERTS && n_faces >= 0 && n_faces <= MAX_FACES &&
-           table_slots >= 1 && table_slots <= MAX_SLOTS && (table_slots & (table_slots - 1)) == 0 && table_slots > 3 * n_faces;
+           sc_mesh::slots_ok(table_slots, n_faces);
 }
-static inline long long chunk_slots(int n_images, long long n_verts) { return n_verts / CHUNK + n_images; }
+constexpr auto chunk_slots = sc_mesh::chunk_slots<CHUNK>;
+constexpr auto blocks = sc_mesh::blocks<THREADS, MAX_BLOCKS>;
 
-}  // namespace ms
+}  // namespace sm
 }  // namespace sc
 
 // scratch layout: keys [T] u64 | state 0, state 1 [V][3] f64 | part [slots][4] f64 | count [T] | deg, cursor, fixed [V] | row [V + 1] |
 // raw, nbr [6 F] | ipart [slots][4]
 extern "C" long long sc_mesh_smooth_scratch_bytes(int n_images, int n_verts, int n_faces, int table_slots) {
-    using namespace sc::ms;
+    using namespace sc::sm;
     if (!sizes_ok(n_images, n_verts, n_faces, table_slots)) return 0;
     const long long T = table_slots, F = n_faces, V = n_verts, slots = chunk_slots(n_images, V);
     return align16(8 * T) + 2 * align16(24 * V) + align16(8 * MEASURES * slots) + align16(4 * T) + 3 * align16(4 * V) + align16(4 * (V + 1)) +
@@ -316,7 +246,7 @@ extern "C" long long sc_mesh_smooth_scratch_bytes(int n_images, int n_verts, int
 extern "C" int sc_mesh_smooth(const float* verts, const int32_t* faces, const int64_t* v_off, const int64_t* f_off, int n_images, int n_verts,
                               int n_faces, int table_slots, int iters, double lam, double mu, void* scratch, float* verts_out,
                               int64_t* counts, double* measures, int32_t* bad_vertex, int32_t* bad_index, void* stream_) {
-    using namespace sc::ms;
+    using namespace sc::sm;
     if (n_images <= 0) return 0;
     if (!sizes_ok(n_images, n_verts, n_faces, table_slots) || iters < 0 || iters > SC_MESH_SMOOTH_MAX_ITERS || !(lam > 0.0 && lam <= 1.0) ||
         !(mu >= -1.0 && mu <= 0.0) || !v_off || !f_off || !counts || !measures || !bad_vertex || !bad_index || !scratch ||
@@ -324,42 +254,39 @@ extern "C" int sc_mesh_smooth(const float* verts, const int32_t* faces, const in
         return (int)hipErrorInvalidValue;
     hipStream_t stream = (hipStream_t)stream_;
     const int B = n_images, V = n_verts, F = n_faces, T = table_slots;
-    int shift = 64;                                         // the top log2(T) bits of the mixed key (T >= 4 when F > 0)
-    for (int t = T; t > 1; t >>= 1) --shift;
+    const int shift = sc_mesh::table_shift(T);
     const long long slots = chunk_slots(B, V);
-    char* ws = (char*)scratch;
-    auto take = [&](long long bytes) { char* p = ws; ws += align16(bytes); return p; };
+    sc_mesh::Carver ws{(char*)scratch};
     Scratch s;
-    s.keys = (unsigned long long*)take(8LL * T);
-    s.state[0] = (double*)take(24LL * V), s.state[1] = (double*)take(24LL * V);
-    s.part = (double*)take(8LL * MEASURES * slots);
-    s.count = (int*)take(4LL * T);
-    s.deg = (int*)take(4LL * V), s.cursor = (int*)take(4LL * V), s.fixed = (int*)take(4LL * V);
-    s.row = (int*)take(4LL * (V + 1LL));
-    s.raw = (int*)take(24LL * F), s.nbr = (int*)take(24LL * F);
-    s.ipart = (int*)take(4LL * FIELDS * slots);
-    auto blocks = [](long long n) { const long long g = (n + THREADS - 1) / THREADS; return (unsigned)(g < 1 ? 1 : g > MAX_BLOCKS ? MAX_BLOCKS : g); };
+    ws.take(s.keys, T);
+    ws.take(s.state[0], 3LL * V), ws.take(s.state[1], 3LL * V);
+    ws.take(s.part, MEASURES * slots);
+    ws.take(s.count, T);
+    ws.take(s.deg, V), ws.take(s.cursor, V), ws.take(s.fixed, V);
+    ws.take(s.row, V + 1LL);
+    ws.take(s.raw, 6LL * F), ws.take(s.nbr, 6LL * F);
+    ws.take(s.ipart, FIELDS * slots);
     const long long *vo = (const long long*)v_off, *fo = (const long long*)f_off;
-    hipLaunchKernelGGL(ms_init_kernel, dim3(blocks(T > V ? T : V)), dim3(THREADS), 0, stream, s, T, V, bad_vertex, bad_index);
+    hipLaunchKernelGGL(sm_init_kernel, dim3(blocks(T > V ? T : V)), dim3(THREADS), 0, stream, s, T, V, bad_vertex, bad_index);
     if (F > 0)
-        hipLaunchKernelGGL(ms_insert_kernel, dim3(blocks(F)), dim3(THREADS), 0, stream, faces, vo, fo, B, F, s, T, shift, bad_index);
-    hipLaunchKernelGGL(ms_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, s, V);
-    if (F > 0) hipLaunchKernelGGL(ms_fill_kernel, dim3(blocks(T)), dim3(THREADS), 0, stream, s, T);
+        hipLaunchKernelGGL(sm_insert_kernel, dim3(blocks(F)), dim3(THREADS), 0, stream, faces, vo, fo, B, F, s, T, shift, bad_index);
+    hipLaunchKernelGGL(sm_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, s, V);
+    if (F > 0) hipLaunchKernelGGL(sm_fill_kernel, dim3(blocks(T)), dim3(THREADS), 0, stream, s, T);
     int at = 0;                                             // the state buffer that holds the current state
     if (V > 0) {
-        hipLaunchKernelGGL(ms_rows_kernel, dim3(blocks(V)), dim3(THREADS), 0, stream, verts, s, V, bad_vertex);
+        hipLaunchKernelGGL(sm_rows_kernel, dim3(blocks(V)), dim3(THREADS), 0, stream, verts, s, V, bad_vertex);
         for (int it = 0; it < iters; ++it) {
-            hipLaunchKernelGGL(ms_step_kernel, dim3(blocks(V)), dim3(THREADS), 0, stream, (const double*)s.state[at], s.state[at ^ 1], s, V, lam);
+            hipLaunchKernelGGL(sm_step_kernel, dim3(blocks(V)), dim3(THREADS), 0, stream, (const double*)s.state[at], s.state[at ^ 1], s, V, lam);
             at ^= 1;
             if (mu != 0.0) {
-                hipLaunchKernelGGL(ms_step_kernel, dim3(blocks(V)), dim3(THREADS), 0, stream, (const double*)s.state[at], s.state[at ^ 1], s, V, mu);
+                hipLaunchKernelGGL(sm_step_kernel, dim3(blocks(V)), dim3(THREADS), 0, stream, (const double*)s.state[at], s.state[at ^ 1], s, V, mu);
                 at ^= 1;
             }
         }
     }
-    hipLaunchKernelGGL(ms_measure_kernel, dim3((unsigned)slots), dim3(THREADS), 0, stream, verts, vo, B, s, (const double*)s.state[at],
+    hipLaunchKernelGGL(sm_measure_kernel, dim3((unsigned)slots), dim3(THREADS), 0, stream, verts, vo, B, s, (const double*)s.state[at],
                        verts_out);
-    hipLaunchKernelGGL(ms_final_kernel, dim3((unsigned)((B + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream, vo, B, s, (long long*)counts,
+    hipLaunchKernelGGL(sm_final_kernel, dim3((unsigned)((B + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream, vo, B, s, (long long*)counts,
                        measures);
     return (int)hipGetLastError();
 }

@@ -8,23 +8,20 @@
 //   1. sd_init_kernel     the edge table (keys empty, count 0, owner and omin INT_MAX, omax -1), the per-vertex degree, cursor and fixed
 //                         words, the three flags.
 //   2. sd_insert_kernel   a thread per face: range and repeated-index check, then its three undirected edges go into the open-addressing
-//                         table -- the slot of key (global lo << 32) | global hi is claimed by a 64-bit atomicCAS on the empty key, linear
-//                         probing; the thread that claims a slot adds one to the degree of both ends; every half-edge adds one to the slot's
-//                         count, takes part in the atomicMin of `owner` with its number 3 f + c and in the atomicMin / atomicMax of omin /
-//                         omax with its opposite corner, and remembers its slot.
+//                         table of mesh_edges.hpp; the thread that claims a slot adds one to the degree of both ends; every half-edge
+//                         adds one to the slot's count, takes part in the atomicMin of `owner` with its number 3 f + c and in the
+//                         atomicMin / atomicMax of omin / omax with its opposite corner, and remembers its slot.
 //   3. sd_owner_kernel    a thread per half-edge: the flag "I am my edge's owner".
 //   4. sd_scan_kernel     ONE workgroup: row[i] = the exclusive running sum of the degrees, rank[h] = the exclusive running sum of the owner
-//                         flags (block_scan.hpp, rounds with a carry).  rank[3 f_off[b+1]] - rank[3 f_off[b]] is image b's edge count, and
+//                         flags (scan_array, twice).  rank[3 f_off[b+1]] - rank[3 f_off[b]] is image b's edge count, and
 //                         rank[3 f_off[b]] the new vertices of the images before it: the output offsets.
-//   5. sd_fill_kernel     grid-stride over table slots: each end of an edge goes into the other's row at an integer atomic cursor; a slot
-//                         whose count is not 2 stores 1 into the fixed word of both ends (every writer stores the same word).
-//   6. sd_rows_kernel     a thread per vertex: the finite check, and its row put into ASCENDING order in a second buffer by rank (the
-//                         elements of a row are distinct, so ranks are unique and the arrival order leaves no trace); rows longer than
-//                         SHORT_ROW are ranked by the whole wave, one after the other.
+//   5. sd_fill_kernel     grid-stride over table slots: the rows in arrival order; an edge whose count is not 2 is sharp and fixes both
+//                         its ends (fill_rows).
+//   6. sd_rows_kernel     a thread per vertex: the finite check, and its row put into ASCENDING order in a second buffer (sort_rows).
 //   7. sd_emit_kernel     grid-stride, three passes: a thread per old vertex (the even rule), per half-edge (an owner writes its edge's new
 //                         vertex) and per face (its four faces).  All read the input vertices only.
 //   8. sd_final_kernel    a workgroup per image: the six counts by LDS integer atomics.
-// Every probe ends: the table has more slots than there are half-edges, so an empty slot always exists.  Only integer atomics decide
+// mesh_edges.hpp states why every probe ends and why the sorted rows keep no trace of the arrival order.  Only integer atomics decide
 // anything and no float is accumulated by an atomic: the same bits run to run, for any batch, stream and table size; the numbering follows
 // the input face order.
 // Bound: launch latency (a few thousand to a few hundred thousand faces), the scattered 8-byte compare-and-swaps and the one-workgroup scan.
@@ -32,7 +29,7 @@
 #include <stdint.h>
 #include <limits.h>
 #include "shapeclipper_hip.h"
-#include "block_scan.hpp"
+#include "mesh_edges.hpp"
 
 namespace sc {
 namespace sd {
@@ -46,28 +43,14 @@ constexpr int MAX_BLOCKS = 4096;                            // cap of the grid-s
 constexpr int MAX_IMAGES = 65535;
 constexpr int MAX_FACES = 1 << 24;                          // 4 F <= 2^26: the output is an input of the next level
 constexpr int MAX_VERTS = 1 << 30;                          // V + 3 F < 2^31
-constexpr int MAX_SLOTS = 1 << 30;
-constexpr unsigned long long EMPTY = ~0ull;                 // no key looks like this: hi < 2^31
+using sc_mesh::EMPTY;
+using sc_mesh::image_of;
 
 enum { VERTICES_OUT, EDGES, SHARP_EDGES, FIXED_VERTICES, ISOLATED, DEGREE_MAX, FIELDS };     // rows of counts [FIELDS][n_images]
 static_assert(FIELDS == SC_MESH_SUBDIVIDE_FIELDS, "the header states the number of rows");
 
-// the image of packed item i: the largest b with off[b] <= i (off[0] = 0 <= i < off[B]; empty images share their offset with the next)
-__device__ __forceinline__ int image_of(const long long* __restrict__ off, int B, long long i) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-struct Scratch {
-    unsigned long long* keys;       // [T]
-    int *count, *owner, *omin, *omax;       // [T] faces on the edge, its lowest half-edge, its lowest and highest opposite vertex (global)
-    int *deg, *cursor, *fixed;      // [V]
-    int* row;                       // [V + 1] first entry of every vertex's row
-    int *raw, *nbr;                 // [6 F] the rows in arrival order / in ascending order (batch-global vertex numbers)
+struct Scratch : sc_mesh::Rings {
+    int *owner, *omin, *omax;       // [T] the edge's lowest half-edge, its lowest and highest opposite vertex (global)
     int* hslot;                     // [3 F] the slot of half-edge 3 f + c; -1 for a face that takes part in nothing
     int* rank;                      // [3 F + 1] owner flags, then their exclusive running sum
 };
@@ -96,15 +79,9 @@ __global__ __launch_bounds__(THREADS) void sd_insert_kernel(const int* __restric
         for (int c = 0; c < 3; ++c) {                       // corner c's edge runs from i_c to i_{c+1}; i_{c+2} lies opposite
             const int a = i[c], e = i[c == 2 ? 0 : c + 1], opp = (int)vs + i[c == 0 ? 2 : c - 1];
             const unsigned long long glo = (unsigned long long)(vs + (a < e ? a : e)), ghi = (unsigned long long)(vs + (a < e ? e : a));
-            const unsigned long long key = (glo << 32) | ghi;
-            int at = (int)((key * 0x9E3779B97F4A7C15ull) >> shift);
-            unsigned long long old = EMPTY;
-            for (int p = 0; p < T; ++p) {                   // T > 3 F: an empty or matching slot comes first
-                old = atomicCAS(s.keys + at, EMPTY, key);
-                if (old == EMPTY || old == key) break;
-                at = (at + 1) & (T - 1);
-            }
-            if (old == EMPTY) atomicAdd(s.deg + glo, 1), atomicAdd(s.deg + ghi, 1);       // the one thread that claimed the slot
+            const sc_mesh::EdgeSlot slot = sc_mesh::edge_slot(s.keys, T, shift, glo, ghi);
+            const int at = slot.at;
+            if (slot.claimed) atomicAdd(s.deg + glo, 1), atomicAdd(s.deg + ghi, 1);
             atomicAdd(s.count + at, 1);
             atomicMin(s.owner + at, 3 * f + c);
             atomicMin(s.omin + at, opp);
@@ -121,75 +98,26 @@ __global__ __launch_bounds__(THREADS) void sd_owner_kernel(Scratch s, int H) {
     }
 }
 
-// ONE workgroup: a[i] = a[0] + ... + a[i - 1] for i < n from `in` into `out` (which may be the same array), out[n] = the total
-__device__ __forceinline__ void scan_array(const int* in, int* out, int n, int* wave_tot) {
-    int carry = 0;
-    for (long long base = 0; base < n; base += SCAN_THREADS * SCAN_ITEMS) {             // workgroup-uniform
-        const long long i0 = base + (long long)threadIdx.x * SCAN_ITEMS;
-        int d[SCAN_ITEMS], sum = 0;
-#pragma unroll
-        for (int k = 0; k < SCAN_ITEMS; ++k) d[k] = i0 + k < n ? in[i0 + k] : 0, sum += d[k];
-        int total;
-        int before = carry + sc_scan::block_exclusive<SCAN_THREADS / 64>(sum, wave_tot, total);
-#pragma unroll
-        for (int k = 0; k < SCAN_ITEMS; ++k) {
-            if (i0 + k < n) out[i0 + k] = before;
-            before += d[k];
-        }
-        carry += total;
-        __syncthreads();                                    // the next round writes wave_tot again
-    }
-    if (threadIdx.x == 0) out[n] = carry;
-}
-
 __global__ __launch_bounds__(SCAN_THREADS) void sd_scan_kernel(Scratch s, int V, int H) {
     __shared__ int wave_tot[SCAN_THREADS / 64];
-    scan_array(s.deg, s.row, V, wave_tot);
-    scan_array(s.rank, s.rank, H, wave_tot);
+    sc_mesh::scan_array<SCAN_THREADS, SCAN_ITEMS>(s.deg, s.row, V, wave_tot);
+    sc_mesh::scan_array<SCAN_THREADS, SCAN_ITEMS>(s.rank, s.rank, H, wave_tot);
 }
 
-__global__ __launch_bounds__(THREADS) void sd_fill_kernel(Scratch s, int T) {
-    for (int i = blockIdx.x * THREADS + threadIdx.x; i < T; i += gridDim.x * THREADS) {
-        const unsigned long long key = s.keys[i];
-        if (key == EMPTY) continue;
-        const int lo = (int)(key >> 32), hi = (int)(key & 0xFFFFFFFFull);
-        s.raw[s.row[lo] + atomicAdd(s.cursor + lo, 1)] = hi;
-        s.raw[s.row[hi] + atomicAdd(s.cursor + hi, 1)] = lo;
-        if (s.count[i] != 2) s.fixed[lo] = 1, s.fixed[hi] = 1;                      // a sharp edge; every writer stores the same word
-    }
-}
-
-// raw[r0 + k], k in lanes `first`, first + stride, ... of a row of d distinct elements -> nbr[r0 + rank]
-__device__ __forceinline__ void rank_row(const int* __restrict__ raw, int* __restrict__ nbr, int r0, int d, int first, int stride) {
-    for (int k = first; k < d; k += stride) {
-        const int e = raw[r0 + k];
-        int rank = 0;
-        for (int t = 0; t < d; ++t) rank += raw[r0 + t] < e;
-        nbr[r0 + rank] = e;
-    }
-}
+__global__ __launch_bounds__(THREADS) void sd_fill_kernel(Scratch s, int T) { sc_mesh::fill_rows<THREADS, false>(s, T); }
 
 __global__ __launch_bounds__(THREADS) void sd_rows_kernel(const float* __restrict__ verts, Scratch s, int V, int* bad_vertex) {
-    for (int base = blockIdx.x * THREADS; base < V; base += gridDim.x * THREADS) {   // wave-uniform: the waves cooperate below
+    for (int base = blockIdx.x * THREADS; base < V; base += gridDim.x * THREADS) {   // wave-uniform: the waves cooperate in sort_rows
         const int i = base + threadIdx.x;
         int r0 = 0, d = 0;
         if (i < V) {
             r0 = s.row[i], d = s.row[i + 1] - r0;
             bool finite = true;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float x = verts[3 * (size_t)i + c];
-                finite = finite && x - x == 0.0f;           // false for an infinity and for a NaN
-            }
+            for (int c = 0; c < 3; ++c) finite = finite && sc_mesh::finite(verts[3 * (size_t)i + c]);
             if (!finite) atomicOr(bad_vertex, 1);
-            if (d <= SHORT_ROW) rank_row(s.raw, s.nbr, r0, d, 0, 1);
         }
-        unsigned long long todo = __ballot(d > SHORT_ROW);
-        while (todo) {                                      // wave-uniform
-            const int lane = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            rank_row(s.raw, s.nbr, __shfl(r0, lane), __shfl(d, lane), threadIdx.x & 63, 64);
-        }
+        sc_mesh::sort_rows<SHORT_ROW>(s, r0, d);
     }
 }
 
@@ -313,7 +241,7 @@ __global__ __launch_bounds__(THREADS) void sd_project_kernel(const float* __rest
         const float f = sdf[i];
         const float g2 = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
         float out[3] = {v[0], v[1], v[2]};
-        if (!fixed[i] && f - f == 0.0f && g2 - g2 == 0.0f && !(g2 < 1e-12f)) {
+        if (!fixed[i] && sc_mesh::finite(f) && sc_mesh::finite(g2) && !(g2 < 1e-12f)) {
             const float t = __fdiv_rn(f, g2);
             float d[3];
 #pragma unroll
@@ -323,7 +251,7 @@ __global__ __launch_bounds__(THREADS) void sd_project_kernel(const float* __rest
             }
             // sqrtf is the correctly rounded one (hipcc's default); __fsqrt_rn is not, see emd3d.hip
             const float l = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-            if (l - l == 0.0f) {
+            if (sc_mesh::finite(l)) {
                 if (l > max_step) {
                     const float r = __fdiv_rn(max_step, l);
 #pragma unroll
@@ -338,15 +266,12 @@ __global__ __launch_bounds__(THREADS) void sd_project_kernel(const float* __rest
     }
 }
 
-static inline long long align16(long long n) { return (n + 15) / 16 * 16; }
+using sc_mesh::align16;
 static inline bool sizes_ok(int n_images, long long n_verts, long long n_faces, long long table_slots) {
     return n_images >= 1 && n_images <= MAX_IMAGES && n_verts >= 0 && n_verts <= MAX_VERTS && n_faces >= 0 && n_faces <= MAX_FACES &&
-           table_slots >= 1 && table_slots <= MAX_SLOTS && (table_slots & (table_slots - 1)) == 0 && table_slots > 3 * n_faces;
+           sc_mesh::slots_ok(table_slots, n_faces);
 }
-static inline unsigned blocks(long long n) {
-    const long long g = (n + THREADS - 1) / THREADS;
-    return (unsigned)(g < 1 ? 1 : g > MAX_BLOCKS ? MAX_BLOCKS : g);
-}
+constexpr auto blocks = sc_mesh::blocks<THREADS, MAX_BLOCKS>;
 
 }  // namespace sd
 }  // namespace sc
@@ -373,18 +298,16 @@ extern "C" int sc_mesh_subdivide(const float* verts, const int32_t* faces, const
         return (int)hipErrorInvalidValue;
     hipStream_t stream = (hipStream_t)stream_;
     const int B = n_images, V = n_verts, F = n_faces, T = table_slots;
-    int shift = 64;                                         // the top log2(T) bits of the mixed key (T >= 4 when F > 0)
-    for (int t = T; t > 1; t >>= 1) --shift;
-    char* ws = (char*)scratch;
-    auto take = [&](long long bytes) { char* p = ws; ws += align16(bytes); return p; };
+    const int shift = sc_mesh::table_shift(T);
+    sc_mesh::Carver ws{(char*)scratch};
     Scratch s;
-    s.keys = (unsigned long long*)take(8LL * T);
-    s.count = (int*)take(4LL * T), s.owner = (int*)take(4LL * T), s.omin = (int*)take(4LL * T), s.omax = (int*)take(4LL * T);
-    s.deg = (int*)take(4LL * V), s.cursor = (int*)take(4LL * V), s.fixed = (int*)take(4LL * V);
-    s.row = (int*)take(4LL * (V + 1LL));
-    s.raw = (int*)take(24LL * F), s.nbr = (int*)take(24LL * F);
-    s.hslot = (int*)take(12LL * F);
-    s.rank = (int*)take(4LL * (3LL * F + 1));
+    ws.take(s.keys, T);
+    ws.take(s.count, T), ws.take(s.owner, T), ws.take(s.omin, T), ws.take(s.omax, T);
+    ws.take(s.deg, V), ws.take(s.cursor, V), ws.take(s.fixed, V);
+    ws.take(s.row, V + 1LL);
+    ws.take(s.raw, 6LL * F), ws.take(s.nbr, 6LL * F);
+    ws.take(s.hslot, 3LL * F);
+    ws.take(s.rank, 3LL * F + 1);
     const long long *vo = (const long long*)v_off, *fo = (const long long*)f_off;
     hipLaunchKernelGGL(sd_init_kernel, dim3(blocks(T > V ? T : V)), dim3(THREADS), 0, stream, s, T, V, bad_vertex, bad_index, bad_face);
     if (F > 0) {

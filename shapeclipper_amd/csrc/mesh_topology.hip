@@ -5,12 +5,10 @@
 // Seven launches on one stream, no spin barrier, no cooperative launch, no host read:
 //   1. mt_init_kernel      the edge table (keys empty, count 0, fwd 0, minface INT_MAX), the per-vertex words and the outputs.
 //   2. mt_insert_kernel    a thread per face: range check, degenerate check, then its three undirected edges go into the open-addressing
-//                          table -- the slot of key (global lo << 32) | global hi is claimed by a 64-bit atomicCAS on the empty key,
-//                          linear probing; integer atomicAdd on count and fwd, atomicMin on minface.  The slot of every half-edge is kept.
+//                          table of mesh_edges.hpp; integer atomicAdd on count and fwd, atomicMin on minface.  The slot of every
+//                          half-edge is kept.
 //   3. mt_unite_kernel     a thread per half-edge: the face unites with the edge's minface, its two corners on the edge with minface's
-//                          corners at the same vertices.  Two union-finds (faces, corners) with the atomicMin hooking of
-//                          level_components.hip: a parent is a SMALLER index, every find loop walks strictly decreasing labels and ends
-//                          whatever other threads do.
+//                          corners at the same vertices.  Two union-finds (faces, corners), the one of mesh_edges.hpp.
 //   4. mt_flatten_kernel   a thread per face: face_component = root - first face of the image; roots count components, every face adds
 //                          one to its root's size; every corner root adds one fan to its vertex.
 //   5. mt_count_kernel     grid-stride over table slots (edges by count and fwd), vertices (referenced, fans) and faces (largest
@@ -18,13 +16,14 @@
 //   6. mt_measure_kernel   a workgroup per chunk of SC_MESH_TOPOLOGY_CHUNK faces of ONE image: a thread per face writes its two
 //                          float64 terms to LDS, one lane adds each of the two columns in ascending face index; plain stores.
 //   7. mt_final_kernel     a thread per image: the chunk partials in ascending chunk number, euler, the three flags, genus.
-// Every probe ends: the table has more slots than there are half-edges, so an empty slot always exists.  Only integer atomics decide
-// integer outputs and no float is accumulated by an atomic: the same bits run to run, for any batch, stream or table size.
+// mesh_edges.hpp states why every probe and every find loop ends.  Only integer atomics decide integer outputs and no float is
+// accumulated by an atomic: the same bits run to run, for any batch, stream or table size.
 // Bound: latency of scattered 8- and 4-byte atomics on the table and of dependent label loads; not a hot path of training.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <limits.h>
 #include "shapeclipper_hip.h"
+#include "mesh_edges.hpp"
 
 namespace sc {
 namespace mt {
@@ -34,71 +33,14 @@ constexpr int CHUNK = 256;                                  // faces per chunk o
 constexpr int MAX_BLOCKS = 4096;                            // cap of the grid-stride passes
 constexpr int MAX_IMAGES = 65535;
 constexpr int MAX_FACES = 1 << 26;                          // 3 F < 2^28: half-edge and corner numbers fit an int
-constexpr int MAX_SLOTS = 1 << 30;
-constexpr unsigned long long EMPTY = ~0ull;                 // no key looks like this: hi < 2^31
+using sc_mesh::EMPTY;
+using sc_mesh::image_of;
 static_assert(CHUNK == SC_MESH_TOPOLOGY_CHUNK && CHUNK == THREADS, "the header states the chunk size; one thread per face of a chunk");
 
 // rows of counts [SC_MESH_TOPOLOGY_FIELDS][n_images]
 enum { VERTICES, UNREFERENCED, FACES, DEGENERATE, EDGES, BOUNDARY, NONMANIFOLD_E, INCONSISTENT, COMPONENTS, LARGEST, NONMANIFOLD_V, EULER,
        GENUS, WATERTIGHT, ORIENTED, MANIFOLD, FIELDS };
 static_assert(FIELDS == SC_MESH_TOPOLOGY_FIELDS, "the header states the number of rows");
-
-// the image of packed item i: the largest b with off[b] <= i (off[0] = 0 <= i < off[B]; empty images share their offset with the next)
-__device__ __forceinline__ int image_of(const long long* __restrict__ off, int B, long long i) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-// first chunk slot of image b: chunks of different images never share a slot (ceil(n / CHUNK) <= floor(n / CHUNK) + 1)
-__device__ __forceinline__ long long chunk_start(const long long* __restrict__ f_off, int b) { return f_off[b] / CHUNK + b; }
-
-__device__ __forceinline__ int find(const int* L, int x) {
-    for (;;) {
-        const int p = __hip_atomic_load(L + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p >= x || p < 0) return x;
-        x = p;
-    }
-}
-__device__ __forceinline__ void unite(int* L, int a, int b) {
-    for (;;) {
-        a = find(L, a);
-        b = find(L, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(L + a, b);                // a > b: a's parent becomes min(its parent, b)
-        if (old == a) return;                               // a was a root: linked
-        a = old;                                            // a had a parent: that one and b are still to be united
-    }
-}
-
-// counts[field[k]][b] += v[k] for every lane with b >= 0.  Called by whole waves: when the lanes that have something agree on the image
-// the wave folds its values and lane 0 adds them, else every lane adds its own.  Integer sums: the order does not matter.
-template <int K>
-__device__ __forceinline__ void image_add(unsigned long long* counts, int B, int b, const int (&field)[K], int (&v)[K]) {
-    int lo = b < 0 ? INT_MAX : b, hi = b;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const int l = __shfl_xor(lo, d), h = __shfl_xor(hi, d);
-        lo = l < lo ? l : lo, hi = h > hi ? h : hi;
-    }
-    if (hi < 0) return;                                     // wave-uniform
-    if (lo == hi) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            int s = b < 0 ? 0 : v[k];
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-            if ((threadIdx.x & 63) == 0 && s != 0) atomicAdd(counts + (size_t)field[k] * B + lo, (unsigned long long)s);
-        }
-    } else if (b >= 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            if (v[k] != 0) atomicAdd(counts + (size_t)field[k] * B + b, (unsigned long long)v[k]);
-    }
-}
 
 struct Scratch {
     unsigned long long* keys;       // [T]
@@ -145,13 +87,7 @@ __global__ __launch_bounds__(THREADS) void mt_insert_kernel(const int* __restric
                     s.vref[vs + i[k]] = 1;                  // every writer stores the same word
                     const int a = i[k], c = i[k == 2 ? 0 : k + 1];
                     const unsigned long long glo = (unsigned long long)(vs + (a < c ? a : c)), ghi = (unsigned long long)(vs + (a < c ? c : a));
-                    const unsigned long long key = (glo << 32) | ghi;
-                    int at = (int)((key * 0x9E3779B97F4A7C15ull) >> shift);
-                    for (int n = 0; n < T; ++n) {           // T > 3 F: an empty or matching slot comes first
-                        const unsigned long long old = atomicCAS(s.keys + at, EMPTY, key);
-                        if (old == EMPTY || old == key) break;
-                        at = (at + 1) & (T - 1);
-                    }
+                    const int at = sc_mesh::edge_slot(s.keys, T, shift, glo, ghi).at;
                     atomicAdd(s.count + at, 1);
                     if (a < c) atomicAdd(s.fwd + at, 1);    // the face lists the lower end first
                     atomicMin(s.minface + at, f);
@@ -160,7 +96,7 @@ __global__ __launch_bounds__(THREADS) void mt_insert_kernel(const int* __restric
             }
         }
         const int field[2] = {FACES, DEGENERATE};
-        image_add<2>(counts, B, b, field, v);
+        sc_mesh::image_add<2>(counts, B, b, field, v);
     }
 }
 
@@ -170,12 +106,12 @@ __global__ __launch_bounds__(THREADS) void mt_unite_kernel(const int* __restrict
         if (at < 0) continue;
         const int f = h / 3, k = h - 3 * f, m = s.minface[at];
         if (m == f) continue;
-        unite(s.flabel, f, m);
+        sc_mesh::unite(s.flabel, f, m);
         const int k1 = k == 2 ? 0 : k + 1;
         const int a = faces[3 * f + k], c = faces[3 * f + k1];
         const int m0 = faces[3 * m], m1 = faces[3 * m + 1];     // m lies on the edge: it holds a and c
-        unite(s.clabel, 3 * f + k, 3 * m + (m0 == a ? 0 : m1 == a ? 1 : 2));
-        unite(s.clabel, 3 * f + k1, 3 * m + (m0 == c ? 0 : m1 == c ? 1 : 2));
+        sc_mesh::unite(s.clabel, 3 * f + k, 3 * m + (m0 == a ? 0 : m1 == a ? 1 : 2));
+        sc_mesh::unite(s.clabel, 3 * f + k1, 3 * m + (m0 == c ? 0 : m1 == c ? 1 : 2));
     }
 }
 
@@ -188,16 +124,16 @@ __global__ __launch_bounds__(THREADS) void mt_flatten_kernel(const int* __restri
         int v[1] = {0};
         if (f < F && s.slot[3 * f] >= 0) {                  // a face that takes part
             b = image_of(f_off, B, f);
-            const int r = find(s.flabel, f);
+            const int r = sc_mesh::find(s.flabel, f);
             face_component[f] = r - (int)f_off[b];
             atomicAdd(s.fsize + r, 1);
             v[0] = r == f;
             const long long vs = v_off[b];
             for (int k = 0; k < 3; ++k)
-                if (find(s.clabel, 3 * f + k) == 3 * f + k) atomicAdd(s.vfans + vs + faces[3 * f + k], 1);
+                if (sc_mesh::find(s.clabel, 3 * f + k) == 3 * f + k) atomicAdd(s.vfans + vs + faces[3 * f + k], 1);
         }
         const int field[1] = {COMPONENTS};
-        image_add<1>(counts, B, b, field, v);
+        sc_mesh::image_add<1>(counts, B, b, field, v);
     }
 }
 
@@ -217,7 +153,7 @@ __global__ __launch_bounds__(THREADS) void mt_count_kernel(const long long* __re
             }
         }
         const int field[4] = {EDGES, BOUNDARY, NONMANIFOLD_E, INCONSISTENT};
-        image_add<4>(counts, B, b, field, v);
+        sc_mesh::image_add<4>(counts, B, b, field, v);
     }
     for (int base = blockIdx.x * THREADS; base < V; base += step) {
         const int i = base + threadIdx.x;
@@ -229,7 +165,7 @@ __global__ __launch_bounds__(THREADS) void mt_count_kernel(const long long* __re
             v[0] = ref, v[1] = !ref, v[2] = s.vfans[i] > 1;
         }
         const int field[3] = {VERTICES, UNREFERENCED, NONMANIFOLD_V};
-        image_add<3>(counts, B, b, field, v);
+        sc_mesh::image_add<3>(counts, B, b, field, v);
     }
     for (int f = blockIdx.x * THREADS + threadIdx.x; f < F; f += step)
         if (s.flabel[f] == f) atomicMax(counts + (size_t)LARGEST * B + image_of(f_off, B, f), (unsigned long long)s.fsize[f]);
@@ -240,13 +176,9 @@ __global__ __launch_bounds__(THREADS) void mt_measure_kernel(const float* __rest
                                                              const long long* __restrict__ v_off, const long long* __restrict__ f_off, int B,
                                                              double* __restrict__ part) {
     __shared__ double term[2][CHUNK];
-    int lo = 0, hi = B;                                     // the largest b with chunk_start(b) <= blockIdx.x
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (chunk_start(f_off, mid) <= (long long)blockIdx.x) lo = mid; else hi = mid;
-    }
-    const int b = lo;
-    const long long first = f_off[b] + ((long long)blockIdx.x - chunk_start(f_off, b)) * CHUNK, end = f_off[b + 1];
+    long long first;
+    const int b = sc_mesh::chunk_image<CHUNK>(f_off, B, first);
+    const long long end = f_off[b + 1];
     if (first >= end) return;                               // a slot no image uses (workgroup-uniform)
     const long long f = first + threadIdx.x, vs = v_off[b], nv = v_off[b + 1] - vs;
     double a = 0.0, w = 0.0;                                // a face that takes part in nothing adds +0.0
@@ -284,7 +216,7 @@ __global__ __launch_bounds__(THREADS) void mt_final_kernel(const long long* __re
                                                            long long* counts, double* __restrict__ area, double* __restrict__ volume) {
     const int b = blockIdx.x * THREADS + threadIdx.x;
     if (b >= B) return;
-    const long long chunks = (f_off[b + 1] - f_off[b] + CHUNK - 1) / CHUNK, start = chunk_start(f_off, b);
+    const long long chunks = (f_off[b + 1] - f_off[b] + CHUNK - 1) / CHUNK, start = sc_mesh::chunk_start<CHUNK>(f_off, b);
     double a = 0.0, w = 0.0;
     for (long long c = 0; c < chunks; ++c) a += part[2 * (start + c)], w += part[2 * (start + c) + 1];
     area[b] = a, volume[b] = w;
@@ -297,12 +229,13 @@ __global__ __launch_bounds__(THREADS) void mt_final_kernel(const long long* __re
     at(GENUS) = (watertight && oriented && manifold && at(FACES) > 0) ? at(COMPONENTS) - euler / 2 : -1;
 }
 
-static inline long long align16(long long n) { return (n + 15) / 16 * 16; }
+using sc_mesh::align16;
 static inline bool sizes_ok(int n_images, long long n_verts, long long n_faces, long long table_slots) {
     return n_images >= 1 && n_images <= MAX_IMAGES && n_verts >= 0 && n_verts <= INT_MAX && n_faces >= 0 && n_faces <= MAX_FACES &&
-           table_slots >= 1 && table_slots <= MAX_SLOTS && (table_slots & (table_slots - 1)) == 0 && table_slots > 3 * n_faces;
+           sc_mesh::slots_ok(table_slots, n_faces);
 }
-static inline long long chunk_slots(int n_images, long long n_faces) { return n_faces / CHUNK + n_images; }
+constexpr auto chunk_slots = sc_mesh::chunk_slots<CHUNK>;
+constexpr auto blocks = sc_mesh::blocks<THREADS, MAX_BLOCKS>;
 
 }  // namespace mt
 }  // namespace sc
@@ -326,19 +259,16 @@ extern "C" int sc_mesh_topology(const float* verts, const int32_t* faces, const 
         return (int)hipErrorInvalidValue;
     hipStream_t stream = (hipStream_t)stream_;
     const int B = n_images, V = n_verts, F = n_faces, T = table_slots;
-    int shift = 64;                                         // the top log2(T) bits of the mixed key (T >= 2 when F > 0)
-    for (int t = T; t > 1; t >>= 1) --shift;
-    char* ws = (char*)scratch;
-    auto take = [&](long long bytes) { char* p = ws; ws += align16(bytes); return p; };
+    const int shift = sc_mesh::table_shift(T);
+    sc_mesh::Carver ws{(char*)scratch};
     Scratch s;
-    s.keys = (unsigned long long*)take(8LL * T);
-    s.part = (double*)take(16LL * chunk_slots(B, F));
-    s.count = (int*)take(4LL * T), s.fwd = (int*)take(4LL * T), s.minface = (int*)take(4LL * T);
-    s.slot = (int*)take(12LL * F);
-    s.flabel = (int*)take(4LL * F), s.fsize = (int*)take(4LL * F);
-    s.clabel = (int*)take(12LL * F);
-    s.vref = (int*)take(4LL * V), s.vfans = (int*)take(4LL * V);
-    auto blocks = [](long long n) { const long long g = (n + THREADS - 1) / THREADS; return (unsigned)(g < 1 ? 1 : g > MAX_BLOCKS ? MAX_BLOCKS : g); };
+    ws.take(s.keys, T);
+    ws.take(s.part, 2 * chunk_slots(B, F));
+    ws.take(s.count, T), ws.take(s.fwd, T), ws.take(s.minface, T);
+    ws.take(s.slot, 3LL * F);
+    ws.take(s.flabel, F), ws.take(s.fsize, F);
+    ws.take(s.clabel, 3LL * F);
+    ws.take(s.vref, V), ws.take(s.vfans, V);
     const long long widest = T > V ? T : V;
     const long long *vo = (const long long*)v_off, *fo = (const long long*)f_off;
     unsigned long long* acc = (unsigned long long*)counts;

@@ -2329,6 +2329,21 @@ def mesh_topology_slots(n_faces: int) -> int:
     return 1 << (6 * n_faces + 1).bit_length()
 
 
+def _edge_table_slots(who, n_faces, table_slots, default=True):
+    """table_slots, validated for a mesh of n_faces faces; for None, the default size (or None where the caller sizes the table later)."""
+    if table_slots is None:
+        return mesh_topology_slots(n_faces) if default else None
+    if (isinstance(table_slots, bool) or not isinstance(table_slots, int) or table_slots < 1 or table_slots & (table_slots - 1)
+            or table_slots <= 3 * n_faces or table_slots > MESH_TOPOLOGY_MAX_SLOTS):
+        raise ValueError("%s: table_slots must be a power of two greater than 3 F = %d (and at most 2^30), got %r"
+                         % (who, 3 * n_faces, table_slots))
+    return table_slots
+
+
+def _finite_number(x):
+    return isinstance(x, (int, float)) and not isinstance(x, bool) and x == x and abs(x) != float("inf")
+
+
 def mesh_topology(verts, faces, v_count, f_count, table_slots=None):
     """A PackedMesh (mesh_pack.py) of B images, passed as `*mesh` -- verts and faces on the device, v_count / f_count [B] int64 or int32,
     on the host (as every producer returns them) or on the device -> MeshTopology of [B] int64 device tensors vertices (referenced
@@ -2354,11 +2369,7 @@ def mesh_topology(verts, faces, v_count, f_count, table_slots=None):
     B, V, F, _, offsets = check_packed(who, verts, faces, v_count, f_count, max_images=MESH_TOPOLOGY_MAX_IMAGES,
                                        max_faces=MESH_TOPOLOGY_MAX_FACES)
     dev = verts.device
-    if table_slots is None:
-        table_slots = mesh_topology_slots(F)
-    if (isinstance(table_slots, bool) or not isinstance(table_slots, int) or table_slots < 1 or table_slots & (table_slots - 1)
-            or table_slots <= 3 * F or table_slots > MESH_TOPOLOGY_MAX_SLOTS):
-        raise ValueError("%s: table_slots must be a power of two greater than 3 F = %d (and at most 2^30), got %r" % (who, 3 * F, table_slots))
+    table_slots = _edge_table_slots(who, F, table_slots)
     counts = torch.empty(len(MESH_TOPOLOGY_COUNTS) + len(MESH_TOPOLOGY_FLAGS), B, device=dev, dtype=torch.int64)
     measures = torch.empty(2, B, device=dev, dtype=torch.float64)
     face_component = torch.empty(F, device=dev, dtype=torch.int32)
@@ -2470,16 +2481,15 @@ def mesh_cluster_simplify(verts, faces, v_count, f_count, origin, pitch, cells, 
     B, V, F, counts_host, offsets = check_packed(who, verts, faces, v_count, f_count, max_images=MESH_TOPOLOGY_MAX_IMAGES,
                                                  max_faces=MESH_TOPOLOGY_MAX_FACES)
     dev = verts.device
-    number = lambda x: isinstance(x, (int, float)) and not isinstance(x, bool) and x == x and abs(x) != float("inf")
     if isinstance(origin, torch.Tensor):
         origin = origin.detach().cpu().reshape(-1).tolist()
-    if not isinstance(origin, (list, tuple)) or len(origin) != 3 or not all(number(x) for x in origin):
+    if not isinstance(origin, (list, tuple)) or len(origin) != 3 or not all(_finite_number(x) for x in origin):
         raise ValueError("%s: origin must be three finite numbers, got %r" % (who, origin))
-    if not number(pitch) or not pitch > 0 or not float(torch.tensor(float(pitch), dtype=torch.float32)) > 0:
+    if not _finite_number(pitch) or not pitch > 0 or not float(torch.tensor(float(pitch), dtype=torch.float32)) > 0:
         raise ValueError("%s: pitch must be a finite number > 0 (as fp32), got %r" % (who, pitch))
     if isinstance(cells, bool) or not isinstance(cells, int) or not 1 <= cells <= MESH_SIMPLIFY_MAX_CELLS:
         raise ValueError("%s: cells must be an integer in 1..%d, got %r" % (who, MESH_SIMPLIFY_MAX_CELLS, cells))
-    if not number(reg) or not reg > 0:
+    if not _finite_number(reg) or not reg > 0:
         raise ValueError("%s: reg must be a finite number > 0, got %r" % (who, reg))
     if B * ((cells ** 3 + 63) // 64) > MESH_SIMPLIFY_MAX_WORDS:
         raise ValueError("%s takes B ceil(cells^3 / 64) <= 2^28 mask words per call, got B = %d and cells = %d" % (who, B, cells))
@@ -2552,18 +2562,13 @@ def mesh_smooth(verts, faces, v_count, f_count, iters, lam=0.5, mu=MESH_SMOOTH_M
     dev = verts.device
     if V > MESH_SMOOTH_MAX_VERTS:
         raise ValueError("%s: verts: at most 2^30 vertices per call, got %d" % (who, V))
-    number = lambda x: isinstance(x, (int, float)) and not isinstance(x, bool) and x == x and abs(x) != float("inf")
     if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= MESH_SMOOTH_MAX_ITERS:
         raise ValueError("%s: iters must be an integer in 0..%d, got %r" % (who, MESH_SMOOTH_MAX_ITERS, iters))
-    if not number(lam) or not 0 < lam <= 1:
+    if not _finite_number(lam) or not 0 < lam <= 1:
         raise ValueError("%s: lam must be a finite number in (0, 1], got %r" % (who, lam))
-    if not number(mu) or not -1 <= mu <= 0:
+    if not _finite_number(mu) or not -1 <= mu <= 0:
         raise ValueError("%s: mu must be a finite number in [-1, 0], got %r" % (who, mu))
-    if table_slots is None:
-        table_slots = mesh_topology_slots(F)
-    if (isinstance(table_slots, bool) or not isinstance(table_slots, int) or table_slots < 1 or table_slots & (table_slots - 1)
-            or table_slots <= 3 * F or table_slots > MESH_TOPOLOGY_MAX_SLOTS):
-        raise ValueError("%s: table_slots must be a power of two greater than 3 F = %d (and at most 2^30), got %r" % (who, 3 * F, table_slots))
+    table_slots = _edge_table_slots(who, F, table_slots)
     verts_out = torch.empty(V, 3, device=dev, dtype=torch.float32)
     counts = torch.zeros(len(MESH_SMOOTH_COUNTS), B, device=dev, dtype=torch.int64)
     measures = torch.zeros(len(MESH_SMOOTH_MEASURES), B, device=dev, dtype=torch.float64)
@@ -2632,9 +2637,7 @@ def mesh_subdivide(verts, faces, v_count, f_count, levels=1, table_slots=None):
         raise ValueError("%s: levels must be an integer in 1..%d, got %r" % (who, MESH_SUBDIVIDE_MAX_LEVELS, levels))
     if F * 4 ** (levels - 1) > MESH_SUBDIVIDE_MAX_FACES:
         raise ValueError("%s: faces: at most 2^24 faces may go into a level (4 F <= 2^26), got %d into level %d" % (who, F * 4 ** (levels - 1), levels))
-    if table_slots is not None and (isinstance(table_slots, bool) or not isinstance(table_slots, int) or table_slots < 1
-                                    or table_slots & (table_slots - 1) or table_slots <= 3 * F or table_slots > MESH_TOPOLOGY_MAX_SLOTS):
-        raise ValueError("%s: table_slots must be a power of two greater than 3 F = %d (and at most 2^30), got %r" % (who, 3 * F, table_slots))
+    table_slots = _edge_table_slots(who, F, table_slots, default=False)
     fixed = torch.zeros(V, device=dev, dtype=torch.bool)
     n_fields = len(MESH_SUBDIVIDE_COUNTS)
     counts = torch.zeros(n_fields, B, device=dev, dtype=torch.int64)
@@ -2692,10 +2695,9 @@ def mesh_project_step(verts, sdf, grad, fixed, scale, max_step):
                          % (who, tuple(verts.shape), tuple(sdf.shape), tuple(grad.shape), tuple(fixed.shape)))
     if V > MESH_SMOOTH_MAX_VERTS:
         raise ValueError("shapeclipper_amd: %s: verts: at most 2^30 vertices per call, got %d" % (who, V))
-    number = lambda x: isinstance(x, (int, float)) and not isinstance(x, bool) and x == x and abs(x) != float("inf")
-    if not number(scale) or not scale > 0:
+    if not _finite_number(scale) or not scale > 0:
         raise ValueError("shapeclipper_amd: %s: scale must be a finite number > 0, got %r" % (who, scale))
-    if not number(max_step) or not max_step >= 0:
+    if not _finite_number(max_step) or not max_step >= 0:
         raise ValueError("shapeclipper_amd: %s: max_step must be a finite number >= 0, got %r" % (who, max_step))
     out = torch.empty_like(verts)
     if V:
