@@ -420,22 +420,22 @@ def test_sdf_backward_nonfused_float64_budget(case, symmetric, feat):
 K_RGB = dict(out=4.0, point=8.0, w_rgb=4.0, latent=4.0)
 
 
-def _rgb_case(n_images, rpi, seed):
-    """Per-point SDF results from the HIP forward (fp32), points off the rays: the compositing kernel only sees numbers."""
+def _rgb_case(n_images, rpi, seed, S=64):
+    """Per-point SDF results from the HIP forward (fp32), points off the rays: the compositing kernel only sees numbers.  S samples per ray."""
     from oracle import reference_ops as R
     from shapeclipper_amd import ops, packing
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(seed)
-    cfg = R.Cfg()
+    cfg = R.Cfg(n_samples=S)
     Ws, Wr = R.init_sdf_weights(cfg, 1), R.init_rgb_weights(cfg, 2)
     zs, zr = torch.randn(n_images, 64, generator=g) * 0.3, torch.randn(n_images, 64, generator=g) * 0.3
     n_rays = n_images * rpi
-    pts = torch.rand(n_rays * 64, 3, generator=g) * 1.6 - 0.8
-    z = torch.sort(torch.rand(n_rays, 64, generator=g) * 2 + 4, dim=1).values
+    pts = torch.rand(n_rays * S, 3, generator=g) * 1.6 - 0.8
+    z = torch.sort(torch.rand(n_rays, S, generator=g) * 2 + 4, dim=1).values
     dfac = torch.rand(n_rays, generator=g) * 0.2 + 0.9
     sdf_pack, cb = packing.pack_sdf({k: v.to(dev) for k, v in Ws.items()}, zs.to(dev))
-    sdf, grad, feat = ops.sdf_forward(pts.to(dev), sdf_pack, cb, rpi * 64)
-    ins = dict(points=pts, z_vals=z, depth_fac=dfac, sdf=sdf.cpu(), grad=grad.cpu(), feat=packing.tbl_to_rows(feat, n_rays * 64).cpu(),
+    sdf, grad, feat = ops.sdf_forward(pts.to(dev), sdf_pack, cb, rpi * S)
+    ins = dict(points=pts, z_vals=z, depth_fac=dfac, sdf=sdf.cpu(), grad=grad.cpu(), feat=packing.tbl_to_rows(feat, n_rays * S).cpu(),
                beta=torch.tensor([0.1]))
     return cfg, ins, Wr, zr
 
@@ -444,7 +444,7 @@ def _rgb_oracle(cfg, ins, Wr, zr, rpi, cot, dt):
     """float64 / fp32 restatement of the compositing (R.rgb_mlp, R.laplace_density, R.volume_rendering, the sums of R.render)."""
     import torch.nn.functional as F
     from oracle import reference_ops as R
-    S = 64
+    S = ins["z_vals"].shape[1]
     with R.default_dtype(dt):
         L = {k: v.to(dt).clone().requires_grad_(True) for k, v in ins.items()}
         Wl = {k: v.to(dt).clone().requires_grad_(True) for k, v in Wr.items()}
@@ -491,9 +491,9 @@ def _rgb_hip(ins, Wr, zr, rpi, cot):
     return outs, grads
 
 
-def _rgb_refs(n_images, rpi):
+def _rgb_refs(n_images, rpi, S=64):
     """Inputs, the rays that hit, cotangents (normals only where a ray hits) and the float64 / fp32 oracle outputs and gradients."""
-    cfg, ins, Wr, zr = _rgb_case(n_images, rpi, seed=n_images * 100 + rpi)
+    cfg, ins, Wr, zr = _rgb_case(n_images, rpi, seed=n_images * 100 + rpi + (S - 64), S=S)
     n_rays = n_images * rpi
     o64, _ = _rgb_oracle(cfg, ins, Wr, zr, rpi, None, torch.float64)
     hit = (o64["mask"] - 0.5).abs() > 1e-3
