@@ -1189,6 +1189,75 @@ int sc_mesh_subdivide(const float* verts, const int32_t* faces, const int64_t* v
 int sc_mesh_project_step(const float* verts, const float* sdf, const float* grad, const uint8_t* fixed, int n_verts, float scale,
                          float max_step, float* verts_out, void* stream);
 
+/* ---- post-processing: one round of quadric edge-collapse decimation towards a face budget (csrc/mesh_decimate.hip) -------------------
+ * What ops.mesh_decimate runs and {idx}_mesh_decimated.ply holds (`--mesh.decimate`).  A batch of packed meshes in the form of
+ * sc_mesh_topology above (verts, faces with image-local indices, v_off / f_off); everything below is per image.
+ * sc_mesh_decimate_round does ONE round, a pure function of the mesh it is given: quadrics are recomputed from the current faces every
+ * round ("memoryless" simplification) and nothing but the vertex map `parent` is carried from round to round.  The caller repeats rounds
+ * and ends with sc_mesh_decimate_compact.  tests/mesh_decimate_ref.py restates every rule in numpy.  All real arithmetic is float64 from
+ * the exactly widened fp32 positions x_i, every operation rounded once (the file is built without contraction), every sum in the stated
+ * order; a position is rounded to fp32 once, when it is written.
+ *
+ * Faces, half-edges, edges (count, owner, omin, omax) and FIXED vertices (on an edge whose count is not 2: the rim that the grid face
+ *   cuts, non-manifold spots) are those of sc_mesh_subdivide above, with its three flags: flags[0] a vertex that is not finite, flags[1]
+ *   a face index out of range (never dereferenced), flags[2] a face that repeats an index; such faces take part in nothing and the
+ *   caller raises.  A fixed vertex is never moved and never removed.  ring(i) = the vertices that share an edge with i, ASCENDING.
+ * Triangle terms.  For a vertex v and two others u, w:  N = (x_u - x_v) x (x_w - x_v), each component  a b - c d  with the two products
+ *   rounded;  d = (N.x p.x + N.y p.y) + N.z p.z  with p = x_v;  the ten terms are
+ *       N.x N.x, N.x N.y, N.x N.z, N.y N.y, N.y N.z, N.z N.z,   N.x d, N.y d, N.z d,   d d
+ *   None of them depends on the orientation of (u, w).
+ * Vertex quadric.  Q_v = (A00 A01 A02 A11 A12 A22, b0 b1 b2, c) starts at +0.0 and adds, term by term:  for u in ring(v) ascending, the
+ *   terms of (v, u, omin(v,u)), then, if omax(v,u) != omin(v,u), those of (v, u, omax(v,u)).  On a manifold interior vertex every face is
+ *   met twice, which scales every quadric alike.  No float atomic.
+ * Candidates.  An edge (a, b), a < b, is a candidate when  count == 2,  a and b are not both fixed,  ring(a) and ring(b) have exactly two
+ *   common vertices (the link condition),  and not  |ring(a)| == |ring(b)| == 3  (the tetrahedron, which would fold flat).  An edge with
+ *   two faces and a free end that fails the last two is counted in rejected_link.
+ * Target and cost.  Q = Q_a + Q_b component by component;  m = 0.5 (x_a + x_b).  If a is fixed x = x_a, else if b is fixed x = x_b, else
+ *       lam = reg ((A00 + A11) + A22);  if not lam > 0:  x = m;  else
+ *       d00 = A00 + lam; d11 = A11 + lam; d22 = A22 + lam;   r_j = b_j + lam m_j
+ *       l10 = A01 / d00;  l20 = A02 / d00;  e1 = d11 - l10 A01;  t21 = A12 - l20 A01;  l21 = t21 / e1;  e2 = (d22 - l20 A02) - l21 t21
+ *       z1 = r1 - l10 r0;  z2 = (r2 - l20 r0) - l21 z1;  x2 = z2 / e2;  x1 = z1 / e1 - l21 x2;  x0 = (r0 / d00 - l10 x1) - l20 x2
+ *   and x = m if a component of that x is not finite.  With  Ax_0 = (A00 x0 + A01 x1) + A02 x2  and Ax_1, Ax_2 alike,
+ *       cost = (((x0 Ax_0 + x1 Ax_1) + x2 Ax_2) - 2 ((b0 x0 + b1 x1) + b2 x2)) + c,   0 unless cost > 0.
+ *   t = x rounded to fp32 is where the survivor goes.
+ * No flips.  For every face and every corner v of it that is not fixed, with the other corners p, q:  for u in ring(v), u not p or q,
+ *   (v, u) a candidate:  N = (P1 - P0) x (P2 - P0) over the face's corners in its own order, N' the same with corner v at t widened;
+ *   the candidate is dropped unless  (N'.x N.x + N'.y N.y) + N'.z N.z > 0  (rejected_flip).  Validity is settled before the selection.
+ * Independent set.  key = (the bits of cost rounded to fp32) << 32 | owner.  Every valid candidate takes the 64-bit minimum of its key
+ *   on claim[v] for every v of ring(a) U ring(b) (which holds a and b); it is SELECTED iff it holds every one of them.  Two selected
+ *   edges have disjoint closed neighbourhoods: no face is touched by two collapses and the link and flip tests stay true.  The cheapest
+ *   valid candidate is always selected.  Ties between equal costs break by owner, the edge's lowest half-edge number: the result is NOT
+ *   invariant under a permutation of the faces.
+ * Budget.  need = F_b > target_faces ? (F_b - target_faces + 1) / 2 : 0.  The selected edges whose key has fewer than `need` selected
+ *   keys of the image below it collapse (an all-pairs count staged in LDS, only when more than `need` are selected): the image ends at
+ *   target_faces or one below, unless the candidates run out first.
+ * Apply.  The survivor s is the fixed end if there is one, else a; unless fixed it moves to t (verts is updated IN PLACE).  The other
+ *   end r gets parent[r] = s.  parent [n_verts] int32 holds batch-global vertex numbers, parent[i] == i before the first round.
+ *   faces_out [n_faces][3] (the bound; the first sum of faces_out rows are used): every face with its corners i replaced by
+ *   parent[i] that still has three distinct corners, in the input order (an integer block scan).
+ * fixed_out [n_verts] bytes, or NULL: 1 for a vertex that is FIXED in this round's input.
+ * counts [SC_MESH_DECIMATE_FIELDS][n_images] int64, row by row: 0 faces_out, 1 selected, 2 collapsed, 3 candidates (before the flip
+ *   test), 4 rejected_link, 5 rejected_flip, 6 fixed_vertices.
+ * Only integer atomics decide anything: the same bits from run to run, for any batch, stream and table_slots (the edge table of
+ * sc_mesh_subdivide).  14 launches on `stream` (3 when n_faces == 0), no wait on another workgroup, no host synchronisation.  scratch:
+ * sc_mesh_decimate_scratch_bytes(n_images, n_verts, n_faces, table_slots) bytes, 16-byte aligned, contents irrelevant on entry (0 for
+ * sizes the entry point refuses).  n_images <= 0 returns 0; hipErrorInvalidValue for n_images > 65535, n_faces > 2^26, n_verts > 2^30,
+ * a negative count or target, a reg that is not > 0, a bad table_slots, a NULL pointer or a misaligned scratch (verts and parent may be
+ * NULL when n_verts == 0, faces and faces_out when n_faces == 0, fixed_out always).
+ *
+ * sc_mesh_decimate_compact, once after the last round: the vertices that a face still uses, in ascending input number -> verts_out,
+ * fixed_out (the caller's `fixed` bytes of those vertices) and v_count_out [n_images]; faces_out [n_faces][3] renumbered;
+ * vertex_map [n_verts]: the image-local output number of the vertex at the end of i's parent chain, -1 if that one is not used.  4
+ * launches; `scratch` as above (the bytes of a round of the same sizes suffice).                                                         */
+#define SC_MESH_DECIMATE_FIELDS 7
+long long sc_mesh_decimate_scratch_bytes(int n_images, int n_verts, int n_faces, int table_slots);
+int sc_mesh_decimate_round(float* verts, const int32_t* faces, const int64_t* v_off, const int64_t* f_off, int n_images, int n_verts,
+                           int n_faces, int table_slots, int target_faces, double reg, void* scratch, int32_t* parent, int32_t* faces_out,
+                           uint8_t* fixed_out, int64_t* counts, int32_t* flags, void* stream);
+int sc_mesh_decimate_compact(const float* verts, const int32_t* faces, const int64_t* v_off, const int64_t* f_off, int n_images, int n_verts,
+                             int n_faces, const int32_t* parent, const uint8_t* fixed, void* scratch, float* verts_out, int32_t* faces_out,
+                             int32_t* vertex_map, uint8_t* fixed_out, int64_t* v_count_out, void* stream);
+
 /* ---- validity: pairs of faces of a mesh that properly cross (csrc/mesh_intersect.hip) -------------------------------------------------
  * What ops.mesh_self_intersections runs and {idx}_mesh_selfx.txt reports (`--mesh.self_intersect`).  A batch of packed meshes: verts
  * [n_verts][3] fp32, faces [n_faces][3] with image-local indices, v_count / f_count [n_images] int32 on the device, non-negative, summing

@@ -1,7 +1,7 @@
 // mesh_edges.hpp -- what the mesh post-processing kernels share: packed batches (mesh_topology.hip, mesh_simplify.hip, mesh_smooth.hip,
-// mesh_subdivide.hip), the union-find on a global label array (mesh_topology.hip, level_components.hip), the open-addressing table of
-// undirected edges (mesh_topology.hip, mesh_smooth.hip, mesh_subdivide.hip) and the sorted vertex rings built from it (mesh_smooth.hip,
-// mesh_subdivide.hip).
+// mesh_subdivide.hip, mesh_decimate.hip), the union-find on a global label array (mesh_topology.hip, level_components.hip), the
+// open-addressing table of undirected edges (mesh_topology.hip, mesh_smooth.hip, mesh_subdivide.hip, mesh_decimate.hip) and the sorted
+// vertex rings built from it (mesh_smooth.hip, mesh_subdivide.hip, mesh_decimate.hip).
 //
 // The correctness argument of every includer leans on these pieces and on nothing else of the header:
 //   * every probe ends: the table has T > 3 F slots (slots_ok) and at most 3 F keys ever go in, so an empty or matching slot comes first;
@@ -126,6 +126,20 @@ __device__ __forceinline__ EdgeSlot edge_slot(unsigned long long* keys, int T, i
         at = (at + 1) & (T - 1);
     }
     return {at, old == EMPTY};
+}
+
+// the slot of an edge that IS in the finished table (read only, after the launch that filled it); -1 if an empty slot comes first
+__device__ __forceinline__ int edge_find(const unsigned long long* __restrict__ keys, int T, int shift, unsigned long long glo,
+                                         unsigned long long ghi) {
+    const unsigned long long key = (glo << 32) | ghi;
+    int at = (int)((key * 0x9E3779B97F4A7C15ull) >> shift);
+    for (int p = 0; p < T; ++p) {
+        const unsigned long long k = keys[at];
+        if (k == key) return at;
+        if (k == EMPTY) return -1;
+        at = (at + 1) & (T - 1);
+    }
+    return -1;
 }
 
 // ---- vertex rings: the neighbours of every vertex over the table's edges, in ascending order --------------------------------------

@@ -2,9 +2,9 @@
 
 PackedMesh(verts [V,3] fp32, faces [F,3] int32, v_count [B], f_count [B]): image b's mesh is verts[vs:ve], faces[fs:fe] with the running
 sums of the two counts, and faces holds vertex numbers LOCAL to its image.  The producers (ops.isosurface_mesh, ops.dual_contour_mesh,
-ops.mesh_cluster_simplify, ops.mesh_subdivide) return the counts as int64 on the host; verts and faces live on the device.  The counts spelling
-(`*mesh`) goes into ops.mesh_topology, ops.mesh_cluster_simplify, ops.mesh_smooth, ops.mesh_subdivide, ops.mesh_self_intersections and
-ops.point_mesh_distance -- check_packed; the starts spelling
+ops.mesh_cluster_simplify, ops.mesh_subdivide, ops.mesh_decimate) return the counts as int64 on the host; verts and faces live on the device.
+The counts spelling (`*mesh`) goes into ops.mesh_topology, ops.mesh_cluster_simplify, ops.mesh_smooth, ops.mesh_subdivide, ops.mesh_decimate,
+ops.mesh_self_intersections and ops.point_mesh_distance -- check_packed; the starts spelling
 (`*mesh.starts()`) into ops.texture_queries and ops.mesh_raster -- check_starts.  Pure torch: nothing here needs the library or a device."""
 import collections
 

@@ -714,8 +714,12 @@ class Runner:
         Newton steps onto the SDF's zero set, positions and faces) and {idx}_mesh_subdiv.txt (one line: idx levels project vertices_in
         vertices_out faces_in faces_out edges sharp_edges fixed resid_before resid_after disp_mean disp_max area_before area_after
         volume_before volume_after, lengths in object units);
+        with --mesh.decimate also {idx}_mesh_decimated.ply (eval_3D.meshes_decimated: the mesh of {idx}_mesh.ply brought to the face budget
+        by quadric edge collapses, positions and faces) and {idx}_mesh_decimated.txt (one line: idx target vertices_in vertices_out
+        faces_in faces_out rounds collapses rejected_link rejected_flip fixed reached dist_mean dist_max area_before area_after
+        volume_before volume_after, lengths in object units);
         with --mesh.self_intersect also {idx}_mesh_selfx.txt (eval_3D.mesh_intersections: one line per mesh variant written above, in the
-        order mc dual simplified smooth subdiv: idx variant faces degenerate box_pairs pairs pairs_vertex faces_hit first_face
+        order mc dual simplified smooth subdiv decimated: idx variant faces degenerate box_pairs pairs pairs_vertex faces_hit first_face
         first_partner) and, for a variant with a face in a crossing pair only, {idx}_mesh_selfx_{variant}.ply (those faces alone);
         with --eval.icp also {idx}_pointclouds_comp_icp.ply (the ICP-aligned prediction of eval_3D.icp_metrics red, ground truth green);
         with --eval.normals also {idx}_pointclouds_normals.ply (pointclouds_comp's vertices as x y z nx ny nz red green blue: the SDF's
@@ -760,6 +764,11 @@ class Runner:
                     else eval_3D.meshes_subdivided(opt, var, self.graph.module.sdf_network))
             util_vis.dump_meshes(opt, var.idx, "mesh_subdiv", fine, folder=folder)
             util_vis.dump_lines(opt, var.idx, "mesh_subdiv", eval_3D.subdivided_lines(var), folder=folder)
+        if options.decimate_settings(opt) is not None:
+            # (eval_metrics decimated the mesh already and left it in var)
+            few = var.mesh_decimated_world if "mesh_decimated_world" in var else eval_3D.meshes_decimated(opt, var)
+            util_vis.dump_meshes(opt, var.idx, "mesh_decimated", few, folder=folder)
+            util_vis.dump_lines(opt, var.idx, "mesh_decimated", eval_3D.decimated_lines(var), folder=folder)
         if options.self_intersect_settings(opt):
             # (eval_metrics tested the meshes already and left the counts in var)
             if "mesh_intersections" not in var:

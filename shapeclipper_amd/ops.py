@@ -2707,3 +2707,125 @@ def mesh_project_step(verts, sdf, grad, fixed, scale, max_step):
                                             _lib.ptr(out), _lib.stream())
         _lib.check(code, "sc_mesh_project_step")
     return out
+
+
+# ---- post-processing: quadric edge-collapse decimation of indexed triangle meshes to a face budget (csrc/mesh_decimate.hip) --------------
+MESH_DECIMATE_TARGET = (4, 1 << 24)         # the face budget ops.mesh_decimate takes
+MESH_DECIMATE_MAX_ROUNDS = 4096
+MESH_DECIMATE_COUNTS = ("faces_out", "selected", "collapsed", "candidates", "rejected_link", "rejected_flip", "fixed_vertices")   # rows of a round's counts
+MESH_DECIMATE_TALLIES = ("rounds", "collapses", "rejected_link", "rejected_flip", "fixed_vertices", "reached")
+
+
+class DecimatedMesh(collections.namedtuple("DecimatedMesh", ("verts", "faces", "v_count", "f_count", "vertex_map", "fixed") + MESH_DECIMATE_TALLIES)):
+    __slots__ = ()
+    packed = property(lambda self: PackedMesh(*self[:4]), doc="the decimated meshes alone, as a PackedMesh")
+
+
+def mesh_decimate(verts, faces, v_count, f_count, target_faces, reg=1e-3, max_rounds=1024, table_slots=None):
+    """Decimates a PackedMesh (mesh_pack.py) of B images, passed as `*mesh` -- verts and faces on the device, v_count / f_count [B] int64 or
+    int32 (host or device) -- to `target_faces` (4..2^24) faces per image by quadric edge collapses.  One ROUND (sc_mesh_decimate_round) is a
+    pure function of the current mesh: vertex quadrics from the current faces; the candidate edges (two faces, not both ends fixed, the
+    link condition, not the tetrahedron case); for each the minimiser of the summed quadric, regularised towards the midpoint by `reg`
+    (in (0, 1]), or the fixed end's position, and its cost; candidates that would turn a face over are dropped; of the rest a
+    deterministic independent set -- an edge goes iff its key (cost as fp32 bits, then its lowest half-edge) is the minimum over its
+    closed neighbourhood --; at most ceil((F - target_faces) / 2) of them, the cheapest, collapse: the survivor (the fixed end, else the
+    lower number) moves, two faces go.  Vertices on an edge with one face (the rim that the grid face cuts) or three and more are fixed:
+    never moved, never removed.  Rounds repeat until every image is at or below target_faces, an image's round selects nothing (it is
+    then left alone), or `max_rounds` (1..4096) are done; an image ends at target_faces or target_faces - 1 unless its candidates run out.
+    Float64 from the exactly widened input, every operation rounded once, sums in ring order, positions rounded to fp32 once when written.
+    include/shapeclipper_hip.h states every rule; tests/mesh_decimate_ref.py restates them in numpy.
+
+    -> DecimatedMesh(verts [V',3] fp32, faces [F',3] int32 image-local, v_count, f_count [B] int64 on the host -- `.packed` is these four
+    as a PackedMesh again --, vertex_map [V] int32 (the output vertex an input vertex ended in, -1 for one no face uses in the end), fixed
+    [V'] bool (the vertex was fixed in the INPUT mesh), and per image, [B] int64 on the host: rounds, collapses, rejected_link and
+    rejected_flip (sums over the image's rounds), fixed_vertices (of the input mesh), reached (1 iff f_count <= target_faces)).  The
+    output vertices are those a face still uses, in ascending input number; the faces keep their order.  An image already at or below
+    target_faces keeps every bit.  Only integer atomics decide anything: the same bits from run to run, for any batch, stream and
+    table_slots (the edge table's size as in mesh_topology; by default sized for every round's face count).  Ties between equal costs
+    break by half-edge number, so the result is NOT invariant under a permutation of the faces.  Scratch comes from the scratch cache
+    ("mesh decimate").
+
+    ValueError for wrong dtypes, shapes or devices, counts that are negative or do not sum to the packed lengths, a bad target_faces, reg,
+    max_rounds or table_slots -- all before any launch -- and, checked on the device and raised after a round's launches, for a vertex
+    that is not finite, a face index outside its image's vertex range (never dereferenced) and a face that repeats an index.
+
+    Host synchronisation: one read per round, of the per-image counts and the three flags, and one of the output vertex counts.  Runs on
+    the current stream."""
+    who = "shapeclipper_amd: mesh_decimate"
+    B, V, F, counts_host, offsets = check_packed(who, verts, faces, v_count, f_count, max_images=MESH_TOPOLOGY_MAX_IMAGES,
+                                                 max_faces=MESH_TOPOLOGY_MAX_FACES)
+    dev = verts.device
+    if V > MESH_SMOOTH_MAX_VERTS:
+        raise ValueError("%s: verts: at most 2^30 vertices per call, got %d" % (who, V))
+    lo, hi = MESH_DECIMATE_TARGET
+    if isinstance(target_faces, bool) or not isinstance(target_faces, int) or not lo <= target_faces <= hi:
+        raise ValueError("%s: target_faces must be an integer in %d..%d, got %r" % (who, lo, hi, target_faces))
+    if not _finite_number(reg) or not 0 < reg <= 1:
+        raise ValueError("%s: reg must be a finite number in (0, 1], got %r" % (who, reg))
+    if isinstance(max_rounds, bool) or not isinstance(max_rounds, int) or not 1 <= max_rounds <= MESH_DECIMATE_MAX_ROUNDS:
+        raise ValueError("%s: max_rounds must be an integer in 1..%d, got %r" % (who, MESH_DECIMATE_MAX_ROUNDS, max_rounds))
+    table_slots = _edge_table_slots(who, F, table_slots, default=False)
+    tally = {k: torch.zeros(B, dtype=torch.int64) for k in MESH_DECIMATE_TALLIES}
+    if B == 0:
+        return DecimatedMesh(verts, faces, counts_host[0], counts_host[1], torch.zeros(V, device=dev, dtype=torch.int32),
+                             torch.zeros(V, device=dev, dtype=torch.bool), *tally.values())
+    lib = _lib.load()
+    n_fields = len(MESH_DECIMATE_COUNTS)
+    work, faces = verts.contiguous().clone(), faces.contiguous()        # a round moves its survivors in place
+    parent = torch.arange(V, device=dev, dtype=torch.int32)
+    fixed = torch.zeros(V, device=dev, dtype=torch.bool)
+    f_count = counts_host[1].clone()
+    offsets = offsets.to(dev)
+    active = f_count > target_faces
+    for n in range(max_rounds):
+        slots = table_slots if table_slots is not None else mesh_topology_slots(F)
+        faces_out = torch.empty(F, 3, device=dev, dtype=torch.int32)
+        back = torch.zeros(n_fields * B + 2, device=dev, dtype=torch.int64)         # what the host reads: the counts, then the three flags
+        counts, flags = back[:n_fields * B].view(n_fields, B), back[n_fields * B:].view(torch.int32)
+        with torch.cuda.device(dev):
+            ws = _scratch("mesh decimate", dev, (lib.sc_mesh_decimate_scratch_bytes(B, V, F, slots) + 3) // 4)
+            code = lib.sc_mesh_decimate_round(_lib.ptr(work) if V else None, _lib.ptr(faces) if F else None, _lib.ptr(offsets[0]),
+                                              _lib.ptr(offsets[1]), B, V, F, slots, target_faces, float(reg), _lib.ptr(ws),
+                                              _lib.ptr(parent) if V else None, _lib.ptr(faces_out) if F else None,
+                                              _lib.ptr(fixed) if V and n == 0 else None, _lib.ptr(counts), _lib.ptr(flags), _lib.stream())
+        _lib.check(code, "sc_mesh_decimate_round")
+        host = back.cpu()
+        bad = host[n_fields * B:].view(torch.int32).tolist()
+        if bad[0]:
+            raise ValueError("%s: a vertex is not finite" % who)
+        if bad[1]:
+            raise ValueError("%s: a face index lies outside its image's vertex range [0, v_count[b])" % who)
+        if bad[2]:
+            raise ValueError("%s: a face repeats a vertex index" % who)
+        c = dict(zip(MESH_DECIMATE_COUNTS, host[:n_fields * B].view(n_fields, B)))
+        if n == 0:
+            tally["fixed_vertices"] = c["fixed_vertices"].clone()
+        took_part = active.long()
+        tally["rounds"] += took_part
+        tally["collapses"] += took_part * c["collapsed"]
+        tally["rejected_link"] += took_part * c["rejected_link"]
+        tally["rejected_flip"] += took_part * c["rejected_flip"]
+        f_count = c["faces_out"].clone()
+        F = int(f_count.sum())
+        faces = faces_out[:F]
+        offsets = torch.stack([offsets[0], torch.cat([torch.zeros(1, dtype=torch.int64), f_count.cumsum(0)]).to(dev)])
+        active = active & (c["selected"] > 0) & (f_count > target_faces)            # an image whose round selects nothing is left alone
+        if not bool(active.any()):
+            break
+    tally["reached"] = (f_count <= target_faces).long()
+    verts_out = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    faces_final = torch.empty(F, 3, device=dev, dtype=torch.int32)
+    vertex_map = torch.empty(V, device=dev, dtype=torch.int32)
+    fixed_out = torch.empty(V, device=dev, dtype=torch.bool)
+    v_count_out = torch.zeros(B, device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        ws = _scratch("mesh decimate", dev, (lib.sc_mesh_decimate_scratch_bytes(B, V, F, mesh_topology_slots(F)) + 3) // 4)
+        code = lib.sc_mesh_decimate_compact(_lib.ptr(work) if V else None, _lib.ptr(faces) if F else None, _lib.ptr(offsets[0]),
+                                            _lib.ptr(offsets[1]), B, V, F, _lib.ptr(parent) if V else None, _lib.ptr(fixed) if V else None,
+                                            _lib.ptr(ws), _lib.ptr(verts_out) if V else None, _lib.ptr(faces_final) if F else None,
+                                            _lib.ptr(vertex_map) if V else None, _lib.ptr(fixed_out) if V else None, _lib.ptr(v_count_out),
+                                            _lib.stream())
+    _lib.check(code, "sc_mesh_decimate_compact")
+    v_out = v_count_out.cpu()
+    n_out = int(v_out.sum())
+    return DecimatedMesh(verts_out[:n_out], faces_final, v_out, f_count, vertex_map, fixed_out[:n_out], *(tally[k] for k in MESH_DECIMATE_TALLIES))

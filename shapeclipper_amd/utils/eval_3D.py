@@ -34,6 +34,8 @@ Call surface of the reference's utils/eval_3D.py.
   * meshes_subdivided (`--mesh.subdivide=n`): the marching-cubes mesh after n levels of Loop subdivision (ops.mesh_subdivide,
     csrc/mesh_subdivide.hip), its new vertices put back on the network's zero set by mesh.subdivide_project clamped Newton steps
     (ops.mesh_project_step): four times the faces per level for about 1.5 network evaluations per input face and step.
+  * meshes_decimated (`--mesh.decimate=F`): the marching-cubes mesh brought to F faces by quadric edge collapses (ops.mesh_decimate,
+    csrc/mesh_decimate.hip): faces are spent where the surface bends, the rim that the grid face cuts stays where it is.
   * mesh_intersections (`--mesh.self_intersect`): does a written mesh pass through itself?  The pairs of faces that properly cross
     (ops.mesh_self_intersections, csrc/mesh_intersect.hip), for every mesh variant the run writes.
 """
@@ -976,7 +978,61 @@ def subdivided_lines(var):
                                 " ".join("%.9g" % col[b] for col in reals)) for b, i in enumerate(var.idx.cpu().tolist())]
 
 
-INTERSECT_VARIANTS = ("mc", "dual", "simplified", "smooth", "subdiv")      # the order of {idx}_mesh_selfx.txt's lines
+@torch.no_grad()
+def meshes_decimated(opt, var):
+    """`--mesh.decimate=F`: the mesh that is written, brought to a face budget.  ops.mesh_decimate (csrc/mesh_decimate.hip) -- quadric edge
+    collapses down to mesh.decimate faces per sample, with mesh.decimate_reg and at most mesh.decimate_rounds rounds -- on the packed mesh
+    of ops.isosurface_mesh(var.level_vox) -- var.mesh_packed, built here as mesh_stats does when it is absent -- in grid-index units.
+    Sets var.mesh_decimated, a dict (var keeps dicts with attribute access): the fields of ops.DecimatedMesh (verts in grid-index units),
+    target, vertices_in, faces_in [B] int64, dist_mean, dist_max [B] float32 -- the distance from every ORIGINAL vertex to the decimated
+    mesh (ops.point_mesh_distance), in object units as in meshes_simplified; nan for an image whose decimated mesh has no face -- and
+    area_before, area_after, volume_before, volume_after [B] float64, ops.mesh_topology's of the original and of the decimated mesh at
+    the positions the level grid was sampled at, in object units (the "before" pair is taken from var.mesh_stats when `--eval.mesh_stats`
+    left it there).  Returns, and keeps in var.mesh_decimated_world for the dump, the per-image list of (vertices, faces) with
+    meshes_device's v / S rescale, which overlays {idx}_mesh.ply.  The metrics keep sampling the marching-cubes surface; nothing enters a
+    loss."""
+    target, reg, rounds = options.decimate_settings(opt)
+    lo, hi = opt.eval.range
+    B, S = var.level_vox.shape[0], var.level_vox.shape[1]
+    dev = var.level_vox.device
+    mesh = _mesh_packed(var)
+    res = ops.mesh_decimate(*mesh, target, reg, rounds)
+    to_object = lambda v: sampled_position(v, lo, hi, S).contiguous()
+    v_in, f_out = mesh.v_count.tolist(), res.f_count.tolist()
+    dist_mean = torch.full((B,), float("nan"), device=dev)
+    dist_max = torch.full((B,), float("nan"), device=dev)
+    if max(v_in, default=0) > 0 and res.faces.shape[0] > 0:
+        _, rows = mesh.padded_rows()                                    # padding rows repeat the image's first vertex
+        dist = ops.point_mesh_distance(to_object(mesh.verts)[rows].contiguous(), to_object(res.verts), res.faces.contiguous(),
+                                       res.v_count, res.f_count, search="grid").dist2.sqrt()
+        for b in range(B):
+            if v_in[b] > 0 and f_out[b] > 0:
+                dist_mean[b], dist_max[b] = dist[b, :v_in[b]].mean(), dist[b, :v_in[b]].max()
+    after = ops.mesh_topology(*res.packed._replace(verts=to_object(res.verts)))
+    before = var.mesh_stats if "mesh_stats" in var else ops.mesh_topology(*mesh._replace(verts=to_object(mesh.verts)))._asdict()
+    var.mesh_decimated = dict(res._asdict(), target=target, vertices_in=mesh.v_count.long().clone(), faces_in=mesh.f_count.long().clone(),
+                              dist_mean=dist_mean, dist_max=dist_max, area_before=before["area"], area_after=after.area,
+                              volume_before=before["volume"], volume_after=after.volume)
+    var.mesh_decimated_world = res.packed.split(written_position(res.verts, lo, hi, S))
+    return var.mesh_decimated_world
+
+
+def decimated_lines(var):
+    """One line per sample for {idx}_mesh_decimated.txt: idx target vertices_in vertices_out faces_in faces_out rounds collapses
+    rejected_link rejected_flip fixed reached dist_mean dist_max area_before area_after volume_before volume_after (18 fields; one host
+    read per field)."""
+    r = var.mesh_decimated
+    ints = [torch.as_tensor(r[k]).cpu().tolist() for k in ("vertices_in", "v_count", "faces_in", "f_count", "rounds", "collapses",
+                                                           "rejected_link", "rejected_flip", "fixed_vertices", "reached")]
+    reals = [torch.as_tensor(r[k]).cpu().tolist() for k in ("dist_mean", "dist_max", "area_before", "area_after", "volume_before",
+                                                            "volume_after")]
+    return ["%d %d %s %s" % (int(i), r["target"], " ".join("%d" % col[b] for col in ints), " ".join("%.9g" % col[b] for col in reals))
+            for b, i in enumerate(var.idx.cpu().tolist())]
+
+
+# the order of {idx}_mesh_selfx.txt's lines; "decimated" is there with `--mesh.decimate` only
+INTERSECT_VARIANTS = ("mc", "dual", "simplified", "smooth", "subdiv", "decimated")
+_INTERSECT_HELD = {"simplified": "mesh_simplified", "smooth": "mesh_smoothed", "subdiv": "mesh_subdivided", "decimated": "mesh_decimated"}
 
 
 @torch.no_grad()
@@ -984,8 +1040,8 @@ def mesh_intersections(opt, var, sdf_network=None):
     """`--mesh.self_intersect`: does a written mesh pass through itself?  ops.mesh_self_intersections (csrc/mesh_intersect.hip) on every
     mesh variant this run writes, in the order of INTERSECT_VARIANTS: "mc", the marching-cubes mesh (var.mesh_packed, built here as
     mesh_stats does when it is absent); "dual" with `--eval.dual_mesh` (var.mesh_dual_packed, built here with sdf_network when no earlier
-    step left it there; without a network and without that mesh the variant is left out); "simplified", "smooth" and "subdiv" with
-    `--eval.simplify`, `--mesh.smooth` and `--mesh.subdivide`, the meshes eval_metrics' meshers left in var.  Each is tested as it is held:
+    step left it there; without a network and without that mesh the variant is left out); "simplified", "smooth", "subdiv" and "decimated"
+    with `--eval.simplify`, `--mesh.smooth`, `--mesh.subdivide` and `--mesh.decimate`, the meshes eval_metrics' meshers left in var.  Each is tested as it is held:
     packed, in grid-index units.  The rule is strict (proper crossings only; see the op), so every counted pair truly intersects and the
     count is a lower bound.  Sets var.mesh_intersections, a dict per variant (var keeps dicts with attribute access) of the fields of
     ops.MeshIntersections and v_count, f_count [B] int64 on the host.  Runs after the meshers; nothing is repaired, nothing enters a loss."""
@@ -1001,7 +1057,7 @@ def mesh_intersections(opt, var, sdf_network=None):
                 var.mesh_dual_packed = list(ops.PackedMesh.empty(B, var.level_vox.device))
         if "mesh_dual_packed" in var:
             found["dual"] = ops.PackedMesh(*var.mesh_dual_packed)
-    for variant, key in (("simplified", "mesh_simplified"), ("smooth", "mesh_smoothed"), ("subdiv", "mesh_subdivided")):
+    for variant, key in _INTERSECT_HELD.items():
         if key in var:
             found[variant] = ops.PackedMesh(*(var[key][k] for k in ("verts", "faces", "v_count", "f_count")))
     out = {}
@@ -1020,7 +1076,7 @@ def _intersection_meshes(var, variant):
         return _mesh_packed(var)
     if variant == "dual":
         return ops.PackedMesh(*var.mesh_dual_packed)
-    held = var[{"simplified": "mesh_simplified", "smooth": "mesh_smoothed", "subdiv": "mesh_subdivided"}[variant]]
+    held = var[_INTERSECT_HELD[variant]]
     return ops.PackedMesh(*(held[k] for k in ("verts", "faces", "v_count", "f_count")))
 
 
@@ -1080,6 +1136,7 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     mesh_dist = None if vis_only else options.mesh_dist_settings(opt)
     want_stats, simplify = options.mesh_stats_settings(opt), options.simplify_settings(opt)
     smooth, subdivide = options.smooth_settings(opt), options.subdivide_settings(opt)
+    decimate = options.decimate_settings(opt)
     self_intersect = options.self_intersect_settings(opt)
     points_3D = get_dense_3D_grid(opt, var)
     B = points_3D.shape[0]
@@ -1124,6 +1181,8 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
             meshes_smoothed(opt, var)
         if subdivide is not None:               # vis_{ep}/{idx}_mesh_subdiv.ply and .txt
             meshes_subdivided(opt, var, sdf_network)
+        if decimate is not None:                # vis_{ep}/{idx}_mesh_decimated.ply and .txt
+            meshes_decimated(opt, var)
         if self_intersect:                      # vis_{ep}/{idx}_mesh_selfx.txt: after the meshers, on what they left in var
             mesh_intersections(opt, var, sdf_network)
         return
@@ -1152,6 +1211,8 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
         meshes_smoothed(opt, var)
     if subdivide is not None:               # likewise
         meshes_subdivided(opt, var, sdf_network)
+    if decimate is not None:                # likewise
+        meshes_decimated(opt, var)
     if self_intersect:                      # a check of what is written, after the meshers: no metric reads it
         mesh_intersections(opt, var, sdf_network)
     return dist_acc.mean(), dist_comp.mean()

@@ -266,6 +266,24 @@ def self_intersect_settings(opt):
     return _checked("mesh", row, (opt.get("mesh", None) or {}).get(row.key, row.default))
 
 
+# The decimation of the written mesh to a face budget, in a table and a dict of their own with the same rows (MESH stays the five rows
+# of smoothing and refinement).
+MESH_DECIMATE_TABLE = tuple(Setting(*row) for row in (
+    ("decimate", None, (4, 16777216), "edge-collapse mesh {idx}_mesh_decimated.ply / .txt: the face budget (ops.mesh_decimate)", "absent"),
+    ("decimate_reg", 1e-3, (0.0, 1.0), "... the pull of a collapse's vertex towards the midpoint of its edge", "str"),
+    ("decimate_rounds", 1024, (1, 4096), "... the most rounds of independent collapses"),
+))
+MESH_DECIMATE = {row.key: row for row in MESH_DECIMATE_TABLE}
+
+
+def decimate_settings(opt):
+    """None unless `--mesh.decimate=F` is given, else (target, reg, rounds), the arguments of ops.mesh_decimate.  All three values are
+    checked, switch on or off; absent (a key or the whole `mesh` group) means the default."""
+    target, reg, rounds = (_checked("mesh", MESH_DECIMATE[k], (opt.get("mesh", None) or {}).get(k, MESH_DECIMATE[k].default))
+                           for k in ("decimate", "decimate_reg", "decimate_rounds"))
+    return None if target is None else (target, reg, rounds)
+
+
 def parse_arguments(args):
     """--key1.key2=value ; --flag (true) ; --flag! (false)"""
     opt_cmd = {}
@@ -357,7 +375,7 @@ def process_options(opt):
                 raise ValueError("hip.%s must be an integer in %d..%d, got %r" % (row.key, lo, hi, v))
     for check in (dual_mesh_reg, texture_texels, mesh_render, icp_settings, normal_settings, mesh_dist_settings, emd_settings, iou_settings,
                   mesh_stats_settings, simplify_settings,       # every eval.* value is checked here, whether or not its switch is on
-                  smooth_settings, subdivide_settings, self_intersect_settings):        # and every mesh.* value
+                  smooth_settings, subdivide_settings, self_intersect_settings, decimate_settings):        # and every mesh.* value
         check(opt)
     torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
     for row in HIP_TABLE:
