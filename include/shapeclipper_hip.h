@@ -1758,6 +1758,51 @@ int sc_mesh_raster(const float* verts, const int32_t* faces, const long long* v_
                    int32_t* stats, void* scratch, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ambient occlusion from the level grid (csrc/level_ao.hip): how much of the hemisphere over a surface point is free of the solid
+ * {level < iso} within a reach of n_steps * step grid pitches (ops.level_ambient_occlusion, `--mesh.ao`).  The grid is the solid:
+ * there is no triangle and no tree.  All arithmetic is fp32, every operation rounded once (no contraction), division correctly
+ * rounded; tests/level_ao_ref.py restates every line below in numpy and the GPU tests compare bit for bit.
+ *
+ * Inputs: level [n_images][S][S][S] fp32, index (x S + y) S + z, S = n_axis in 2..1024; points [n_points][3] fp32 in grid-index units
+ * (the units of sc_marching_cubes_mesh's vertices); normals [n_points][3] fp32, any length; image [n_points] int32, the image a
+ * point belongs to; dirs [64][3] fp32, the directions, which are data (ops.ao_directions: a Fibonacci set built in float64 on the host
+ * and rounded once -- the device evaluates no sine); step, bias, iso fp32; n_steps = M in 1..4096.
+ *
+ * Per point (p, n) and direction k, D = dirs[k]:
+ *   dn = (D.x n.x + D.y n.y) + D.z n.z;   d = -D if dn < 0, else D (the direction folded into the normal's hemisphere);   w = |dn|;
+ *   p0_c = p_c + bias * n_c   for c = x, y, z;
+ *   for s = 1 .. M:   t = (float)s * step;   q_c = p0_c + t * d_c;
+ *       the ray ends OPEN when !(q_c >= 0 && q_c <= (float)(S - 1)) for any c (the negated form: a NaN ends the ray as well);
+ *       i_c = min((int)floorf(q_c), S - 2);   f_c = q_c - (float)i_c;   the sample's cell is (i_x, i_y, i_z), its corners
+ *       v[a][b][c] = level[image][i_x + a][i_y + b][i_z + c];
+ *       if no corner is < iso the sample cannot occlude and the march goes on -- a rule, not an optimisation: it makes skipping
+ *       a cell that a bit volume calls empty exact;
+ *       else, with lerp(a, b, t) = a + t * (b - a):   u[a][b] = lerp(v[a][b][0], v[a][b][1], f_z);
+ *       u[a] = lerp(u[a][0], u[a][1], f_y);   val = lerp(u[0], u[1], f_x);   the ray ends CLOSED when val < iso;
+ *   a ray that no sample ended is OPEN.
+ *   W = the sum over the 64 directions of w, V = the sum of (open ? w : 0), both by the fixed pairwise tree a[j+1][k] = a[j][2k] +
+ *   a[j][2k+1], j = 0..5, which is what lane 0 holds after a __shfl_xor butterfly over the masks 1, 2, 4, 8, 16, 32.
+ *   ao = V / W;   mask = the open bits, bit k for direction k.
+ *   A point or normal with a component that is not finite, or !(W > 0) (a zero normal; a NaN), gives ao = 1 and mask = -1.
+ *   An image outside 0 .. n_images - 1 sets *bad to 1, gives ao = 1 and mask = -1 and reads nothing of level.
+ *
+ * One wave64 is one point and one lane one direction: __ballot is the mask.  cell_skip != 0: a first launch writes, per image, the
+ * bit volume of the cells with a corner < iso -- [S-1][S-1][ceil((S-1) / 32)] uint32 words, bit z & 31 of word z >> 5 of row (x, y),
+ * one thread per word, plain stores -- into scratch, and the march tests a sample's bit before it loads the 8 corners;
+ * cell_skip == 0: scratch is not used and the corner test comes from the loads.  The same bits either way.
+ * Outputs: ao [n_points] fp32, mask [n_points] int64, bad [1] int32 (zeroed here); every element is written.  scratch:
+ * sc_level_ao_scratch_bytes(n_images, n_axis) bytes, 4-byte aligned (-1 for sizes the call refuses).  One memset and one or two
+ * launches on the caller's stream; no atomics, no LDS, no host synchronisation.  n_points <= 0 returns 0 and launches nothing.
+ * hipErrorInvalidValue for n_axis outside 2..1024, n_steps outside 1..4096, n_images outside 1..65535, more than 2^30 points, a NULL
+ * pointer (scratch may be NULL when cell_skip == 0).                                                                            */
+#define SC_LEVEL_AO_DIRS 64
+#define SC_LEVEL_AO_MAX_STEPS 4096
+long long sc_level_ao_scratch_bytes(int n_images, int n_axis);
+int sc_level_ambient_occlusion(const float* level, const float* points, const float* normals, const int32_t* image, const float* dirs,
+                               int n_images, int n_axis, long long n_points, float step, float bias, float iso, int n_steps,
+                               int cell_skip, void* scratch, float* ao, long long* mask, int32_t* bad, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Launch policy (csrc/device.hip) -- the one process-level setting of the library. The persistent one-workgroup-per-CU grids
  * (stream-K 3x3 convolutions and their weight gradients, stem / 1x1 / stride-2 gradients) are sized for
  * sc_grid_cus() = device CUs - reserved.  Reserve CUs when another stream must make progress beside them: RCCL's

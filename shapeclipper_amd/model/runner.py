@@ -692,13 +692,17 @@ class Runner:
     def dump_mesh_turntable(self, opt, var, folder):
         """{idx}_image_mesh_rotate.gif and {idx}_normal_mesh_rotate.gif of `--eval.mesh_render` in the vis_{ep}/ dump: the textured mesh from
         every pose of var.vis_pose at the size of the per-sample pictures, all views through ONE ops.mesh_raster call
-        (eval_3D.mesh_render), frames by ops.vis_frames."""
+        (eval_3D.mesh_render), frames by ops.vis_frames.  With `--mesh.ao` also {idx}_image_mesh_shaded_rotate.gif and
+        {idx}_clay_mesh_rotate.gif: eval_3D.mesh_shade of those same views."""
         from .. import ops
         B = len(var.idx)
         H, W = (int(s) for s in var.mesh_render.render.depth.shape[-2:])
         pose = var.vis_pose[None].expand(B, -1, -1, -1)
         views = eval_3D.mesh_render(opt, var.level_vox, var.texture, pose, var.intr, H, W)
-        for name, x in (("image_mesh_rotate", views.rgb), ("normal_mesh_rotate", views.normal)):
+        frames = [("image_mesh_rotate", views.rgb), ("normal_mesh_rotate", views.normal)]
+        if options.ao_settings(opt) is not None:
+            frames += zip(("image_mesh_shaded_rotate", "clay_mesh_rotate"), eval_3D.mesh_shade(opt, var, views, pose))
+        for name, x in frames:
             util_vis.dump_gifs(opt, var.idx, name, ops.vis_frames(x.contiguous(), "rgb"), folder=folder)
 
     def dump_geometry(self, opt, var, folder):
@@ -718,6 +722,12 @@ class Runner:
         by quadric edge collapses, positions and faces) and {idx}_mesh_decimated.txt (one line: idx target vertices_in vertices_out
         faces_in faces_out rounds collapses rejected_link rejected_flip fixed reached dist_mean dist_max area_before area_after
         volume_before volume_after, lengths in object units);
+        with --mesh.ao also {idx}_mesh_ao.ply (eval_3D.mesh_ambient_occlusion: the vertices and faces of {idx}_mesh.ply with the unit SDF
+        normals and the ambient occlusion baked from the level grid as a grey in all three colour channels) and {idx}_mesh_ao.txt (one
+        line: idx vertices radius step ao_mean ao_min ao_max open_share, radius and step in grid pitches); beside --eval.texture also
+        {idx}_mesh_tex_ao.png (eval_3D.mesh_ao_atlas: the occlusion in the layout of the colour atlas; the OBJ and MTL keep their bytes)
+        and beside --eval.mesh_render also {idx}_image_mesh_shaded.png and {idx}_clay_mesh.png (eval_3D.mesh_shade: the mesh picture and
+        a plain grey one under the occlusion and a two-sided head light);
         with --mesh.self_intersect also {idx}_mesh_selfx.txt (eval_3D.mesh_intersections: one line per mesh variant written above, in the
         order mc dual simplified smooth subdiv decimated: idx variant faces degenerate box_pairs pairs pairs_vertex faces_hit first_face
         first_partner) and, for a variant with a face in a crossing pair only, {idx}_mesh_selfx_{variant}.ply (those faces alone);
@@ -769,6 +779,12 @@ class Runner:
             few = var.mesh_decimated_world if "mesh_decimated_world" in var else eval_3D.meshes_decimated(opt, var)
             util_vis.dump_meshes(opt, var.idx, "mesh_decimated", few, folder=folder)
             util_vis.dump_lines(opt, var.idx, "mesh_decimated", eval_3D.decimated_lines(var), folder=folder)
+        shade = options.ao_settings(opt) is not None
+        if shade:
+            # (eval_metrics baked the occlusion already and left it in var)
+            lit = var.mesh_ao_world if "mesh_ao_world" in var else eval_3D.mesh_ambient_occlusion(opt, var, self.graph.module.sdf_network)
+            util_vis.dump_meshes(opt, var.idx, "mesh_ao", lit, folder=folder)
+            util_vis.dump_lines(opt, var.idx, "mesh_ao", eval_3D.ao_lines(var), folder=folder)
         if options.self_intersect_settings(opt):
             # (eval_metrics tested the meshes already and left the counts in var)
             if "mesh_intersections" not in var:
@@ -781,6 +797,8 @@ class Runner:
             net = self.graph.module
             var.texture = eval_3D.mesh_texture(opt, net.sdf_network, net.rgb_network, var.proj_latent_sdf, var.proj_latent_rgb, var.level_vox)
             util_vis.dump_textured_meshes(opt, var.idx, "mesh_tex", var.texture, folder=folder)
+            if shade:
+                util_vis.dump_atlases(opt, var.idx, "mesh_tex_ao", eval_3D.mesh_ao_atlas(opt, var, var.texture), folder=folder)
         if options.mesh_render(opt):
             net = self.graph.module
             if "texture" not in var:
@@ -794,6 +812,10 @@ class Runner:
             dump("normal_mesh", as_map(out.normal))
             dump("depth_mesh", as_map(eval_3D.mesh_depth_grey(opt, out, var.intr, var.scale_dist)))
             util_vis.dump_arrays(opt, var.idx, "depth_mesh", out.depth[:, 0], folder=folder)
+            if shade:
+                shaded, clay = eval_3D.mesh_shade(opt, var, out, var.pose)
+                dump("image_mesh_shaded", as_map(shaded))
+                dump("clay_mesh", as_map(clay))
         if "dpc" in var:
             util_vis.dump_pointclouds_compare(opt, var.idx, "pointclouds_comp", var.dpc_pred, var.dpc.points, folder=folder)
             if "dpc_pred_icp" in var:                   # --eval.icp: the ICP-aligned prediction red, the ground truth green

@@ -3,8 +3,10 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import math
 import weakref
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2829,3 +2831,94 @@ def mesh_decimate(verts, faces, v_count, f_count, target_faces, reg=1e-3, max_ro
     v_out = v_count_out.cpu()
     n_out = int(v_out.sum())
     return DecimatedMesh(verts_out[:n_out], faces_final, v_out, f_count, vertex_map, fixed_out[:n_out], *(tally[k] for k in MESH_DECIMATE_TALLIES))
+
+
+# ---- shading: ambient occlusion of surface points from the dense level grid (csrc/level_ao.hip) ------------------------------------------
+LEVEL_AO_DIRS = 64                          # SC_LEVEL_AO_DIRS: one direction per lane of a wave
+LEVEL_AO_MAX_STEPS = 4096                   # SC_LEVEL_AO_MAX_STEPS
+LEVEL_AO_MAX_AXIS = 1024
+LEVEL_AO_MAX_IMAGES = 65535
+LEVEL_AO_MAX_POINTS = 1 << 30
+AmbientOcclusion = collections.namedtuple("AmbientOcclusion", ["ao", "mask"])
+_AO_DIRS = {}                               # device index -> ao_directions() on that device
+
+
+def ao_directions():
+    """The 64 directions of level_ambient_occlusion, [64,3] numpy float32: the Fibonacci set z = 1 - (2 k + 1) / 64, r = sqrt(1 - z^2),
+    phi = k pi (3 - sqrt 5), (r cos phi, r sin phi, z), computed in float64 and rounded once.  They are data to the kernel, which
+    evaluates no sine; a direction and its opposite serve as one, since every direction is folded into the normal's hemisphere."""
+    k = np.arange(LEVEL_AO_DIRS, dtype=np.float64)
+    z = 1.0 - (2.0 * k + 1.0) / LEVEL_AO_DIRS
+    r = np.sqrt(1.0 - z * z)
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1).astype(np.float32)
+
+
+def ao_step_count(radius, step):
+    """M = ceil(radius / step), the samples per ray of level_ambient_occlusion, in host float64; ValueError unless radius and step are
+    finite numbers > 0 and M lies in 1..4096."""
+    who = "shapeclipper_amd: level_ambient_occlusion"
+    for name, x in (("radius", radius), ("step", step)):
+        if not _finite_number(x) or not x > 0:
+            raise ValueError("%s: %s must be a finite number > 0, got %r" % (who, name, x))
+    M = int(math.ceil(radius / step))
+    if not 1 <= M <= LEVEL_AO_MAX_STEPS:
+        raise ValueError("%s: radius / step = %r / %r asks for %d samples per ray; 1..%d are possible" % (who, radius, step, M, LEVEL_AO_MAX_STEPS))
+    return M
+
+
+def level_ambient_occlusion(level, points, normals, image, radius, step=0.5, bias=1.0, iso=0.0, cell_skip=True):
+    """Ambient occlusion of N surface points from the dense level grid: level [B,S,S,S] fp32 (index (x S + y) S + z, 2 <= S <= 1024),
+    points [N,3] fp32 in grid-index units (the units of isosurface_mesh's vertices), normals [N,3] fp32 of any length, image [N] int32,
+    all on one device -> AmbientOcclusion(ao [N] fp32 in [0, 1], mask [N] int64).  From every point 64 rays (ao_directions, each folded
+    into the normal's hemisphere) start at p + bias n and take M = ceil(radius / step) samples `step` grid pitches apart (radius in grid
+    pitches); a ray is closed by the first sample whose trilinear level is < iso and open when it leaves the grid or ends.  ao is the
+    |D . n|-weighted share of the open rays -- 1 on a convex shape, 0.5 in a right-angled crease, towards 0 in a pit -- and bit k of
+    mask says direction k is open.  A point or normal that is not finite and a zero normal give ao = 1 and mask = -1.
+    include/shapeclipper_hip.h states every operation (sc_level_ambient_occlusion); tests/level_ao_ref.py restates them in numpy.
+
+    cell_skip=True: a first launch writes the bit volume of the cells with a corner < iso and the march tests a sample's bit before it
+    loads 8 floats; False: the corner test comes from the loads.  The same bits either way, from run to run, for any batch, stream and
+    order of the points: there are no atomics.  The bit volume comes from the scratch cache ("level ao").
+
+    ValueError for wrong dtypes, shapes or devices, a bad number, radius / step outside 1..4096 samples -- all before any launch -- and,
+    flagged on the device (never dereferenced) and raised after the launches, for an image outside 0..B-1.  N = 0 returns empty tensors
+    without a launch.  Host synchronisation: one read of the flag.  Runs on the current stream."""
+    who = "level_ambient_occlusion"
+    level = device_tensor(who, "level", level, (torch.float32,))
+    dev = level.device
+    points = device_tensor(who, "points", points, (torch.float32,), dev)
+    normals = device_tensor(who, "normals", normals, (torch.float32,), dev)
+    image = device_tensor(who, "image", image, (torch.int32,), dev)
+    if level.dim() != 4 or not (level.shape[1] == level.shape[2] == level.shape[3]) or not 2 <= level.shape[1] <= LEVEL_AO_MAX_AXIS \
+            or not 1 <= level.shape[0] <= LEVEL_AO_MAX_IMAGES:
+        raise ValueError("shapeclipper_amd: %s takes level [B,S,S,S] with 1 <= B <= %d and 2 <= S <= %d, got %s"
+                         % (who, LEVEL_AO_MAX_IMAGES, LEVEL_AO_MAX_AXIS, tuple(level.shape)))
+    B, S, N = level.shape[0], level.shape[1], points.shape[0]
+    if points.dim() != 2 or points.shape[1] != 3 or normals.shape != points.shape or tuple(image.shape) != (N,) or N > LEVEL_AO_MAX_POINTS:
+        raise ValueError("shapeclipper_amd: %s takes points [N,3], normals [N,3] and image [N] with N <= 2^30, got %s, %s and %s"
+                         % (who, tuple(points.shape), tuple(normals.shape), tuple(image.shape)))
+    M = ao_step_count(radius, step)
+    for name, x in (("bias", bias), ("iso", iso)):
+        if not _finite_number(x):
+            raise ValueError("shapeclipper_amd: %s: %s must be a finite number, got %r" % (who, name, x))
+    if not isinstance(cell_skip, bool):
+        raise ValueError("shapeclipper_amd: %s: cell_skip must be a bool, got %r" % (who, cell_skip))
+    ao = torch.empty(N, device=dev, dtype=torch.float32)
+    mask = torch.empty(N, device=dev, dtype=torch.int64)
+    if N == 0:
+        return AmbientOcclusion(ao, mask)
+    dirs = _AO_DIRS.get(dev.index)
+    if dirs is None:
+        dirs = _AO_DIRS[dev.index] = torch.from_numpy(ao_directions()).to(dev)
+    bad = torch.empty(1, device=dev, dtype=torch.int32)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = _scratch("level ao", dev, (lib.sc_level_ao_scratch_bytes(B, S) + 3) // 4) if cell_skip else None
+        code = lib.sc_level_ambient_occlusion(_lib.ptr(level), _lib.ptr(points), _lib.ptr(normals), _lib.ptr(image), _lib.ptr(dirs), B, S, N,
+                                              float(step), float(bias), float(iso), M, 1 if cell_skip else 0, _lib.ptr(ws), _lib.ptr(ao),
+                                              _lib.ptr(mask), _lib.ptr(bad), _lib.stream())
+    _lib.check(code, "sc_level_ambient_occlusion")
+    if bad.tolist()[0]:
+        raise ValueError("shapeclipper_amd: %s: an image index lies outside 0..B-1 = 0..%d" % (who, B - 1))
+    return AmbientOcclusion(ao, mask)

@@ -31,6 +31,8 @@ Call surface of the reference's utils/eval_3D.py.
     quadric placement (ops.mesh_cluster_simplify, csrc/mesh_simplify.hip), and what the smaller file costs in distance.
   * meshes_smoothed (`--mesh.smooth=n`): the marching-cubes mesh after n Taubin lambda|mu iterations of the umbrella operator
     (ops.mesh_smooth, csrc/mesh_smooth.hip): the same faces, the grid's staircase gone, the volume within about a per cent.
+  * mesh_ambient_occlusion (`--mesh.ao`): ambient occlusion of the marching-cubes mesh baked from the level grid itself
+    (ops.level_ambient_occlusion, csrc/level_ao.hip) -- per vertex, per atlas texel (mesh_ao_atlas) and in the mesh pictures (mesh_shade).
   * meshes_subdivided (`--mesh.subdivide=n`): the marching-cubes mesh after n levels of Loop subdivision (ops.mesh_subdivide,
     csrc/mesh_subdivide.hip), its new vertices put back on the network's zero set by mesh.subdivide_project clamped Newton steps
     (ops.mesh_project_step): four times the faces per level for about 1.5 network evaluations per input face and step.
@@ -1030,6 +1032,142 @@ def decimated_lines(var):
             for b, i in enumerate(var.idx.cpu().tolist())]
 
 
+AO_STEP = 0.5      # grid pitches between the samples of a ray of mesh_ambient_occlusion: half a cell, so no cell on the way is jumped
+AO_BIAS = 1.0      # the rays start one normal length (a grid pitch: the normals are unit) off the surface, clear of the vertex's own cells
+
+
+def _grey_bytes(ao):
+    """ao [...] fp32 -> uint8: trunc(clamp(ao, 0, 1) * 255), the recipe of the PNG dumps and of mesh_attributes."""
+    return (ao.clamp(0, 1) * 255).to(torch.uint8)
+
+
+@torch.no_grad()
+def mesh_ambient_occlusion(opt, var, sdf_network):
+    """`--mesh.ao`: where is the written mesh concave?  ops.level_ambient_occlusion (csrc/level_ao.hip) at every vertex of the packed
+    mesh of ops.isosurface_mesh(var.level_vox) -- var.mesh_packed, built here as mesh_stats does when it is absent; its verts are in
+    grid-index units already -- against var.level_vox itself (so --hip.largest_component applies), with the unit SDF gradient at
+    sampled_position(v) as the normal: one SDF evaluation with gradient in mesh_attributes' padded one-launch layout
+    (sdf_network.eager: stock operators).  Reach mesh.ao_radius (S - 1) pitches, samples AO_STEP apart, start AO_BIAS off the surface.
+    Sets var.mesh_ao, a dict (var keeps dicts with attribute access): ao [V] fp32, mask [V] int64, normals [V,3] fp32, v_count, radius
+    and step (grid pitches), and per image, [B] float64 on the device: ao_mean (a float64 sum in a fixed order, _ordered_sums), ao_min,
+    ao_max, open_share (the share of vertices whose 64 rays are all open); nan for an image without a vertex.  Returns, and keeps in
+    var.mesh_ao_world for the dump, per image (vertices, faces, normals, grey): {idx}_mesh.ply's vertices and faces (meshes_device's
+    v / S rescale) and trunc(clamp(ao, 0, 1) * 255) in all three colour channels.  Nothing is measured against the ground truth and
+    nothing enters a loss."""
+    lo, hi = opt.eval.range
+    level = var.level_vox.float().contiguous()
+    B, S = level.shape[0], level.shape[1]
+    radius = options.ao_settings(opt, S)
+    dev = level.device
+    mesh = _mesh_packed(var)
+    v_count = mesh.v_count.to(dev)
+    P, rows = mesh.padded_rows(16)
+    nan = torch.full((B,), float("nan"), dtype=torch.float64, device=dev)
+    stats = dict(ao_mean=nan, ao_min=nan, ao_max=nan, open_share=nan)
+    if P == 0:
+        ao, mask = torch.zeros(0, device=dev), torch.zeros(0, dtype=torch.int64, device=dev)
+        normals = torch.zeros(0, 3, device=dev)
+    else:
+        real = torch.arange(P, device=dev)[None] < v_count[:, None]                      # [B, P]: the rows that are a vertex, in packed order
+        flat = rows.reshape(-1)
+        _, grad = _sdf_at(sdf_network, var.proj_latent_sdf)(sampled_position(mesh.verts[flat], lo, hi, S).contiguous(), B, P, True)
+        normals = torch.nn.functional.normalize(grad[real.reshape(-1)], dim=1, eps=1e-12).contiguous()
+        image = torch.repeat_interleave(torch.arange(B, device=dev, dtype=torch.int32), v_count)
+        ao, mask = ops.level_ambient_occlusion(level, mesh.verts.contiguous(), normals, image, radius, step=AO_STEP, bias=AO_BIAS)
+        padded = ao.double()[flat].view(B, P)
+        zero, inf = torch.zeros((), dtype=torch.float64, device=dev), torch.full((), float("inf"), dtype=torch.float64, device=dev)
+        n = v_count.double()
+        some = v_count > 0
+        share = lambda x: torch.where(some, x / n.clamp_min(1.0), nan)
+        stats = dict(ao_mean=share(_ordered_sums(torch.where(real, padded, zero))),
+                     ao_min=torch.where(some, torch.where(real, padded, inf).amin(1), nan),
+                     ao_max=torch.where(some, torch.where(real, padded, -inf).amax(1), nan),
+                     open_share=share((real & (mask[flat].view(B, P) == -1)).sum(1).double()))
+    var.mesh_ao = dict(ao=ao, mask=mask, normals=normals, v_count=mesh.v_count, radius=radius, step=AO_STEP, **stats)
+    grey = _grey_bytes(ao)[:, None].expand(-1, 3)
+    written = mesh.split(written_position(mesh.verts, lo, hi, S))       # meshes_device's expression: the same bytes as {idx}_mesh.ply
+    var.mesh_ao_world = [(*written[b], n_b, g_b) for b, ((n_b, _), (g_b, _)) in enumerate(zip(mesh.split(normals), mesh.split(grey)))]
+    return var.mesh_ao_world
+
+
+def ao_lines(var):
+    """One line per sample for {idx}_mesh_ao.txt: idx vertices radius step ao_mean ao_min ao_max open_share (8 fields; radius and step in
+    grid pitches; one host read per field)."""
+    r = var.mesh_ao
+    verts = torch.as_tensor(r["v_count"]).cpu().tolist()
+    reals = [torch.as_tensor(r[k]).cpu().tolist() for k in ("ao_mean", "ao_min", "ao_max", "open_share")]
+    return ["%d %d %.9g %.9g %s" % (int(i), verts[b], r["radius"], r["step"], " ".join("%.9g" % col[b] for col in reals))
+            for b, i in enumerate(var.idx.cpu().tolist())]
+
+
+@torch.no_grad()
+def mesh_ao_atlas(opt, var, textured):
+    """`--mesh.ao` with `--eval.texture`: per image the AO atlas uint8 [A,A] in the layout of the colour atlas of `textured`
+    (mesh_texture of var.level_vox).  ops.texture_queries yields the texels' positions again; those of the texels that hold a face go
+    back to grid-index units by (p - lo) * ((S - 1) / (hi - lo)), their normals are decoded from the normal atlas as 2 x / 255 - 1, and
+    one ops.level_ambient_occlusion call with mesh_ambient_occlusion's reach, step and bias serves the batch.  A used texel holds
+    trunc(clamp(ao, 0, 1) * 255), every other one 127.  The TexturedMesh list is not changed."""
+    lo, hi = opt.eval.range
+    T = options.texture_texels(opt, always=True)
+    level = var.level_vox.float().contiguous()
+    B, S = level.shape[0], level.shape[1]
+    dev = level.device
+    mesh = _mesh_packed(var)
+    v_start, f_start, F = mesh.starts()
+    A, _, rows = ops.texture_layout(max(F, default=0), T)
+    blank = torch.full((64, 64), 127, dtype=torch.uint8, device=dev)
+    if rows == 0:
+        return [blank] * B
+    assert all(m.faces.shape[0] == F[b] and (F[b] == 0 or m.atlas.shape[0] == A) for b, m in enumerate(textured)), \
+        "the texture was baked for another mesh"
+    query, face_of_texel = ops.texture_queries(mesh.verts, mesh.faces, v_start, f_start, F, A, T, lo, hi, S, rows)
+    used = (face_of_texel.reshape(-1) >= 0).nonzero().reshape(-1)                      # texel b rows A + y A + x, ascending
+    grey127 = torch.full((rows, A, 3), 127, dtype=torch.uint8, device=dev)
+    bytes_n = torch.stack([m.normal_atlas[:rows] if F[b] else grey127 for b, m in enumerate(textured)]).reshape(-1, 3)
+    points = ((query[used] - lo) * ((S - 1) / (hi - lo))).contiguous()
+    normals = (2 * bytes_n[used].float() / 255 - 1).contiguous()
+    image = (used // (rows * A)).int()
+    ao = ops.level_ambient_occlusion(level, points, normals, image, options.ao_settings(opt, S), step=AO_STEP, bias=AO_BIAS).ao
+    atlas = torch.full((B, A, A), 127, dtype=torch.uint8, device=dev)
+    top = torch.full((B * rows * A,), 127, dtype=torch.uint8, device=dev)
+    top[used] = _grey_bytes(ao)
+    atlas[:, :rows] = top.view(B, rows, A)
+    return [atlas[b] if F[b] else blank for b in range(B)]
+
+
+@torch.no_grad()
+def mesh_shade(opt, var, render, pose):
+    """`--mesh.ao` with `--eval.mesh_render`: a MeshRender of the mesh of var.level_vox (mesh_render) from `pose` [B,3,4] or [B,V,3,4],
+    lit -> (shaded, clay), both [B,V,H,W,3] in [0, 1].  Per pixel ao is the barycentric mix (b0 a0 + b1 a1) + b2 a2 of the winning
+    face's three vertex values of var.mesh_ao (render.face, render.bary); lambert = |n . z_cam| / |n| with n = 2 render.normal - 1 and
+    z_cam the third row of the pose's rotation -- a two-sided head light; shade = ao (0.3 + 0.7 lambert); shaded = render.rgb shade and
+    clay = 0.8 shade in all three channels; a miss is data.bgcolor in both.  The MeshRender is not changed."""
+    mesh = _mesh_packed(var)
+    dev = render.face.device
+    B, V, H, W = render.face.shape
+    bg = torch.full((), float(opt.data.bgcolor), device=dev)
+    covered = (render.face >= 0).view(B, V, H, W, 1)
+    if mesh.faces.shape[0] == 0:
+        miss = bg.expand(B, V, H, W, 3).contiguous()
+        return miss, miss.clone()
+    v_start, f_start, _ = mesh.starts()
+    first_f = torch.tensor(f_start, device=dev).view(B, 1, 1, 1)
+    first_v = torch.tensor(v_start, device=dev).view(B, 1, 1, 1, 1)
+    face = (render.face.clamp(min=0).long() + first_f).clamp(max=mesh.faces.shape[0] - 1)     # a miss reads some face, unused
+    corner = (mesh.faces[face.view(-1)].long().view(B, V, H, W, 3) + first_v).clamp(max=mesh.verts.shape[0] - 1)
+    a = var.mesh_ao["ao"][corner.view(-1)].view(B, V, H, W, 3)
+    t = render.bary * a
+    ao = (t[..., 0] + t[..., 1]) + t[..., 2]
+    pose = pose.float().to(dev)
+    z_cam = (pose[:, None] if pose.dim() == 3 else pose)[..., 2, :3].reshape(B, -1, 1, 1, 3)
+    n = 2 * render.normal - 1
+    lambert = (n * z_cam).sum(-1).abs() / n.norm(dim=-1).clamp_min(1e-12)
+    shade = (ao * (0.3 + 0.7 * lambert)).unsqueeze(-1)
+    shaded = torch.where(covered, render.rgb * shade, bg)
+    clay = torch.where(covered, (0.8 * shade).expand(-1, -1, -1, -1, 3), bg)
+    return shaded, clay
+
+
 # the order of {idx}_mesh_selfx.txt's lines; "decimated" is there with `--mesh.decimate` only
 INTERSECT_VARIANTS = ("mc", "dual", "simplified", "smooth", "subdiv", "decimated")
 _INTERSECT_HELD = {"simplified": "mesh_simplified", "smooth": "mesh_smoothed", "subdiv": "mesh_subdivided", "decimated": "mesh_decimated"}
@@ -1138,6 +1276,7 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
     smooth, subdivide = options.smooth_settings(opt), options.subdivide_settings(opt)
     decimate = options.decimate_settings(opt)
     self_intersect = options.self_intersect_settings(opt)
+    shade = options.ao_settings(opt)
     points_3D = get_dense_3D_grid(opt, var)
     B = points_3D.shape[0]
     level_vox = compute_level_grid(opt, sdf_network, var.proj_latent_sdf, points_3D)
@@ -1185,6 +1324,8 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
             meshes_decimated(opt, var)
         if self_intersect:                      # vis_{ep}/{idx}_mesh_selfx.txt: after the meshers, on what they left in var
             mesh_intersections(opt, var, sdf_network)
+        if shade is not None:                   # vis_{ep}/{idx}_mesh_ao.ply and .txt
+            mesh_ambient_occlusion(opt, var, sdf_network)
         return
     dist_acc, dist_comp, idx1, idx2 = chamfer_distance(opt, X1=var.dpc_pred, X2=var.dpc.points)
     var.f_score = compute_fscore(dist_acc, dist_comp, opt.eval.f_thresholds)
@@ -1215,4 +1356,6 @@ def eval_metrics(opt, var, sdf_network, vis_only=False):
         meshes_decimated(opt, var)
     if self_intersect:                      # a check of what is written, after the meshers: no metric reads it
         mesh_intersections(opt, var, sdf_network)
+    if shade is not None:                   # shading of what is written: no metric reads it
+        mesh_ambient_occlusion(opt, var, sdf_network)
     return dist_acc.mean(), dist_comp.mean()

@@ -284,6 +284,26 @@ def decimate_settings(opt):
     return None if target is None else (target, reg, rounds)
 
 
+# The shading of what is written for a viewer, in a table and a dict of their own with the same rows (the tables above stay as they are):
+# ambient occlusion baked from the level grid changes no mesh and measures nothing; it adds files beside the ones that are written.
+MESH_SHADE_TABLE = tuple(Setting(*row) for row in (
+    ("ao", False, bool, "ambient occlusion from the level grid: {idx}_mesh_ao.ply / .txt, an AO atlas beside --eval.texture and shaded pictures "
+                        "beside --eval.mesh_render (ops.level_ambient_occlusion)"),
+    ("ao_radius", 0.125, (0.0, 1.0), "... the reach of a ray as a fraction of the grid's S - 1 pitches", "str"),
+))
+MESH_SHADE = {row.key: row for row in MESH_SHADE_TABLE}
+
+
+def ao_settings(opt, S=None):
+    """None unless `--mesh.ao` is set, else the reach of ops.level_ambient_occlusion: mesh.ao_radius (S - 1) grid pitches for a level grid
+    of S points per axis, the fraction mesh.ao_radius itself while S is None.  Both values are checked, switch on or off; absent (a key
+    or the whole `mesh` group) means the default."""
+    on, radius = (_checked("mesh", MESH_SHADE[k], (opt.get("mesh", None) or {}).get(k, MESH_SHADE[k].default)) for k in ("ao", "ao_radius"))
+    if not on:
+        return None
+    return radius if S is None else radius * (int(S) - 1)
+
+
 def parse_arguments(args):
     """--key1.key2=value ; --flag (true) ; --flag! (false)"""
     opt_cmd = {}
@@ -375,7 +395,7 @@ def process_options(opt):
                 raise ValueError("hip.%s must be an integer in %d..%d, got %r" % (row.key, lo, hi, v))
     for check in (dual_mesh_reg, texture_texels, mesh_render, icp_settings, normal_settings, mesh_dist_settings, emd_settings, iou_settings,
                   mesh_stats_settings, simplify_settings,       # every eval.* value is checked here, whether or not its switch is on
-                  smooth_settings, subdivide_settings, self_intersect_settings, decimate_settings):        # and every mesh.* value
+                  smooth_settings, subdivide_settings, self_intersect_settings, decimate_settings, ao_settings):    # and every mesh.* value
         check(opt)
     torch.backends.cudnn.deterministic = bool(hip(opt, "deterministic_conv"))
     for row in HIP_TABLE:

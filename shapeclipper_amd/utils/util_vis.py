@@ -213,3 +213,12 @@ def dump_textured_meshes(opt, idx, name, meshes, folder="dump"):
         write_mtl(base + ".mtl", base + ".png")
         Image.fromarray(_numpy(mesh.atlas)).save(base + ".png")
         Image.fromarray(_numpy(mesh.normal_atlas)).save(base + "_normal.png")
+
+
+def dump_atlases(opt, idx, name, atlases, folder="dump"):
+    """{idx}_{name}.png per sample of a uint8 atlas [A,A] (grey) or [A,A,3] each, the bytes as they are (sizes may differ from sample to
+    sample): a further map in the layout of {idx}_mesh_tex.png, e.g. the ambient occlusion of `--mesh.ao`."""
+    if Image is None:
+        return
+    for i, atlas in zip(idx, atlases):
+        Image.fromarray(_numpy(atlas)).save("{}/{}/{}_{}.png".format(opt.output_path, folder, int(i), name))
